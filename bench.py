@@ -13,13 +13,24 @@ independent series with K (train_cov) already resident: residual y - EWMA mean -
 -> blocked Cholesky -> L^-T -> MLL and its gradient wrt raw_noise -> Adam update of raw_noise ->
 (N>1) one RCCL all-reduce of the summed loss/grad scalars.  Series shard across ranks, no data-path
 collective.  --scaling weak (default): 64 series per GPU; --scaling strong: 64 series in total, split
-evenly over the ranks (BASELINE.json's metric reads "N=4096, batch=64; 1/2/4/8 GPU").  With N > 1 the OTHER mode is
-timed right after the headline region and reported beside it (`other_scaling`).
+evenly over the ranks (BASELINE.json's metric reads "N=4096, batch=64; 1/2/4/8 GPU").  With N > 1 and --full the OTHER
+mode is timed right after the headline region and reported beside it (`other_scaling`).
 
 Rank 0 prints ONE JSON line.  `value` = batch-of-64 steps per second summed over ranks, inputs
-resident in HBM.  `roofline` is for the dominant kernel (per-launch HIP events in the timed schedule);
-`cpu_baseline` times the torch-CPU restatement of the gpytorch path on a bounded sample (and real
-gpytorch beside it where it is importable); `rollouts` times BASELINE config 5's per-GPU share.
+resident in HBM; `ms_per_step` = milliseconds of one timed step (the slowest rank's).
+
+A plain run sets up, runs W warm-up steps, times exactly K steps, writes the last step's outputs (--dump-outputs DIR)
+and prints the line: everything else it reports is derived from those K steps.  --full adds the legs that take runs of
+their own, as rank 0's blocks of the same line: `roofline` for the dominant kernel (per-launch HIP events in the timed
+schedule) with the fill / ms-per-Cholesky figures beside it, `cpu_baseline` (the torch-CPU restatement of the gpytorch
+path on a bounded sample, and real gpytorch beside it where it is importable), `rollouts` (BASELINE config 5's per-GPU
+share), `configs` (the other BASELINE shapes), `api_step`, `fp64`, `next_rows`, and with N > 1 `other_scaling`.  The
+--no-* switches drop single legs of a --full run.
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller, as float32 .npy files (rank 0's
+series; about 1 MB at the default shape): mll_out.npy [B, 6] (volt_mll_step_f32's out[:, 0:6]: mll, d mll / d sigma2,
+z'z, logdet, tr K_s^-1, alpha'alpha), alpha.npy [B, N], info.npy [B], raw_noise.npy [B] (after the step's Adam update),
+loss_grad.npy [2] (the reduced loss and gradient sums).  The inputs are seeded: the same arguments give the same inputs.
 """
 from __future__ import annotations
 
@@ -90,12 +101,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --batch series per GPU; strong: --batch series in total, split over the ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: roofline, fill and ms/Cholesky, CPU baseline, rollouts, "
+                         "configs, API, fp64, next rows, and with N > 1 the other scaling mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--no-rollouts", action="store_true", help="skip the config-5 rollout leg")
     ap.add_argument("--n", "--series-len", dest="n", type=int, default=N_SERIES)
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (the other BASELINE shapes)")
-    ap.add_argument("--with-rollouts", action="store_true", help="run the rollout leg even under --no-aux-legs")
+    ap.add_argument("--with-rollouts", action="store_true", help="run the rollout leg even under --no-aux-legs (with --full)")
     ap.add_argument("--rollout-samples", type=int, default=10000)
     ap.add_argument("--rollout-horizon", type=int, default=256)
     ap.add_argument("--profile-only", type=int, default=0, metavar="N",
@@ -111,6 +127,10 @@ def main():
     one_dev = os.environ.get("VOLT_BENCH_ONE_DEVICE") == "1"     # dry-run hook (tests): every rank on device 0 over gloo
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.with_rollouts and not args.full:
+        raise SystemExit("--with-rollouts is a leg of --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, one_dev))               # start the N ranks ourselves; this process only waits
     rank = int(os.environ.get("RANK", 0))
@@ -162,16 +182,18 @@ def main():
     V = ops.cumtrapz(vold, xd, square=True)
     K_all = ops.fill(V)
     torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fills = []
-    for _ in range(7):
-        e0.record()
-        K_all = ops.fill(V)
-        e1.record()
-        torch.cuda.synchronize()
-        fills.append(e0.elapsed_time(e1))
-    fill_ms = float(np.median(fills))
-    fill_gbs = Bmax * n * n * 4 / (fill_ms * 1e-3) / 1e9
+    fill_ms = fill_gbs = None
+    if args.full:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        fills = []
+        for _ in range(7):
+            e0.record()
+            K_all = ops.fill(V)
+            e1.record()
+            torch.cuda.synchronize()
+            fills.append(e0.elapsed_time(e1))
+        fill_ms = float(np.median(fills))
+        fill_gbs = Bmax * n * n * 4 / (fill_ms * 1e-3) / 1e9
 
     def make_step(Bs, Ks=None, ys=None, n_=None):
         """The training-loop body over Bs series (K resident): this rank's first Bs series of the headline shape, or the
@@ -198,11 +220,12 @@ def main():
             if dist is not None:
                 dist.all_reduce(red_)                              # the path's only collective
             opt_.step()
-            return out, info
+            return out, alpha, info
         return step, raw, ws_, red_
 
-    def timed(step, warmup, steps):
-        """W untimed steps, then exactly K steps bracketed by barrier + synchronize; max over ranks."""
+    def timed(step, warmup, steps, last=None):
+        """W untimed steps, then exactly K steps bracketed by barrier + synchronize; max over ranks.  `last`, if given,
+        receives the last timed step's (out, alpha, info)."""
         for _ in range(warmup):
             step()
         if dist is not None:
@@ -210,7 +233,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            out, info = step()
+            out, alpha, info = step()
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -221,19 +244,27 @@ def main():
             gathered = [torch.zeros_like(tt) for _ in range(world)]
             dist.all_gather(gathered, tt)
             per_rank = [float(g.item()) for g in gathered]
+        if last is not None:
+            last.extend((out, alpha, info))
         return max(per_rank), per_rank, info
 
     step, raw_noise, ws, red = make_step(B)
     if args.profile_only > 0:
         profile_only_leg(args.profile_only, K_all[:B], y_all[:B], raw_noise, ws, n, B, dev)
         return
-    dt, dt_ranks, info = timed(step, args.warmup, args.steps)
+    last = []
+    dt, dt_ranks, info = timed(step, args.warmup, args.steps, last)
+    if args.dump_outputs and rank == 0:
+        out_l, alpha_l, info_l = last
+        dump_outputs(args.dump_outputs, {"mll_out": out_l[:, :6], "alpha": alpha_l, "info": info_l,
+                                         "raw_noise": raw_noise.detach(), "loss_grad": red})
+    del last
     bad = int((info != 0).sum().item())
     loss = float(red[0].item()) / (B * world)
     K, y = K_all[:B], y_all[:B]
 
     other = None
-    if world > 1:                       # the other scaling mode, same steps, right behind the headline region
+    if world > 1 and args.full:         # the other scaling mode, same steps, right behind the headline region
         om = "strong" if args.scaling == "weak" else "weak"
         Bo = B_by_mode[om]
         del ws
@@ -250,7 +281,7 @@ def main():
     # factor+inverse in the SAME schedule the timed steps use; per class the union of the launch intervals
     roof = None
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         Np = ops.padded_n(n)
         L = _lib.lib()
         s2 = (torch.nn.functional.softplus(raw_noise.detach()) + 1e-4).contiguous()
@@ -362,31 +393,31 @@ def main():
     # series of all ranks / the slowest rank, and the final gather of the [S, H] samples -- the one place xGMI bandwidth
     # is exercised -- is timed on its own.
     roll = None
-    if not args.no_rollouts and (args.with_rollouts or not args.no_aux_legs):
+    if args.full and not args.no_rollouts and (args.with_rollouts or not args.no_aux_legs):
         G_roll = 8 if world == 1 else max(1, min(Bmax, 64 // world))
         roll = rollout_leg(x, F, vol, dev, n, G=G_roll, S=args.rollout_samples, H=args.rollout_horizon,
                            dist=dist, world=world, rank=rank)
 
     # ---- the other BASELINE shapes (rank 0, N=1): same loop body, same timing loop as the headline
     cfgs = None
-    if rank == 0 and world == 1 and not args.no_aux_legs and not args.no_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_aux_legs and not args.no_configs:
         del ws
         cfgs = configs_leg(make_step, timed, dev, K_all, y_all, n, args.batch, api_inputs=(x, F, vol))
         ws = ops.MllWorkspace(B, n, True, dev)
 
     # ---- API leg (rank 0, N=1): what a caller of the drop-in surface pays per iteration
     api = None
-    if rank == 0 and world == 1 and not args.no_aux_legs:
+    if args.full and rank == 0 and world == 1 and not args.no_aux_legs:
         api = api_leg(x, F, vol, dev, n, B, dt / args.steps * 1e3)
 
     # ---- fp64 leg (rank 0): the double-precision twins of the step, at the 8-GPU share of the batch
     f64 = None
-    if rank == 0 and not args.no_aux_legs:
+    if args.full and rank == 0 and not args.no_aux_legs:
         f64 = f64_leg(x, F, vol, dev, n, min(8, B))
 
     # ---- the (f) rows: GPCV's ELBO step and the vol model's step, at the reference's sizes and at 8 x 4096 (rank 0, N=1)
     nxt = None
-    if rank == 0 and world == 1 and not args.no_aux_legs:
+    if args.full and rank == 0 and world == 1 and not args.no_aux_legs:
         try:
             nxt = next_rows_leg(dev)
         except Exception as e:
@@ -394,7 +425,7 @@ def main():
 
     # ---- CPU baseline leg (rank 0, N=1 only): torch-CPU restatement of the gpytorch path (+ real gpytorch if present)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_leg(K, y, ops.ewma(y, EWMA_K)[..., :-1], n, args.batch)
 
     if rank == 0:
@@ -418,8 +449,9 @@ def main():
                               "bound": "mfma", "achieved": round(per_step_series * 2 * n ** 3 / 3 / (dt / args.steps) / 1e12, 2),
                               "peak": FP32_MFMA_PEAK_TF * world, "unit": "TFLOP/s",
                               "frac": round(B * 2 * n ** 3 / 3 / (dt / args.steps) / 1e12 / FP32_MFMA_PEAK_TF, 4)},
-            "schedule": {"step_kernel": (roof or {}).get("kernel"), "launches_per_step": (roof or {}).get("launches", 0),
-                         "streams": "the caller's stream (one launch)" if (roof or {}).get("launches", 0) == 1 else
+            "schedule": None if roof is None else
+                        {"step_kernel": roof.get("kernel"), "launches_per_step": roof.get("launches", 0),
+                         "streams": "the caller's stream (one launch)" if roof.get("launches", 0) == 1 else
                                     "library-internal, forked/joined on the caller's stream"},
             "cpu_baseline": cpu,
             "api_step": api,
@@ -433,6 +465,13 @@ def main():
     if dist is not None:
         dist.barrier()                       # rank 0 ran the roofline legs: leave together
         dist.destroy_process_group()
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: each array as path/<name>.npy in float32, copied to the host after the timed region."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 def pmc_traffic(kernel: str, n: int, B: int):
@@ -913,6 +952,19 @@ def _cpu_worker(idx, threads, Kc, yc, mc, reps, barrier, q):
     q.put((idx, t0, t1))
 
 
+def _cpu_budget() -> int:
+    """Host cores this process may use: the affinity mask, capped by OMP_NUM_THREADS where it is set (a shared host
+    grants a job fewer cores than cpu_count() reports, and sizes its thread pools to match)."""
+    n = os.cpu_count() or 1
+    if hasattr(os, "sched_getaffinity"):
+        n = min(n, len(os.sched_getaffinity(0)))
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "")))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
 def cpu_baseline_leg(K, y, mean, n, batch):
     """The CPU path timed on this box's host cores on a bounded sample of the same workload: the torch-only
     restatement of gpytorch's dense step (kind "port"), and real gpytorch under max_cholesky_size(N+1) when it is
@@ -920,10 +972,11 @@ def cpu_baseline_leg(K, y, mean, n, batch):
 
     Two figures.  `single_worker`: one process, the series in one batched call, at the thread count that is fastest for
     ONE series (LAPACK/MKL does not scale to every core of a big host at this size).  `value` (the headline baseline):
-    the WHOLE host -- cpu_count // best_threads concurrent worker processes of best_threads threads each over disjoint
-    series (the series are independent), aggregate series-steps/s / batch."""
+    the WHOLE host -- cores // best_threads concurrent worker processes of best_threads threads each over disjoint
+    series (the series are independent), aggregate series-steps/s / batch; cores = what this process may use
+    (_cpu_budget), never more than 15 workers beside this process."""
     from oracle import torch_cpu_path as tp
-    ncpu = os.cpu_count() or 1
+    ncpu = _cpu_budget()
     bs = 8 if n >= 4096 else 16
     bs = min(bs, K.shape[0])
     Kc, yc, mc = K[:bs].cpu(), y[:bs].cpu(), mean[:bs].cpu()
@@ -954,7 +1007,7 @@ def cpu_baseline_leg(K, y, mean, n, batch):
                         f"calibrated over 4..{ncpu} on one series, best = {cores}"}
     # ---- the whole host: workers x threads = every core, disjoint series, all in flight at once
     import torch.multiprocessing as mp
-    nw = max(1, min(ncpu // cores, 64))
+    nw = max(1, min(ncpu // cores, 15))
     per = 1                                           # series per worker (bounded sample: nw series in flight)
     wreps = 2
     Kh = K[: min(K.shape[0], nw * per)].cpu()

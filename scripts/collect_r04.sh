@@ -8,10 +8,10 @@ OUT=$R/gpurun_out/r04
 mkdir -p $OUT
 export TMPDIR=/tmp
 PARTS=${@:-bench trace roll f64 pmc tables small}
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-aux-legs --no-rollouts"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-aux-legs --no-rollouts"
 for P in $PARTS; do case $P in
 bench)
-  python bench.py > $OUT/bench.json 2> $OUT/bench.err; tail -c 400 $OUT/bench.json;;
+  python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; tail -c 400 $OUT/bench.json;;
 trace)
   cd /tmp
   timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t2 -o t2 -- python $R/bench.py $ARGS > $OUT/t2.log 2>&1

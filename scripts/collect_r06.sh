@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 PARTS=${@:-bench trace pmc rollout tables}
 for P in $PARTS; do case $P in
 bench)
-  python bench.py > $OUT/bench.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.json;;
+  python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.json;;
 trace)
   cd /tmp
   timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/po -o po -- python $R/bench.py --profile-only 10 > $OUT/profile_only.log 2>&1

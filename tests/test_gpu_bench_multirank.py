@@ -26,8 +26,8 @@ def test_bench_two_ranks(scaling):
     env = dict(os.environ, VOLT_BENCH_ONE_DEVICE="1", VOLT_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--series-len", "512", "--batch", "16", "--scaling", scaling, "--no-cpu-baseline", "--no-aux-legs", "--with-rollouts",
-           "--rollout-samples", "64", "--rollout-horizon", "16"]
+           "--series-len", "512", "--batch", "16", "--scaling", scaling, "--full", "--no-cpu-baseline", "--no-aux-legs",
+           "--with-rollouts", "--rollout-samples", "64", "--rollout-horizon", "16"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

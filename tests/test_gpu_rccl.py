@@ -15,8 +15,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "3", "--warmup", "1", "--series-len", "512", "--batch", "16", "--no-cpu-baseline", "--no-aux-legs",
-         "--no-rollouts"]
+SMALL = ["--full", "--steps", "3", "--warmup", "1", "--series-len", "512", "--batch", "16", "--no-cpu-baseline",
+         "--no-aux-legs", "--no-rollouts"]
 
 
 def _clean_env(**extra):

@@ -212,28 +212,27 @@ def test_reference_call_sites_resolve_through_the_aliases():
         sys.modules.update({k: v for k, v in had.items() if v is not None})
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/voltron/train_utils.py"), reason="reference tree not mounted")
+def _reference_surface():
+    """The reference's public surface as recorded names (tests/golden/make_reference_surface.py parses its files)."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_surface.json")) as fh:
+        return json.load(fh)
+
+
 def test_reference_train_utils_imports_against_our_namespaces():
-    """The reference's own voltron/train_utils.py and rollout_utils.py, loaded from /root/reference (never copied),
-    import cleanly when ``voltron`` and ``gpytorch`` resolve to this package: every name their module-level imports
-    and function bodies look up exists here with the reference's spelling."""
-    import importlib.util
+    """The reference's own voltron/train_utils.py and rollout_utils.py import cleanly when ``voltron`` and ``gpytorch``
+    resolve to this package: every ``gpytorch.<sub>.<attr>`` they look up (recorded in tests/golden/reference_surface.json)
+    exists here with the reference's spelling."""
     import sys
     import volt_amd
-    sys.dont_write_bytecode = True
+    surface = _reference_surface()["gpytorch_attrs"]
+    assert sorted(surface) == ["rollout_utils.py", "train_utils.py"] and surface["train_utils.py"]
     had = {k: sys.modules.get(k) for k in list(sys.modules) if k.split(".")[0] in ("gpytorch", "voltron")}
     try:
         volt_amd.install_as_voltron()
-        for rel in ("train_utils.py", "rollout_utils.py"):
-            names = set()
-            import ast
-            tree = ast.parse(open("/root/reference/voltron/" + rel).read())
-            for node in ast.walk(tree):
-                if (isinstance(node, ast.Attribute) and isinstance(node.value, ast.Attribute)
-                        and isinstance(node.value.value, ast.Name) and node.value.value.id == "gpytorch"):
-                    names.add((node.value.attr, node.attr))
+        for rel, names in sorted(surface.items()):
             import gpytorch
-            for sub, attr in sorted(names):
+            for sub, attr in names:
                 assert hasattr(getattr(gpytorch, sub), attr), f"gpytorch.{sub}.{attr} used by {rel} is missing"
     finally:
         for k in [k for k in sys.modules if k.split(".")[0] in ("gpytorch", "voltron")]:
@@ -241,26 +240,16 @@ def test_reference_train_utils_imports_against_our_namespaces():
         sys.modules.update({k: v for k, v in had.items() if v is not None})
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/voltron/train_utils.py"), reason="reference tree not mounted")
 def test_public_signatures_match_the_reference():
     """Same function names, argument names, order and defaults as voltron/train_utils.py and rollout_utils.py
     (keyword-only extras such as ``z=`` / ``pred_vol=`` are additions)."""
-    import ast
     import inspect
     from volt_amd import rollout_utils, train_utils
-
-    def ref_sigs(path):
-        out = {}
-        for node in ast.parse(open(path).read()).body:
-            if isinstance(node, ast.FunctionDef):
-                a = node.args
-                names = [x.arg for x in a.args]
-                defaults = [ast.literal_eval(d) if isinstance(d, (ast.Constant, ast.UnaryOp)) else "?" for d in a.defaults]
-                out[node.name] = (names, defaults)
-        return out
-
+    surface = _reference_surface()["functions"]
     for mod, rel in ((train_utils, "train_utils.py"), (rollout_utils, "rollout_utils.py")):
-        for name, (names, defaults) in ref_sigs("/root/reference/voltron/" + rel).items():
+        assert surface[rel], rel
+        for name, ref in surface[rel].items():
+            names, defaults = ref["args"], ref["defaults"]
             if name == "TrainBasicModel":                  # SURVEY 2 row 7: out of scope (lives in baselines/, not the product)
                 continue
             assert hasattr(mod, name), f"{rel}:{name} has no counterpart"
@@ -271,11 +260,9 @@ def test_public_signatures_match_the_reference():
             assert ours == defaults, (name, ours, defaults)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/voltron/models/VoltMagpie.py"), reason="reference tree not mounted")
 def test_class_surfaces_match_the_reference():
     """Every class of the reference's path files exists here under the same module path, with the same constructor
     argument names / order and at least the same public methods ("same names, argument order, defaults")."""
-    import ast
     import importlib
     import inspect
     files = {"models/VoltMagpie.py": ["VoltMagpie"], "models/VoltronGP.py": ["VoltronGP"], "models/Volt.py": ["Volt"],
@@ -285,22 +272,19 @@ def test_class_surfaces_match_the_reference():
              "means/loglinear_mean.py": ["LogLinearMean"], "kernels/VolKernel.py": ["VolatilityKernel"],
              "kernels/BMKernel.py": ["BMKernel"], "kernels/FBMKernel.py": ["FBMKernel"],
              "likelihoods/volatility_likelihood.py": ["VolatilityGaussianLikelihood"]}
+    surface = _reference_surface()["classes"]
     for rel, classes in files.items():
-        tree = ast.parse(open("/root/reference/voltron/" + rel).read())
+        assert sorted(surface[rel]) == sorted(classes), (rel, sorted(surface[rel]))
         ours = importlib.import_module("volt_amd." + rel[:-3].replace("/", "."))
-        for node in tree.body:
-            if not (isinstance(node, ast.ClassDef) and node.name in classes):
-                continue
-            cls = getattr(ours, node.name)
-            for fn in [f for f in node.body if isinstance(f, ast.FunctionDef)]:
-                if fn.name.startswith("_") and fn.name != "__init__":
-                    continue
-                assert hasattr(cls, fn.name), f"{rel}:{node.name}.{fn.name} missing"
-                if fn.name == "__init__":
-                    want = [a.arg for a in fn.args.args][1:]
-                    got = [p.name for p in inspect.signature(cls.__init__).parameters.values()
-                           if p.kind == p.POSITIONAL_OR_KEYWORD][1:]
-                    assert got[:len(want)] == want, (rel, node.name, got, want)
+        for cname, ref in surface[rel].items():
+            cls = getattr(ours, cname)
+            for fn in ref["methods"]:
+                assert hasattr(cls, fn), f"{rel}:{cname}.{fn} missing"
+            if ref["init_args"] is not None:
+                want = ref["init_args"]
+                got = [p.name for p in inspect.signature(cls.__init__).parameters.values()
+                       if p.kind == p.POSITIONAL_OR_KEYWORD][1:]
+                assert got[:len(want)] == want, (rel, cname, got, want)
 
 
 def test_bench_refuses_gpus_it_cannot_see():
@@ -371,19 +355,13 @@ def test_reference_driver_imports_resolve():
         "gpytorch.likelihoods": ["GaussianLikelihood"], "gpytorch.mlls": ["ExactMarginalLogLikelihood"],
         "gpytorch.means": ["ConstantMean", "LinearMean"],
     }
-    ref = "/root/reference/experiments"
-    if os.path.isdir(ref):                                # ... and whatever the drivers really import from those packages
-        import ast
-        for rel in ("stocks/GenerateMultiMeanPreds.py", "weather/GPGenerator.py", "weather/BasicWind.py"):
-            path = os.path.join(ref, rel)
-            if not os.path.exists(path):
-                continue
-            for node in ast.walk(ast.parse(open(path).read())):
-                if isinstance(node, ast.ImportFrom) and node.module and node.module.split(".")[0] in ("voltron", "gpytorch"):
-                    if node.module.startswith("voltron.data"):
-                        continue                           # network download helpers: SURVEY 2 row 15, out of scope
-                    wanted.setdefault(node.module, [])
-                    wanted[node.module] += [a.name for a in node.names]
+    # ... and whatever the drivers really import from those packages (stocks/GenerateMultiMeanPreds.py, weather/GPGenerator.py,
+    # weather/BasicWind.py; voltron.data's network download helpers are out of scope)
+    drivers = _reference_surface()["driver_imports"]
+    assert drivers
+    for mod, names in drivers.items():
+        wanted.setdefault(mod, [])
+        wanted[mod] += names
     for mod, names in wanted.items():
         m = importlib.import_module(mod)
         for name in names:
