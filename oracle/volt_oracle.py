@@ -100,19 +100,24 @@ def volatility_kernel(x: np.ndarray, vol_path: np.ndarray, diag: bool = False) -
 
 
 # --------------------------------------------------------------------------- a4
-def ewma_weights(k: int) -> np.ndarray:
-    """EWMA.py:21-24: w_j ~ alpha (1-alpha)^(k-1-j), normalised; fp32 like torch."""
+def ewma_weights(k: int, dtype=np.float32) -> np.ndarray:
+    """EWMA.py:21-24: w_j ~ alpha (1-alpha)^(k-1-j), normalised; fp32 like torch (fp64 under torch's fp64 default dtype)."""
     alpha = 2.0 / (k + 1)
+    if dtype == np.float64:
+        w = alpha * np.power(1.0 - alpha, np.arange(k - 1, -1, -1, dtype=np.float64))
+        return w / w.sum()
     w = np.float32(alpha) * np.power(np.float32(1.0 - alpha), np.arange(k - 1, -1, -1)).astype(np.float32)
     return (w / w.sum(dtype=np.float32)).astype(np.float32)
 
 
-def ewma(y: np.ndarray, k: int) -> np.ndarray:
+def ewma(y: np.ndarray, k: int, dtype=np.float32) -> np.ndarray:
     """EWMA.py:20-37.  Left-pad with k copies of y[..., 0], valid correlation with the
     k weights: out[..., t] = sum_j w_j * padded[..., t + j],  t = 0..N  (length N+1).
-    out[t] only sees y[t-k .. t-1]; out[N] is the one-step-ahead value."""
-    y = np.asarray(y, dtype=np.float32)
-    w = ewma_weights(k)
+    out[t] only sees y[t-k .. t-1]; out[N] is the one-step-ahead value.  ``dtype``: the precision of
+    the input and the weights (fp64 = the reference run under torch's fp64 default dtype); the result
+    is fp32 either way (the reference's ``.type(torch.FloatTensor)``, :37)."""
+    y = np.asarray(y, dtype=dtype)
+    w = ewma_weights(k, dtype)
     pad = np.repeat(y[..., :1], k, axis=-1)
     padded = np.concatenate([pad, y], axis=-1)
     n = y.shape[-1]
@@ -132,34 +137,35 @@ def _select(ma: np.ndarray, x: np.ndarray, train_x: np.ndarray) -> np.ndarray:
     return ma
 
 
-def ewma_mean(x, train_x, train_y, k=20):
+def ewma_mean(x, train_x, train_y, k=20, dtype=np.float32):
     """EWMAMean.forward, EWMA.py:46-54."""
-    return _select(ewma(train_y, k), x, train_x)
+    return _select(ewma(train_y, k, dtype), x, train_x)
 
 
-def dewma_mean(x, train_x, train_y, k=20):
+def dewma_mean(x, train_x, train_y, k=20, dtype=np.float32):
     """DEWMAMean.forward, EWMA.py:81-91: 2*ema - ema(ema)[:-1]."""
-    ema = ewma(train_y, k)
-    ema_ema = ewma(ema, k)[..., :-1]
+    ema = ewma(train_y, k, dtype)
+    ema_ema = ewma(ema, k, dtype)[..., :-1]
     return _select((2 * ema - ema_ema).astype(np.float32), x, train_x)
 
 
-def tewma_mean(x, train_x, train_y, k=20):
+def tewma_mean(x, train_x, train_y, k=20, dtype=np.float32):
     """TEWMAMean.forward, EWMA.py:102-113: 3*ema - 3*ema2 + ema3."""
-    ema = ewma(train_y, k)
-    ema2 = ewma(ema, k)[..., :-1]
-    ema3 = ewma(ema2, k)[..., :-1]
+    ema = ewma(train_y, k, dtype)
+    ema2 = ewma(ema, k, dtype)[..., :-1]
+    ema3 = ewma(ema2, k, dtype)[..., :-1]
     return _select((3 * ema - 3 * ema2 + ema3).astype(np.float32), x, train_x)
 
 
-def meanrevert_mean(x, train_x, train_y, k=20, theta=0.5, latent=None):
+def meanrevert_mean(x, train_x, train_y, k=20, theta=0.5, latent=None, dtype=np.float32):
     """MeanRevertingEMAMean.forward, EWMA.py:126-135.  ``latent`` is the mean of train_y
-    taken at CONSTRUCTION time (:124); Rollouts later mutates train_y but not it."""
-    train_y = np.asarray(train_y, dtype=np.float32)
+    taken at CONSTRUCTION time (:124); Rollouts later mutates train_y but not it.  It enters the
+    fp32 update rounded to fp32, whatever precision it was taken in."""
+    train_y = np.asarray(train_y, dtype=dtype)
     if latent is None:
-        latent = train_y.mean(dtype=np.float32)
+        latent = train_y.mean(dtype=dtype)
     latent = np.float32(latent)
-    ema = ewma(train_y, k).copy()
+    ema = ewma(train_y, k, dtype).copy()
     ema[..., 1:] -= np.float32(theta) * (ema[..., :-1] - latent)
     return _select(ema, x, train_x)
 
@@ -254,22 +260,23 @@ def mll_and_grads(K: np.ndarray, y: np.ndarray, mean: np.ndarray, raw_noise: flo
 
 # --------------------------------------------------------------------------- a7
 def generate_prediction(model_train_x, model_train_y, log_vol_path, test_x, pred_vol, z,
-                        mean_fn, latent_mean=None, theta=0.5, jitter=1e-4):
+                        mean_fn, latent_mean=None, theta=0.5, jitter=1e-4, dtype=np.float32):
     """rollout_utils.py:6-53 with the N(0,1) draw ``z`` [S,1,1] passed in instead of
     ``torch.randn`` (:47) so paths are comparable draw by draw.
 
     model_train_x [N'] or [S,N'], model_train_y [N'] or [S,N'] (log prices), log_vol_path
     [N'] or [S,N'] -- the *model attributes* GeneratePrediction reads (:7,:17,:32);
     test_x [T]; pred_vol [S,T]; z [S,T,1]; mean_fn(x) -> the model's mean module (:31,:39).
-    Everything in fp32 like the reference; Cholesky via LAPACK spotrf.
+    Everything in fp32 like the reference; Cholesky via LAPACK spotrf.  ``dtype=np.float64``: the
+    reference run under torch's fp64 default dtype (the mean values mean_fn returns stay fp32).
     Returns samples [S, T] (matches ``(samples + pred_mean).squeeze(-1)``, :53).
     """
-    f32 = np.float32
-    train_x = np.asarray(model_train_x, dtype=f32)
-    train_y = np.asarray(model_train_y, dtype=f32)
-    test_x = np.asarray(test_x, dtype=f32)
-    pred_vol = np.asarray(pred_vol, dtype=f32)
-    vol = np.exp(np.asarray(log_vol_path, dtype=f32))
+    ft = np.dtype(dtype).type
+    train_x = np.asarray(model_train_x, dtype=ft)
+    train_y = np.asarray(model_train_y, dtype=ft)
+    test_x = np.asarray(test_x, dtype=ft)
+    pred_vol = np.asarray(pred_vol, dtype=ft)
+    vol = np.exp(np.asarray(log_vol_path, dtype=ft))
     S = pred_vol.shape[0]
     if train_x.ndim != test_x.ndim:                              # :8-11
         test_x_for_stack = np.repeat(test_x[None, :], train_x.shape[0], axis=0)
@@ -283,33 +290,33 @@ def generate_prediction(model_train_x, model_train_y, log_vol_path, test_x, pred
     K_tr = cov[..., :idx_cut, :idx_cut]
     K_tr_te = cov[..., :idx_cut, idx_cut:]
     K_te = cov[..., idx_cut:, idx_cut:]
-    train_mean = np.asarray(mean_fn(train_x), dtype=f32)                           # :31
+    train_mean = np.asarray(mean_fn(train_x), dtype=ft)                           # :31
     train_diffs = (train_y - train_mean)[..., None]                                # :32
     if train_diffs.ndim == 2:
         train_diffs = np.broadcast_to(train_diffs, (S,) + train_diffs.shape)
     T = test_x.shape[0]
-    out = np.zeros((S, T), dtype=f32)
-    tm = np.asarray(mean_fn(test_x), dtype=f32)                                    # :39
+    out = np.zeros((S, T), dtype=ft)
+    tm = np.asarray(mean_fn(test_x), dtype=ft)                                    # :39
     tm = tm.T[..., None]                                   # .T.unsqueeze(-1): [T,1] / [1,1] / [S,1,1]
     tm = np.broadcast_to(tm, (S, T, 1))
-    z = np.asarray(z, dtype=f32).reshape(S, T, 1)
+    z = np.asarray(z, dtype=ft).reshape(S, T, 1)
     for s in range(S):
-        L, _ = psd_safe_cholesky(K_tr[s].astype(f32), jitter=jitter)              # :35
-        L = L.astype(f32)
-        sol = sla.cho_solve((L, True), train_diffs[s].astype(f32)).astype(f32)     # :36
-        pm = (K_tr_te[s].T @ sol).astype(f32) + tm[s]                              # :36,:39
+        L, _ = psd_safe_cholesky(K_tr[s].astype(ft), jitter=jitter)              # :35
+        L = L.astype(ft)
+        sol = sla.cho_solve((L, True), train_diffs[s].astype(ft)).astype(ft)     # :36
+        pm = (K_tr_te[s].T @ sol).astype(ft) + tm[s]                              # :36,:39
         if latent_mean is not None:                                                # :41-42
-            pm = pm - f32(theta) * (pm - f32(latent_mean))
-        sol2 = sla.cho_solve((L, True), K_tr_te[s].astype(f32)).astype(f32)        # :44
-        pc = (K_te[s] - K_tr_te[s].T @ sol2).astype(f32)
+            pm = pm - ft(theta) * (pm - ft(latent_mean))
+        sol2 = sla.cho_solve((L, True), K_tr_te[s].astype(ft)).astype(ft)        # :44
+        pc = (K_te[s] - K_tr_te[s].T @ sol2).astype(ft)
         pcL, _ = psd_safe_cholesky(pc, jitter=jitter)                              # :46
-        out[s, :] = (pcL.astype(f32) @ z[s] + pm)[:, 0]                            # :48,:53
+        out[s, :] = (pcL.astype(ft) @ z[s] + pm)[:, 0]                            # :48,:53
     return out
 
 
 # --------------------------------------------------------------------------- a8
 def rollouts(train_x, train_y, test_x, log_vol_path, pred_vol, z, mean_name="ewma", k=25,
-             theta=None, mean_theta=0.5):
+             theta=None, mean_theta=0.5, dtype=np.float32, stacked_latent=False):
     """rollout_utils.py:57-93 (method == "volt") with ``pred_vol`` [S,H] (:66, out of scope:
     a sample of the BM vol model) and the normal draws ``z`` [S,H] passed in.
 
@@ -317,27 +324,31 @@ def rollouts(train_x, train_y, test_x, log_vol_path, pred_vol, z, mean_name="ewm
     entry (model.train_x = train_x, model.train_y = log(train_y[1:]), mean module built on
     those).  Reproduces the in-place mutation of the model between steps (:80-86) by
     rebuilding the state each step.  Returns samples [S,H] fp32 (log-price units).
+    ``dtype=np.float64``: the reference run under torch's fp64 default dtype (fp64 samples).
+    ``stacked_latent``: a deliberately WRONG variant for the tests' negative control -- the mean-reverting
+    latent taken from the current stacked series at every step instead of the one fixed at construction.
     """
-    f32 = np.float32
-    train_x = np.asarray(train_x, dtype=f32)
-    train_y = np.asarray(train_y, dtype=f32)
-    test_x = np.asarray(test_x, dtype=f32)
-    pred_vol = np.asarray(pred_vol, dtype=f32)
-    z = np.asarray(z, dtype=f32)
+    ft = np.dtype(dtype).type
+    train_x = np.asarray(train_x, dtype=ft)
+    train_y = np.asarray(train_y, dtype=ft)
+    test_x = np.asarray(test_x, dtype=ft)
+    pred_vol = np.asarray(pred_vol, dtype=ft)
+    z = np.asarray(z, dtype=ft)
     S, H = pred_vol.shape
-    latent_mean = None if theta is None else np.log(train_y).mean(dtype=f32)       # :60-63
-    means = {"ewma": lambda x, tx, ty: ewma_mean(x, tx, ty, k),
-             "dewma": lambda x, tx, ty: dewma_mean(x, tx, ty, k),
-             "tewma": lambda x, tx, ty: tewma_mean(x, tx, ty, k),
-             "meanrevert": lambda x, tx, ty: meanrevert_mean(x, tx, ty, k, mean_theta, mr_latent)}
+    latent_mean = None if theta is None else np.log(train_y).mean(dtype=ft)       # :60-63
+    means = {"ewma": lambda x, tx, ty: ewma_mean(x, tx, ty, k, dtype),
+             "dewma": lambda x, tx, ty: dewma_mean(x, tx, ty, k, dtype),
+             "tewma": lambda x, tx, ty: tewma_mean(x, tx, ty, k, dtype),
+             "meanrevert": lambda x, tx, ty: meanrevert_mean(x, tx, ty, k, mean_theta,
+                                                             ty.mean() if stacked_latent else mr_latent, dtype)}
     mfn = means[mean_name]
-    samples = np.zeros((S, H), dtype=f32)
-    log_y = np.log(train_y[1:]).astype(f32)
-    mr_latent = log_y.mean(dtype=f32)
-    m_tx, m_ty, m_lv = train_x, log_y, np.asarray(log_vol_path, dtype=f32)
+    samples = np.zeros((S, H), dtype=ft)
+    log_y = np.log(train_y[1:]).astype(ft)
+    mr_latent = log_y.mean(dtype=ft)
+    m_tx, m_ty, m_lv = train_x, log_y, np.asarray(log_vol_path, dtype=ft)
     samples[:, 0] = generate_prediction(m_tx, m_ty, m_lv, test_x[0:1], pred_vol[:, 0:1], z[:, 0],
                                         lambda x: mfn(x, m_tx, m_ty), latent_mean,
-                                        0.5 if theta is None else theta)[:, 0]     # :67-70
+                                        0.5 if theta is None else theta, dtype=dtype)[:, 0]   # :67-70
     stack_y0 = np.repeat(log_y[None, :], S, axis=0)                                # :71
     stack_v0 = np.repeat(m_lv[None, :], S, axis=0)                                 # :72
     for idx in range(1, H):                                                        # :74
@@ -347,7 +358,7 @@ def rollouts(train_x, train_y, test_x, log_vol_path, pred_vol, z, mean_name="ewm
         samples[:, idx] = generate_prediction(
             rolling_x, stack_y, stack_vol, test_x[idx:idx + 1], pred_vol[:, idx:idx + 1], z[:, idx],
             lambda x, rx=rolling_x, sy=stack_y: mfn(x, rx, sy), latent_mean,
-            0.5 if theta is None else theta)[:, 0]                                 # :87-90
+            0.5 if theta is None else theta, dtype=dtype)[:, 0]                    # :87-90
     return samples
 
 

@@ -131,3 +131,96 @@ def test_last_dim_is_batch_matches_the_reference_code(golden, tag):
     x, vol = g[f"{tag}_x"], g[f"{tag}_vol"]
     assert np.array_equal(vo.volatility_kernel_last_dim_is_batch(x, vol), g[f"{tag}_K"])
     assert np.array_equal(vo.volatility_kernel_last_dim_is_batch(x, vol, diag=True), g[f"{tag}_diag"])
+
+
+# ----------------------------------------------------------------------------- reference shapes, fp64 (make_golden_refshape.py)
+_EPS64 = np.finfo(np.float64).eps
+
+
+def _refshape_tol(d, iset, out_max):
+    """cond(K) * eps64 * max|path|, K the noise-free train block at the rollout's largest size (N + H - 1 points): the
+    forward error of the fp64 solves the reference and the oracle both make, relative to the paths they produce.  The
+    mean values are fp32 in both runs (the reference's FloatTensor casts); they are computed the same way, so they add
+    nothing unless an fp32 rounding falls differently (a ~1e-9 chance per value)."""
+    x = np.concatenate((d[f"{iset}_train_x"], d[f"{iset}_test_x"][:-1])).astype(np.float64)
+    vol = np.concatenate((d[f"{iset}_vol"], d[f"{iset}_pred_vol"][0, :-1])).astype(np.float64)
+    cond = np.linalg.cond(vo.volatility_kernel(x, vol))
+    return cond * _EPS64 * max(1.0, out_max)
+
+
+def _oracle_refshape(d, tag, **kw):
+    iset = str(d[f"{tag}_set"])
+    theta = float(d[f"{tag}_theta"])
+    return vo.rollouts(d[f"{iset}_train_x"], d[f"{iset}_train_y"], d[f"{iset}_test_x"], np.log(d[f"{iset}_vol"]),
+                       d[f"{iset}_pred_vol"], d[f"{iset}_z"], mean_name=str(d[f"{tag}_mean"]), k=int(d[f"{tag}_k"]),
+                       theta=None if np.isnan(theta) else theta, dtype=np.float64, **kw)
+
+
+@pytest.mark.parametrize("tag", ["tewma_k400", "meanrevert_k25", "ewma_k25_theta"])
+def test_oracle_rollouts_match_reference_fp64(golden, tag):
+    """oracle.rollouts in fp64 vs the reference's Rollouts run in fp64 with the same draws (tests/golden/rollouts_refshape.npz,
+    N = 399, H = 100, S = 8; k > N - 1 at tewma k = 400), at cond(K) * eps64 * max|path| (~1e-8)."""
+    d = golden("rollouts_refshape")
+    out = _oracle_refshape(d, tag)
+    ref = d[f"{tag}_s64"]
+    assert out.dtype == np.float64 and out.shape == ref.shape
+    tol = _refshape_tol(d, str(d[f"{tag}_set"]), float(np.abs(ref).max()))
+    assert tol < 1e-7
+    np.testing.assert_allclose(out, ref, rtol=0, atol=tol)
+
+
+def test_meanrevert_latent_choice_cancels(golden):
+    """The one negative control the GPU gate cannot see, pinned here: MeanRevertingEMAMean with its latent taken from the
+    stacked series at every step instead of the one fixed at construction (EWMA.py:124).  The latent shifts every mean value
+    of a step by the same theta * latent, and the predictive mean of the noise-free volatility kernel is
+    y_last - m[N-1] + m_new (K^-1 u = e_last), so the shift cancels: the wrong variant matches the fp64 fixture too, up to
+    how the shifted fp32 mean values round -- at most an fp32 ulp on each of m[N-1] and m_new per step, 2 H ulp(|y|) = 4.8e-5
+    over H = 100 steps (measured 3.8e-6), under the GPU gate's 2e-4: harmless to the outputs, and invisible to it."""
+    d = golden("rollouts_refshape")
+    tag = "meanrevert_k25"
+    ref = d[f"{tag}_s64"]
+    out = _oracle_refshape(d, tag, stacked_latent=True)
+    H = ref.shape[1]
+    assert np.abs(out - ref).max() <= 2 * H * np.spacing(np.float32(np.abs(ref).max()))
+
+
+@pytest.mark.parametrize("tag", ["voltron_T100_n3", "voltron_T1_n1", "magpie_k400_T1_n3"])
+def test_oracle_generate_prediction_matches_model_twins_fp64(golden, tag):
+    """The model-method twins (VoltronGP.py:62-95 with a linear mean, VoltMagpie.py:67-99 with EWMAMean at k > N) run in fp64:
+    oracle.generate_prediction (default jitter, one column of draws at a time) at cond(K) * eps64 * max|path|."""
+    t = golden("refshape_twins")
+    T_, k = int(t[f"{tag}_T"]), int(t[f"{tag}_k"])
+    x, ty, vol = t["in_train_x"], t["in_train_y"].astype(np.float64), t["in_vol"]
+    ly = np.log(ty[1:])
+    tx, pv = t["in_test_x"][:T_], t["in_pred_vol"][0, :T_]
+    if tag.startswith("voltron"):
+        w, b = float(t["lin_w"]), float(t["lin_b"])
+        mfn = lambda q: w * np.asarray(q, dtype=np.float64).reshape(-1) + b
+    else:
+        mfn = lambda q: vo.ewma_mean(q, x, ly, k, dtype=np.float64)
+    z = t[f"{tag}_z"].reshape(T_, -1)
+    ref = t[f"{tag}_s64"].reshape(T_, -1)
+    out = np.stack([vo.generate_prediction(x, ly, np.log(vol.astype(np.float64)), tx, pv[None], z[None, :, c:c + 1], mfn,
+                                           jitter=None, dtype=np.float64)[0] for c in range(z.shape[1])], -1)
+    xx = np.concatenate((x, tx)).astype(np.float64)
+    tol = np.linalg.cond(vo.volatility_kernel(xx, np.concatenate((vol, pv)).astype(np.float64))) * _EPS64 * np.abs(ref).max()
+    np.testing.assert_allclose(out, ref, rtol=0, atol=tol)
+
+
+@pytest.mark.parametrize("k", [200, 400])
+@pytest.mark.parametrize("cname", ["ewma", "dewma", "tewma", "meanrevert"])
+def test_mean_functions_match_reference_fp64_beyond_n(golden, cname, k):
+    """The oracle's mean functions with fp64 inputs and weights (the reference under torch's fp64 default dtype, its
+    FloatTensor casts kept) at N = 399 with k > N / 2 and k > N, single and stacked [8, N+50]: one fp32 ulp (the same
+    fp64 sums in another order may round the other way)."""
+    t = golden("refshape_twins")
+    fn = {"ewma": vo.ewma_mean, "dewma": vo.dewma_mean, "tewma": vo.tewma_mean, "meanrevert": vo.meanrevert_mean}[cname]
+    x, y, xs, ys = (t[f"mc_{n}"].astype(np.float64) for n in ("x", "y", "xstack", "ystack"))
+    kw = {"latent": y.mean()} if cname == "meanrevert" else {}
+    q = {"train": (x, x, y), "one": (x[-1:] + 1 / 252., x, y), "other": (x[: x.shape[0] // 2], x, y),
+         "btrain": (xs, xs, ys), "bone": (xs[-1:] + 1 / 252., xs, ys), "bother": (x, xs, ys)}
+    for br, (xq, tx, ty) in q.items():
+        ref = t[f"mc_{cname}_k{k}_{br}_64"]
+        out = fn(xq, tx, ty, k, dtype=np.float64, **kw)
+        assert out.dtype == np.float32 and out.shape == ref.shape, (br, out.shape, ref.shape)
+        np.testing.assert_allclose(out, ref, rtol=0, atol=np.spacing(np.float32(4.0)), err_msg=br)

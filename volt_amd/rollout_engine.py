@@ -95,7 +95,8 @@ def rollout_series(train_x, log_y, log_vol_path, test_x, pred_vol, z, mean_mode,
     alone (the weather driver's default constant mean, experiments/weather/GPGenerator.py:68-82; the stocks driver's
     constant / loglinear choices, GenerateMultiMeanPreds.py:168-177) -- the mean of an appended point is then history-free.
     ``resubstitute``: re-solve every sample's triangular system from its stored rows at every step (H^3/6 * 4 B of HBM
-    traffic per path) instead of extending it by one entry -- bitwise the same paths; the cross-check of the default."""
+    traffic per path) instead of extending it by one entry -- the same paths to rounding (<= 5e-5 of the paths'
+    magnitude: the default engine keeps fp64 running sums where this one re-sums in fp32); the cross-check of the default."""
     dev = train_x.device
     G, N = log_y.shape
     S, H = pred_vol.shape[-2:]
