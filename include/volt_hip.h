@@ -284,6 +284,45 @@ int volt_gpcv_step_f32(const float* K, int64_t ldk, int64_t bsk, float jitter, c
                        float min_scale, float w_ell, float w_kl, float* out, float* grad_m, float* grad_mu,
                        float* grad_Lq, float* grad_K, int* info, void* workspace, int B, int N, int ws_flags, void* stream);
 
+/* ---- Kronecker multi-task vol forecaster  (MultitaskBMGP, voltron/models/BMGP.py:30-56: botorch KroneckerMultiTaskGP with
+ * MultitaskKernel(BMKernel(), T) and MultitaskGaussianLikelihood(T); built by the batched constructors VoltMagpie.py:51-55,
+ * VoltronGP.py:46-50, Volt.py:67-71, trained through ExactMarginalLogLikelihood + loss.backward()).
+ * Sigma = K_x (x) K_t + I_N (x) D, element (n,t) of vec Y at n*T + t;  K_x = vol M, M = min(x_i,x_k), vol = sigmoid(raw_vol);
+ * K_t = F F' + diag(softplus(raw_var)), F = covar_factor [T] (rank 1);  d_t = softplus(raw_task_noises_t) + 1e-4 +
+ * softplus(raw_noise) + 1e-4;  mu[n,t] = -1/2 vol^2 x_n K_t[t,t];  mll = log N(vec Y; vec mu, Sigma) / (N T).
+ * With S = D^-1/2 K_t D^-1/2 = Q Lambda Q', W = D^-1/2 Q, kappa_j = vol lambda_j, the MLL is T exact-GP steps over ONE M:
+ *     volt_kron_prologue_*  ->  volt_mll_step_* (K = M for every j: ldk = N, bsk = 0 or M repeated; resid = r [T,N];
+ *                               sigma2 = 1 / kappa [T]; B = T, VOLT_WANT_GRAD)  ->  volt_kron_epilogue_*
+ * No host synchronisation in between: the three calls replay from a hipGraph.  T <= 64.  All parameters are device
+ * pointers in the step's dtype; the eigendecomposition and the algebra around the step run in fp64 in either variant. */
+
+/* Batched symmetric eigensolver, T <= 64: S [B,T,T] (batch stride bss >= T*T, contiguous rows) -> lam [B,T] ascending,
+ * Q [B,T,T] row-major with the eigenvectors as columns (S Q = Q diag(lam)).  One workgroup per matrix, parallel cyclic
+ * Jacobi in LDS; info[b] = sweeps used (>= 0), or -1 if 30 sweeps did not converge.  Replaces the torch.linalg.eigh that
+ * gpytorch's KroneckerProductLinearOperator runs on the task covariance. */
+int volt_syev_small_f64(const double* S, int64_t bss, double* lam, double* Q, int* info, int B, int T, void* stream);
+/* Bytes of the caller's `state` of the prologue (doubles: vol, Lambda [T], d [T], W [T,T], Q [T,T]); 0 if T is out of range. */
+size_t volt_kron_state_bytes(int T);
+/* From the raw parameters (raw_vol [1], covar_factor [T], raw_var [T], raw_task_noises [T], raw_noise [1]), x [N] and Y [N,T]
+ * (row stride ldy, contiguous rows): resid [T,N] = r_j = (R W)_j / sqrt(kappa_j), R = Y - mu; sigma2 [T] = 1 / kappa_j;
+ * state (volt_kron_state_bytes(T)); info[0] = sweeps of the eigensolver or -1.  One launch. */
+int volt_kron_prologue_f32(const float* raw_vol, const float* covar_factor, const float* raw_var, const float* raw_task_noises,
+                           const float* raw_noise, const float* x, const float* Y, int64_t ldy, float* resid, float* sigma2,
+                           double* state, int* info, int N, int T, void* stream);
+int volt_kron_prologue_f64(const double* raw_vol, const double* covar_factor, const double* raw_var,
+                           const double* raw_task_noises, const double* raw_noise, const double* x, const double* Y, int64_t ldy,
+                           double* resid, double* sigma2, double* state, int* info, int N, int T, void* stream);
+/* From the step's out [T,8] and alpha [T,N] (with the prologue's resid and state): res [3 + 3T] =
+ *     mll, d mll / d raw_vol, d mll / d raw_noise, d mll / d covar_factor [T], d / d raw_var [T], d / d raw_task_noises [T].
+ * One launch (one workgroup: the reductions over N, then T x T algebra). */
+int volt_kron_epilogue_f32(const float* raw_vol, const float* covar_factor, const float* raw_var, const float* raw_task_noises,
+                           const float* raw_noise, const float* x, const float* resid, const float* out, const float* alpha,
+                           const double* state, float* res, int N, int T, void* stream);
+int volt_kron_epilogue_f64(const double* raw_vol, const double* covar_factor, const double* raw_var,
+                           const double* raw_task_noises, const double* raw_noise, const double* x, const double* resid,
+                           const double* out, const double* alpha, const double* state, double* res, int N, int T,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 the reference's own ``voltron`` surface for that path (voltron/__init__.py:2-11):
 
     from volt_amd.kernels import VolatilityKernel
-    from volt_amd.models import VoltronGP, VoltMagpie, BMGP
+    from volt_amd.models import VoltronGP, VoltMagpie, BMGP, MultitaskBMGP
     from volt_amd.rollout_utils import Rollouts, GeneratePrediction
     from volt_amd.train_utils import TrainVoltMagpieModel, TrainDataModel
 
@@ -13,7 +13,7 @@ CPU fallback.
 __version__ = "0.1"
 
 from .kernels import BMKernel, VolatilityKernel            # noqa: F401
-from .models import BMGP, VoltronGP, VoltMagpie            # noqa: F401
+from .models import BMGP, MultitaskBMGP, VoltronGP, VoltMagpie     # noqa: F401
 from .rollout_utils import Rollouts, GeneratePrediction    # noqa: F401
 from .train_utils import LearnGPCV                        # noqa: F401
 

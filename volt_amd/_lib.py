@@ -58,6 +58,12 @@ _SIGS = {
     "volt_gpcv_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "volt_gpcv_step_f32": (C.c_int, [_ptr, _i64, _i64, _f32] + [_ptr] * 6 + [_i32, _f32, _f32, _f32, _f32] + [_ptr] * 7
                            + [_i32, _i32, _i32, _ptr]),
+    "volt_syev_small_f64": (C.c_int, [_ptr, _i64, _ptr, _ptr, _ptr, _i32, _i32, _ptr]),
+    "volt_kron_state_bytes": (_sz, [_i32]),
+    "volt_kron_prologue_f32": (C.c_int, [_ptr] * 7 + [_i64] + [_ptr] * 4 + [_i32, _i32, _ptr]),
+    "volt_kron_prologue_f64": (C.c_int, [_ptr] * 7 + [_i64] + [_ptr] * 4 + [_i32, _i32, _ptr]),
+    "volt_kron_epilogue_f32": (C.c_int, [_ptr] * 11 + [_i32, _i32, _ptr]),
+    "volt_kron_epilogue_f64": (C.c_int, [_ptr] * 11 + [_i32, _i32, _ptr]),
 }
 
 # measurement / tuning hooks: include/volt_hip_tune.h, not part of the drop-in boundary

@@ -326,6 +326,108 @@ class MultivariateNormal:
             return self.rsample(sample_shape, base_samples)
 
 
+class _KroneckerPrior:
+    """Lazy prior covariance of MultitaskBMGP (training mode): K_x (x) K_t with K_x = vol * M, M = min(x_i, x_k) and
+    K_t = F F' + diag(var) of ``covar_module`` (a MultitaskKernel over a BMKernel).  Element (n, t) of vec Y sits at n*T + t
+    (gpytorch's interleaved order).  ExactMarginalLogLikelihood reads the raw parameters from it (the Kronecker step,
+    _KronMLL); the dense matrix is built only on request."""
+
+    def __init__(self, covar_module, x, M):
+        self.covar_module, self.x, self.M = covar_module, x, M
+
+    def evaluate(self):
+        vol = self.covar_module.data_covar_module.vol.reshape(())
+        Kt = self.covar_module.task_covar_module.covar_matrix.evaluate()
+        return torch.kron(vol * self.M.to(Kt.dtype), Kt)
+
+    to_dense = evaluate
+
+    @property
+    def shape(self):
+        n = self.M.shape[-1] * self.covar_module.num_tasks
+        return torch.Size((n, n))
+
+
+class MultitaskMultivariateNormal:
+    """gpytorch.distributions.MultitaskMultivariateNormal stand-in for MultitaskBMGP (VoltMagpie.py:101-118 take
+    ``.sample()`` / ``.mean`` of it).  ``mean`` is [n, T]; the joint covariance is over vec(mean) in gpytorch's interleaved
+    order (element (n, t) at n*T + t).  Two forms:
+      * a prior (``covariance_matrix`` a _KroneckerPrior or a dense [nT, nT] tensor): what ExactMarginalLogLikelihood takes;
+      * a Kronecker posterior (``blocks=(V, C)``): cov = (I (x) V) blockdiag_j(C_j) (I (x) V'), V [T,T] = D^1/2 Q, C [T,n,n]
+        (MultitaskBMGP.posterior_call).  A draw is mean + (L_j z_j)_j V' with L_j L_j' = C_j (HIP potrf), i.e. the root
+        R[(h,t), (h',j)] = V[t,j] L_j[h,h'].
+    ``base_samples`` (sample_shape + [n, T]): element [..., h, j] is the N(0,1) draw of block j at point h (posterior form);
+    of vec position h*T + j of the dense root (prior form).  The dense ``covariance_matrix`` is built only when asked for."""
+
+    def __init__(self, mean, covariance_matrix=None, blocks=None):
+        self.loc = mean
+        self._covar = covariance_matrix
+        self._blocks = blocks
+        self._root = None
+
+    @property
+    def mean(self):
+        return self.loc
+
+    @property
+    def num_tasks(self):
+        return self.loc.shape[-1]
+
+    @property
+    def event_shape(self):
+        return self.loc.shape
+
+    @property
+    def lazy_covariance_matrix(self):
+        return self._covar
+
+    @property
+    def covariance_matrix(self):
+        if self._blocks is not None:
+            V, C = self._blocks
+            n, T = self.loc.shape
+            return torch.einsum("tj,sj,jhk->htks", V, V, C).reshape(n * T, n * T)
+        return _dense(self._covar)
+
+    @property
+    def variance(self):
+        if self._blocks is not None:
+            V, C = self._blocks
+            return torch.einsum("jh,tj->ht", torch.diagonal(C, dim1=-2, dim2=-1), V * V)
+        return torch.diagonal(self.covariance_matrix).reshape(self.loc.shape)
+
+    def root_blocks(self):
+        """(V [T,T], L [T,n,n]) of the posterior form: L_j L_j' = C_j from the HIP potrf (psd_safe_cholesky's jitter policy)."""
+        if self._blocks is None:
+            raise ValueError("root_blocks: not a Kronecker posterior")
+        if self._root is None:
+            V, C = self._blocks
+            self._root = (V, psd_safe_cholesky(C))
+        return self._root
+
+    def rsample(self, sample_shape=torch.Size(), base_samples=None):
+        n, T = self.loc.shape
+        shape = torch.Size(sample_shape) + self.loc.shape
+        if base_samples is None:
+            base_samples = torch.randn(shape, dtype=self.loc.dtype, device=self.loc.device)
+        if tuple(base_samples.shape[-2:]) != (n, T):
+            raise ValueError(f"base_samples must end in the mean's shape {tuple(self.loc.shape)}")
+        if self._blocks is None:                                  # prior form: the dense root, on the HIP factorisation
+            flat = MultivariateNormal(self.loc.reshape(-1), self.covariance_matrix)
+            return flat.rsample(base_samples=base_samples.reshape(*base_samples.shape[:-2], n * T)).reshape(base_samples.shape)
+        V, L = self.root_blocks()
+        z = base_samples.reshape(-1, n, T).to(torch.float32)
+        S = z.shape[0]
+        lz = ops.gemm_nt(z.permute(2, 0, 1).contiguous(), L.to(torch.float32), uplo_b=1)      # [T,S,n]: (L_j z_j)'
+        lz = lz.permute(1, 2, 0).reshape(S * n, T)
+        out = self.loc + ops.gemm_nt(lz, V.to(torch.float32)).reshape(S, n, T).to(self.loc.dtype)
+        return out.reshape(base_samples.shape)
+
+    def sample(self, sample_shape=torch.Size(), base_samples=None):
+        with torch.no_grad():
+            return self.rsample(sample_shape, base_samples)
+
+
 # --------------------------------------------------------------------------------- likelihood
 class _NoiseCovar(Module):
     def __init__(self, batch_shape):
@@ -368,6 +470,56 @@ class GaussianLikelihood(Module):
         noise = self.noise.reshape(*self.noise.shape[:-1], 1, 1)
         return MultivariateNormal(function_dist.mean, cov + noise * torch.eye(n, dtype=cov.dtype, device=cov.device))
 
+
+
+def _inv_softplus_floor(value, like, floor):
+    value = torch.as_tensor(value, dtype=like.dtype, device=like.device)
+    v = (value - floor).clamp_min(1e-12).expand_as(like)
+    return v + torch.log(-torch.expm1(-v))
+
+
+class MultitaskGaussianLikelihood(Module):
+    """gpytorch.likelihoods.MultitaskGaussianLikelihood(num_tasks, rank=0) stand-in (VoltMagpie.py:51-55 build it beside
+    MultitaskBMGP).  Restated from gpytorch's published behaviour (not executed here; gpytorch is not installed):
+    ``raw_task_noises`` [T] then ``raw_noise`` [1] are registered, both zeros, each through GreaterThan(1e-4), i.e.
+    softplus(raw) + 1e-4; the noise covariance is I_n (x) diag(task_noises + noise).  ``likelihood.noise = v`` sets
+    raw_noise to the constraint's inverse (VoltMagpie.py:54: 1e-3).  Only rank 0 with both noise terms is provided."""
+    NOISE_FLOOR = 1e-4
+
+    def __init__(self, num_tasks, rank=0, batch_shape=torch.Size(), task_prior=None, noise_prior=None, noise_constraint=None,
+                 has_global_noise=True, has_task_noise=True):
+        super().__init__()
+        if rank != 0 or not (has_global_noise and has_task_noise) or task_prior is not None or noise_prior is not None:
+            raise NotImplementedError("MultitaskGaussianLikelihood: rank 0 with task and global noise, no priors, is what "
+                                      "the reference builds; nothing else is provided")
+        self.register_parameter("raw_task_noises", nn.Parameter(torch.zeros(*batch_shape, num_tasks)))
+        self.register_parameter("raw_noise", nn.Parameter(torch.zeros(*batch_shape, 1)))
+        self.num_tasks, self.rank = num_tasks, rank
+
+    @property
+    def noise(self):
+        return F.softplus(self.raw_noise) + self.NOISE_FLOOR
+
+    @noise.setter
+    def noise(self, value):
+        with torch.no_grad():
+            self.raw_noise.copy_(_inv_softplus_floor(value, self.raw_noise, self.NOISE_FLOOR))
+
+    @property
+    def task_noises(self):
+        return F.softplus(self.raw_task_noises) + self.NOISE_FLOOR
+
+    @task_noises.setter
+    def task_noises(self, value):
+        with torch.no_grad():
+            self.raw_task_noises.copy_(_inv_softplus_floor(value, self.raw_task_noises, self.NOISE_FLOOR))
+
+    def forward(self, function_dist):
+        """p(y|f): I_n (x) diag(d) added to the dense covariance (outside the Kronecker MLL only)."""
+        cov = function_dist.covariance_matrix
+        n = function_dist.mean.shape[0]
+        d = (self.task_noises + self.noise).to(cov.dtype)
+        return MultitaskMultivariateNormal(function_dist.mean, cov + torch.diag(d.repeat(n)))
 
 
 # -------------------------------------------------------------------------------------- model
@@ -520,6 +672,52 @@ class _ExactMLL(torch.autograd.Function):
         return gK, gm, g * dsig, -gm, None, gscale
 
 
+class _KronMLL(torch.autograd.Function):
+    """mll = log N(vec Y; vec mu, K_x (x) K_t + I (x) D) / (N T) of MultitaskBMGP and its gradient wrt the five raw
+    parameters, from ONE prologue -> batched step (B = T over the shared M) -> epilogue sequence (ops.kron_mll_step,
+    include/volt_hip.h).  No host read when the check is deferred, so the iteration captures into a hipGraph.
+    Unlike _ExactMLL there is no jitter ladder: gpytorch would add jitter to the NT x NT matrix, which this path never
+    forms; a failed factorisation (each M + sigma_j^2 I has sigma_j^2 = 1 / (vol lambda_j) > 0) raises NotPSDError."""
+
+    @staticmethod
+    def forward(ctx, raw_vol, covar_factor, raw_var, raw_task_noises, raw_noise, x, target, M, holder):
+        params = (raw_vol, covar_factor, raw_var, raw_task_noises, raw_noise)
+        n, T = target.shape
+        ws = holder.kron_workspace(n, T, M.device, M.dtype)
+        res, info, eig_info, _ = ops.kron_mll_step(params, x, target, M, ws)
+        chk = deferred_checks.deferring()
+        eig_bad = eig_info.clamp(max=0)                       # sweeps used >= 0; -1: the eigensolver hit its sweep cap
+        if chk is not None:
+            chk.note(info)
+            chk.note(eig_bad)
+        else:
+            if deferred_checks._active is not None:
+                deferred_checks._active.reserve(info)
+                deferred_checks._active.reserve(eig_bad)
+            nbad, ebad, internal = torch.stack([(info != 0).sum(), (eig_bad != 0).sum(),
+                                                (info <= ops._lib.INFO_INTERNAL_MAX).sum()]).tolist()
+            if ebad:
+                raise ops._lib.VoltHipError("volt_kron_prologue: the eigensolver of the task covariance did not converge")
+            if internal:
+                raise ops._lib.VoltHipError(f"volt_mll_step: internal error, info = {info.tolist()}")
+            if nbad:
+                if not bool(torch.isfinite(target).all()) or not all(bool(torch.isfinite(p).all()) for p in params):
+                    raise NanError("Kronecker MLL: NaN / inf in the targets or the parameters")
+                raise NotPSDError(f"M + sigma_j^2 I not positive definite for {nbad} of {T} eigen-directions")
+        res = res.clone()                                     # the workspace is overwritten by the next forward
+        ctx.save_for_backward(res)
+        ctx.meta = [(p.shape, p.dtype) for p in params]
+        return res[0].to(raw_vol.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        (res,) = ctx.saved_tensors
+        T = (res.numel() - 3) // 3
+        parts = (res[1:2], res[3:3 + T], res[3 + T:3 + 2 * T], res[3 + 2 * T:], res[2:3])
+        grads = tuple((g * p).reshape(shape).to(dt) for p, (shape, dt) in zip(parts, ctx.meta))
+        return (*grads, None, None, None, None)
+
+
 class ExactMarginalLogLikelihood(Module):
     """gpytorch.mlls.ExactMarginalLogLikelihood stand-in: ``mll(model(x), y)`` returns the marginal
     log likelihood divided by the number of data points (a scalar, or [T] for a batched model)."""
@@ -537,7 +735,36 @@ class ExactMarginalLogLikelihood(Module):
             self._ws = ws = ops.MllWorkspace(B, n, want_grad, device, dtype)
         return ws
 
+    def kron_workspace(self, n, T, device, dtype=torch.float32):
+        ws = getattr(self, "_kws", None)
+        if ws is None or not ws.fits(n, T, dtype) or ws.state.device != device:
+            self._kws = ws = ops.KronWorkspace(n, T, device, dtype)
+        return ws
+
+    def _kron_forward(self, function_dist, target):
+        """MultitaskBMGP's prior: the Kronecker step (_KronMLL).  ``target`` has the model's layout, [N, T]."""
+        prior = function_dist.lazy_covariance_matrix
+        if tuple(target.shape) != tuple(function_dist.mean.shape):
+            raise ValueError(f"ExactMarginalLogLikelihood: target {tuple(target.shape)} does not have the multitask mean's "
+                             f"shape {tuple(function_dist.mean.shape)} ([N, T], the layout the model was built with)")
+        if not prior.M.is_cuda or not target.is_cuda:
+            raise ops._lib.VoltHipError("ExactMarginalLogLikelihood: tensors must live on the MI355X; no CPU fallback")
+        task, data = prior.covar_module.task_covar_module, prior.covar_module.data_covar_module
+        lh = self.likelihood
+        params = (data.raw_vol, task.covar_factor, task.raw_var, lh.raw_task_noises, lh.raw_noise)
+        f64 = any(t.dtype == torch.float64 for t in (prior.x, target, *params))
+        dt = torch.float64 if f64 else torch.float32           # torch's promotion of the reference's own arithmetic
+        res = _KronMLL.apply(*params, prior.x, target.to(dt), prior.M.to(dt), self)
+        num_data = target.numel()                              # gpytorch: the MultitaskMultivariateNormal's event size
+        priors = self.model.named_priors() if isinstance(self.model, Module) else ()
+        for _, module, prior_, closure in priors:
+            res = res + prior_.log_prob(closure(module)).sum() / num_data
+        return res
+
     def forward(self, function_dist, target):
+        if isinstance(function_dist, MultitaskMultivariateNormal) and isinstance(function_dist.lazy_covariance_matrix,
+                                                                                 _KroneckerPrior):
+            return self._kron_forward(function_dist, target)
         mean = function_dist.mean
         lazy = function_dist.lazy_covariance_matrix
         scale = None

@@ -37,6 +37,8 @@ def _baseline_kernel(name):
 
 
 def build() -> types.ModuleType:
+    from .kernels.MultitaskKernel import IndexKernel, MultitaskKernel
+
     def mod(name, **attrs):
         m = types.ModuleType(name)
         m.__dict__.update(attrs)
@@ -48,11 +50,14 @@ def build() -> types.ModuleType:
     utils = mod("gpytorch.utils", cholesky=cholesky, errors=errors, warnings=warns)
     subs = {
         "means": mod("gpytorch.means", Mean=gp.Mean, ConstantMean=gp.ConstantMean, LinearMean=gp.LinearMean),
-        "kernels": mod("gpytorch.kernels", Kernel=gp.Kernel, __getattr__=_baseline_kernel),
-        "likelihoods": mod("gpytorch.likelihoods", GaussianLikelihood=gp.GaussianLikelihood),
+        "kernels": mod("gpytorch.kernels", Kernel=gp.Kernel, IndexKernel=IndexKernel, MultitaskKernel=MultitaskKernel,
+                       __getattr__=_baseline_kernel),
+        "likelihoods": mod("gpytorch.likelihoods", GaussianLikelihood=gp.GaussianLikelihood,
+                           MultitaskGaussianLikelihood=gp.MultitaskGaussianLikelihood),
         "mlls": mod("gpytorch.mlls", ExactMarginalLogLikelihood=gp.ExactMarginalLogLikelihood,
                     VariationalELBO=variational.VariationalELBO),
-        "distributions": mod("gpytorch.distributions", MultivariateNormal=gp.MultivariateNormal),
+        "distributions": mod("gpytorch.distributions", MultivariateNormal=gp.MultivariateNormal,
+                             MultitaskMultivariateNormal=gp.MultitaskMultivariateNormal),
         "models": mod("gpytorch.models", ExactGP=gp.ExactGP),
         "priors": mod("gpytorch.priors", NormalPrior=gp.NormalPrior),
         "settings": mod("gpytorch.settings", num_gauss_hermite_locs=variational.num_gauss_hermite_locs,

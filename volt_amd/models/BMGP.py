@@ -4,7 +4,8 @@ SURVEY 8(f) row 1: it supplies ``pred_vol`` at voltron/rollout_utils.py:66 throu
 ``model.vol_model(test_x).sample(...)``.  Training-mode call -> prior MVN (for an MLL); eval-mode
 call -> exact-GP posterior at the test points, computed with the same HIP Cholesky / triangular
 inverse as the data model (K_s^-1 = Y Y^T, Y = L^-T), the products on the library's own MFMA GEMM (ops.gemm_nt).
-The botorch-based MultitaskBMGP (:30-56) is out of scope.
+MultitaskBMGP (:30-56, botorch's KroneckerMultiTaskGP) is below: the vol forecaster of the batched models when they are
+built with ``multitask_vol=True``; its MLL runs on the Kronecker step (gp._KronMLL, csrc/kron.hip).
 
 Addition: ``train_y`` [T,N] builds T independent vol models over shared inputs in one object (batched kernel
 parameter, noise and posterior) -- what the batched forecast driver trains instead of looping over tickers.
@@ -12,9 +13,10 @@ parameter, noise and posterior) -- what the batched forecast driver trains inste
 import torch
 
 from .. import ops
-from ..gp import ExactGP, MultivariateNormal, _safe_factor
+from ..gp import ExactGP, MultitaskMultivariateNormal, MultivariateNormal, _KroneckerPrior, _safe_factor, same_values
 from ..kernels.BMKernel import BMKernel
 from ..kernels.FBMKernel import FBMKernel
+from ..kernels.MultitaskKernel import MultitaskKernel
 
 
 class BMGP(ExactGP):
@@ -58,3 +60,83 @@ class BMGP(ExactGP):
             if not batched:
                 mean, cov = mean[0], cov[0]
             return MultivariateNormal(mean, cov)
+
+
+class MultitaskBMGP(ExactGP):
+    """voltron/models/BMGP.py:30-56: train_x [N], train_y [N,T], a MultitaskGaussianLikelihood(T).  Covariance
+    K_x (x) K_t (MultitaskKernel(BMKernel(), T), rank-1 IndexKernel), element (n, t) at n*T + t; mean
+    mu[n,t] = -1/2 vol^2 x_n K_t[t,t] -- inter-task correlation left out of the mean on purpose, as the reference's comment
+    says (:44-49).
+
+    The reference subclasses botorch's KroneckerMultiTaskGP and then replaces its covariance module and deletes its mean
+    module; what is left of botorch is ExactGP's plumbing.  Restated from botorch's published (2022-era, unpinned in
+    setup.py) behaviour, not executed here: the inputs are stored as [N,1], the targets as [N,T], no outcome transform, no
+    priors remain (botorch's own modules, which carried them, are replaced).  Parameters, in registration order:
+    likelihood.raw_task_noises [T], likelihood.raw_noise [1], covar_module.task_covar_module.covar_factor [T,1],
+    .task_covar_module.raw_var [T], covar_module.data_covar_module.raw_vol [1].
+
+    Initial values: botorch builds (and the reference discards) modules of its own first, and those draw from the
+    generator, so the reference's draws cannot be reproduced.  Here ``covar_factor = randn(T,1)`` then ``raw_var =
+    randn(T)`` from torch's default generator, in that order; then, as in the reference (:38-40), ``covar_factor /= 10``
+    while ``task_covar_module.var.data /= 10.`` divides a computed temporary and changes nothing."""
+
+    def __init__(self, train_x, train_y, likelihood, base_mean=None, **kwargs):
+        super().__init__(train_x, train_y, likelihood)
+        if train_y.ndim != 2:
+            raise ValueError("MultitaskBMGP: train_y must be [N, T]")
+        ops._check_tasks(train_y.shape[-1])
+        self.covar_module = MultitaskKernel(BMKernel(), num_tasks=train_y.shape[-1], **kwargs).to(train_x.device)
+        self.covar_module.task_covar_module.var.data /= 10.              # a computed property: no effect (BMGP.py:39)
+        self.covar_module.task_covar_module.covar_factor.data /= 10.
+        x = train_x.reshape(-1)
+        self._base = torch.minimum(x.unsqueeze(-1), x.unsqueeze(-2))      # M = min(x_i, x_k): K_x = vol M, filled once
+        self._post_ws = None
+
+    def mean_module(self, x):
+        if x.ndim == 1:
+            x = x.unsqueeze(-1)
+        scaled_mean = -0.5 * self.covar_module.data_covar_module.vol.pow(2.0) * x.repeat(1, self.covar_module.num_tasks)
+        return scaled_mean * self.covar_module.task_covar_module.covar_matrix.evaluate().diag()
+
+    def forward(self, x):
+        xs = x[..., 0] if x.ndim > 1 else x
+        if same_values(x, self.train_inputs[0]):
+            M = self._base
+        else:
+            M = torch.minimum(xs.unsqueeze(-1), xs.unsqueeze(-2))
+        return MultitaskMultivariateNormal(self.mean_module(xs), _KroneckerPrior(self.covar_module, xs, M))
+
+    def posterior_call(self, x):
+        """Exact latent posterior at x [H] (gpytorch's eval-mode ExactGP call): a MultitaskMultivariateNormal with mean [H,T].
+        Block by block in the eigenbasis of the task covariance: the prologue (fp64) gives W, Lambda and
+        r_j; then per block m~_j = sqrt(kappa_j) M_*x (M + sigma_j^2 I)^-1 r_j and C_j = kappa_j [M_** - M_*x (M +
+        sigma_j^2 I)^-1 M_x*] on the HIP potrf / triangular inverse / GEMM, as BMGP.posterior_call does; finally
+        mean = mu_* + m~ V' and cov = (I (x) V) blockdiag(C_j) (I (x) V'), V = D^1/2 Q."""
+        with torch.no_grad():
+            xt = self.train_inputs[0][:, 0]
+            Y = self.train_targets
+            n, T = Y.shape
+            xs = x[..., 0] if x.ndim > 1 else x
+            H = xs.shape[0]
+            dev = xt.device
+            if self._post_ws is None or self._post_ws.state.device != dev:
+                self._post_ws = ops.KronWorkspace(n, T, dev, torch.float64)
+            ws = self._post_ws
+            task, data = self.covar_module.task_covar_module, self.covar_module.data_covar_module
+            params = (data.raw_vol, task.covar_factor, task.raw_var, self.likelihood.raw_task_noises, self.likelihood.raw_noise)
+            ops.kron_prologue(params, xt, Y, ws)
+            kap = (ws.state[0] * ws.lam()).to(torch.float32)                               # [T]
+            M = self._base.to(torch.float32)
+            A = M.unsqueeze(0) + ws.sigma2.to(torch.float32).reshape(T, 1, 1) * torch.eye(n, device=dev)
+            f, _ = _safe_factor(A)
+            Linv = ops.trtri(f).mT.contiguous()                                            # L_j^-1
+            xs32, xt32 = xs.to(torch.float32), xt.to(torch.float32)
+            Mst = torch.minimum(xs32.unsqueeze(-1), xt32.unsqueeze(-2)).expand(T, H, n).contiguous()
+            G = ops.gemm_nt(Mst, Linv, uplo_b=1)                                           # M_*x L^-T
+            w = ops.gemm_nt(ws.resid.to(torch.float32).reshape(T, 1, n), Linv, uplo_b=1)   # (L^-1 r)'
+            mt = kap.sqrt().reshape(T, 1) * ops.gemm_nt(G, w).reshape(T, H)               # m~_j
+            Mss = torch.minimum(xs32.unsqueeze(-1), xs32.unsqueeze(-2))
+            C = kap.reshape(T, 1, 1) * (Mss.unsqueeze(0) - ops.gemm_nt(G, G))
+            V = (ws.d().sqrt().unsqueeze(-1) * ws.Q()).to(torch.float32)                   # D^1/2 Q
+            mean = self.mean_module(xs).to(torch.float32) + ops.gemm_nt(mt.t().contiguous(), V)
+            return MultitaskMultivariateNormal(mean, blocks=(V, C))

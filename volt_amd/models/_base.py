@@ -4,15 +4,19 @@ training step, plus a Brownian-motion GP over the log-vol path that forecasts it
 (rollout_utils.py:7-32,81-86 and train_utils.py:222-224 read and write them); the subclasses only choose the mean."""
 import torch
 
-from ..gp import ExactGP, ExactMarginalLogLikelihood, GaussianLikelihood, MultivariateNormal, same_values
+from ..gp import (ExactGP, ExactMarginalLogLikelihood, GaussianLikelihood, MultitaskGaussianLikelihood, MultivariateNormal,
+                  same_values)
 from ..kernels import VolatilityKernel
-from .BMGP import BMGP
+from .BMGP import BMGP, MultitaskBMGP
 
 
 class VolGP(ExactGP):
-    def _init_vol_state(self, x, y, vol_path):
+    def _init_vol_state(self, x, y, vol_path, multitask_vol=False):
         """x [N], y [N] or [T,N] (batched layout: one shared input grid, T target / vol rows), vol_path like y or None.
-        Call after ``mean_module`` is set so that the modules register in the reference's order."""
+        Call after ``mean_module`` is set so that the modules register in the reference's order.  ``multitask_vol`` (batched
+        models only): the reference's own vol forecaster, a MultitaskBMGP over the [N,T] log-vol paths with a
+        MultitaskGaussianLikelihood(T) at noise 1e-3 (VoltMagpie.py:51-55) -- the T forecasts are then jointly drawn and
+        correlated; without it T independent BM-GPs (the batched BMGP)."""
         dev = x.device
         batch_shape = y.shape[:-1]
         self.covar_module = VolatilityKernel().to(dev)
@@ -20,9 +24,16 @@ class VolGP(ExactGP):
         self.train_y = y
         self.log_vol_path = vol_path.log() if vol_path is not None else -torch.ones(x.shape[0], device=dev)
         self.train_cov = self.covar_module(self.train_x.unsqueeze(-1), self.log_vol_path.exp().unsqueeze(-1)).detach()
-        # vol forecaster: one BM-GP per series.  (The reference's batched models use botorch's Kronecker multitask GP
-        # there, out of scope; the batched BMGP -- T independent vol models over the shared grid -- takes its place,
-        # so SamplePrediction / MeanPrediction work on batched models too.)
+        # vol forecaster: one BM-GP per series by default.  (The reference's batched models use botorch's Kronecker multitask
+        # GP there: MultitaskBMGP, opt-in with multitask_vol=True; the default batched BMGP -- T independent vol models over
+        # the shared grid -- leaves out the cross-series correlation.)
+        if multitask_vol:
+            if not len(batch_shape) or self.log_vol_path.shape[:-1] != batch_shape:
+                raise ValueError("multitask_vol=True needs a batched model with a [T,N] vol_path")
+            self.vol_lh = MultitaskGaussianLikelihood(num_tasks=batch_shape[0]).to(dev)
+            self.vol_lh.noise = 1e-3
+            self.vol_model = MultitaskBMGP(x, self.log_vol_path.t(), self.vol_lh)   # [N] inputs, [N,T] targets
+            return
         self.vol_lh = GaussianLikelihood(batch_shape=batch_shape).to(dev)
         self.vol_model = BMGP(x, self.log_vol_path, self.vol_lh) if self.log_vol_path.shape[:-1] == batch_shape else None
 
@@ -33,6 +44,10 @@ class VolGP(ExactGP):
 
     def VolMLL(self):
         vol_mll = ExactMarginalLogLikelihood(self.vol_lh, self.vol_model)
+        if isinstance(self.vol_model, MultitaskBMGP):
+            # the reference passes the [T,N] inputs and targets (VoltMagpie.py:62-65) to a model built on [N] / [N,T]; the
+            # layouts the model was built with are passed here
+            return vol_mll(self.vol_model(self.vol_model.train_inputs[0]), self.log_vol_path.t())
         return vol_mll(self.vol_model(self.train_x), self.log_vol_path)
 
     def GeneratePrediction(self, test_x, pred_vol, n_sample=1):
@@ -43,13 +58,17 @@ class VolGP(ExactGP):
         prediction = self.GeneratePrediction(test_x, pred_vol, n_sample)
         return (prediction, pred_vol) if return_vol else prediction
 
+    def _vol_layout(self, v):
+        # a MultitaskBMGP forecasts [H,T]: the reference transposes to [T,H] (VoltMagpie.py:103,113)
+        return v.transpose(-1, -2) if isinstance(self.vol_model, MultitaskBMGP) else v
+
     def SamplePrediction(self, test_x, n_sample=1, return_vol=False):
         self.vol_model.eval()
-        return self._predict_with(self.vol_model(test_x).sample().exp(), test_x, n_sample, return_vol)
+        return self._predict_with(self._vol_layout(self.vol_model(test_x).sample().exp()), test_x, n_sample, return_vol)
 
     def MeanPrediction(self, test_x, n_sample=1, return_vol=False):
         self.vol_model.eval()
-        return self._predict_with(self.vol_model(test_x).mean.exp(), test_x, n_sample, return_vol)
+        return self._predict_with(self._vol_layout(self.vol_model(test_x).mean.exp()), test_x, n_sample, return_vol)
 
     def forward(self, x):
         mean_x = self.mean_module(x)

@@ -368,3 +368,130 @@ def mll_grad_k(ws: MllWorkspace) -> torch.Tensor:
     _lib.check(_lib.lib().volt_mll_grad_k_f32(ws.ptr, ws.alpha.data_ptr(), scratch.data_ptr(), gK.data_ptr(), B, n,
                                               _lib.stream_ptr()), "volt_mll_grad_k")
     return gK
+
+
+# ------------------------------------------------------------------ Kronecker multi-task vol forecaster (MultitaskBMGP)
+KRON_T_MAX = 64                     # include/volt_hip.h: volt_syev_small_f64 / volt_kron_*: T <= 64
+# The T steps of one Kronecker iteration all factor M + sigma_j^2 I over the SAME M: it is handed to the step with batch
+# stride 0 (no [T,N,N] copy) -- the step only reads K, and tests/test_gpu_multitask.py checks that this gives bitwise the
+# result of T materialised copies.
+KRON_SHARED_K = True
+
+
+def _check_tasks(T: int):
+    if T < 1 or T > KRON_T_MAX:
+        raise ValueError(f"the Kronecker multi-task path takes 1 <= T <= {KRON_T_MAX} tasks (got T = {T})")
+
+
+def syev_small(S: torch.Tensor):
+    """Eigendecomposition of symmetric [B,T,T] (or [T,T]) fp64 matrices, T <= 64 (volt_syev_small_f64: parallel cyclic
+    Jacobi, one workgroup per matrix).  Returns (lam [B,T] ascending, Q [B,T,T] with the eigenvectors as columns, info [B]
+    = sweeps used, -1 if the sweep cap was hit)."""
+    _need_gpu(S)
+    two_d = S.ndim == 2
+    S3 = (S.unsqueeze(0) if two_d else S).to(torch.float64).contiguous()
+    B, T = S3.shape[0], S3.shape[-1]
+    _check_tasks(T)
+    lam = torch.empty(B, T, dtype=torch.float64, device=S.device)
+    Q = torch.empty(B, T, T, dtype=torch.float64, device=S.device)
+    info = torch.empty(B, dtype=torch.int32, device=S.device)
+    _lib.check(_lib.lib().volt_syev_small_f64(S3.data_ptr(), T * T, lam.data_ptr(), Q.data_ptr(), info.data_ptr(), B, T,
+                                              _lib.stream_ptr()), "volt_syev_small_f64")
+    return (lam[0], Q[0], info[0]) if two_d else (lam, Q, info)
+
+
+class KronWorkspace:
+    """Caller-owned buffers of one Kronecker MLL iteration of shape (N, T, dtype): the prologue's state (fp64: vol, Lambda,
+    d, W, Q), the step's inputs (resid [T,N], sigma2 [T]) and workspace (B = T, with gradient), the eigensolver's info
+    and the epilogue's packed result res [3 + 3T]."""
+
+    def __init__(self, N: int, T: int, device, dtype=torch.float32):
+        _check_tasks(T)
+        self.N, self.T, self.dtype = N, T, dtype
+        L = _lib.lib()
+        self.state = torch.zeros(int(L.volt_kron_state_bytes(T)) // 8, dtype=torch.float64, device=device)
+        self.resid = torch.empty(T, N, dtype=dtype, device=device)
+        self.sigma2 = torch.empty(T, dtype=dtype, device=device)
+        self.eig_info = torch.zeros(1, dtype=torch.int32, device=device)
+        self.res = torch.empty(3 + 3 * T, dtype=dtype, device=device)
+        self.mll = MllWorkspace(T, N, True, device, dtype)
+        self._K = None
+
+    def fits(self, N, T, dtype):
+        return self.N == N and self.T == T and self.dtype == dtype
+
+    def shared_k(self, M: torch.Tensor) -> torch.Tensor:
+        """M as the step's [T,N,N] operand: batch stride 0 (KRON_SHARED_K), or T copies made once per M."""
+        if KRON_SHARED_K:
+            return M.expand(self.T, self.N, self.N)
+        if self._K is None or self._K[0] is not M:
+            self._K = (M, M.expand(self.T, self.N, self.N).contiguous())
+        return self._K[1]
+
+    # views of the state (include/volt_hip.h: vol, Lambda [T], d [T], W [T,T], Q [T,T])
+    def lam(self):
+        return self.state[8: 8 + self.T]
+
+    def d(self):
+        return self.state[8 + self.T: 8 + 2 * self.T]
+
+    def W(self):
+        T = self.T
+        return self.state[8 + 2 * T: 8 + 2 * T + T * T].view(T, T)
+
+    def Q(self):
+        T = self.T
+        return self.state[8 + 2 * T + T * T: 8 + 2 * T + 2 * T * T].view(T, T)
+
+
+def _kron_params(params, dt):
+    out = []
+    for p in params:
+        p = p.detach().reshape(-1)
+        out.append(p if p.dtype == dt and p.is_contiguous() else p.to(dt).contiguous())
+    return out
+
+
+def kron_prologue(params, x: torch.Tensor, Y: torch.Tensor, ws: KronWorkspace):
+    """volt_kron_prologue_*: params = (raw_vol [1], covar_factor [T,1], raw_var [T], raw_task_noises [T], raw_noise [1]),
+    x [N], Y [N,T] -> ws.resid, ws.sigma2, ws.state, ws.eig_info."""
+    _need_gpu(x, Y, *params)
+    dt = ws.dtype
+    rv, cf, var, rtn, rn = _kron_params(params, dt)
+    x = x.reshape(-1).to(dt).contiguous()
+    Y = Y.to(dt)
+    if Y.stride(-1) != 1:
+        Y = Y.contiguous()
+    N, T = ws.N, ws.T
+    if tuple(Y.shape) != (N, T) or x.numel() != N or cf.numel() != T:
+        raise ValueError(f"kron_prologue: x [N], Y [N,T] and covar_factor [T,1] must agree with the workspace (N={N}, T={T})")
+    fn = _lib.lib().volt_kron_prologue_f32 if dt == torch.float32 else _lib.lib().volt_kron_prologue_f64
+    _lib.check(fn(rv.data_ptr(), cf.data_ptr(), var.data_ptr(), rtn.data_ptr(), rn.data_ptr(), x.data_ptr(), Y.data_ptr(),
+                  Y.stride(0), ws.resid.data_ptr(), ws.sigma2.data_ptr(), ws.state.data_ptr(), ws.eig_info.data_ptr(), N, T,
+                  _lib.stream_ptr()), "volt_kron_prologue")
+    return ws
+
+
+def kron_mll_step(params, x: torch.Tensor, Y: torch.Tensor, M: torch.Tensor, ws: KronWorkspace | None = None):
+    """One Kronecker MLL + gradient evaluation: prologue -> the existing batched step (B = T, K = M, sigma2 = 1 / kappa)
+    -> epilogue.  params as for `kron_prologue`; M [N,N] = min(x_i, x_k) in the step's dtype (fp32 or fp64).  Returns
+    (res [3 + 3T], step info [T], eigensolver info [1], ws); res = mll, d/d raw_vol, d/d raw_noise, d/d covar_factor [T],
+    d/d raw_var [T], d/d raw_task_noises [T] (include/volt_hip.h)."""
+    _need_gpu(x, Y, M, *params)
+    dt = torch.float64 if M.dtype == torch.float64 else torch.float32
+    N, T = Y.shape
+    _check_tasks(T)
+    if ws is None or not ws.fits(N, T, dt) or ws.state.device != M.device:
+        ws = KronWorkspace(N, T, M.device, dt)
+    M = M.to(dt)
+    if M.stride(-1) != 1:
+        M = M.contiguous()
+    kron_prologue(params, x, Y, ws)
+    out, alpha, info = mll_step(ws.shared_k(M), ws.resid, ws.sigma2, ws.mll, want_grad=True)
+    rv, cf, var, rtn, rn = _kron_params(params, dt)
+    xd = x.reshape(-1).to(dt).contiguous()
+    fn = _lib.lib().volt_kron_epilogue_f32 if dt == torch.float32 else _lib.lib().volt_kron_epilogue_f64
+    _lib.check(fn(rv.data_ptr(), cf.data_ptr(), var.data_ptr(), rtn.data_ptr(), rn.data_ptr(), xd.data_ptr(),
+                  ws.resid.data_ptr(), out.data_ptr(), alpha.data_ptr(), ws.state.data_ptr(), ws.res.data_ptr(), N, T,
+                  _lib.stream_ptr()), "volt_kron_epilogue")
+    return ws.res, info, ws.eig_info, ws
