@@ -284,6 +284,39 @@ int volt_gpcv_step_f32(const float* K, int64_t ldk, int64_t bsk, float jitter, c
                        float min_scale, float w_ell, float w_kl, float* out, float* grad_m, float* grad_mu,
                        float* grad_Lq, float* grad_K, int* info, void* workspace, int B, int N, int ws_flags, void* stream);
 
+/* ---- Multi-task GPCV  (MultitaskVariationalGP, voltron/models/multi_task_variational_gp.py:11-146; the trainer is this
+ * library's: the reference has none) ------------------------------------------------------------------------------------
+ * One ELBO + gradient evaluation of the Kronecker variational GP over T <= 64 series that share the N inducing points
+ * (= the inputs).  Element (n,t) of vec F at n*T + t.
+ *     q(F) = N(M, S_x (x) S_t),  S_x = Lx Lx', S_t = Lt Lt'  (Lx [N,N], Lt [T,T]: the parts above the diagonals are ignored)
+ *     p(F) = N(mu, (K + jitter I) (x) K_t),  mu[n,t] = c[t],  K_t = f f' + diag(softplus(raw_var)),  f = covar_factor [T]
+ *     ell  = sum_nt sum_k w_k log N(y_nt; 0, max(exp(M_nt + sqrt(2 var_nt) x_k), min_scale)),
+ *            var_nt = max((sum_k Lx_nk^2)(sum_s Lt_ts^2), min_var)
+ *     KL   = 1/2 [tau_x tau_t + q - N T + T logdet K + N logdet K_t - T logdet S_x - N logdet S_t],
+ *            tau_x = tr(K^-1 S_x), tau_t = tr(K_t^-1 S_t), A = K^-1 (M - mu), q = tr(K_t^-1 (M - mu)'A)
+ *     F    = w_ell ell - w_kl KL      (VariationalELBO over the [N,T] event: w_ell = 1/N, w_kl = beta/num_data)
+ * K [N,N] (ldk) without jitter; M, y [N,T], Lx [N,N], Lt [T,T] contiguous; c, covar_factor, raw_var [T];
+ * gh_x, gh_w [Q] Gauss-Hermite nodes and weights / sqrt(pi).
+ *     out[0..15] = ell, KL, q, logdet K, logdet K_t, logdet S_x, logdet S_t, tau_x, tau_t, tr K^-1, |K^-1 Lx|_F^2,
+ *                  tr(K_t^-1 A'A), F, jitter, 0, 0
+ *     grad_M [N,T], grad_c [T], grad_Lx [N,N], grad_Lt [T,T], grad_covar_factor [T], grad_raw_var [T]: gradients of F;
+ *     grad_K [N,N] (nullable) = dF/dK.
+ * K + jitter I is factored ONCE (volt_mll_step_f32 at B = 1); the T solves are two NT products with the T rows in one
+ * 128-row tile.  No host synchronisation, no allocation, every reduction in a fixed order (bitwise repeatable); the launch
+ * sequence replays from a hipGraph on one stream.
+ * info[0]: LAPACK-style for K + jitter I (or an internal error of the factorisation, as for volt_mll_step_f32);
+ * info[1]: 0, or the 1-based index of the first non-positive pivot of K_t;  info[2]: 1 if F came out non-finite (NaN or
+ * inf in the inputs, or a failed factorisation), else 0.  info holds 3 ints.
+ * workspace: volt_gpcv_mt_workspace_bytes(N, T, want_dk) bytes (0 if T is out of range), 256-byte aligned; it begins with
+ * an MLL workspace for (B = 1, N, want_grad = 1): volt_mll_workspace_init_f32 + VOLT_WS_INITIALISED in ws_flags as there. */
+size_t volt_gpcv_mt_workspace_bytes(int N, int T, int want_dk);
+int volt_gpcv_mt_step_f32(const float* K, int64_t ldk, float jitter, const float* M, const float* c, const float* Lx,
+                          const float* Lt, const float* covar_factor, const float* raw_var, const float* y,
+                          const float* gh_x, const float* gh_w, int Q, float min_var, float min_scale, float w_ell,
+                          float w_kl, float* out, float* grad_M, float* grad_c, float* grad_Lx, float* grad_Lt,
+                          float* grad_covar_factor, float* grad_raw_var, float* grad_K, int* info, void* workspace, int N,
+                          int T, int ws_flags, void* stream);
+
 /* ---- Kronecker multi-task vol forecaster  (MultitaskBMGP, voltron/models/BMGP.py:30-56: botorch KroneckerMultiTaskGP with
  * MultitaskKernel(BMKernel(), T) and MultitaskGaussianLikelihood(T); built by the batched constructors VoltMagpie.py:51-55,
  * VoltronGP.py:46-50, Volt.py:67-71, trained through ExactMarginalLogLikelihood + loss.backward()).

@@ -11,6 +11,7 @@
 // The factorisation, Y = L^-T, beta, tr K^-1 and logdet K come from the exact-GP step (mll.hip); what is new
 // here is a batched structured "NT" GEMM on the same 128x128 MFMA core for T' = Lq' L^-T and G = Y T'.
 #include "common.h"
+#include "gpcv_shared.h"
 #include "../../include/volt_hip.h"
 #include <math.h>
 
@@ -41,19 +42,7 @@ __global__ __launch_bounds__(256) void transpose_tri_kernel(const float* __restr
     }
 }
 
-// C[b] tile (tm, tn) = alpha * A[b][tm, :] B[b][tn, :]^T + beta * C, K restricted by the operands' triangles:
-// s = 0 dense, 1 lower (k-block <= row-block), 2 upper (k-block >= row-block).  sc: 0 every tile, 1 only
-// tn <= tm, 2 only tn >= tm (other tiles are not touched).  frob (nullable) [B, mt*nt] receives each
-// tile's sum of squares (0 for skipped tiles).  All dimensions are multiples of 128.
-struct GemmArgs {
-    const float *A, *B;
-    float* C;
-    int64_t lda, bsa, ldb, bsb, ldc, bsc;
-    int mt, nt, kt, sa, sb, sc;
-    float alpha, beta;
-    float* frob;
-};
-
+// The structured NT GEMM; GemmArgs and the meaning of its flags: gpcv_shared.h
 __global__ __launch_bounds__(NT, 2) void gemm_nt_struct_kernel(GemmArgs g, int nbatch) {
     __shared__ __attribute__((aligned(16))) float smem[2 * STAGE_FLOATS];
     int tile, b;
@@ -98,8 +87,15 @@ __global__ __launch_bounds__(NT, 2) void gemm_nt_struct_kernel(GemmArgs g, int n
     }
 }
 
-static int launch_gemm(const GemmArgs& g, int B, hipStream_t s) {
+int launch_gemm(const GemmArgs& g, int B, hipStream_t s) {
     hipLaunchKernelGGL(gemm_nt_struct_kernel, dim3(g.mt * g.nt * B), dim3(NT), 0, s, g, B);
+    VOLT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_transpose_tri(const float* src, int64_t lds, int64_t bss, float* dst, int N, int Np, int keep, int B,
+                         hipStream_t s) {
+    hipLaunchKernelGGL(transpose_tri_kernel, dim3(Np / 32, Np / 32, B), dim3(256), 0, s, src, lds, bss, dst, N, Np, keep);
     VOLT_LAUNCH_CHECK();
     return 0;
 }
@@ -280,8 +276,6 @@ static GpcvWs carve_gpcv(void* base, int B, int N, int want_dk) {
 }  // namespace volt
 
 using namespace volt;
-
-const float* volt_internal_mll_y(void* workspace, int B, int N);      // mll.hip
 
 extern "C" {
 

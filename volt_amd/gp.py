@@ -282,6 +282,24 @@ class LinearMean(Mean):
         return res
 
 
+class MultitaskMean(Mean):
+    """gpytorch.means.MultitaskMean(base_means, num_tasks): one mean per task, stacked on a trailing task axis ([N,T]).
+    A single base mean is deep-copied ``num_tasks - 1`` times (parameters ``base_means.<t>.*``), as gpytorch does."""
+
+    def __init__(self, base_means, num_tasks):
+        super().__init__()
+        if isinstance(base_means, Mean):
+            import copy
+            base_means = [base_means] + [copy.deepcopy(base_means) for _ in range(num_tasks - 1)]
+        if len(base_means) != num_tasks:
+            raise RuntimeError("MultitaskMean: one base mean, or one per task")
+        self.base_means = nn.ModuleList(base_means)
+        self.num_tasks = num_tasks
+
+    def forward(self, x):
+        return torch.cat([m(x).unsqueeze(-1) for m in self.base_means], dim=-1)
+
+
 class MultivariateNormal:
     """gpytorch.distributions.MultivariateNormal stand-in (VoltMagpie.py:127)."""
 

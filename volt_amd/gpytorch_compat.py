@@ -49,7 +49,8 @@ def build() -> types.ModuleType:
     warns = mod("gpytorch.utils.warnings", NumericalWarning=gp.NumericalWarning)
     utils = mod("gpytorch.utils", cholesky=cholesky, errors=errors, warnings=warns)
     subs = {
-        "means": mod("gpytorch.means", Mean=gp.Mean, ConstantMean=gp.ConstantMean, LinearMean=gp.LinearMean),
+        "means": mod("gpytorch.means", Mean=gp.Mean, ConstantMean=gp.ConstantMean, LinearMean=gp.LinearMean,
+                     MultitaskMean=gp.MultitaskMean),
         "kernels": mod("gpytorch.kernels", Kernel=gp.Kernel, IndexKernel=IndexKernel, MultitaskKernel=MultitaskKernel,
                        __getattr__=_baseline_kernel),
         "likelihoods": mod("gpytorch.likelihoods", GaussianLikelihood=gp.GaussianLikelihood,

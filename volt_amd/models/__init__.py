@@ -2,6 +2,7 @@ from .BMGP import BMGP, MultitaskBMGP                    # voltron/models/__init
 from .VoltronGP import VoltronGP
 from .single_task_variational_gp import SingleTaskVariationalGP
 from .VoltMagpie import VoltMagpie
+from .multi_task_variational_gp import MultitaskVariationalGP
 
 
 def __getattr__(name):                                   # MaternGP / SMGP (voltron/models/__init__.py:5): out of scope, but

@@ -1,0 +1,122 @@
+"""MultitaskVariationalGP, voltron/models/multi_task_variational_gp.py:11-146 -- the joint GPCV model of T series that
+share one time grid: q(F) = N(M, S_x (x) S_t) against the Kronecker prior N(mu, K_x (x) K_t), inducing points fixed at
+the inputs.  Parameter names, shapes, registration order and start values are the reference's; the ELBO and all of its
+gradients come from ONE HIP step (volt_gpcv_mt_step_f32) that factors K_x once for all T series.
+
+Stated differences from the reference file (README, quirk table):
+* ``model(x)`` is defined at the inducing points only, where the reference's three-term covariance (:113-146) collapses
+  to S_x (x) S_t and its mean to M (K_uu^-1 K_ux = I); anything else raises NotImplementedError.
+* the prior's data block carries the single-task path's jitter 1e-3 (variational.PRIOR_JITTER); the reference adds none
+  (:95-111) and leans on gpytorch's jitter ladder when x[0] = 0 makes K_x[0,0] = 0.
+* only param="exp", rank=1, fp32.
+The reference has no trainer for this class; train_utils.FitGPCVMultitask is LearnGPCV's loop over it.  gpytorch is not
+installed here, so none of this is pinned by executing the reference's class."""
+import torch
+from torch import nn
+
+from .. import ops
+from ..gp import ConstantMean, EqualMemo, Module, MultitaskMean, _dense, _safe_factor
+from ..kernels.MultitaskKernel import IndexKernel
+from ..variational import MIN_VARIANCE, PRIOR_JITTER, MultitaskVariationalLatent, _gauss_hermite
+
+
+class MultitaskVariationalGP(Module):
+    def __init__(self, inducing_points, num_tasks, covar_module=None, rank=1, **kwargs):
+        super().__init__()
+        if rank != 1:
+            raise NotImplementedError("MultitaskVariationalGP: only the rank-1 IndexKernel has an accelerated ELBO")
+        if covar_module is None:
+            raise NotImplementedError("pass covar_module (BMKernel / FBMKernel): the data kernel of the Kronecker prior")
+        ops._check_tasks(num_tasks)
+        n = inducing_points.shape[-1]
+        # registration and draw order of the reference's __init__ (:15-36): the mean's randn comes before IndexKernel's two
+        self.register_parameter("variational_mean", nn.Parameter(0.01 * torch.randn(n, num_tasks), requires_grad=True))
+        self.register_parameter("variational_covar_root", nn.Parameter(torch.eye(n), requires_grad=True))
+        self.register_parameter("variational_task_covar_root", nn.Parameter(torch.eye(num_tasks), requires_grad=True))
+        self.index_kernel = IndexKernel(num_tasks=num_tasks, rank=rank, **kwargs)
+        self.data_kernel = covar_module
+        self.inducing_points = inducing_points
+        self.num_tasks = num_tasks
+        self.mean_module = MultitaskMean(ConstantMean(), num_tasks=num_tasks)
+        object.__setattr__(self, "_eq_memo", EqualMemo())
+        object.__setattr__(self, "_kl_ws", None)
+        self.to(inducing_points.device)
+
+    @property
+    def variational_strategy(self):
+        return self                                              # "hacky af for now" (:90-93): the ELBO asks it for the KL
+
+    def _task_params(self):
+        c = torch.cat([m.constant.reshape(1) for m in self.mean_module.base_means])
+        return c, self.index_kernel.covar_factor, self.index_kernel.raw_var
+
+    def kl_divergence(self):
+        """KL(q || p) (:95-111), from the HIP step (no likelihood term: one quadrature node, y = 0)."""
+        M = self.variational_mean
+        if not M.is_cuda:
+            raise ops._lib.VoltHipError("MultitaskVariationalGP.kl_divergence: tensors must live on the MI355X; no CPU fallback")
+        n, T = M.shape
+        with torch.no_grad():
+            K = _dense(self.data_kernel(self.inducing_points)).to(torch.float32)
+            c, cf, rv = self._task_params()
+            gx, gw = _gauss_hermite(1, M.device)
+            ws = self._kl_ws
+            if ws is None or ws.N != n or ws.T != T or ws.buf.device != M.device:
+                ws = ops.GpcvMtWorkspace(n, T, False, M.device)
+                object.__setattr__(self, "_kl_ws", ws)
+            ops.gpcv_mt_step(K, M, c, self.variational_covar_root, self.variational_task_covar_root, cf, rv,
+                             torch.zeros_like(M), gx, gw, ws, jitter=PRIOR_JITTER, min_var=MIN_VARIANCE)
+            return ws.out[1].clone()
+
+    def forward(self, x, **kwargs):
+        raise NotImplementedError("MultitaskVariationalGP.forward(x) away from the inducing points (:113-146) is outside "
+                                  "the accelerated path; call model(inducing_points)")
+
+    def __call__(self, x, **kwargs):
+        Z = self.inducing_points
+        xs = x.reshape(Z.shape) if x.numel() == Z.numel() else x
+        if xs.shape == Z.shape and self._eq_memo.equal(x, Z, lambda: torch.equal(xs, Z)):
+            return MultitaskVariationalLatent(self)
+        return self.forward(x, **kwargs)
+
+    def initialize_variational_parameters(self, likelihood, x, f=None, y=None):
+        """:38-88 for the "exp" likelihood.  y [N,T]: mean = log running std of each column, S_root = L C^-T with
+        L = chol(K_uu), C = chol(L' H L + I), H the mean over tasks of the clamped inverse Hessians (whose off-diagonal
+        1e-4 survives the mean); stored as the reference stores it -- 10 * S_root, a FULL matrix of which only tril() is
+        ever used.  (gpytorch's root_inv_decomposition is taken on its Cholesky route.)"""
+        if getattr(likelihood, "param", "exp") != "exp":
+            raise NotImplementedError('the "cv" initialisation (multi_task_variational_gp.py:58-69) is not implemented')
+        assert y is not None
+        with torch.no_grad():
+            kuu = _dense(self.data_kernel(self.inducing_points)).to(torch.float32)
+            y2 = y.to(torch.float32)
+            N, T = y2.shape
+            # running std of y[:i] (unbiased) per column, one prefix-sum pass instead of the reference's N slices
+            idx = torch.arange(N, device=y2.device, dtype=torch.float64).unsqueeze(-1)
+            zero = torch.zeros(1, T, dtype=torch.float64, device=y2.device)
+            s1 = torch.cat([zero, torch.cumsum(y2.double(), 0)[:-1]], 0)
+            s2 = torch.cat([zero, torch.cumsum(y2.double() ** 2, 0)[:-1]], 0)
+            var = (s2 - s1 * s1 / idx.clamp_min(1)) / (idx - 1).clamp_min(1)
+            running_std = var.clamp_min(0).sqrt().to(torch.float32)
+            running_std[:10] = running_std[10]
+            if f is None:
+                f = running_std.clamp(min=1e-4).log()
+            # torch.diag_embed(...).clamp(min=1e-4, max=1000.).mean(0): diagonal = mean of the clamped entries, elsewhere 1e-4
+            h = (0.5 * y2.pow(-2.0) * (f * 2.0).exp()).T.clamp(min=1e-4, max=1000.0).mean(0)
+            ih = torch.full((N, N), 1e-4, device=y2.device)
+            ih.diagonal().copy_(h)
+            L = _safe_factor(kuu.reshape(1, N, N))[0].L[0]                                   # kuu.cholesky()
+            Lt = L.mT.contiguous()
+            HL = ops.gemm_nt(ih, Lt, uplo_b=2)                                               # H L
+            inner = ops.gemm_nt(Lt, HL.mT.contiguous(), uplo_a=2)                            # L' H L
+            inner = inner + torch.eye(N, device=y2.device)                                   # .add_jitter(1.0)
+            Yi = ops.trtri(_safe_factor(inner.reshape(1, N, N))[0])[0]                       # C^-T
+            S_root = ops.gemm_nt(L.contiguous(), Yi.mT.contiguous(), uplo_a=1, uplo_b=1)     # L C^-T
+            self.variational_mean.data = f.to(torch.float32).contiguous()
+            self.variational_covar_root.data = (S_root * 10.0).contiguous()
+            log_means = running_std.clamp(min=1e-4).mean(0).log()
+            for i, m in enumerate(self.mean_module.base_means):
+                m.constant.data.add_(log_means[i])
+            if type(self.index_kernel) is IndexKernel:
+                # (`index_kernel.var.data /= 10.` at :87 divides a temporary, as in BMGP.py:39: a no-op)
+                self.index_kernel.covar_factor.data /= 10.

@@ -356,6 +356,65 @@ def gpcv_step(K, resid, m, Lq, y, gh_x, gh_w, ws: GpcvWorkspace | None = None, w
     return ws
 
 
+GPCV_MT_T_MAX = 64                  # include/volt_hip.h: volt_gpcv_mt_step_f32 takes 1 <= T <= 64 series
+
+
+class GpcvMtWorkspace:
+    """Caller-owned scratch and outputs of volt_gpcv_mt_step_f32, reusable across steps of the same (N, T).
+    info[0]: the factorisation of K + jitter I; info[1]: a non-positive pivot of K_t; info[2]: F is not finite."""
+
+    def __init__(self, N: int, T: int, want_dk: bool, device):
+        if T < 1 or T > GPCV_MT_T_MAX:
+            raise ValueError(f"the multi-task GPCV step takes 1 <= T <= {GPCV_MT_T_MAX} series (got T = {T})")
+        self.N, self.T, self.want_dk = N, T, bool(want_dk)
+        nbytes = _lib.lib().volt_gpcv_mt_workspace_bytes(N, T, int(want_dk))
+        self.buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+        self.ptr = (self.buf.data_ptr() + 255) // 256 * 256
+        with torch.cuda.device(self.buf.device):        # it begins with an MLL workspace for ONE series
+            _lib.check(_lib.lib().volt_mll_workspace_init_f32(self.ptr, 1, N, 1, _lib.stream_ptr()), "volt_mll_workspace_init")
+        f32 = dict(dtype=torch.float32, device=device)
+        self.out = torch.empty(16, **f32)
+        self.grad_M = torch.empty(N, T, **f32)
+        self.grad_c = torch.empty(T, **f32)
+        self.grad_Lx = torch.empty(N, N, **f32)
+        self.grad_Lt = torch.empty(T, T, **f32)
+        self.grad_covar_factor = torch.empty(T, **f32)
+        self.grad_raw_var = torch.empty(T, **f32)
+        self.grad_K = torch.empty(N, N, **f32) if want_dk else None
+        self.info = torch.empty(3, dtype=torch.int32, device=device)
+
+
+def gpcv_mt_step(K, M, c, Lx, Lt, covar_factor, raw_var, y, gh_x, gh_w, ws: GpcvMtWorkspace | None = None,
+                 want_dk: bool = False, jitter: float = 1e-3, min_var: float = 1e-6, min_scale: float = 1e-3,
+                 w_ell: float = 1.0, w_kl: float = 1.0):
+    """One ELBO + gradient evaluation of the multi-task GPCV variational GP (include/volt_hip.h, volt_gpcv_mt_step_f32).
+    K [N,N] data prior covariance without jitter; M, y [N,T]; c, covar_factor ([T] or [T,1]), raw_var [T]; Lx [N,N],
+    Lt [T,T] (what lies above their diagonals is ignored).  Gradients are those of F = w_ell * ell - w_kl * KL (out[12]).
+    Returns the workspace: .out [16], .grad_M, .grad_c, .grad_Lx, .grad_Lt, .grad_covar_factor, .grad_raw_var
+    (.grad_K if want_dk), .info [3]."""
+    _need_gpu(K, M, c, Lx, Lt, covar_factor, raw_var, y, gh_x, gh_w)
+    if K.ndim != 2 or K.dtype != torch.float32:
+        raise ValueError("K must be [N,N] fp32")
+    n = K.shape[0]
+    T = M.shape[-1]
+    if K.stride(-1) != 1:
+        K = K.contiguous()
+    f = lambda t, shape: t.detach().reshape(shape).to(torch.float32).contiguous()
+    M, y, Lx, Lt = f(M, (n, T)), f(y, (n, T)), f(Lx, (n, n)), f(Lt, (T, T))
+    c, cf, rv = f(c, (T,)), f(covar_factor, (T,)), f(raw_var, (T,))
+    gh_x, gh_w = gh_x.to(torch.float32).contiguous(), gh_w.to(torch.float32).contiguous()
+    if ws is None or ws.N != n or ws.T != T or ws.want_dk != bool(want_dk) or ws.buf.device != K.device:
+        ws = GpcvMtWorkspace(n, T, want_dk, K.device)
+    _lib.check(_lib.lib().volt_gpcv_mt_step_f32(
+        K.data_ptr(), K.stride(0), float(jitter), M.data_ptr(), c.data_ptr(), Lx.data_ptr(), Lt.data_ptr(), cf.data_ptr(),
+        rv.data_ptr(), y.data_ptr(), gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var), float(min_scale),
+        float(w_ell), float(w_kl), ws.out.data_ptr(), ws.grad_M.data_ptr(), ws.grad_c.data_ptr(), ws.grad_Lx.data_ptr(),
+        ws.grad_Lt.data_ptr(), ws.grad_covar_factor.data_ptr(), ws.grad_raw_var.data_ptr(),
+        ws.grad_K.data_ptr() if want_dk else None, ws.info.data_ptr(), ws.ptr, n, T, _lib.WS_INITIALISED,
+        _lib.stream_ptr()), "volt_gpcv_mt_step")
+    return ws
+
+
 def mll_grad_k(ws: MllWorkspace) -> torch.Tensor:
     """d mll / d K = 1/2 (alpha alpha' - K_s^-1) / N  [B,N,N], from the Y = L^-T the last ``mll_step(want_grad=True)``
     left in ``ws`` (volt_mll_grad_k_f32) -- for kernels with trainable parameters."""

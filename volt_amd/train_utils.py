@@ -1,5 +1,5 @@
 """Training loops on the HIP path -- the ``voltron.train_utils`` surface for SURVEY 8 rows a5 (the exact-GP data
-model: TrainVoltMagpieModel :192-257, TrainDataModel :98-144), (f)1 (TrainVolModel :69-95) and (f)4 (LearnGPCV :15-67).
+model: TrainVoltMagpieModel :192-257, TrainDataModel :98-144), (f)1 (TrainVolModel :69-95) and (f)4 (LearnGPCV :15-67; LearnGPCVMultitask is the same loop over the joint multi-task model).
 
 Signatures, defaults, the set of trained parameters and the arithmetic of one iteration are the reference's; the code
 is organised differently: ONE loop driver (``_run_iterations``), ONE table of mean functions (``_MEANS``) and ONE
@@ -298,6 +298,56 @@ def LearnGPCV(train_x, train_y, train_iters=1000, printing=False, early_stopping
     graph = _auto_graph(graph, train_y[..., 1:], n3_coeff=5.0 / 3.0)   # (only the fitted scale is returned: nothing per-iteration is lost)
     model, likelihood, _ = FitGPCV(train_x, train_y, train_iters=train_iters, printing=printing, kernel=kernel, graph=graph)
     return likelihood(model(train_x), return_gaussian=False).scale.mean(0).detach()      # :60-67
+
+
+def FitGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None):
+    """LearnGPCV's fit (train_utils.py:15-58) over the JOINT model of T series that share the time grid
+    (MultitaskVariationalGP, voltron/models/multi_task_variational_gp.py; the reference has no trainer for it):
+    train_y [T,N+1] prices -> (model, likelihood, losses).  One HIP ELBO step per iteration factors the N x N prior ONCE
+    for all T series (the batched FitGPCV factors it T times and keeps T variational roots)."""
+    from .kernels import BMKernel, FBMKernel
+    from .likelihoods import VolatilityGaussianLikelihood
+    from .models import MultitaskVariationalGP
+    from .variational import VariationalELBO, num_gauss_hermite_locs
+    if train_y.ndim != 2:
+        raise ValueError("FitGPCVMultitask: train_y must be [T,N+1] (one row of prices per series)")
+    dt = train_x[1] - train_x[0]
+    yy = ((train_y[..., 1:] - train_y[..., :-1]) / train_y[..., :-1] / dt ** 0.5).t().contiguous()   # :16-18, [N,T]
+    likelihood = VolatilityGaussianLikelihood(param="exp")
+    covar_module = {"bm": BMKernel, "fbm": FBMKernel}[kernel]()
+    model = MultitaskVariationalGP(train_x, num_tasks=yy.shape[-1], covar_module=covar_module)
+    model.initialize_variational_parameters(likelihood, train_x, y=yy)
+    model.train()
+    likelihood.train()
+    graph = bool(graph)                                  # (this entry returns the per-iteration losses: captured only on request)
+    optimizer = _adam([{"params": model.parameters()}], LR_GPCV, graph)
+    elbo = VariationalELBO(likelihood, model, yy.numel(), combine_terms=True)
+    losses = []
+
+    def iteration():                                     # :50-54
+        with num_gauss_hermite_locs(75):
+            loss = -elbo(model(train_x), yy)
+            if not graph:
+                losses.append(loss.detach())
+            loss.backward()
+        return loss
+
+    last = _run_iterations(iteration, optimizer, train_iters, printing, graph)
+    if graph and last is not None:
+        losses.append(last.detach())
+    model.eval()
+    likelihood.eval()
+    return model, likelihood, losses
+
+
+def LearnGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None):
+    """LearnGPCV for T series through the joint model: train_y [T,N+1] prices -> pred_scale [T,N] (the 10-sample
+    predictive scale of train_utils.py:60-67, per series)."""
+    # one series' N^3 chain whatever T is: the capture gate sees ONE [N] target
+    graph = _auto_graph(graph, train_y[0, 1:], n3_coeff=5.0 / 3.0)
+    model, likelihood, _ = FitGPCVMultitask(train_x, train_y, train_iters=train_iters, printing=printing, kernel=kernel,
+                                            graph=graph)
+    return likelihood(model(train_x), return_gaussian=False).scale.mean(0).t().detach()
 
 
 # ------------------------------------------------------------------------------------------------ (f)1: vol forecaster

@@ -174,6 +174,111 @@ class _GPCVElbo(torch.autograd.Function):
         return g1 * gm, g2 * gL, g1 * gmu, gK, None, None, gscale, None, None, None
 
 
+class MultitaskVariationalLatent(MultivariateNormal):
+    """What ``MultitaskVariationalGP(inducing_points)`` returns: q(F) = N(M, S_x (x) S_t) itself (event shape [N,T]), tied
+    to its model so the ELBO can reach the prior."""
+
+    def __init__(self, model):
+        self.model = model
+        self.loc = model.variational_mean
+
+    @property
+    def num_tasks(self):
+        return self.loc.shape[-1]
+
+    @property
+    def event_shape(self):
+        return self.loc.shape
+
+    @property
+    def _roots(self):
+        return self.model.variational_covar_root.tril(), self.model.variational_task_covar_root.tril()
+
+    @property
+    def _covar(self):
+        Lx, Lt = (r.detach() for r in self._roots)
+        return torch.kron(ops.gemm_nt(Lx, Lx, uplo_a=1, uplo_b=1), ops.gemm_nt(Lt, Lt, uplo_a=1, uplo_b=1))
+
+    @property
+    def variance(self):
+        Lx, Lt = self._roots
+        return (Lx.pow(2).sum(-1).unsqueeze(-1) * Lt.pow(2).sum(-1).unsqueeze(-2)).clamp_min(MIN_VARIANCE)
+
+    def rsample(self, sample_shape=torch.Size(), base_samples=None):
+        """M + Lx E Lt', E ~ N(0, I) of shape sample_shape + [N,T] (the Kronecker root applied factor by factor)."""
+        n, T = self.loc.shape
+        if base_samples is None:
+            base_samples = torch.randn(torch.Size(sample_shape) + self.loc.shape, dtype=self.loc.dtype,
+                                       device=self.loc.device)
+        Lx, Lt = (r.detach() for r in self._roots)
+        E = base_samples.reshape(-1, n, T)
+        S = E.shape[0]
+        X = ops.gemm_nt(E.reshape(S * n, T), Lt, uplo_b=1).reshape(S, n, T)                    # E Lt'
+        Z = ops.gemm_nt(X.transpose(1, 2).reshape(S * T, n), Lx, uplo_b=1).reshape(S, T, n)    # (Lx X)'
+        return self.loc.detach() + Z.transpose(1, 2).reshape(base_samples.shape)
+
+
+def _raise_step_failure(what, info, tensors, which):
+    if ops.info_internal(info):
+        raise ops._lib.VoltHipError(f"{what}: internal error, info = {info.tolist()[:8]}")
+    if any(torch.isnan(t).any() for t in tensors):
+        raise NanError(f"{what}: NaN in the prior covariance or the variational parameters")
+    raise NotPSDError(f"{what}: {which} is not positive definite")
+
+
+def mt_dkl_dscale(out, scale, n, T, jitter=PRIOR_JITTER):
+    """dKL/ds of the multi-task step for K_x = s M0 (BMKernel: s = vol), from the scalars in the step's ``out``:
+    [T (N - j tr K^-1) - tau_t (tau_x - j |G|_F^2) - (q - j tr(K_t^-1 A'A))] / (2 s),  K = s M0 + j I."""
+    q, tau_x, tau_t, tr_inv, gg, tr_aa = out[2], out[7], out[8], out[9], out[10], out[11]
+    return 0.5 * (T * (n - jitter * tr_inv) - tau_t * (tau_x - jitter * gg) - (q - jitter * tr_aa)) / scale.reshape(())
+
+
+class _GPCVMtElbo(torch.autograd.Function):
+    """F = w_ell ell - w_kl KL of the multi-task model with the analytic gradients the HIP step returns."""
+
+    @staticmethod
+    def forward(ctx, M, Lx, Lt, c, cf, rv, K, y, holder, scale, num_gh, w_ell, w_kl):
+        n, T = M.shape
+        want_dk = bool(ctx.needs_input_grad[6])
+        gh_x, gh_w = _gauss_hermite(num_gh, M.device)
+        ws = holder.mt_workspace(n, T, want_dk, M.device)
+        ops.gpcv_mt_step(K.detach(), M, c, Lx, Lt, cf, rv, y, gh_x, gh_w, ws, want_dk=want_dk, jitter=PRIOR_JITTER,
+                         min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
+        chk = gp.deferred_checks.deferring()
+        if chk is None and gp.deferred_checks._active is not None:
+            gp.deferred_checks._active.reserve(ws.info)
+        if chk is not None:
+            chk.note(ws.info)
+        elif bool((ws.info != 0).any().item()):
+            info = ws.info.cpu()
+            # info[0]: K_x + jitter I (LAPACK-style or an internal code);  info[1]: a pivot of K_t;  info[2]: F not finite
+            which = "prior covariance K_x + 1e-3 I" if int(info[0]) != 0 else "task covariance K_t"
+            _raise_step_failure("multi-task GPCV step", info[:1], (K, M, Lx, Lt, c, cf, rv, y), which)
+        ctx.n, ctx.T, ctx.w_kl, ctx.has_scale, ctx.want_dk = n, T, w_kl, scale is not None, want_dk
+        ctx.cf_shape = cf.shape
+        saved = [ws.grad_M.clone(), ws.grad_Lx.clone(), ws.grad_Lt.clone(), ws.grad_c.clone(),
+                 ws.grad_covar_factor.clone(), ws.grad_raw_var.clone()]
+        if want_dk:
+            saved.append(ws.grad_K.clone())
+        if scale is not None:
+            saved += [ws.out.clone(), scale.detach().clone()]
+        ctx.save_for_backward(*saved)
+        return ws.out[12].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        sv = list(ctx.saved_tensors)
+        gM, gLx, gLt, gc, gcf, grv = sv[:6]
+        gK = g * sv[6] if ctx.want_dk else None
+        gscale = None
+        if ctx.has_scale:
+            dkl = mt_dkl_dscale(sv[-2], sv[-1], ctx.n, ctx.T)
+            s = sv[-1]
+            gscale = (-ctx.w_kl * g * dkl).reshape(s.shape)
+        return (g * gM, g * gLx, g * gLt, g * gc, (g * gcf).reshape(ctx.cf_shape), g * grv, gK, None, None, gscale,
+                None, None, None)
+
+
 class VariationalELBO(Module):
     """gpytorch.mlls.VariationalELBO(likelihood, model, num_data, beta=1.0, combine_terms=True) stand-in
     (train_utils.py:44): ``mll(model(train_x), yy)`` -> scalar ELBO (or [T] for a batched model)."""
@@ -188,6 +293,7 @@ class VariationalELBO(Module):
         object.__setattr__(self, "model", model)
         self.num_data, self.beta = float(num_data), float(beta)
         self._ws = None
+        self._mt_ws = None
 
     def workspace(self, B, n, want_dk, device):
         ws = self._ws
@@ -195,7 +301,37 @@ class VariationalELBO(Module):
             self._ws = ws = ops.GpcvWorkspace(B, n, want_dk, device)
         return ws
 
+    def mt_workspace(self, n, T, want_dk, device):
+        ws = self._mt_ws
+        if ws is None or ws.N != n or ws.T != T or ws.want_dk != bool(want_dk) or ws.buf.device != device:
+            self._mt_ws = ws = ops.GpcvMtWorkspace(n, T, want_dk, device)
+        return ws
+
+    def _forward_multitask(self, latent, target):
+        """VariationalELBO over a MultitaskMultivariateNormal (event shape [N,T]): the likelihood term is summed over
+        tasks and divided by N, the KL by num_data / beta."""
+        model = latent.model
+        M = model.variational_mean
+        if not M.is_cuda:
+            raise ops._lib.VoltHipError("VariationalELBO: tensors must live on the MI355X; no CPU fallback")
+        n, T = M.shape
+        if tuple(target.shape) != (n, T):
+            raise ValueError(f"VariationalELBO: the multi-task target must be [N,T] = [{n},{T}] (got {tuple(target.shape)})")
+        lazy = model.data_kernel(model.inducing_points)
+        scale = None
+        if isinstance(lazy, _ScaledDense) and lazy.scale.numel() == 1:
+            scale = lazy.scale
+            K = scale.detach().reshape(()) * lazy.base
+        else:
+            K = _dense(lazy)
+        c, cf, rv = model._task_params()
+        return _GPCVMtElbo.apply(M, model.variational_covar_root, model.variational_task_covar_root, c, cf, rv,
+                                 K.to(torch.float32), target.to(torch.float32), self, scale,
+                                 num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data)
+
     def forward(self, approximate_dist_f, target):
+        if isinstance(approximate_dist_f, MultitaskVariationalLatent):
+            return self._forward_multitask(approximate_dist_f, target)
         if not isinstance(approximate_dist_f, VariationalLatent):
             raise TypeError("VariationalELBO expects the output of SingleTaskVariationalGP(train_x)")
         model = approximate_dist_f.model
