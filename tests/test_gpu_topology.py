@@ -5,7 +5,7 @@ short-series one-launch step and the long-series one-launch step -- against the 
   * planned for a faked 64-CU / 2-XCD device (VOLT_TUNE=1 VOLT_FAKE_CUS=64 VOLT_FAKE_XCCS=2) on the real one;
   * under HSA_CU_MASK (a quarter of the CUs), where the hand-offs of whatever schedule runs must still complete.
 Round 6: the one-launch batched steps no longer assume where a workgroup runs -- pullers read their XCC id
-and take tickets from the queues that XCD owns (csrc/common.h).  So the same subprocess also runs shapes that take the
+and take tickets from the queues that XCD owns (csrc/handoff.h).  So the same subprocess also runs shapes that take the
 fence-free LOCAL hand-offs (8 x 2048 and 64 x 1024 in fp32, 8 x 1024 in fp64: batches that are multiples of 8)
   * under the CU mask (XCDs with no CU at all leave orphan queues that the others adopt),
   * with the queues shifted against the XCD numbers (VOLT_BATCH_XSKEW),

@@ -6,7 +6,7 @@
 // chol64.hip walks a block column as three launches on a chain / bulk multi-stream schedule: 130 us per block column of which
 // the diagonal block is 58 -- the rest is launch boundaries and event hand-offs (1 x 4096: 4.1 ms for 32 columns).  Here, as
 // in batch_step.hip for fp32, workgroup w runs piece w of a topologically ordered list and the pieces hand their tiles on
-// through per-matrix progress words, chasing their inputs one 128-wide K block at a time (common.h, Chase):
+// through per-matrix progress words, chasing their inputs one 128-wide K block at a time (handoff.h, Chase):
 //     D(i)      i >= 1: tile (i,i-1) -- A[i,i-1] -= L[i,:i-1] L[i-1,:i-1]^T chasing rows i and i-1 -- parked in an LDS image and
 //               solved against L[i-1,i-1] 32 COLUMNS AT A TIME while that block is still being factored (its workgroup
 //               publishes every 32-column slice and the slice's inverse as they become final: tiles64.h, diag64_body /
@@ -23,7 +23,7 @@
 // The list needs no table: D(0), then per block column k: LA(k+1), D(k+1) -- its sums under way while D(k) is still at its
 // pivots --, US(k+2 .. n-1, k), then row k-1 of the inverse (TD, T longest first); every position for all B matrices with the
 // matrix innermost, and a piece is a closed-form function of its index.  The pieces are pulled BY TICKET by a grid of resident
-// workgroups (round 6; common.h, "who runs which piece"): every piece waits only for pieces listed before it and a ticket is
+// workgroups (round 6; handoff.h, "who runs which piece"): every piece waits only for pieces listed before it and a ticket is
 // taken by a running workgroup, so whatever is waited for is running or finished -- wherever and in whatever order workgroups
 // start.  The diagonal block's image takes 133 KB of LDS: ONE workgroup per CU,
 // which is also what the latency chain wants (batch_step.hip: a pivot chain that shares its CU runs 2.5 x slower) -- and why
@@ -209,8 +209,8 @@ constexpr int BATCH64_LDS_BYTES = DIAG64_LDS_BYTES + TRSM64_STAGE_BYTES;   // 15
 static __shared__ int g_piece64;                                     // the piece thread 0 pulled
 
 // One piece of the list.  LOCAL: the batch is a multiple of 8 -- every piece of a matrix runs under ONE XCD's L2 (the pullers read
-// their XCC id and take the matrices of that XCD's queues: common.h) and that L2 is where its tiles are handed on: plain stores
-// and a drain, no fences (common.h, LOCALP).
+// their XCC id and take the matrices of that XCD's queues: handoff.h) and that L2 is where its tiles are handed on: plain stores
+// and a drain, no fences (handoff.h, LOCALP).
 template <bool LOCAL>
 __device__ __forceinline__ void batch64_piece(const Batch64Args a, const int w) {
     double* const sT = g_sT64;
@@ -253,9 +253,9 @@ __device__ __forceinline__ void batch64_piece(const Batch64Args a, const int w) 
         ch.p0 = ch.p1 = rowp + i;
         const double* Li = Ab + (int64_t)i * TS * Np;
         gemm64_nt_128<true, LOCAL, 2>(Li, Np, Li, Np, (i - 1) * CPB, acc, smem, &ch, &ok);
-        if (!ok && lane == 0) atomicCAS(info_b, 0, (int)0x80000000);
+        if (!ok && lane == 0) report_timeout(info_b);
         tile64_store<!LOCAL>(acc, C, Np, -1.0);
-        batch_publish_wt<LOCAL>(la + i, 1);
+        publish_wt<LOCAL>(la + i, 1);
         return;
     }
     if (pc.kind == P64_DIAG || pc.kind == P64_PANEL) {
@@ -366,9 +366,9 @@ __device__ __forceinline__ void batch64_piece(const Batch64Args a, const int w) 
                 VOLT_B64_DSTEP(3)
 #undef VOLT_B64_DSTEP
             }
-            if (!ok && lane == 0) atomicCAS(info_b, 0, (int)0x80000000);
+            if (!ok && lane == 0) report_timeout(info_b);
             if (!dg) {
-                batch_publish_release<LOCAL>(rowp + i, k + 1);
+                publish_release<LOCAL>(rowp + i, k + 1);
                 VOLT_B64_STAMP(5);
                 return;
             }
@@ -407,14 +407,14 @@ __device__ __forceinline__ void batch64_piece(const Batch64Args a, const int w) 
 #else
         diag64_body<false, LOCAL>(A, Winv, info, Np, i, b, sT, nullptr, image, sub + i);
 #endif
-        batch_publish_release<LOCAL>(wdone, i + 1);
+        publish_release<LOCAL>(wdone, i + 1);
         return;
     }
     if (pc.kind == P64_TRTRI_DIAG) {
         const int i = pc.row;
         batch_wait<LOCAL>(wdone, i + 1, nullptr, 0, info_b);
         trtri64_diag_body(Wb + (int64_t)i * TS * TS, Y + (int64_t)b * Np * Np + (int64_t)i * TS * Np + (int64_t)i * TS, Np, smem);
-        batch_publish_release<LOCAL>(tcol + i, 1);
+        publish_release<LOCAL>(tcol + i, 1);
         return;
     }
     // ---- a tile (i,j) of the inverse: a chased sum, then the product with W_i
@@ -438,9 +438,9 @@ __device__ __forceinline__ void batch64_piece(const Batch64Args a, const int w) 
         zero_acc64(acc);
         gemm64_nt_128<false, false, 2>(mid, Np, Wb + (int64_t)i * TS * TS, TS, CPB, acc, smem);   // (all of `mid` is read before the closing barrier)
         VOLT_B64_STAMP(5);
-        if (!ok && lane == 0) atomicCAS(info_b, 0, (int)0x80000000);
+        if (!ok && lane == 0) report_timeout(info_b);
         tile64_store<!LOCAL>(acc, Yb + (int64_t)j * TS * Np + (int64_t)i * TS, Np, -1.0);
-        batch_publish_wt<LOCAL>(tcol + j, i - j + 1);
+        publish_wt<LOCAL>(tcol + j, i - j + 1);
     }
 #undef VOLT_B64_STAMP
 }
@@ -511,7 +511,7 @@ int volt_internal_batch64_step(double* A, double* Winv, int* info, double* Y, in
     if (blocks > 256) blocks = 256;
     if (blocks * 256 < B) blocks = (B + 255) / 256;
     hipLaunchKernelGGL(batch64_begin_kernel, dim3(blocks), dim3(256), 0, s, info, B, prog, nprog, 0, pstride, B * pstride);
-    // eight queues, one per XCD, when the matrices divide among them evenly (the pullers read their XCC id: common.h)
+    // eight queues, one per XCD, when the matrices divide among them evenly (the pullers read their XCC id: handoff.h)
     const bool local = (B & 7) == 0 && tunables().batch_local != 0 && tunables().xccs == 8;
     const int64_t npieces = batch64_count(B, n, Y != nullptr);
     if (npieces > 0x7fffffff) return 0;

@@ -3,10 +3,10 @@
 // One MLL + gradient step of B matrices of n block columns is B * (n (n + 3) / 2 + ...) tiles with a fixed dependency
 // graph.  The launch-per-column schedules (chol.hip) cut that graph at every block column: 32 launches, each as long as
 // its longest tile plus a tail.  Here the whole step is ONE launch whose workgroups pull the pieces of this list by ticket
-// (common.h, "who runs which piece").  The list is in TOPOLOGICAL order: a piece only waits for pieces listed before it, a
+// (handoff.h, "who runs which piece").  The list is in TOPOLOGICAL order: a piece only waits for pieces listed before it, a
 // ticket is taken by a running workgroup, so whatever is waited for is running or finished -- in whatever order the
 // dispatcher starts workgroups; tiles do not wait for their inputs before they start but chase them K block by K block
-// (common.h, Chase).
+// (handoff.h, Chase).
 //
 // Order: for k = 0 .. n-1 the pieces of block column k --
 //     D(k)        diagonal tile (k,k): last K block, factor, invert -> W_k

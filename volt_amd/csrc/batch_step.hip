@@ -5,7 +5,7 @@
 // its longest tile and ended by a tail in which most CUs idle; two stream groups hide part of that, a hipGraph capture
 // cannot (one group), and 8 .. 16 matrices at N = 4096 or 64 at N = 2048 are bounded by exactly these boundaries.  Here the
 // pieces of the host's topologically ordered list (batch_sched.h) -- diagonal tiles, look-ahead tiles, two-phase panel tiles,
-// rows of the triangular inverse -- are pulled BY TICKET by a grid of resident workgroups (round 6, common.h "who runs which
+// rows of the triangular inverse -- are pulled BY TICKET by a grid of resident workgroups (round 6, handoff.h "who runs which
 // piece": nothing is assumed about where or in what order workgroups start); the tile bodies are the ones every other
 // schedule runs (tiles.h), so the arithmetic, and with it every bit of the result, is the launch-per-column path's.  What is new:
 //   * hand-offs by PROGRESS WORDS per matrix in the caller's scratch (cleared by batch_begin_kernel ahead of the launch):
@@ -13,7 +13,7 @@
 //       tcol[j]  = tiles of block column j of X = L^-1 that are complete (TD(j) stores 1, T(i,j) stores i - j + 1)
 //       la[k]    = the look-ahead part of A[k,k] is parked
 //       W_k's first word as before (diag_body)
-//   * tiles CHASE their inputs (common.h): a panel tile (i,k) follows rowp[k] and rowp[i], a tile (i,j) of the inverse
+//   * tiles CHASE their inputs (handoff.h): a panel tile (i,k) follows rowp[k] and rowp[i], a tile (i,j) of the inverse
 //     rowp[i] and tcol[j], asking once per 128-wide K segment and only while its inputs are incomplete.  A tile dispatched
 //     a block column early has all but its last K block behind it when that column completes.
 //   * panel and inverse tiles are stored WRITTEN THROUGH (sc1, non-temporal) and published behind the storing waves' own
@@ -47,7 +47,6 @@ __global__ void batch_begin_kernel(float* __restrict__ Winv, int nflags, int* __
     for (int c = i; c < nprog; c += gridDim.x * blockDim.x) prog[c] = 0;
 }
 
-// (word_ge / batch_wait / batch_publish_*: common.h -- shared with the fp64 one-launch step, batch64_step.hip)
 constexpr int AUX_WT = AUX_SC1;                // sc1: written through at agent scope (never nt on a hand-off: MI355X_MICROARCH.md)
 
 // First diagonal tile straight from the caller's K (+ sigma2 / jitter on the diagonal, identity in the padding) into the
@@ -129,7 +128,6 @@ __device__ __forceinline__ void alpha_item(const float* __restrict__ Y, const Tr
 // the two-phase tiles the time the pipeline is entered and left
 static long long* g_batch_stamps = nullptr;
 
-// (who runs which piece -- the pullers, their queues and BATCH_QWORDS: common.h)
 struct BatchArgs {
     float* A; float* Winv; float* Y; int* info;
     int Np, B;
@@ -208,23 +206,23 @@ __device__ __forceinline__ void batch_piece(const BatchArgs a, const int w, cons
         ch.p0 = ch.p1 = rowp + k + 1;
         bool ok = true;
         update_body<FROMK, 0, true, LOCAL>(A, Np, k + 1, k + 1, 0, k, true, b, src, smem, false, &ch, &ok);
-        if (!ok && (threadIdx.x & 63) == 0) atomicCAS(info_b, 0, (int)0x80000000);
-        batch_publish_release<LOCAL>(la + k + 1, 1);
+        if (!ok && (threadIdx.x & 63) == 0) report_timeout(info_b);
+        publish_release<LOCAL>(la + k + 1, 1);
         return;
     }
     if (kind == BK_TRTRI_DIAG) {
         const int i = d.y;
         batch_wait<LOCAL>(reinterpret_cast<const int*>(Winv + ((int64_t)b * n + i) * TS * TS), 1, nullptr, 0, info_b);
         trtri_diag_body(Winv, Y, Np, i, b, red, smem);
-        batch_publish_release<LOCAL>(tcol + i, 1);
+        publish_release<LOCAL>(tcol + i, 1);
         return;
     }
     if (kind == BK_ALPHA) {
         const int c = d.y;
         if (threadIdx.x < 64) {                              // row c of the inverse is complete: tcol[j] >= c - j + 1, j <= c
             bool ok = true;
-            for (int j = 0; j <= c; ++j) ok = wait_word_ge<LOCAL>(tcol + j, c - j + 1) && ok;   // (wave-uniform addresses)
-            if (!ok && threadIdx.x == 0) atomicCAS(info_b, 0, (int)0x80000000);
+            for (int j = 0; j <= c; ++j) ok = wait_word<AtLeast>(tcol + j, c - j + 1) && ok;   // (wave-uniform addresses)
+            if (!ok && threadIdx.x == 0) report_timeout(info_b);
             acquire_unless_local<LOCAL>();
         }
         __syncthreads();
@@ -255,7 +253,7 @@ __device__ __forceinline__ void batch_piece(const BatchArgs a, const int w, cons
     }
     f32x16 T[4], O[4];
     ChasePre pre = {0, 0};
-    if (jb.t.n1 > 0) pre = chase_issue<LOCAL>(jb.t.ch);             // the polls go out ahead of the input tile's loads: one round trip
+    if (jb.t.n1 > 0) pre = chase_issue(jb.t.ch);                    // the polls go out ahead of the input tile's loads: one round trip
     job_t0(jb, T);
     if (stamps && threadIdx.x == 0) stamps[(int64_t)w * 8 + 3] = __builtin_amdgcn_s_memrealtime();
     const bool ok = tri_tile_run<true, LOCAL>(jb.t, T, O, smem, &pre);
@@ -266,7 +264,7 @@ __device__ __forceinline__ void batch_piece(const BatchArgs a, const int w, cons
     __builtin_amdgcn_s_setprio(3);
 #endif
     if (stamps && threadIdx.x == 0) stamps[(int64_t)w * 8 + 4] = __builtin_amdgcn_s_memrealtime();
-    if (!ok && (threadIdx.x & 63) == 0) atomicCAS(info_b, 0, (int)0x80000000);   // a hand-off timed out: internal error
+    if (!ok && (threadIdx.x & 63) == 0) report_timeout(info_b);   // a hand-off timed out: internal error
     // The NEXT piece's ticket goes out here, ahead of the epilogue: the atomic's round trip (~1 us beside busy neighbours) rides
     // under the reductions and the tile's stores, whose drain (tri_store_lds ends on vmcnt(0)) also brings it back; its table
     // entry is then requested ahead of the publish's drain + barrier.  At the top of the loop both are there -- a tile every
@@ -290,7 +288,7 @@ __device__ __forceinline__ void batch_piece(const BatchArgs a, const int w, cons
             pull.q = -1;                                     // this queue is dry: the loop's own pull looks for another
         }
     }
-    batch_publish_wt<LOCAL>(word, val);
+    publish_wt<LOCAL>(word, val);
     if (threadIdx.x == 0 && w_next >= 0) {                   // (the loop's barriers order these against the other waves' reads)
         g_ahead[par ^ 1] = 1;
         g_piece = w_next;
@@ -304,7 +302,7 @@ __global__ __launch_bounds__(256, 2) void batch_step_kernel(BatchArgs a, int che
         const int4 h0 = a.tab[0];
         if (h0.x != BATCH_MAGIC || h0.y != a.B || h0.z != a.Np / TS || h0.w != check) {
             if (blockIdx.x == 0)
-                for (int b = threadIdx.x; b < a.B; b += NT) a.info[b] = (int)0x80000001;
+                for (int b = threadIdx.x; b < a.B; b += NT) a.info[b] = INFO_BAD_WORKSPACE;
             return;
         }
     }

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256, 2) void factor_step_kernel(float* __restrict__
         zero_acc(T);
     }
     const bool ok = tri_tile_run(jb.t, T, O, smem);
-    if (threadIdx.x == 0 && !ok) atomicCAS(info + jb.b, 0, (int)0x80000000);   // hand-off timed out: internal error
+    if (threadIdx.x == 0 && !ok) report_timeout(info + jb.b);   // hand-off timed out: internal error
     tri_store(O, jb.out, Np);
     if (jb.i >= 0 && red.rpad) trtri_reduce(O, Np, jb.i, jb.j, jb.b, red, smem);
 }
@@ -260,7 +260,7 @@ __device__ __forceinline__ void tri_slice(TriJob& jb, int sl, int nsl, int b0, i
         jb.t.n1 = 0;                                         // phase 1 is done: the W product alone
     }                                                        // (FUSE: an uncut tile runs both phases in one pipelined pass)
     const bool ok = tri_tile_run(jb.t, T, O, smem);
-    if (threadIdx.x == 0 && !ok) atomicCAS(info + jb.b, 0, (int)0x80000000);
+    if (threadIdx.x == 0 && !ok) report_timeout(info + jb.b);
     tri_store(O, jb.out, Np);
     if (jb.i >= 0 && red.rpad) trtri_reduce(O, Np, jb.i, jb.j, jb.b, red, smem);
 }
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(256, 1) void factor_step_sched_kernel(float* __rest
         if (h0.x != key0.x || h0.y != key0.y || h0.z != key0.z || h0.w != key0.w || h1.x != key1.x || h1.y != key1.y ||
             h1.z != key1.z || h1.w != key1.w) {
             if (blockIdx.x == 0)
-                for (int b = threadIdx.x; b < B; b += NT) info[b] = (int)0x80000001;
+                for (int b = threadIdx.x; b < B; b += NT) info[b] = INFO_BAD_WORKSPACE;
             return;
         }
     }
@@ -405,7 +405,7 @@ __global__ __launch_bounds__(256, 2) void tune_update_kernel(float* __restrict__
             for (int e = 0; e < 4; ++e) T[tm][4 * g + e] = -v[e];
         }
     const bool ok = tri_tile_run(jb.t, T, O, smem);
-    if (threadIdx.x == 0 && !ok) atomicCAS(info + jb.b, 0, (int)0x80000000);
+    if (threadIdx.x == 0 && !ok) report_timeout(info + jb.b);
     tri_store(O, jb.out, Np);
 }
 // The 2x2-wave update alone (the diagonal look-ahead's product), same grid.  ABL: ablations for the c0 breakdown.

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "handoff.h"
 
 #define VOLT_ABI_VERSION 5
 
@@ -291,85 +292,7 @@ __device__ __forceinline__ void chunk_run(const float* cur, float* nxt, Frag<WL>
     VOLT_SB();
 }
 
-// ---- chasing tiles (batch_step.hip: the whole batched step in ONE launch) ------------------------------------------
-// A left-looking tile reads K blocks 0 .. k-1 of two block rows that other workgroups of the SAME launch are still
-// producing.  Instead of waiting for all of them before it starts, a chasing tile follows two progress words ("blocks
-// [0, *p - base) of this operand are complete") and asks only at the top of a 128-wide K segment, for the segment whose
-// loads it is about to issue -- so the long products run as far ahead as their inputs allow and what is left on the
-// critical path behind a finished block column is ONE K block, as in a right-looking sweep, with the left-looking
-// traffic.  Every wave polls for itself (the chunk barriers keep the waves of a workgroup within a chunk of each other,
-// and each has seen for itself that what it loads is there); a tile that finds everything complete on entry -- the
-// common case in a large batch -- never polls again.
-#ifndef VOLT_WAIT_TICKS
-#define VOLT_WAIT_TICKS 300000000ull
-#endif
-constexpr unsigned long long CHASE_LIMIT_TICKS = VOLT_WAIT_TICKS;   // 3 s of the 100 MHz s_memrealtime counter (WAIT_LIMIT_TICKS below)
-// A poll of a hand-off word: an sc1 load -- past this CU's L1, served by the XCD's L2 (or by memory when the line was
-// dropped there by a written-through store).
-// LOCALP, the template switch of the waits below: the writer of everything handed on is known to sit on the SAME XCD as the
-// reader (batch_step.hip with a batch that is a multiple of 8) and every address handed on is written ONCE per launch,
-// before anything in the launch reads it.  The XCD's L2 is then the point of coherence and no line of the data can be stale
-// in the reader's L1 (invalidated at kernel start, never filled since), so the waits carry NO acquire fence -- an
-// agent-scope acquire (buffer_inv sc1) costs 1.7 us and more per wave that issues it (MI355X_MICROARCH.md).
-// (A scalar poll -- s_load_dword glc, served by the L2 without queueing behind the co-resident tile's vector loads -- was
-// measured too: no faster at 64 matrices, 12 % slower at 8, where tiles spin on their inputs: 3.73 -> 4.18 ms.)
-template <bool LOCALP>
-__device__ __forceinline__ int poll_word(const int* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <bool LOCALP>
-__device__ __forceinline__ void acquire_unless_local() {
-    if constexpr (!LOCALP) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    else asm volatile("" ::: "memory");                      // (the compiler keeps later loads behind the poll all the same)
-}
-struct Chase {
-    const int* p0 = nullptr;     // progress word of the X operand's source
-    const int* p1 = nullptr;     // ... of the Z operand's
-    int base0 = 0, base1 = 0;    // the word's value when block 0 of this tile's K range is NOT yet there
-};
-template <bool LOCALP = false>
-__device__ __forceinline__ int chase_poll(const Chase& ch) {
-    const int v0 = poll_word<LOCALP>(ch.p0) - ch.base0;
-    const int v1 = poll_word<LOCALP>(ch.p1) - ch.base1;
-    return __builtin_amdgcn_readfirstlane(v0 < v1 ? v0 : v1);
-}
-// The two polls issued EARLY (their results are not waited for here): a tile puts them ahead of the loads of its input
-// tile, so that one memory round trip covers both; chase_wait_pre then starts from what they brought.
-struct ChasePre { int v0, v1; };
-template <bool LOCALP = false>
-__device__ __forceinline__ ChasePre chase_issue(const Chase& ch) {
-    ChasePre p;
-    p.v0 = poll_word<LOCALP>(ch.p0);
-    p.v1 = poll_word<LOCALP>(ch.p1);
-    return p;
-}
-// leading K blocks of the tile that are complete: >= need on return, or the last value seen after a time-out (ok = false)
-template <bool LOCALP = false>
-__device__ __forceinline__ int chase_wait(const Chase& ch, int need, bool& ok) {
-    int r = chase_poll<LOCALP>(ch);
-    if (r < need) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        unsigned spins = 0;
-        while ((r = chase_poll<LOCALP>(ch)) < need) {
-            __builtin_amdgcn_s_sleep(2);
-            if ((++spins & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > CHASE_LIMIT_TICKS) {
-                ok = false;
-                break;
-            }
-        }
-    }
-    acquire_unless_local<LOCALP>();
-    return r;
-}
-template <bool LOCALP = false>
-__device__ __forceinline__ int chase_wait_pre(const Chase& ch, const ChasePre& pre, int need, bool& ok) {
-    const int a = pre.v0 - ch.base0, b = pre.v1 - ch.base1;
-    const int r = __builtin_amdgcn_readfirstlane(a < b ? a : b);
-    if (r < need) return chase_wait<LOCALP>(ch, need, ok);
-    acquire_unless_local<LOCALP>();
-    return r;
-}
-
+// CHASE: the tile follows the progress words of its operands' sources, one K segment at a time (handoff.h, chasing tiles)
 template <int WL, bool CHASE = false, bool LOCALP = false>
 __device__ __forceinline__ void gemm_nt_128(const float* __restrict__ A, int64_t lda, const float* __restrict__ B,
                                                int64_t ldb, int nchunks, f32x16 (&acc)[4], float* smem,
@@ -557,51 +480,6 @@ __device__ __forceinline__ void tri_chunk_p2(const float* cur, float* nxt, f32x1
     VOLT_SB();
 }
 
-// Hand-off waits are bounded by WALL CLOCK (s_memrealtime: a constant 100 MHz counter), not by an iteration count: a
-// preempted or profiled run spins more often, not longer.  3 s -- only a bug or a wedged device gets there.
-#ifndef VOLT_WAIT_TICKS
-#define VOLT_WAIT_TICKS 300000000ull
-#endif
-constexpr unsigned long long WAIT_LIMIT_TICKS = VOLT_WAIT_TICKS;
-// `want` = 0: wait for a non-zero word;  else wait for the word to EQUAL `want` (flags that carry the number of the step
-// they belong to and are never cleared: small_step_kernel in chol.hip).
-template <bool LOCALP = false>
-__device__ __forceinline__ bool flag_is_set(const int* flag, int want) {
-    const int v = poll_word<LOCALP>(flag);
-    return want ? v == want : v != 0;
-}
-template <bool LOCALP = false>
-__device__ __forceinline__ bool wait_flag(const int* flag, int want, int sleep) {
-    if (flag_is_set<LOCALP>(flag, want)) return true;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    unsigned spins = 0;
-    while (!flag_is_set<LOCALP>(flag, want)) {
-        if (sleep == 2) __builtin_amdgcn_s_sleep(2);
-        else __builtin_amdgcn_s_sleep(4);
-        if ((++spins & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > WAIT_LIMIT_TICKS) return false;
-    }
-    return true;
-}
-__device__ __forceinline__ bool wait_nonzero(const int* flag, int sleep) { return wait_flag(flag, 0, sleep); }
-template <bool LOCALP = false>
-__device__ __forceinline__ bool flag_wait_one_lane(const int* flag, int want = 0) {
-    bool ok = true;
-    if (threadIdx.x == 0) {
-        ok = wait_flag<LOCALP>(flag, want, 4);
-        acquire_unless_local<LOCALP>();
-    }
-    return ok;       // meaningful in thread 0 only
-}
-__device__ __forceinline__ void flag_publish(int* flag) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // every storing wave drains
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // restate the wait the compiler may drop
-        __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
 // T holds T0 on entry; O (zeroed here) holds the product on exit.  Returns false if a wait timed out (the W flag: in
 // thread 0;  CHASE: in every lane of the wave that gave up).
 template <bool CHASE = false, bool LOCALP = false>
@@ -760,61 +638,6 @@ __device__ __forceinline__ void rowpair_dot(const f32x4& y, const f32x4& z, floa
     hi = __int_as_float(__builtin_amdgcn_readlane(pi, 32)) + __int_as_float(__builtin_amdgcn_readlane(pi, 48));
 }
 
-// ---- hand-offs of the one-launch batched steps (batch_step.hip, batch64_step.hip) ---------------------------------------
-// thread 0 waits for *p >= want (p may be nullptr), then one agent-scope acquire; a barrier for the rest
-template <bool LOCALP>
-__device__ __forceinline__ bool word_ge(const int* p, int want) { return poll_word<LOCALP>(p) >= want; }
-template <bool LOCALP>
-__device__ __forceinline__ bool wait_word_ge(const int* p, int want) {
-    if (word_ge<LOCALP>(p, want)) return true;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    unsigned spins = 0;
-    while (!word_ge<LOCALP>(p, want)) {
-        __builtin_amdgcn_s_sleep(2);
-        if ((++spins & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > WAIT_LIMIT_TICKS) return false;
-    }
-    return true;
-}
-template <bool LOCALP>
-__device__ __forceinline__ void batch_wait(const int* p0, int want0, const int* p1, int want1, int* info_b) {
-    if (threadIdx.x == 0) {
-        bool ok = true;
-        if (p0) ok = wait_word_ge<LOCALP>(p0, want0);
-        if (p1) ok = wait_word_ge<LOCALP>(p1, want1) && ok;
-        acquire_unless_local<LOCALP>();
-        if (!ok) atomicCAS(info_b, 0, (int)0x80000000);
-    }
-    __syncthreads();
-}
-// behind plain stores: drain, barrier, agent-scope release, the word.  LOCALP (readers on this XCD): the drain alone -- the
-// stores are in this L2 -- and a plain store of the word, which keeps its line there for the polls
-// pub_tid: the thread that fences and stores the word -- a wave the caller's latency chain does not wait for, if it has one
-template <bool LOCALP>
-__device__ __forceinline__ void batch_publish_release(int* word, int val, int pub_tid = 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if ((int)threadIdx.x == pub_tid) {
-        if constexpr (LOCALP) {
-            *reinterpret_cast<volatile int*>(word) = val;
-        } else {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(word, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-// behind written-through (sc1) stores: every storing wave drains, then the word -- nothing is left in L2 to write back
-template <bool LOCALP>
-__device__ __forceinline__ void batch_publish_wt(int* word, int val) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if constexpr (LOCALP) *reinterpret_cast<volatile int*>(word) = val;
-        else __hip_atomic_store(word, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-
 // log of the product of up to 16 pivots L_ii (a thread's chunk of the diagonal): ONE double log instead of sixteen software
 // logs -- but with a single pivot's semantics kept: any pivot <= 0 or NaN makes the result NaN (an even number
 // of negative pivots must not give a finite, plausible log-determinant in the loops that read info late), and a product that
@@ -836,66 +659,5 @@ __device__ __forceinline__ double log_pivot_product(const float (&dg)[16], int n
         if ((nvalid_mask >> u) & 1) s += log((double)dg[u]);
     return s;
 }
-
-// ---- who runs which piece (round 6) ------------------------------------------------------------------------------------
-// Round 5 ran piece w as workgroup w and leaned on two things HIP does not promise (MI355X_MICROARCH.md, "Workgroup
-// dispatch, XCD placement"): workgroups start in grid order (deadlock freedom) and workgroup w sits on XCD w % 8 (LOCAL's
-// fence-free hand-offs through one L2).  Now the grid is a set of PULLERS -- as many workgroups as the chip holds at once,
-// though nothing depends on that number -- and a piece is whatever the next ticket of a queue says:
-//   * a waiter only ever waits for a piece with a SMALLER ticket of its own queue (the list is topologically ordered), and
-//     a ticket is taken by a workgroup that is running: whatever is waited for is running or finished, whatever order
-//     and wherever the dispatcher starts workgroups;
-//   * LOCAL (batch a multiple of 8): eight queues, queue q = the pieces of the matrices b = q (mod 8) -- piece 8 t + q of
-//     the list is ticket t of queue q, the list being matrix-innermost.  A workgroup asks the HARDWARE which XCD it is on
-//     (s_getreg HW_REG_XCC_ID) and pulls from the queues that XCD owns; ownership is one compare-and-swap per queue
-//     (claim[q] = XCD + 1): first its own number, and when that queue is dry, any queue nobody has claimed (an XCD that got
-//     no workgroup at all -- a CU mask -- leaves an orphan that the others adopt whole).  So every piece of a matrix runs
-//     under ONE L2 because the workgroups that run them read their own XCC_ID, not because of where workgroup w landed.
-//   * otherwise: one queue, the agent-scope protocol, any workgroup anywhere.
-// Queue words (ints, behind the progress words, cleared with them): head of queue q at [32 q], claim at [32 q + 1].
-constexpr int BATCH_QWORDS = 8 * 32;
-
-// HW_REG_XCC_ID (hwreg 20), bits 3:0: the XCD this wave runs on
-__device__ __forceinline__ int hw_xcc_id() { return (int)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 7; }
-
-// Thread 0's view of the queues: which one it pulls from and how many it has tried to claim (see the block comment above).
-//   xskew (tuning / tests): added to the hardware's XCC id -- the queues then sit on other XCDs than their numbers say;
-//   xdrop (tuning / tests): bit x set = the workgroups on XCD x leave at once, as if a CU mask had emptied it -- their queues
-//   are adopted by the others.
-struct BatchPull {
-    int q = -1, scan = 0;
-};
-template <bool LOCAL>
-__device__ __forceinline__ int batch_next_piece(BatchPull& p, int* __restrict__ qw, int xcc, int per_queue) {
-    for (;;) {
-        if (p.q >= 0) {
-            const int t = __hip_atomic_fetch_add(qw + 32 * p.q, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (t < per_queue) return LOCAL ? 8 * t + p.q : t;
-            p.q = -1;
-        }
-        if (!LOCAL) {
-            if (p.scan) return -1;
-            p.scan = 1;
-            p.q = 0;
-            continue;
-        }
-        while (p.q < 0 && p.scan < 8) {
-            const int cand = (xcc + p.scan) & 7;
-            ++p.scan;
-            int seen = __hip_atomic_load(qw + 32 * cand + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (seen == 0) {
-                int expect = 0;
-                if (__hip_atomic_compare_exchange_strong(qw + 32 * cand + 1, &expect, xcc + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                         __HIP_MEMORY_SCOPE_AGENT))
-                    seen = xcc + 1;
-                else
-                    seen = expect;
-            }
-            if (seen == xcc + 1) p.q = cand;
-        }
-        if (p.q < 0) return -1;
-    }
-}
-
 
 }  // namespace volt

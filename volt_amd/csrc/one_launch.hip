@@ -78,38 +78,6 @@ struct SmallTail {
     int N;
 };
 
-// thread 0 polls with a growing pause (f1 may be nullptr), one agent-scope acquire, a barrier for the rest
-__device__ __forceinline__ bool wait_flag_backoff(const int* flag, int want) {
-    if (flag_is_set(flag, want)) return true;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    unsigned spins = 0;
-    while (!flag_is_set(flag, want)) {
-        if (spins < 16) __builtin_amdgcn_s_sleep(2);
-        else if (spins < 64) __builtin_amdgcn_s_sleep(8);
-        else __builtin_amdgcn_s_sleep(24);
-        if ((++spins & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > WAIT_LIMIT_TICKS) return false;
-    }
-    return true;
-}
-__device__ __forceinline__ void small_wait(const int* f0, const int* f1, int want, int* info_b) {
-    if (threadIdx.x == 0) {
-        bool ok = wait_flag_backoff(f0, want);
-        if (f1) ok = wait_flag_backoff(f1, want) && ok;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        if (!ok) atomicCAS(info_b, 0, (int)0x80000000);
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ void small_publish(int* flag, int val) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // every storing wave drains
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(flag, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
 // A tile below diagonal block k, solved by SUBSTITUTION against the column slabs that block's workgroup hands on while
 // it is still pivoting (diag_body<.., SLABS>) -- nothing here waits for the inverse W_k.  On entry T = -U^T, U the tile
 // with every block column m < k already subtracted (tri_tile_run's accumulator layout: T[j] register q <-> column
@@ -127,35 +95,7 @@ __device__ __forceinline__ void small_publish(int* flag, int val) {
 // the rank-32 update L'_j L'_j^T in that pipeline's K order, so that after the last slab only a quarter of the product is
 // left, and the result lands in the pivot image (lower triangle, zeros above) that diag_body works on.  MODE 2: a tile of
 // Y = L^-T (the same right-hand product against W_i): the slabs' products are kept in O for the reductions.
-// The four slab flags of a diagonal block sit in one aligned 16-byte word and go up in order: ONE load tells how many of
-// them are up, so a tile that arrives late polls once, not once per slab (every poll is a round trip on the chain).
-// Lane 0: returns how many leading flags equal `want` once that is more than j; -1 on a time-out.
-__device__ __forceinline__ int wait_slab_flags(const int* slab, int j, int want) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)slab, 0, 16, 0x00020000);
-    auto count = [&]() {
-        asm volatile("" ::: "memory");
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, 0, 0, AUX_SC1);
-        int c = 0;
-        if ((int)v[0] == want) {
-            c = 1;
-            if ((int)v[1] == want) {
-                c = 2;
-                if ((int)v[2] == want) c = (int)v[3] == want ? 4 : 3;
-            }
-        }
-        return c;
-    };
-    int c = count();
-    if (c > j) return c;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    unsigned spins = 0;
-    while ((c = count()) <= j) {
-        __builtin_amdgcn_s_sleep(2);
-        if ((++spins & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > WAIT_LIMIT_TICKS) return -1;
-    }
-    return c;
-}
-
+// (the four slab flags are read with one load: wait_slab_flags, handoff.h)
 struct NoOp { __device__ __forceinline__ void operator()() const {} };
 template <int MODE, class F = NoOp, int AUXL = 16 /* AUX_SC1 */>
 __device__ __forceinline__ bool substitute_tile(f32x16 (&T)[4], const float* __restrict__ Lkk, int Np,
@@ -239,7 +179,7 @@ __device__ __forceinline__ bool substitute_tile(f32x16 (&T)[4], const float* __r
                 if (c < 0) { ok = false; c = 4; }
                 nready = c;
             } else if (lane == 0) {
-                ok = wait_flag(slab + j, want, 2) && ok;
+                ok = wait_word<IsSet>(slab + j, want) && ok;
             }
         }
         asm volatile("" ::: "memory");                             // the loads below stay below the poll
@@ -467,7 +407,7 @@ __device__ __forceinline__ void small_diag_tile_out(float* __restrict__ Y, int N
         const int c = e >> 7, r = e & 127;                          // Y row c, column r
         Yd[(int64_t)c * Np + r] = (r >= c) ? smem[r * WLD + c] : 0.f;
     }
-    small_publish(yflag, want);
+    publish_release<false>(yflag, want);
 }
 constexpr int SMALL_SPARE = TS * WLD + TS + NT;                      // floats of the staging area small_diag_tile leaves alone
 
@@ -563,7 +503,7 @@ __global__ __launch_bounds__(256, 2) void small_step_kernel(float* __restrict__ 
     __shared__ int s_last;
     const int n = Np / TS, tid = threadIdx.x;
     if (st.hdr[0] != SMALL_MAGIC || st.hdr[1] != B || st.hdr[2] != n) {          // not (or no longer) what init wrote
-        if (tid == 0 && (int)blockIdx.x < B) info[blockIdx.x] = (int)0x80000001;
+        if (tid == 0 && (int)blockIdx.x < B) info[blockIdx.x] = INFO_BAD_WORKSPACE;
         return;
     }
     const int want = __hip_atomic_load(st.hdr + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
@@ -653,7 +593,7 @@ __global__ __launch_bounds__(256, 2) void small_step_kernel(float* __restrict__ 
         SMALL_STAMP(1);
         update_body<true>(A, Np, k, k, 0, k - 1, true, b, src, smem);
         SMALL_STAMP(3);
-        small_publish(uf + k, want);
+        publish_release<false>(uf + k, want);
         SMALL_STAMP(4);
     } else if (kind <= 1) {
         // ---- ahead of diagonal block kd (spine: k - 1, panel piece: k): everything the earlier block columns owe this tile
@@ -679,13 +619,13 @@ __global__ __launch_bounds__(256, 2) void small_step_kernel(float* __restrict__ 
         } else {
             ok = substitute_tile<0>(T, Lkk, Np, Wk, sf + 4 * kd, want, jb.out, smem, X);
         }
-        if ((tid & 63) == 0 && !ok) atomicCAS(info_b, 0, (int)0x80000000);
+        if ((tid & 63) == 0 && !ok) report_timeout(info_b);
         SMALL_STAMP(3);
         if (kind == 0) {                                           // L[k,k-1] is handed on by a spare wave of diag_body
             SMALL_STAMP(4);
             diag_body<false, true>(A, Winv, info, Np, k, b, smem, nullptr, true, wf + k, want, sf + 4 * k, lf + k * n + kd);
         } else {
-            small_publish(lf + ti * n + kd, want);
+            publish_release<false>(lf + ti * n + kd, want);
         }
     } else {
         if (i == j) {
@@ -702,11 +642,11 @@ __global__ __launch_bounds__(256, 2) void small_step_kernel(float* __restrict__ 
             SMALL_STAMP(2);
             const bool ok = substitute_tile<2>(T, Ab + (int64_t)i * TS * Np + (int64_t)i * TS, Np,
                                                Winv + ((int64_t)b * n + i) * TS * TS, sf + 4 * i, want, jb.out, smem, O);
-            if ((tid & 63) == 0 && !ok) atomicCAS(info_b, 0, (int)0x80000000);
+            if ((tid & 63) == 0 && !ok) report_timeout(info_b);
             __syncthreads();                                       // the reductions' scratch overlays the waves' L rows
             trtri_reduce(O, Np, i, j, b, red, smem);
             // the tile and its partials are out; the row's count, z_i, this tile's share of alpha
-            small_publish(yf + i * n + j, want);
+            publish_release<false>(yf + i * n + j, want);
             if (tid == 0) __hip_atomic_fetch_add(rowc + i, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
             small_wait(rowc + i, nullptr, (int)((unsigned)want * (unsigned)(i + 1)), info_b);
             row_z(red, tl, Np, i, j, b, smem);
@@ -836,7 +776,7 @@ __device__ __forceinline__ void long_piece(float* __restrict__ A, float* __restr
     float* Ab = A;
     LONG_STAMP(0);
     auto wait_slices = [&]() {
-        if (tid == 0 && !wait_flag_backoff(ecnt + item.w, (int)((unsigned)want * (unsigned)nslices))) atomicCAS(info_b, 0, (int)0x80000000);
+        if (tid == 0 && !wait_word<IsSet, PauseBackoff>(ecnt + item.w, (int)((unsigned)want * (unsigned)nslices))) report_timeout(info_b);
         __syncthreads();
     };
 
@@ -880,7 +820,7 @@ __device__ __forceinline__ void long_piece(float* __restrict__ A, float* __restr
                         acc[tm * 2 + tn][q] -= input_elem(src, src.K, add, Ab, Np, true, kk * TS + r, kk * TS + c);
                     }
             const int4 ui = st.uinfo[kk];
-            if (tid == 0 && !wait_flag_backoff(ecnt + ui.w, want)) atomicCAS(info_b, 0, (int)0x80000000);
+            if (tid == 0 && !wait_word<IsSet, PauseBackoff>(ecnt + ui.w, want)) report_timeout(info_b);
             __syncthreads();
             slab_add_sc1(acc, st.eslab + (int64_t)ui.z * TS * TS, 1);
             float* C = Ab + (int64_t)kk * TS * Np + (int64_t)kk * TS;
@@ -894,7 +834,7 @@ __device__ __forceinline__ void long_piece(float* __restrict__ A, float* __restr
                         const int c = wc * 64 + tn * 32 + (lane & 31);
                         C[(int64_t)r * Np + c] = -acc[tm * 2 + tn][q];
                     }
-            small_publish(uf + kk, want);
+            publish_release<false>(uf + kk, want);
         }
     } else if (pk == LG_R) {
         // ---- the second half of a split spine: -A[k,k] (parked by U(k)) into the accumulators, the rank-32 update behind
@@ -906,7 +846,7 @@ __device__ __forceinline__ void long_piece(float* __restrict__ A, float* __restr
             if (ui.x) small_wait(uf + k, nullptr, want, info_b);
             spine_load_c(A, Np, k, 0, src, X, !ui.x);
             if (k == 2) {
-                if (tid == 0 && !wait_flag_backoff(ecnt + ui.w, want)) atomicCAS(info_b, 0, (int)0x80000000);
+                if (tid == 0 && !wait_word<IsSet, PauseBackoff>(ecnt + ui.w, want)) report_timeout(info_b);
                 __syncthreads();
                 slab_add_sc1(X, st.eslab + (int64_t)ui.z * TS * TS, 1);
             }
@@ -918,7 +858,7 @@ __device__ __forceinline__ void long_piece(float* __restrict__ A, float* __restr
         const int row = tid >> 1, half = tid & 1;
 #pragma unroll 1
         for (int j = 0; j < 4; ++j) {
-            if (tid == 0 && !wait_flag(hf + 4 * k + j, 4 * want, 2)) atomicCAS(info_b, 0, (int)0x80000000);
+            if (tid == 0 && !wait_word<IsSet>(hf + 4 * k + j, 4 * want)) report_timeout(info_b);
             __syncthreads();
             if (st.stamps && tid == 0) st.stamps[(int64_t)pw * 16 + 6 + j] = __builtin_amdgcn_s_memrealtime();
 #pragma unroll
@@ -1001,7 +941,7 @@ __device__ __forceinline__ void long_piece(float* __restrict__ A, float* __restr
                 // split spine: the tile by substitution, handed on slab by slab to R(k); its flag goes up here
                 ok = substitute_tile<0>(T, Lkk, Np, Wk, sf + 4 * kd, want, jb.out, smem, X,
                                         st.stamps ? st.stamps + (int64_t)pw * 16 : nullptr, NoOp(), hf + 4 * pa);
-                if ((tid & 63) == 0 && !ok) atomicCAS(info_b, 0, (int)0x80000000);
+                if ((tid & 63) == 0 && !ok) report_timeout(info_b);
                 // every word of the tile went out written through and has been waited for (hand_on): the flag needs no
                 // release fence -- an L2-wide write-back that would sit on the chain
                 __syncthreads();
@@ -1017,7 +957,7 @@ __device__ __forceinline__ void long_piece(float* __restrict__ A, float* __restr
                     if (ui.x) small_wait(uf + k, nullptr, want, info_b);
                     spine_load_c(A, Np, k, 0, src, X, !ui.x);      // final, parked by U(k) -- or (k <= 2) the input tile itself ...
                     if (k == 2) {                                  // ... plus, for k = 2, the one slab there is
-                        if (tid == 0 && !wait_flag_backoff(ecnt + ui.w, want)) atomicCAS(info_b, 0, (int)0x80000000);
+                        if (tid == 0 && !wait_word<IsSet, PauseBackoff>(ecnt + ui.w, want)) report_timeout(info_b);
                         __syncthreads();
                         slab_add_sc1(X, st.eslab + (int64_t)ui.z * TS * TS, 1);
                     }
@@ -1031,12 +971,12 @@ __device__ __forceinline__ void long_piece(float* __restrict__ A, float* __restr
                 else
                     ok = substitute_tile<1>(T, Lkk, Np, Wk, sf + 4 * kd, want, jb.out, smem, X,
                                             st.stamps ? st.stamps + (int64_t)pw * 16 : nullptr);
-                if ((tid & 63) == 0 && !ok) atomicCAS(info_b, 0, (int)0x80000000);
+                if ((tid & 63) == 0 && !ok) report_timeout(info_b);
                 LONG_STAMP(4);
                 diag_body<false, true>(A, Winv, info, Np, k, 0, smem, nullptr, true, wf + k, want, sf + 4 * k, lf + k * n + kd);
             } else {
                 ok = substitute_tile<0>(T, Lkk, Np, Wk, sf + 4 * kd, want, jb.out, smem, X);
-                if ((tid & 63) == 0 && !ok) atomicCAS(info_b, 0, (int)0x80000000);
+                if ((tid & 63) == 0 && !ok) report_timeout(info_b);
                 if (pa == kd + 2) {
                     __syncthreads();                               // every wave's rows of the tile are in LDS
                     // L[k,k-2] is the last block diagonal tile k = pa is still owed, and it sits in this workgroup's LDS: its
@@ -1061,17 +1001,17 @@ __device__ __forceinline__ void long_piece(float* __restrict__ A, float* __restr
                     }
                     slice_out(X, st.eslab + (int64_t)ui.z * TS * TS, ecnt + ui.w);
                 }
-                small_publish(lf + pa * n + kd, want);
+                publish_release<false>(lf + pa * n + kd, want);
             }
         } else {
             const int i = pa, j = pb;
             f32x16 O[4];
             const bool ok = substitute_tile<2>(T, Ab + (int64_t)i * TS * Np + (int64_t)i * TS, Np, Winv + (int64_t)i * TS * TS,
                                                sf + 4 * i, want, jb.out, smem, O);
-            if ((tid & 63) == 0 && !ok) atomicCAS(info_b, 0, (int)0x80000000);
+            if ((tid & 63) == 0 && !ok) report_timeout(info_b);
             __syncthreads();                                       // the reductions' scratch overlays the waves' L rows
             trtri_reduce(O, Np, i, j, 0, red, smem);
-            small_publish(yf + i * n + j, want);
+            publish_release<false>(yf + i * n + j, want);
             if (tid == 0) __hip_atomic_fetch_add(rowc + i, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
             small_wait(rowc + i, nullptr, (int)((unsigned)want * (unsigned)(i + 1)), info_b);
             row_z(red, tl, Np, i, j, 0, smem);
@@ -1101,7 +1041,7 @@ __device__ __forceinline__ void long_piece(float* __restrict__ A, float* __restr
 }
 
 
-// The pieces are pulled BY TICKET by a grid of resident workgroups (round 6; the scheme of batch_step.hip / common.h, one queue):
+// The pieces are pulled BY TICKET by a grid of resident workgroups (round 6; the scheme of batch_step.hip / handoff.h, one queue):
 // a piece only waits for pieces listed before it and a ticket is taken by a running workgroup, so the step no longer leans on
 // workgroups being dispatched in grid order.  The ticket word (hdr[32], a line of its own) is never cleared: a step of G
 // pullers takes exactly npieces + G tickets (every puller one too many), so step number `want` starts at
@@ -1113,7 +1053,7 @@ __global__ __launch_bounds__(256, 1) void long_step_kernel(float* __restrict__ A
                                                           int never) {
     const int n = Np / TS, tid = threadIdx.x;
     if (st.hdr[0] != SMALL_MAGIC || st.hdr[1] != 1 || st.hdr[2] != n) {          // not (or no longer) what init wrote
-        if (tid == 0 && blockIdx.x == 0) info[0] = (int)0x80000001;
+        if (tid == 0 && blockIdx.x == 0) info[0] = INFO_BAD_WORKSPACE;
         return;
     }
     const int want = __hip_atomic_load(st.hdr + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;

@@ -268,7 +268,6 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int PSC = 17;                                         // row stride of the 16x16 private scratch tiles
 constexpr int PIVOT_SCRATCH_FLOATS = 2 * 16 * PSC;              // per pivot wave: L21 and the updated A22
 static_assert(DIAG_LDS_FLOATS + 3 * PIVOT_SCRATCH_FLOATS <= 2 * STAGE_FLOATS, "pivot scratch must fit behind the image");
@@ -357,8 +356,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t w_rsrc(float* W) {
     return __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, TS * TS * 4, 0x00020000);
 }
 // AUX = 16 (sc1): written through at agent scope -- what a workgroup on another XCD reads with an sc1 load once it has
-// seen the flag, with no L2-wide write-back / invalidate on either side (small_step_kernel's slab hand-off).
-constexpr int AUX_SC1 = 16;
+// seen the flag, with no L2-wide write-back / invalidate on either side (small_step_kernel's slab hand-off; AUX_SC1: handoff.h).
 template <int AUX = 0>
 __device__ __forceinline__ void w_store(__amdgpu_buffer_rsrc_t rs, int voff, int soff, float v) {
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, voff, soff, AUX);

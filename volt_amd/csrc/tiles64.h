@@ -85,7 +85,7 @@ __device__ __forceinline__ void chunk64_run(const float* cur, float* nxt, bool m
 // acc += A[0:128, 0:16 nchunks] * B[0:128, 0:16 nchunks]^T (doubles; lda / ldb in doubles).  The software pipeline of
 // gemm_nt_128 on the float view of the operands: loads two chunks ahead, double-buffered LDS, one barrier per chunk.
 // CHASE (batch64_step.hip): the operands' 128-wide K blocks are still being produced by other workgroups of the launch; the
-// loop asks the two progress words (common.h, Chase) before it requests a chunk of a block it has not yet seen complete.
+// loop asks the two progress words (handoff.h, Chase) before it requests a chunk of a block it has not yet seen complete.
 // SETS: staging register sets = chunks the global loads run ahead of the LDS stores.
 //   1  (chol64.hip's kernels, two workgroups per CU): with two sets a wave needs 242 + 128 registers and a SIMD holds one wave;
 //      one set fits two, whose barrier and LDS waits cover each other.
@@ -641,7 +641,7 @@ __device__ __forceinline__ void store64x2(double* __restrict__ p, double a, doub
     } while (0)
 // The diagonal block of matrix b, block column k.  image_ready: the caller has already put the (lower triangle of the)
 // block into the image sT (batch64_step.hip: the tile's last update lands there instead of in memory).
-// sub (batch64_step.hip; LOCALPUB as in common.h): PROGRESSIVE hand-off.  The tiles below this block do not wait for the whole
+// sub (batch64_step.hip; LOCALPUB as LOCALP in handoff.h): PROGRESSIVE hand-off.  The tiles below this block do not wait for the whole
 // inverse W: they solve against L_kk 32 columns at a time (trsm64_step) and need, for sub-block column kb, the final blocks
 // L[kb..3, kb] and X_kb = L[kb,kb]^-1.  With sub != nullptr those go to memory as soon as they exist -- the column slice
 // behind its pivot phase, X_kb (into the diagonal block of W where it stays) behind the phase that inverts it -- and *sub is
@@ -732,7 +732,7 @@ __device__ __forceinline__ void diag64_body(double* __restrict__ A, double* __re
         }
         VOLT_STAMP64(3 + 4 * kb);
         // (drain, barrier; release + word by wave 3, which has nothing to do in the next pivot phase)
-        if (sub) batch_publish_release<LOCALPUB>(sub, kb + 1, 192);
+        if (sub) publish_release<LOCALPUB>(sub, kb + 1, 192);
         else __syncthreads();
         VOLT_STAMP64(5 + 4 * kb);
     }

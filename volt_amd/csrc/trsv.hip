@@ -11,16 +11,13 @@
 // loads are issued before the wait for the current tile's dependency, so what remains on the critical path per
 // hop is: flag seen -> acquire -> 512 B of solution -> FMAs -> LDS reduction -> W_i product -> publish.
 //
-// Inter-workgroup protocol: a solution block is 128 values -- the producer stores it WRITTEN THROUGH (agent-scope relaxed
-// atomic stores = sc1), every storing thread drains, __syncthreads, lane 0 sets flag[b][i]; a consumer polls that one word
-// relaxed from one lane, __syncthreads, and fetches the block with agent-scope (sc1) loads.  (Rounds 1-4 had plain stores
-// behind an agent-scope release and plain loads behind an acquire -- Guideline 16 of cdna_hip_programming.md -- which puts an
-// L2 write-back and an L2 / L1 invalidate on every hop of the chain: 8 x 4096 in fp32 4.1 us per hop against 3.0 now, in fp64
-// 7.4 against 6.2; 64 x 2048 0.194 -> 0.139 ms per solve; scripts/bench_trsv.py.)  Block indices are handed out by an
-// atomic ticket in dependency order (all matrices' block 0 first, ...), so a workgroup only ever waits for
-// workgroups that started before it: no co-residency or dispatch-order assumption.  Every spin is bounded by wall
-// clock; a time-out poisons the output with NaN instead of hanging and raises sync[1], the error word the caller can
-// read back.  sync[] (ticket, error word, flags) is zeroed by the launcher.
+// Inter-workgroup protocol (handoff.h, written-through stores): a solution block is 128 values -- the producer stores it with
+// agent-scope relaxed atomic stores (sc1), every storing thread drains, __syncthreads, lane 0 sets flag[b][i]; a consumer polls
+// that one word from one lane, __syncthreads, and fetches the block with agent-scope (sc1) loads: no release, no acquire, no
+// L2 write-back or invalidate on any hop of the chain.  Block indices are handed out by an atomic ticket in dependency order
+// (all matrices' block 0 first, ...), so a workgroup only ever waits for workgroups that started before it.  A time-out
+// poisons the output with NaN instead of hanging and raises sync[1], the error word the caller can read back.  sync[]
+// (ticket, error word, flags) is zeroed by the launcher.
 #include "common.h"
 #include "host.h"
 #include "../../include/volt_hip.h"
@@ -33,18 +30,11 @@ template <typename T> struct V16;
 template <> struct V16<float> { typedef f32x4 type; static constexpr int N = 4; };
 template <> struct V16<double> { typedef f64x2 type; static constexpr int N = 2; };
 
+// thread 0 polls the flag of a solution block (no acquire: the block it announces is fetched with sc1 loads)
 __device__ __forceinline__ bool trsv_wait(const int* flag) {
-    // one lane polls one word, relaxed, agent scope (bounded by wall clock, common.h); then one acquire for the workgroup
     bool ok = true;
-    if (threadIdx.x == 0) ok = wait_nonzero(flag, 2);           // (no acquire: the block it announces is fetched with sc1 loads)
+    if (threadIdx.x == 0) ok = wait_word<IsSet>(flag, 0);
     return ok;      // meaningful in thread 0 only
-}
-
-__device__ __forceinline__ void trsv_publish(int* flag) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // every storing wave drains its stores
-    __syncthreads();
-    // (no release: the block went out written through -- sc1 -- and every storing thread has drained)
-    if (threadIdx.x == 0) __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Lane mapping of a 128 x CW sub-tile (CW = 32 VEC columns): lane = (half = l >> 5, lc = l & 31); wave w owns rows
@@ -144,7 +134,7 @@ __global__ __launch_bounds__(256) void trsv_kernel(const T* __restrict__ A, cons
                     sFail = 1;
                     atomicOr(&sync[1], 1);                  // the error word of the C ABI: this solve timed out
                 }
-                __syncthreads();                            // the acquire covers the workgroup
+                __syncthreads();                            // the poll covers the workgroup
                 if (tid < TS) sV[dep & 1][tid] = __hip_atomic_load(&ob[m * TS + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __syncthreads();
             }
@@ -216,7 +206,7 @@ __global__ __launch_bounds__(256) void trsv_kernel(const T* __restrict__ A, cons
     // sV[0] is still being read by slower waves of the W phase: the barriers inside finish_phase order that
     finish_phase(false);                                    // sV[0] = the solution block
     if (tid < TS) __hip_atomic_store(&ob[i * TS + tid], sFail ? (T)__builtin_nanf("") : sV[0][tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    trsv_publish(flags + i);
+    publish_wt<false>(flags + i, 1);                        // (no release: the block went out written through and has drained)
 }
 
 template <typename T, bool TRANS>
