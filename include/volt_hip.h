@@ -284,6 +284,24 @@ int volt_gpcv_step_f32(const float* K, int64_t ldk, int64_t bsk, float jitter, c
                        float min_scale, float w_ell, float w_kl, float* out, float* grad_m, float* grad_mu,
                        float* grad_Lq, float* grad_K, int* info, void* workspace, int B, int N, int ws_flags, void* stream);
 
+/* The same step for the copula-process ("cv") parameterisation of the likelihood -- the call site it replaces is
+ * volatility_likelihood.py:43-51 under the quadrature of its expected_log_prob (:53-58):
+ *     scale(f) = sum_k a_k log(1 + exp(b_k f + c_k)),  k < Kc,   y_i | f ~ N(0, max(scale(f), min_scale))
+ * abc [B,3,Kc]: the TRANSFORMED a, b, c of every series (rows a, b, c; the constraints' chain rule is the caller's).
+ * Everything else is volt_gpcv_step_f32's: the same arguments, out[b,0..11], gradients and info with the same meaning;
+ *     grad_abc [B,3,Kc] = dF/d(a,b,c) = w_ell d ell / d(a,b,c)      (the KL does not see the likelihood).
+ * The row sums behind grad_abc are reduced in a fixed order (per-workgroup partials, then one pass): no float atomics,
+ * the step is bitwise repeatable.  1 <= Kc <= VOLT_GPCV_CV_K_MAX, otherwise a negative argument code (Kc is argument 10).
+ * workspace: volt_gpcv_cv_workspace_bytes(B, N, want_dk, Kc) bytes (0 if Kc is out of range); it begins with the
+ * workspace of volt_gpcv_step_f32 for the same (B, N, want_dk), initialised the same way. */
+#define VOLT_GPCV_CV_K_MAX 8
+size_t volt_gpcv_cv_workspace_bytes(int B, int N, int want_dk, int Kc);
+int volt_gpcv_cv_step_f32(const float* K, int64_t ldk, int64_t bsk, float jitter, const float* resid, const float* m,
+                          const float* Lq, const float* y, const float* abc, int Kc, const float* gh_x, const float* gh_w,
+                          int Q, float min_var, float min_scale, float w_ell, float w_kl, float* out, float* grad_m,
+                          float* grad_mu, float* grad_Lq, float* grad_K, float* grad_abc, int* info, void* workspace,
+                          int B, int N, int ws_flags, void* stream);
+
 /* ---- Multi-task GPCV  (MultitaskVariationalGP, voltron/models/multi_task_variational_gp.py:11-146; the trainer is this
  * library's: the reference has none) ------------------------------------------------------------------------------------
  * One ELBO + gradient evaluation of the Kronecker variational GP over T <= 64 series that share the N inducing points

@@ -58,6 +58,9 @@ _SIGS = {
     "volt_gpcv_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "volt_gpcv_step_f32": (C.c_int, [_ptr, _i64, _i64, _f32] + [_ptr] * 6 + [_i32, _f32, _f32, _f32, _f32] + [_ptr] * 7
                            + [_i32, _i32, _i32, _ptr]),
+    "volt_gpcv_cv_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "volt_gpcv_cv_step_f32": (C.c_int, [_ptr, _i64, _i64, _f32] + [_ptr] * 5 + [_i32, _ptr, _ptr, _i32, _f32, _f32, _f32, _f32]
+                              + [_ptr] * 8 + [_i32, _i32, _i32, _ptr]),
     "volt_gpcv_mt_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "volt_gpcv_mt_step_f32": (C.c_int, [_ptr, _i64, _f32] + [_ptr] * 9 + [_i32, _f32, _f32, _f32, _f32] + [_ptr] * 10
                               + [_i32, _i32, _i32, _ptr]),

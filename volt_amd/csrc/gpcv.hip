@@ -150,6 +150,124 @@ __global__ __launch_bounds__(256) void gh_ell_kernel(const float* __restrict__ m
     }
 }
 
+// The same rows for the copula-process ("cv") warp  s(f) = sum_k a_k softplus(b_k f + c_k)  (KC terms, per series):
+//   sc = max(s, min_scale),  logp = -y^2 / (2 sc^2) - log sc - log sqrt(2 pi),  g_s = dlogp/ds = (y^2/sc^2 - 1)/sc [s > min_scale],
+//   dlogp/df = g_s sum_k a_k b_k sigmoid(u_k),  dlogp/d(a_k, b_k, c_k) = g_s (softplus(u_k), a_k sigmoid(u_k) f, a_k sigmoid(u_k)).
+// Layout as gh_ell_kernel: one wave per row, lane q takes nodes q, q+64 and loops over k with the 3 KC parameter sums
+// in registers (KC is a template argument so that they stay there).  rowstat as above; the 3 KC sums of a workgroup's 4
+// rows go to part[b][blockIdx.x][3 KC] = (row0 + row1) + (row2 + row3), which cv_abc_reduce_kernel adds up in a fixed order.
+template <int KC>
+__global__ __launch_bounds__(256) void gh_cv_ell_kernel(const float* __restrict__ m, const float* __restrict__ Lq,
+                                                        const float* __restrict__ y, const float* __restrict__ abc,
+                                                        const float* __restrict__ ghx, const float* __restrict__ ghw,
+                                                        int Q, float min_var, float min_scale,
+                                                        float* __restrict__ rowstat, float* __restrict__ part, int N) {
+    __shared__ float red[4][3 * KC];
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * 4 + wave;
+    const bool row_live = i < N;
+    float pa[KC], pb[KC], pc[KC], ga[KC], gb[KC], gc[KC];
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+        pa[k] = abc[((int64_t)b * 3 + 0) * KC + k];
+        pb[k] = abc[((int64_t)b * 3 + 1) * KC + k];
+        pc[k] = abc[((int64_t)b * 3 + 2) * KC + k];
+        ga[k] = gb[k] = gc[k] = 0.f;
+    }
+    if (row_live) {
+        const float* row = Lq + ((int64_t)b * N + i) * N;
+        float s2 = 0.f;
+        for (int j = lane; j <= i; j += 64) {
+            const float v = row[j];
+            s2 += v * v;
+        }
+        float var = wave_sum_f(s2);
+        const bool floored = var < min_var;
+        if (floored) var = min_var;
+        const float mi = m[(int64_t)b * N + i], yi = y[(int64_t)b * N + i];
+        const float sd2 = sqrtf(2.f * var);
+        float e = 0.f, gm = 0.f, gv = 0.f;
+        for (int q = lane; q < Q; q += 64) {
+            const float xq = ghx[q], wq = ghw[q];
+            const float f = mi + sd2 * xq;
+            float sp[KC], sg[KC];
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < KC; ++k) {
+                const float u = pb[k] * f + pc[k];
+                const float t = expf(-fabsf(u));
+                const float inv = 1.f / (1.f + t);
+                sp[k] = fmaxf(u, 0.f) + log1pf(t);
+                sg[k] = u >= 0.f ? inv : t * inv;
+                s += pa[k] * sp[k];
+            }
+            const bool live = s > min_scale;
+            const float sc = live ? s : min_scale;
+            const float r = yi / sc;
+            const float logp = -0.5f * r * r - logf(sc) - 0.91893853320467274f;
+            const float wg = live ? wq * (r * r - 1.f) / sc : 0.f;      // w_q g_s
+            float dsdf = 0.f;
+#pragma unroll
+            for (int k = 0; k < KC; ++k) {
+                const float as = pa[k] * sg[k];
+                dsdf += as * pb[k];
+                ga[k] += wg * sp[k];
+                gb[k] += wg * as * f;
+                gc[k] += wg * as;
+            }
+            e += wq * logp;
+            gm += wg * dsdf;
+            gv += wg * dsdf * xq;
+        }
+        e = wave_sum_f(e);
+        gm = wave_sum_f(gm);
+        gv = wave_sum_f(gv);
+        if (lane == 0) {
+            const float dii = row[i];
+            float* o = rowstat + ((int64_t)b * N + i) * 4;
+            o[0] = e;
+            o[1] = gm;
+            o[2] = floored ? 0.f : gv / sd2;                 // df/dvar = x_q / sqrt(2 var)
+            o[3] = logf(dii * dii);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {                           // (rows past N carry zeros)
+        const float ra = wave_sum_f(ga[k]), rb = wave_sum_f(gb[k]), rc = wave_sum_f(gc[k]);
+        if (lane == 0) {
+            red[wave][k] = ra;
+            red[wave][KC + k] = rb;
+            red[wave][2 * KC + k] = rc;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 * KC) {
+        const int j = threadIdx.x;
+        part[((int64_t)b * gridDim.x + blockIdx.x) * (3 * KC) + j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
+    }
+}
+
+// grad_abc[b][j] = we * sum over the row kernel's workgroups of part[b][.][j], j < n3 = 3 KC: thread t adds blocks
+// t, t+256, ... in order, then the binary tree of gpcv_scalars_kernel (fp64, fixed order: bitwise repeatable).
+__global__ __launch_bounds__(256) void cv_abc_reduce_kernel(const float* __restrict__ part, int nblk, int n3, float we,
+                                                            float* __restrict__ grad_abc) {
+    __shared__ double red[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    for (int j = 0; j < n3; ++j) {
+        double v = 0;
+        for (int k = tid; k < nblk; k += 256) v += part[((int64_t)b * nblk + k) * n3 + j];
+        red[tid] = v;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (tid < s) red[tid] += red[tid + s];
+            __syncthreads();
+        }
+        if (tid == 0) grad_abc[(int64_t)b * n3 + j] = (float)(we * red[0]);
+        __syncthreads();
+    }
+}
+
 // Gradient of F = we ell - wk KL:
 //   dF/dLq[i,j] = we 2 gv_i Lq_ij - wk (G_ij - [i == j] / Lq_ii)   (j <= i, zero above),
 //   dF/dm = we gm - wk beta,  dF/dmu = wk beta.
@@ -244,12 +362,14 @@ __global__ __launch_bounds__(256) void gpcv_scalars_kernel(const float* __restri
 static inline size_t al256g(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct GpcvWs {
-    float *LqT, *W, *Tt, *G, *P, *mllout, *beta, *rowstat, *frobT, *frobG;
+    float *LqT, *W, *Tt, *G, *P, *mllout, *beta, *rowstat, *frobT, *frobG, *cvpart;
     void* mll;
     size_t bytes;
 };
 
-static GpcvWs carve_gpcv(void* base, int B, int N, int want_dk) {
+// Kc > 0 (the "cv" step): the row kernel's per-workgroup partial sums [B, ceil(N/4), 3 Kc] follow everything else, so
+// the "exp" layout is a prefix of the "cv" one.
+static GpcvWs carve_gpcv(void* base, int B, int N, int want_dk, int Kc = 0) {
     const size_t Np = (size_t)volt_padded_n(N), n = Np / TS;
     size_t off = al256g(volt_mll_workspace_bytes(B, N, 1));
     auto take = [&](size_t floats) {
@@ -269,8 +389,76 @@ static GpcvWs carve_gpcv(void* base, int B, int N, int want_dk) {
     w.rowstat = take((size_t)B * N * 4);
     w.frobT = take((size_t)B * n * n);
     w.frobG = take((size_t)B * n * n);
+    w.cvpart = Kc > 0 ? take((size_t)B * ((N + 3) / 4) * 3 * Kc) : nullptr;
     w.bytes = off;
     return w;
+}
+
+// The "cv" row kernel for Kc warp terms + the fixed-order reduction of its parameter sums.
+static void launch_cv_rows(const float* m, const float* Lq, const float* y, const float* abc, int Kc, const float* gh_x,
+                           const float* gh_w, int Q, float min_var, float min_scale, float w_ell, const GpcvWs& w,
+                           float* grad_abc, int B, int N, hipStream_t s) {
+    const dim3 grid((N + 3) / 4, B), blk(256);
+#define VOLT_CV_ROWS(KC)                                                                                              \
+    case KC:                                                                                                          \
+        hipLaunchKernelGGL(gh_cv_ell_kernel<KC>, grid, blk, 0, s, m, Lq, y, abc, gh_x, gh_w, Q, min_var, min_scale,   \
+                           w.rowstat, w.cvpart, N);                                                                   \
+        break;
+    switch (Kc) {
+        VOLT_CV_ROWS(1) VOLT_CV_ROWS(2) VOLT_CV_ROWS(3) VOLT_CV_ROWS(4) VOLT_CV_ROWS(5) VOLT_CV_ROWS(6) VOLT_CV_ROWS(7)
+        VOLT_CV_ROWS(8)
+    }
+#undef VOLT_CV_ROWS
+    hipLaunchKernelGGL(cv_abc_reduce_kernel, dim3(B), dim3(256), 0, s, w.cvpart, (N + 3) / 4, 3 * Kc, w_ell, grad_abc);
+}
+
+// Both variational steps of one series per batch entry: abc == nullptr is the "exp" likelihood (volt_gpcv_step_f32, whose
+// launch sequence this is), otherwise the "cv" one -- only the row kernel differs.
+static int gpcv_step_impl(const float* K, int64_t ldk, int64_t bsk, float jitter, const float* resid, const float* m,
+                          const float* Lq, const float* y, const float* abc, int Kc, const float* gh_x, const float* gh_w,
+                          int Q, float min_var, float min_scale, float w_ell, float w_kl, float* out, float* grad_m,
+                          float* grad_mu, float* grad_Lq, float* grad_K, float* grad_abc, int* info, void* workspace,
+                          int B, int N, int ws_flags, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const int Np = volt_padded_n(N), n = Np / TS;
+    const int64_t mat = (int64_t)Np * Np;
+    const int want_dk = grad_K != nullptr;
+    GpcvWs w = carve_gpcv(workspace, B, N, want_dk, abc ? Kc : 0);
+
+    // the O(N^2) likelihood rows do not depend on the factorisation: enqueue them first
+    if (abc)
+        launch_cv_rows(m, Lq, y, abc, Kc, gh_x, gh_w, Q, min_var, min_scale, w_ell, w, grad_abc, B, N, s);
+    else
+        hipLaunchKernelGGL(gh_ell_kernel, dim3((N + 3) / 4, B), dim3(256), 0, s, m, Lq, y, gh_x, gh_w, Q, min_var, min_scale,
+                           w.rowstat, N);
+    hipLaunchKernelGGL(transpose_tri_kernel, dim3(Np / 32, Np / 32, B), dim3(256), 0, s, Lq, (int64_t)N,
+                       (int64_t)N * N, w.LqT, N, Np, 1);
+    // K + jitter I = L L',  Y = L^-T,  beta = K^-1 resid,  quad, logdet K, tr K^-1, |beta|^2  (exact-GP step)
+    int rc = volt_mll_step_f32(K, ldk, bsk, resid, nullptr, jitter, w.mllout, w.beta, info, w.mll, B, N,
+                               VOLT_WANT_GRAD | (ws_flags & VOLT_WS_INITIALISED), stream);
+    if (rc) return rc;
+    const float* Y = volt_internal_mll_y(workspace, B, N);
+    hipLaunchKernelGGL(transpose_tri_kernel, dim3(Np / 32, Np / 32, B), dim3(256), 0, s, Y, (int64_t)Np, mat, w.W, Np, Np,
+                       2);
+    // T' = Lq' L^-T : rows of Lq' (upper) against rows of W = L^-1 (lower); upper triangle of tiles only
+    GemmArgs g1{w.LqT, w.W, w.Tt, Np, mat, Np, mat, Np, mat, n, n, n, 2, 1, 2, 1.f, 0.f, w.frobT};
+    if ((rc = launch_gemm(g1, B, s))) return rc;
+    // G = K^-1 Lq = Y T : rows of Y (upper) against rows of T' (upper)
+    GemmArgs g2{Y, w.Tt, w.G, Np, mat, Np, mat, Np, mat, n, n, n, 2, 2, 0, 1.f, 0.f, w.frobG};
+    if ((rc = launch_gemm(g2, B, s))) return rc;
+    hipLaunchKernelGGL(gpcv_grad_kernel, dim3((N + 255) / 256, N, B), dim3(256), 0, s, Lq, w.G, w.rowstat, w.beta,
+                       grad_Lq, grad_m, grad_mu, N, Np, w_ell, w_kl);
+    if (want_dk) {
+        GemmArgs g3{Y, Y, w.P, Np, mat, Np, mat, Np, mat, n, n, n, 2, 2, 0, 1.f, 0.f, nullptr};       // K^-1 = Y Y'
+        if ((rc = launch_gemm(g3, B, s))) return rc;
+        GemmArgs g4{w.G, w.G, w.P, Np, mat, Np, mat, Np, mat, n, n, n, 0, 0, 0, -1.f, 1.f, nullptr};   // - G G'
+        if ((rc = launch_gemm(g4, B, s))) return rc;
+        hipLaunchKernelGGL(gpcv_dk_kernel, dim3((N + 255) / 256, N, B), dim3(256), 0, s, w.P, w.beta, grad_K, N, Np, w_kl);
+    }
+    hipLaunchKernelGGL(gpcv_scalars_kernel, dim3(B), dim3(256), 0, s, w.rowstat, w.mllout, w.frobT, w.frobG, jitter, out,
+                       N, n * n, w_ell, w_kl);
+    VOLT_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // namespace volt
@@ -329,43 +517,43 @@ int volt_gpcv_step_f32(const float* K, int64_t ldk, int64_t bsk, float jitter, c
     if (B < 0 || B > 65535) return -23;
     if (N < 1) return -24;
     if (B == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const int Np = volt_padded_n(N), n = Np / TS;
-    const int64_t mat = (int64_t)Np * Np;
-    const int want_dk = grad_K != nullptr;
-    GpcvWs w = carve_gpcv(workspace, B, N, want_dk);
+    return gpcv_step_impl(K, ldk, bsk, jitter, resid, m, Lq, y, nullptr, 0, gh_x, gh_w, Q, min_var, min_scale, w_ell, w_kl, out,
+                          grad_m, grad_mu, grad_Lq, grad_K, nullptr, info, workspace, B, N, ws_flags, stream);
+}
 
-    // the O(N^2) likelihood rows do not depend on the factorisation: enqueue them first
-    hipLaunchKernelGGL(gh_ell_kernel, dim3((N + 3) / 4, B), dim3(256), 0, s, m, Lq, y, gh_x, gh_w, Q, min_var, min_scale,
-                       w.rowstat, N);
-    hipLaunchKernelGGL(transpose_tri_kernel, dim3(Np / 32, Np / 32, B), dim3(256), 0, s, Lq, (int64_t)N,
-                       (int64_t)N * N, w.LqT, N, Np, 1);
-    // K + jitter I = L L',  Y = L^-T,  beta = K^-1 resid,  quad, logdet K, tr K^-1, |beta|^2  (exact-GP step)
-    int rc = volt_mll_step_f32(K, ldk, bsk, resid, nullptr, jitter, w.mllout, w.beta, info, w.mll, B, N,
-                               VOLT_WANT_GRAD | (ws_flags & VOLT_WS_INITIALISED), stream);
-    if (rc) return rc;
-    const float* Y = volt_internal_mll_y(workspace, B, N);
-    hipLaunchKernelGGL(transpose_tri_kernel, dim3(Np / 32, Np / 32, B), dim3(256), 0, s, Y, (int64_t)Np, mat, w.W, Np, Np,
-                       2);
-    // T' = Lq' L^-T : rows of Lq' (upper) against rows of W = L^-1 (lower); upper triangle of tiles only
-    GemmArgs g1{w.LqT, w.W, w.Tt, Np, mat, Np, mat, Np, mat, n, n, n, 2, 1, 2, 1.f, 0.f, w.frobT};
-    if ((rc = launch_gemm(g1, B, s))) return rc;
-    // G = K^-1 Lq = Y T : rows of Y (upper) against rows of T' (upper)
-    GemmArgs g2{Y, w.Tt, w.G, Np, mat, Np, mat, Np, mat, n, n, n, 2, 2, 0, 1.f, 0.f, w.frobG};
-    if ((rc = launch_gemm(g2, B, s))) return rc;
-    hipLaunchKernelGGL(gpcv_grad_kernel, dim3((N + 255) / 256, N, B), dim3(256), 0, s, Lq, w.G, w.rowstat, w.beta,
-                       grad_Lq, grad_m, grad_mu, N, Np, w_ell, w_kl);
-    if (want_dk) {
-        GemmArgs g3{Y, Y, w.P, Np, mat, Np, mat, Np, mat, n, n, n, 2, 2, 0, 1.f, 0.f, nullptr};       // K^-1 = Y Y'
-        if ((rc = launch_gemm(g3, B, s))) return rc;
-        GemmArgs g4{w.G, w.G, w.P, Np, mat, Np, mat, Np, mat, n, n, n, 0, 0, 0, -1.f, 1.f, nullptr};   // - G G'
-        if ((rc = launch_gemm(g4, B, s))) return rc;
-        hipLaunchKernelGGL(gpcv_dk_kernel, dim3((N + 255) / 256, N, B), dim3(256), 0, s, w.P, w.beta, grad_K, N, Np, w_kl);
-    }
-    hipLaunchKernelGGL(gpcv_scalars_kernel, dim3(B), dim3(256), 0, s, w.rowstat, w.mllout, w.frobT, w.frobG, jitter, out,
-                       N, n * n, w_ell, w_kl);
-    VOLT_LAUNCH_CHECK();
-    return 0;
+size_t volt_gpcv_cv_workspace_bytes(int B, int N, int want_dk, int Kc) {
+    if (B <= 0 || N <= 0 || Kc < 1 || Kc > VOLT_GPCV_CV_K_MAX) return 0;
+    return carve_gpcv(nullptr, B, N, want_dk, Kc).bytes;
+}
+
+int volt_gpcv_cv_step_f32(const float* K, int64_t ldk, int64_t bsk, float jitter, const float* resid, const float* m,
+                          const float* Lq, const float* y, const float* abc, int Kc, const float* gh_x, const float* gh_w,
+                          int Q, float min_var, float min_scale, float w_ell, float w_kl, float* out, float* grad_m,
+                          float* grad_mu, float* grad_Lq, float* grad_K, float* grad_abc, int* info, void* workspace,
+                          int B, int N, int ws_flags, void* stream) {
+    if (!K) return -1;
+    if (ldk < N) return -2;
+    if (!resid) return -5;
+    if (!m) return -6;
+    if (!Lq) return -7;
+    if (!y) return -8;
+    if (!abc) return -9;
+    if (Kc < 1 || Kc > VOLT_GPCV_CV_K_MAX) return -10;
+    if (!gh_x) return -11;
+    if (!gh_w) return -12;
+    if (Q < 1 || Q > 1024) return -13;
+    if (!out) return -18;
+    if (!grad_m) return -19;
+    if (!grad_mu) return -20;
+    if (!grad_Lq) return -21;
+    if (!grad_abc) return -23;
+    if (!info) return -24;
+    if (!workspace || ((uintptr_t)workspace & 255)) return -25;
+    if (B < 0 || B > 65535) return -26;
+    if (N < 1) return -27;
+    if (B == 0) return 0;
+    return gpcv_step_impl(K, ldk, bsk, jitter, resid, m, Lq, y, abc, Kc, gh_x, gh_w, Q, min_var, min_scale, w_ell, w_kl, out,
+                          grad_m, grad_mu, grad_Lq, grad_K, grad_abc, info, workspace, B, N, ws_flags, stream);
 }
 
 int volt_mll_grad_k_f32(void* mll_workspace, const float* alpha, float* scratch, float* grad_K, int B, int N,

@@ -2,8 +2,14 @@
 
 ``y | f ~ N(0, scale(f))`` with ``scale = clamp(exp f, 1e-3)`` ("exp", what LearnGPCV uses, train_utils.py:20) or the
 copula-process warp ``sum_k a_k log(1 + exp(b_k f + c_k))`` ("cv").  ``forward`` is elementwise and stays in torch; the
-expectation under q(f) that the ELBO needs (75-node Gauss-Hermite, train_utils.py:50) runs in the HIP step
-(volt_gpcv_step_f32) for the "exp" parameterisation -- the "cv" one has no accelerated ELBO here."""
+expectation under q(f) that the ELBO needs (75-node Gauss-Hermite, train_utils.py:50) runs in the HIP step for both:
+volt_gpcv_step_f32 for "exp", volt_gpcv_cv_step_f32 for "cv" (K <= 8 terms; it also returns the gradients for a, b, c,
+and VariationalELBO applies the constraints' chain rule).  "cv" is accelerated for SingleTaskVariationalGP latents,
+unbatched and batched; the multi-task model takes "exp" only.
+
+``batch_shape=[T]`` stores [T,K] parameters, one set per series.  The reference's ``forward`` multiplies them against
+samples [...,T,N,1] as they are, which lines T up with N (it fails unless N = T); here they broadcast as [T,1,K], so
+series t of the samples meets parameter set t."""
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -40,7 +46,10 @@ class VolatilityGaussianLikelihood(Module):
 
     def forward(self, function_samples, *args, **kwargs):
         if self.param == "cv":
-            transform = ((self.trans_b * function_samples.unsqueeze(-1) + self.trans_c).exp() + 1).log() * self.trans_a
+            a, b, c = self.trans_a, self.trans_b, self.trans_c
+            if a.ndim > 1:                                        # [T,K] -> [T,1,K]: one parameter set per series
+                a, b, c = a.unsqueeze(-2), b.unsqueeze(-2), c.unsqueeze(-2)
+            transform = ((b * function_samples.unsqueeze(-1) + c).exp() + 1).log() * a
             summed_transform = transform.sum(-1)
         else:
             summed_transform = function_samples.exp()
@@ -52,8 +61,8 @@ class VolatilityGaussianLikelihood(Module):
         torch for direct callers; LearnGPCV's loop gets the same numbers (and their gradients) from the fused HIP step."""
         import math
         from ..variational import _gauss_hermite, num_gauss_hermite_locs
-        gx, gw = _gauss_hermite(num_gauss_hermite_locs.value(), target.device)
         mean, var = input.mean, input.variance
+        gx, gw = _gauss_hermite(num_gauss_hermite_locs.value(), target.device, mean.dtype)      # nodes in q(f)'s precision
         locs = torch.sqrt(2.0 * var).unsqueeze(-1) * gx + mean.unsqueeze(-1)
         logp = self.forward(locs.movedim(-1, 0)).log_prob(target)               # [Q, ..., N]
         res = (logp * gw.reshape(-1, *([1] * (logp.ndim - 1)))).sum(0)

@@ -59,11 +59,20 @@ class SingleTaskVariationalGP(Module):
                                   "path: LearnGPCV only evaluates the model at train_x (train_utils.py:51,60)")
 
     def initialize_variational_parameters(self, likelihood, x, f=None, y=None):
-        """single_task_variational_gp.py:190-236 for the "exp" likelihood: mean = log running std of y, covariance
-        S = L (L'HL + I)^-1 L' with H the (clamped) inverse Hessian, stored as 10 * chol(S).
+        """single_task_variational_gp.py:204-254: covariance S = L (L'HL + I)^-1 L' with H the inverse Hessian of the
+        likelihood, stored as 10 * chol(S); the mean constant is the log of the mean running std of y.
+        "exp": mean = log running std, H clamped to [1e-4, 1000] (off-diagonal zeros included).
+        "cv" (:227-238, K = 1 only) with the reference's quirks kept: ``y = f.t()`` replaces the returns by the log running
+        std, so H sees the data only through it; mean = ((y/a).exp() - 1 - c)/b; no clamp on this branch.  The reference's
+        ``y / trans_a`` broadcasts [N] against [K], which works for K = 1 only: K > 1 raises here.
         y [N], or [T,N] for T series sharing the inducing points (batched parameters)."""
-        if getattr(likelihood, "param", "exp") != "exp":
-            raise NotImplementedError('the "cv" initialisation (single_task_variational_gp.py:214-224) is not implemented')
+        param = getattr(likelihood, "param", "exp")
+        if param not in ("exp", "cv"):
+            raise NotImplementedError(f"unknown volatility likelihood parameterisation {param!r}")
+        if param == "cv" and likelihood.raw_a.shape[-1] != 1:
+            raise NotImplementedError('the "cv" initialisation divides y [N] by trans_a [K] (single_task_variational_gp.py:229: '
+                                      '`y / likelihood.trans_a`), a broadcast that only works for K = 1; K = '
+                                      f'{likelihood.raw_a.shape[-1]} has no start-up values')
         with torch.no_grad():
             Z = self.variational_strategy.inducing_points
             kuu = _dense(self.covar_module(Z)).to(torch.float32)
@@ -81,9 +90,19 @@ class SingleTaskVariationalGP(Module):
             if f is None:
                 f = running_std.clamp(min=1e-4).log()
             f = f.reshape(T, N)
-            # torch.diag_embed(...).clamp(min=1e-4, max=1000.): the clamp also lifts the off-diagonal zeros to 1e-4
-            h = (0.5 * y2.pow(-2.0) * (f * 2.0).exp()).clamp(min=1e-4, max=1000.0)
-            ih = torch.full((T, N, N), 1e-4, device=y2.device)
+            if param == "exp":
+                # torch.diag_embed(...).clamp(min=1e-4, max=1000.): the clamp also lifts the off-diagonal zeros to 1e-4
+                h = (0.5 * y2.pow(-2.0) * (f * 2.0).exp()).clamp(min=1e-4, max=1000.0)
+                ih = torch.full((T, N, N), 1e-4, device=y2.device)
+            else:
+                a, b, c = (p.detach().to(y2.device, torch.float32).reshape(-1, 1)
+                           for p in (likelihood.trans_a, likelihood.trans_b, likelihood.trans_c))      # [1,1] or [T,1]
+                yl = f                                                                       # `y = f.t()`: the returns are gone
+                f = ((yl / a).exp() - 1 - c) / b
+                sigma = ((b * f + c).exp() + 1).log().mul(a).clamp(min=likelihood.MIN_SCALE)  # likelihood(f).scale, K = 1
+                scaling = ((2 + 3 * yl.pow(2.0)) * (a * b.pow(2.0) / 2)).pow(-1.0)
+                h = scaling * sigma.pow(2.0) * (1 + torch.cosh(b * yl + c))
+                ih = torch.zeros((T, N, N), device=y2.device)
             ih.diagonal(dim1=-2, dim2=-1).copy_(h)
             L = _safe_factor(kuu.reshape(-1, N, N))[0].L.expand(T, N, N)                 # kuu.cholesky()
             Lt = L.mT.contiguous()

@@ -310,12 +310,22 @@ def gemm_nt(A: torch.Tensor, B: torch.Tensor, uplo_a: int = 0, uplo_b: int = 0) 
     return C[0] if two_d else C
 
 
-class GpcvWorkspace:
-    """Caller-owned scratch and outputs of volt_gpcv_step_f32, reusable across steps of the same (B,N)."""
+GPCV_CV_K_MAX = 8                   # include/volt_hip.h: VOLT_GPCV_CV_K_MAX, volt_gpcv_cv_step_f32 takes 1 <= Kc <= 8 warp terms
 
-    def __init__(self, B: int, N: int, want_dk: bool, device):
-        self.B, self.N, self.want_dk = B, N, bool(want_dk)
-        nbytes = _lib.lib().volt_gpcv_workspace_bytes(B, N, int(want_dk))
+
+class GpcvWorkspace:
+    """Caller-owned scratch and outputs of volt_gpcv_step_f32, reusable across steps of the same (B,N).
+    Kc > 0: the workspace of volt_gpcv_cv_step_f32 for Kc warp terms (adds .grad_abc [B,3,Kc])."""
+
+    def __init__(self, B: int, N: int, want_dk: bool, device, Kc: int = 0):
+        self.B, self.N, self.want_dk, self.Kc = B, N, bool(want_dk), int(Kc)
+        if Kc:
+            if Kc < 1 or Kc > GPCV_CV_K_MAX:
+                raise _lib.VoltHipError(f'the "cv" GPCV step takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms (got Kc = {Kc})')
+            nbytes = _lib.lib().volt_gpcv_cv_workspace_bytes(B, N, int(want_dk), int(Kc))
+            self.grad_abc = torch.empty(B, 3, Kc, dtype=torch.float32, device=device)
+        else:
+            nbytes = _lib.lib().volt_gpcv_workspace_bytes(B, N, int(want_dk))
         self.buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
         self.ptr = (self.buf.data_ptr() + 255) // 256 * 256
         with torch.cuda.device(self.buf.device):        # it begins with an MLL workspace: the schedule table of that step
@@ -356,7 +366,42 @@ def gpcv_step(K, resid, m, Lq, y, gh_x, gh_w, ws: GpcvWorkspace | None = None, w
     return ws
 
 
-GPCV_MT_T_MAX = 64                  # include/volt_hip.h: volt_gpcv_mt_step_f32 takes 1 <= T <= 64 series
+def gpcv_cv_step(K, resid, m, Lq, y, abc, gh_x, gh_w, ws: GpcvWorkspace | None = None, want_dk: bool = False,
+                 jitter: float = 1e-3, min_var: float = 1e-6, min_scale: float = 1e-3, w_ell: float = 1.0,
+                 w_kl: float = 1.0):
+    """``gpcv_step`` for the copula-process ("cv") likelihood, scale(f) = sum_k a_k softplus(b_k f + c_k)
+    (include/volt_hip.h, volt_gpcv_cv_step_f32).  abc [B,3,Kc]: the TRANSFORMED a, b, c of every series.
+    Returns the workspace: what ``gpcv_step`` returns plus .grad_abc [B,3,Kc] = dF/d(a,b,c)."""
+    _need_gpu(K, resid, m, Lq, y, abc, gh_x, gh_w)
+    if K.ndim != 3 or K.dtype != torch.float32:
+        raise ValueError("K must be [B,N,N] fp32")
+    B, n, _ = K.shape
+    if abc.ndim != 3 or abc.shape[0] != B or abc.shape[1] != 3:
+        raise ValueError("abc must be [B,3,Kc]")
+    Kc = abc.shape[2]
+    if K.stride(-1) != 1:
+        K = K.contiguous()
+    c = lambda t, shape: t.reshape(shape).to(torch.float32).contiguous()
+    resid, m, y, Lq, abc = c(resid, (B, n)), c(m, (B, n)), c(y, (B, n)), c(Lq, (B, n, n)), c(abc, (B, 3, Kc))
+    gh_x, gh_w = gh_x.to(torch.float32).contiguous(), gh_w.to(torch.float32).contiguous()
+    if Kc < 1 or Kc > GPCV_CV_K_MAX:                  # no workspace can be sized: let the entry name the argument
+        _lib.check(_lib.lib().volt_gpcv_cv_step_f32(
+            K.data_ptr(), K.stride(1), K.stride(0), float(jitter), resid.data_ptr(), m.data_ptr(), Lq.data_ptr(),
+            y.data_ptr(), abc.data_ptr(), Kc, gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var), float(min_scale),
+            float(w_ell), float(w_kl), None, None, None, None, None, None, None, None, B, n, 0, _lib.stream_ptr()),
+            "volt_gpcv_cv_step")
+    if ws is None or ws.B != B or ws.N != n or ws.want_dk != bool(want_dk) or ws.Kc != Kc:
+        ws = GpcvWorkspace(B, n, want_dk, K.device, Kc=Kc)
+    _lib.check(_lib.lib().volt_gpcv_cv_step_f32(
+        K.data_ptr(), K.stride(1), K.stride(0), float(jitter), resid.data_ptr(), m.data_ptr(), Lq.data_ptr(),
+        y.data_ptr(), abc.data_ptr(), Kc, gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var), float(min_scale),
+        float(w_ell), float(w_kl), ws.out.data_ptr(), ws.grad_m.data_ptr(), ws.grad_mu.data_ptr(), ws.grad_Lq.data_ptr(),
+        ws.grad_K.data_ptr() if want_dk else None, ws.grad_abc.data_ptr(), ws.info.data_ptr(), ws.ptr, B, n,
+        _lib.WS_INITIALISED, _lib.stream_ptr()), "volt_gpcv_cv_step")
+    return ws
+
+
+GPCV_MT_T_MAX = 64                 # include/volt_hip.h: volt_gpcv_mt_step_f32 takes 1 <= T <= 64 series
 
 
 class GpcvMtWorkspace:

@@ -252,8 +252,13 @@ def _fit_exact(model, lh, train_x, target, params, lr, train_iters, printing, gr
 
 
 # ------------------------------------------------------------------------------------------------ (f)4: GPCV
-def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None):
-    """The fit inside LearnGPCV (train_utils.py:15-58), returning what it builds: (model, likelihood, losses)."""
+def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None, *, param="exp", K=1,
+            train_likelihood=False):
+    """The fit inside LearnGPCV (train_utils.py:15-58), returning what it builds: (model, likelihood, losses).
+    ``param="cv"`` fits the copula-process likelihood with K warp terms (volatility_likelihood.py:43-51; the start-up
+    values exist for K = 1 only, as in the reference); ``train_likelihood=True`` adds its raw_a, raw_b, raw_c to the one
+    Adam group at LR_GPCV (the reference's loop trains the model's parameters only, :37-43; its commented-out
+    likelihood group is not reference behaviour).  The defaults are the reference's loop."""
     from .kernels import BMKernel, FBMKernel
     from .likelihoods import VolatilityGaussianLikelihood
     from .models import SingleTaskVariationalGP
@@ -261,7 +266,10 @@ def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", gra
     dt = train_x[1] - train_x[0]
     yy = (train_y[..., 1:] - train_y[..., :-1]) / train_y[..., :-1] / dt ** 0.5        # scaled returns, :16-18
     kw = {"batch_shape": yy.shape[:-1]} if yy.ndim > 1 else {}
-    likelihood = VolatilityGaussianLikelihood(param="exp")
+    if param == "exp":
+        likelihood = VolatilityGaussianLikelihood(param="exp")
+    else:
+        likelihood = VolatilityGaussianLikelihood(K=K, param=param, **kw).to(train_x.device)
     covar_module = {"bm": BMKernel, "fbm": FBMKernel}[kernel](**kw)
     model = SingleTaskVariationalGP(init_points=train_x.view(-1, 1), likelihood=likelihood, use_piv_chol_init=False,
                                     mean_module=gp.ConstantMean(**kw), covar_module=covar_module,
@@ -270,6 +278,8 @@ def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", gra
     model.train()
     likelihood.train()
     graph = bool(graph)                                  # (this entry returns the per-iteration losses: captured only on request)
+    for p in likelihood.parameters():                    # the model registers its likelihood: model.parameters() holds these,
+        p.requires_grad_(bool(train_likelihood))         # and Adam steps the ones that receive a gradient
     optimizer = _adam([{"params": model.parameters()}], LR_GPCV, graph)
     elbo = VariationalELBO(likelihood, model, yy.shape[-1], combine_terms=True)
     losses = []
@@ -291,12 +301,15 @@ def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", gra
     return model, likelihood, losses
 
 
-def LearnGPCV(train_x, train_y, train_iters=1000, printing=False, early_stopping=False, kernel="bm", graph=None):
+def LearnGPCV(train_x, train_y, train_iters=1000, printing=False, early_stopping=False, kernel="bm", graph=None, *,
+              param="exp", K=1, train_likelihood=False):
     """voltron/train_utils.py:15-67: the volatility path of a price series from a variational GP (BM or FBM prior over
     log-vol, ``y | f ~ N(0, exp f)``) fitted to the scaled returns; one HIP ELBO step per iteration.
-    train_y [N+1] prices -> pred_scale [N]; train_y [T,N+1] fits T series at once (batched parameters)."""
+    train_y [N+1] prices -> pred_scale [N]; train_y [T,N+1] fits T series at once (batched parameters).
+    ``param``, ``K``, ``train_likelihood``: the copula-process likelihood, see FitGPCV."""
     graph = _auto_graph(graph, train_y[..., 1:], n3_coeff=5.0 / 3.0)   # (only the fitted scale is returned: nothing per-iteration is lost)
-    model, likelihood, _ = FitGPCV(train_x, train_y, train_iters=train_iters, printing=printing, kernel=kernel, graph=graph)
+    model, likelihood, _ = FitGPCV(train_x, train_y, train_iters=train_iters, printing=printing, kernel=kernel, graph=graph,
+                                   param=param, K=K, train_likelihood=train_likelihood)
     return likelihood(model(train_x), return_gaussian=False).scale.mean(0).detach()      # :60-67
 
 

@@ -1,4 +1,5 @@
-"""Variational-GP plumbing of the GPCV stage, backed by volt_gpcv_step_f32.
+"""Variational-GP plumbing of the GPCV stage, backed by volt_gpcv_step_f32 ("exp" likelihood),
+volt_gpcv_cv_step_f32 ("cv") and volt_gpcv_mt_step_f32 (the multi-task model).
 
 The reference builds this stage from gpytorch parts (voltron/train_utils.py:20-44,
 voltron/models/single_task_variational_gp.py:69-122): ``CholeskyVariationalDistribution`` +
@@ -53,13 +54,13 @@ class num_gauss_hermite_locs:
 _GH_CACHE = {}
 
 
-def _gauss_hermite(n, device):
+def _gauss_hermite(n, device, dtype=torch.float32):
     """GaussHermiteQuadrature1D's nodes and weights (numpy hermgauss), weights pre-divided by sqrt(pi)."""
-    key = (n, str(device))
+    key = (n, str(device), dtype)
     if key not in _GH_CACHE:
         x, w = np.polynomial.hermite.hermgauss(n)
-        _GH_CACHE[key] = (torch.tensor(x, dtype=torch.float32, device=device),
-                          torch.tensor(w / math.sqrt(math.pi), dtype=torch.float32, device=device))
+        _GH_CACHE[key] = (torch.tensor(x, dtype=dtype, device=device),
+                          torch.tensor(w / math.sqrt(math.pi), dtype=dtype, device=device))
     return _GH_CACHE[key]
 
 
@@ -122,6 +123,16 @@ class VariationalLatent(MultivariateNormal):
         return self.loc.detach() + f.transpose(0, 1).reshape(base_samples.shape)
 
 
+def _dkl_dscale_grad(o, c, n, w_kl, g):
+    """dF/dc for K = c M + j I from the step's scalars o = out[:, 2:9]:
+    tr(K^-1 M) = (N - j tr K^-1)/c,  tr(G'MG) = (tr(K^-1 S) - j |G|^2)/c,  beta'M beta = (r'K^-1 r - j |beta|^2)/c;
+    dKL/dc = 1/2 (first - second - third)."""
+    quad, tr_s, tr_inv, gg, bb = o[:, 0], o[:, 3], o[:, 4], o[:, 5], o[:, 6]
+    j = PRIOR_JITTER
+    dkl = 0.5 * ((n - j * tr_inv) - (tr_s - j * gg) - (quad - j * bb)) / c.reshape(-1)
+    return (-w_kl * g * dkl).reshape(c.shape) if c.numel() == g.numel() else (-w_kl * g * dkl).sum().reshape(c.shape)
+
+
 class _GPCVElbo(torch.autograd.Function):
     """F[b] = w_ell ell_b - w_kl KL_b with the analytic gradient the HIP step returns."""
 
@@ -163,15 +174,61 @@ class _GPCVElbo(torch.autograd.Function):
         gK = g2 * sv[3] if ctx.want_dk else None
         gscale = None
         if ctx.has_scale:
-            # K = c M + j I:  tr(K^-1 M) = (N - j tr K^-1)/c,  tr(G'MG) = (tr(K^-1 S) - j |G|^2)/c,
-            #                 beta'M beta = (r'K^-1 r - j |beta|^2)/c;   dKL/dc = 1/2 (first - second - third)
-            o, c = sv[-2], sv[-1]
-            quad, tr_s, tr_inv, gg, bb = o[:, 0], o[:, 3], o[:, 4], o[:, 5], o[:, 6]
-            j = PRIOR_JITTER
-            dkl = 0.5 * ((ctx.n - j * tr_inv) - (tr_s - j * gg) - (quad - j * bb)) / c.reshape(-1)
-            gscale = (-ctx.w_kl * g * dkl).reshape(c.shape) if c.numel() == g.numel() else \
-                (-ctx.w_kl * g * dkl).sum().reshape(c.shape)
+            gscale = _dkl_dscale_grad(sv[-2], sv[-1], ctx.n, ctx.w_kl, g)
         return g1 * gm, g2 * gL, g1 * gmu, gK, None, None, gscale, None, None, None
+
+
+class _GPCVCvElbo(torch.autograd.Function):
+    """``_GPCVElbo`` for the copula-process ("cv") likelihood: F[b] = w_ell ell_b - w_kl KL_b with
+    scale(f) = sum_k a_k softplus(b_k f + c_k), a = softplus(raw_a), b = 3 sigmoid(raw_b), c = 6 sigmoid(raw_c) - 3
+    (volatility_likelihood.py:24-26).  The HIP step returns dF/d(a,b,c); the constraints' chain rule is applied here.
+    raw_a, raw_b, raw_c are [Kc] (one likelihood for every series: its gradient sums over them) or [B,Kc]."""
+
+    @staticmethod
+    def forward(ctx, m, Lq, mean, K, y, raw_a, raw_b, raw_c, holder, scale, num_gh, w_ell, w_kl):
+        B, n = m.shape
+        want_dk = bool(ctx.needs_input_grad[3])
+        gh_x, gh_w = _gauss_hermite(num_gh, m.device)
+        Kc = raw_a.shape[-1]
+        ws = holder.workspace(B, n, want_dk, m.device, Kc=Kc)
+        sa, sb, sc = torch.sigmoid(raw_a.detach()), torch.sigmoid(raw_b.detach()), torch.sigmoid(raw_c.detach())
+        abc = torch.stack([torch.nn.functional.softplus(raw_a.detach()), 3.0 * sb, 6.0 * sc - 3.0], -2)     # [..., 3, Kc]
+        ops.gpcv_cv_step(K.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y,
+                         abc.to(torch.float32).expand(B, 3, Kc), gh_x, gh_w, ws, want_dk=want_dk, jitter=PRIOR_JITTER,
+                         min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
+        chk = gp.deferred_checks.deferring()
+        if chk is None and gp.deferred_checks._active is not None:
+            gp.deferred_checks._active.reserve(ws.info)
+        if chk is not None:
+            chk.note(ws.info)
+        elif bool((ws.info != 0).any().item()):
+            _raise_step_failure("GPCV cv step", ws.info, (K, m, Lq, abc), "prior covariance K + 1e-3 I")
+        ctx.n, ctx.w_kl, ctx.has_scale, ctx.want_dk = n, w_kl, scale is not None, want_dk
+        ctx.shared = raw_a.ndim == 1
+        ctx.raw_shape = raw_a.shape
+        # d a / d raw_a = sigmoid(raw_a);  d b / d raw_b = 3 s (1 - s);  d c / d raw_c = 6 s (1 - s)
+        jac = torch.stack([sa, 3.0 * sb * (1.0 - sb), 6.0 * sc * (1.0 - sc)], -2)
+        saved = [ws.grad_m.clone(), ws.grad_Lq.clone(), ws.grad_mu.clone(), ws.grad_abc * jac]
+        if want_dk:
+            saved.append(ws.grad_K.clone())
+        if scale is not None:
+            saved += [ws.out[:, 2:9].clone(), scale.detach().clone()]
+        ctx.save_for_backward(*saved)
+        return ws.out[:, 9].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        sv = list(ctx.saved_tensors)
+        gm, gL, gmu, graw = sv[:4]
+        g1, g2 = g.reshape(-1, 1), g.reshape(-1, 1, 1)
+        gK = g2 * sv[4] if ctx.want_dk else None
+        gscale = None
+        if ctx.has_scale:
+            gscale = _dkl_dscale_grad(sv[-2], sv[-1], ctx.n, ctx.w_kl, g)
+        graw = g2 * graw                                              # [B,3,Kc]
+        graw = graw.sum(0) if ctx.shared else graw.transpose(0, 1)    # [3,Kc] / [3,B,Kc]
+        ga, gb, gc = (graw[i].reshape(ctx.raw_shape) for i in range(3))
+        return g1 * gm, g2 * gL, g1 * gmu, gK, None, ga, gb, gc, None, gscale, None, None, None
 
 
 class MultitaskVariationalLatent(MultivariateNormal):
@@ -287,18 +344,24 @@ class VariationalELBO(Module):
         super().__init__()
         if not combine_terms:
             raise NotImplementedError("combine_terms=False is not used on this path (train_utils.py:44)")
-        if getattr(likelihood, "param", "exp") != "exp":
-            raise NotImplementedError('only the "exp" volatility likelihood has an accelerated ELBO (train_utils.py:20)')
+        param = getattr(likelihood, "param", "exp")
+        if param not in ("exp", "cv"):
+            raise NotImplementedError(f"unknown volatility likelihood parameterisation {param!r}")
+        if param == "cv" and hasattr(model, "variational_task_covar_root"):      # MultitaskVariationalGP
+            raise NotImplementedError('the multi-task model has an accelerated ELBO for the "exp" volatility likelihood only; '
+                                      '"cv" runs on SingleTaskVariationalGP')
+        if param == "cv" and not 1 <= likelihood.raw_a.shape[-1] <= ops.GPCV_CV_K_MAX:
+            raise NotImplementedError(f'the accelerated "cv" ELBO takes 1 <= K <= {ops.GPCV_CV_K_MAX} warp terms')
         object.__setattr__(self, "likelihood", likelihood)
         object.__setattr__(self, "model", model)
         self.num_data, self.beta = float(num_data), float(beta)
         self._ws = None
         self._mt_ws = None
 
-    def workspace(self, B, n, want_dk, device):
+    def workspace(self, B, n, want_dk, device, Kc=0):
         ws = self._ws
-        if ws is None or ws.B != B or ws.N != n or ws.want_dk != bool(want_dk) or ws.buf.device != device:
-            self._ws = ws = ops.GpcvWorkspace(B, n, want_dk, device)
+        if ws is None or ws.B != B or ws.N != n or ws.want_dk != bool(want_dk) or ws.buf.device != device or ws.Kc != Kc:
+            self._ws = ws = ops.GpcvWorkspace(B, n, want_dk, device, Kc=Kc)
         return ws
 
     def mt_workspace(self, n, T, want_dk, device):
@@ -352,6 +415,18 @@ class VariationalELBO(Module):
             K3 = (scale.detach().reshape(-1, 1, 1) * lazy.base).expand(B, n, n)
         else:
             K3 = _dense(lazy).expand(B, n, n) if _dense(lazy).ndim == 2 else _dense(lazy).reshape(-1, n, n)
+        lik = self.likelihood
+        if getattr(lik, "param", "exp") == "cv":
+            Kc = lik.raw_a.shape[-1]
+            raws = [lik.raw_a, lik.raw_b, lik.raw_c]
+            if lik.raw_a.ndim > 1:                                   # batched likelihood: one parameter set per series
+                if lik.raw_a.numel() != B * Kc:
+                    raise ValueError(f"VariationalELBO: the likelihood's batch shape {tuple(lik.raw_a.shape[:-1])} does not "
+                                     f"match the model's {tuple(m.shape[:-1])}")
+                raws = [r.reshape(B, Kc) for r in raws]
+            res = _GPCVCvElbo.apply(m2.to(torch.float32), L3.to(torch.float32), mean2.to(torch.float32), K3, y2, *raws, self,
+                                    scale, num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data)
+            return res.reshape(m.shape[:-1]) if batched else res.reshape(())
         res = _GPCVElbo.apply(m2.to(torch.float32), L3.to(torch.float32), mean2.to(torch.float32), K3, y2, self, scale,
                               num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data)
         return res.reshape(m.shape[:-1]) if batched else res.reshape(())
