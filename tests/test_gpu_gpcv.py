@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import spd_families
 from oracle import gpcv_oracle as GO
 from volt_amd.synthetic import sde_series
 
@@ -26,8 +27,24 @@ def _problem(n, seed, dtype=torch.float64):
     return x, yy, m, Lq, c0.reshape(1)
 
 
+def _prior(kernel, x, vol, seed):
+    """The prior covariance of one series, fp64.  "bm" / "fbm": the model's kernels, whose Cholesky factor has rank-one blocks
+    below the diagonal (K = vol^2 min(x_i, x_j): tests/spd_families.py).  "rbf" / "wishart": priors without that structure --
+    rbf_irregular as it is, wishart scaled by 2^-5 to the Brownian-motion prior's magnitude (0.2^2 x: up to 0.06 at n = 399);
+    both exactly representable in fp32."""
+    if kernel in ("bm", "fbm"):
+        return GO.bm_cov(x, vol) if kernel == "bm" else GO.fbm_cov(x, vol)
+    n = x.shape[0]
+    if kernel == "rbf":
+        return torch.as_tensor(spd_families.rbf_irregular(1, n, seed=seed)[0])
+    return torch.as_tensor(spd_families.wishart(1, n, seed=seed)[0]) * 2.0 ** -5
+
+
+GENERIC_SHAPES = [(399, 2, "rbf"), (640, 2, "rbf"), (399, 2, "wishart"), (640, 2, "wishart")]
+
+
 @pytest.mark.parametrize("n,B,kernel", [(200, 1, "bm"), (399, 3, "bm"), (512, 2, "bm"), (300, 2, "fbm"),
-                                        (33, 1, "bm"), (129, 2, "bm"), (257, 1, "fbm"), (640, 9, "bm")])
+                                        (33, 1, "bm"), (129, 2, "bm"), (257, 1, "fbm"), (640, 9, "bm")] + GENERIC_SHAPES)
 def test_gpcv_step_matches_oracle(n, B, kernel):
     from volt_amd import ops
     dev = "cuda:0"
@@ -35,10 +52,10 @@ def test_gpcv_step_matches_oracle(n, B, kernel):
     raw_vol = torch.logit(torch.tensor([0.2], dtype=torch.float64))
     gh_x, gh_w = GO.gauss_hermite(75)
     Ks, vals, grads, terms = [], [], [], []
-    for (x, yy, m, Lq, c) in probs:
+    for b, (x, yy, m, Lq, c) in enumerate(probs):
         ps = [t.clone().requires_grad_(True) for t in (m, Lq, c)]
         vol = torch.sigmoid(raw_vol)
-        K = (GO.bm_cov(x, vol) if kernel == "bm" else GO.fbm_cov(x, vol)).detach().requires_grad_(True)
+        K = _prior(kernel, x, vol, 2019 + b).detach().requires_grad_(True)
         t = GO.elbo_terms(ps[0], ps[1], ps[2], K, yy, gh_x, gh_w)
         g = torch.autograd.grad(t["elbo"], ps + [K])
         Ks.append(K.detach())

@@ -13,12 +13,12 @@ import torch
 
 import gpcv_cv_ref as R
 from oracle import gpcv_oracle as GO
-from test_gpu_gpcv import _prices, _problem
+from test_gpu_gpcv import GENERIC_SHAPES, _prices, _prior, _problem
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SHAPES = [(200, 1, "bm"), (399, 3, "bm"), (512, 2, "bm"), (300, 2, "fbm"), (33, 1, "bm"), (129, 2, "bm"), (257, 1, "fbm"),
-          (640, 9, "bm")]                                    # test_gpcv_step_matches_oracle's
+          (640, 9, "bm")] + GENERIC_SHAPES                   # test_gpcv_step_matches_oracle's
 
 
 def _reference(n, B, kernel, Kc, root_scale=1.0):
@@ -32,7 +32,7 @@ def _reference(n, B, kernel, Kc, root_scale=1.0):
         abc = torch.stack(R.constrain(*R.draw_raw(Kc, 7000 + 31 * b + Kc)))     # [3,Kc] transformed
         ps = [t.clone().requires_grad_(True) for t in (m, Lq, c, abc)]
         vol = torch.sigmoid(raw_vol)
-        K = (GO.bm_cov(x, vol) if kernel == "bm" else GO.fbm_cov(x, vol)).detach().requires_grad_(True)
+        K = _prior(kernel, x, vol, 2019 + b).detach().requires_grad_(True)
         t = dict(GO.elbo_terms(ps[0], ps[1], ps[2], K, yy, gh_x, gh_w))         # KL and its pieces
         e, clamped = R.ell(ps[0], ps[1], yy, ps[3][0], ps[3][1], ps[3][2], gh_x, gh_w)
         t.update(ell=e, elbo=e / n - t["kl"] / n)
