@@ -4,7 +4,7 @@
  *
  * Environment knobs.  The schedule defaults below are compiled in and were measured on MI355X; a
  * deployment reads NO environment variable.  Only a process started with VOLT_TUNE=1 (the experiment scripts) may
- * override them, through ONE table read once per process (csrc/chol.hip `tunables()`, csrc/chol64.hip `tune_int`):
+ * override them, through ONE table read once per process (csrc/host.h `Tunables`, filled by csrc/chol.hip `tunables()`):
  *   VOLT_GROUPS            stream groups for batches >= 16 (2)        VOLT_SPLITK_TARGET  workgroups per split launch (512)
  *   VOLT_SPLITK_MINL       shortest K-slice in blocks (2)            VOLT_SPLITK_MAXS    most slices per tile (8)
  *   VOLT_SPLITK_GROUPS / _MAXB   two split groups for 10 <= B < 22   VOLT_SCHED          balanced schedule on/off (1)
@@ -31,7 +31,7 @@
  *                          leave at once (their queues are adopted): tests/test_gpu_topology.py
  *   VOLT_ROLLOUT_LANE      rollouts: one lane per path (1; 0: the wave-per-path engine everywhere)
  *   VOLT_F64_LOOKAHEAD     fp64 factorisation: look-ahead depth of the chain / bulk multi-stream schedule, 0 = one stream,
- *                          1 = one column, 2 = two columns (2 from 6 matrices on, else 1)           (read in csrc/chol64.hip)
+ *                          1 = one column, 2 = two columns (2 from 6 matrices on, else 1)           (used in csrc/chol64.hip)
  *   VOLT_F64_TRTRI_LOOKAHEAD  fp64 inverse: one-row look-ahead on its own stream, 0 / 1 (on up to 4 matrices)
  *   VOLT_F64_SPREAD        fp64: launches of up to this many workgroups run one workgroup per CU (512)
  *   VOLT_F64_SPLIT_TARGET  fp64: workgroups per K-sliced launch (512)

@@ -491,48 +491,41 @@ bool volt_internal_batch64_applies(int B, int n, int has_y) {
     return tiles <= tn.batch64_max;
 }
 
+static size_t batch64_prog_bytes(int B, int n) {               // progress words of every matrix, then the pullers' queue words
+    return al256(((size_t)B * batch64_pstride(n) + BATCH_QWORDS) * sizeof(int));
+}
 size_t volt_internal_batch64_bytes(int B, int n, int has_y) {
-    if (!volt_internal_batch64_applies(B, n, has_y)) return 0;
-    return (((size_t)B * batch64_pstride(n) + BATCH_QWORDS) * sizeof(int) + 255) & ~(size_t)255;   // progress words, then the pullers' queue words
+    return volt_internal_batch64_applies(B, n, has_y) ? batch64_prog_bytes(B, n) : 0;
+}
+
+// Clear the progress words (and the error words: info, or the inverse's ierr), then the one launch: as many pullers as the chip
+// holds at once -- one per CU (the image's LDS); nothing depends on the number.  Returns 1: enqueued, 0: too many pieces for
+// this schedule, a HIP error otherwise.
+static int batch64_launch(const Batch64Args& args, int64_t npieces, int tri_n, hipStream_t s) {
+    const int B = args.B, nprog = B * args.pstride + BATCH_QWORDS;
+    hipLaunchKernelGGL(batch64_begin_kernel, dim3(begin_grid(B, nprog)), dim3(256), 0, s, args.info, B, args.prog, nprog, tri_n, args.pstride,
+                       B * args.pstride);
+    if (npieces > 0x7fffffff) return 0;
+    const bool local = batch_local_handoffs(B);
+    const unsigned grid = (unsigned)std::min<int64_t>(npieces, tunables().batch_pullers > 0 ? (int64_t)tunables().cus * tunables().batch_pullers : npieces);
+    const int xskew = tunables().batch_xskew, xdrop = tunables().batch_xdrop;
+    auto* const kernel = local ? batch64_step_kernel<true> : batch64_step_kernel<false>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH64_LDS_BYTES);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), BATCH64_LDS_BYTES, s, args, xskew, xdrop);
+    e = hipGetLastError();
+    return e != hipSuccess ? (int)e : 1;
 }
 
 // Returns 1 when the step was enqueued, 0 when the shape is not this schedule's (nothing enqueued), a HIP error otherwise.
-// src (optional): the caller's K -- the tiles are read from it and A only receives the factor (no copy-in pass).
-int volt_internal_batch64_step(double* A, double* Winv, int* info, double* Y, int B, int Np, void* state, size_t state_bytes,
-                               void* stream, const KSource64* ksrc) {
+// ksrc (optional): the caller's K -- the tiles are read from it and A only receives the factor (no copy-in pass).
+int volt_internal_batch64_step(const StepMats64& m, Region state, const KSource64* ksrc) {
+    const int B = m.B, Np = m.Np, n = Np / TS, has_y = m.Y != nullptr;
     const KSource64 src = ksrc ? *ksrc : KSource64{nullptr, 0, 0, nullptr, 0.0, Np};
-    const int n = Np / TS;
-    const int has_y = Y != nullptr;
-    if (!state || !volt_internal_batch64_applies(B, n, has_y) || state_bytes < volt_internal_batch64_bytes(B, n, has_y)) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    int* prog = reinterpret_cast<int*>(state);
-    const int pstride = batch64_pstride(n), nprog = B * pstride + BATCH_QWORDS;
-    int blocks = (std::max(B, nprog) + 255) / 256;
-    if (blocks > 256) blocks = 256;
-    if (blocks * 256 < B) blocks = (B + 255) / 256;
-    hipLaunchKernelGGL(batch64_begin_kernel, dim3(blocks), dim3(256), 0, s, info, B, prog, nprog, 0, pstride, B * pstride);
-    // eight queues, one per XCD, when the matrices divide among them evenly (the pullers read their XCC id: handoff.h)
-    const bool local = (B & 7) == 0 && tunables().batch_local != 0 && tunables().xccs == 8;
-    const int64_t npieces = batch64_count(B, n, Y != nullptr);
-    if (npieces > 0x7fffffff) return 0;
-    // as many pullers as the chip holds at once: one per CU (the image's LDS); nothing depends on the number
-    const unsigned grid = (unsigned)std::min<int64_t>(npieces, tunables().batch_pullers > 0 ? (int64_t)tunables().cus * tunables().batch_pullers : npieces);
-    const Batch64Args args{A, Winv, Y, info, Np, B, prog, pstride, src, g_batch64_stamps, (int)npieces, 0};
-    const int xskew = tunables().batch_xskew, xdrop = tunables().batch_xdrop;
-    hipError_t e;
-    if (local) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(batch64_step_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, BATCH64_LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(batch64_step_kernel<true>, dim3(grid), dim3(256), BATCH64_LDS_BYTES, s, args, xskew, xdrop);
-    } else {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(batch64_step_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, BATCH64_LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(batch64_step_kernel<false>, dim3(grid), dim3(256), BATCH64_LDS_BYTES, s, args, xskew, xdrop);
-    }
-    e = hipGetLastError();
-    return e != hipSuccess ? (int)e : 1;
+    if (!state.p || !volt_internal_batch64_applies(B, n, has_y) || state.bytes < volt_internal_batch64_bytes(B, n, has_y)) return 0;
+    const int64_t npieces = batch64_count(B, n, has_y);
+    const Batch64Args args{m.A, m.Winv, m.Y, m.info, Np, B, reinterpret_cast<int*>(state.p), batch64_pstride(n), src, g_batch64_stamps, (int)npieces, 0};
+    return batch64_launch(args, npieces, 0, m.stream);
 }
 
 // The triangular inverse alone as one launch: the rows of the inverse are pieces of the one-launch step already
@@ -545,43 +538,18 @@ size_t volt_internal_batch64_trtri_bytes(int B, int n) {
     const Tunables& tn = tunables();
     if (tn.batch64 <= 0 || B < 1 || n < 2 || B > 65535) return 0;
     if (tn.batch64 < 2 && (int64_t)B * (n + 1) > tn.batch64_max) return 0;
-    return ((((size_t)B * batch64_pstride(n) + BATCH_QWORDS) * sizeof(int) + 255) & ~(size_t)255) + (((size_t)B * sizeof(int) + 255) & ~(size_t)255);
+    return batch64_prog_bytes(B, n) + al256((size_t)B * sizeof(int));
 }
 
-int volt_internal_batch64_trtri(const double* A, const double* Winv, double* Y, int B, int Np, void* state, size_t state_bytes,
-                                void* stream) {
+int volt_internal_batch64_trtri(const double* A, const double* Winv, double* Y, int B, int Np, Region state, void* stream) {
     const int n = Np / TS;
     const size_t need = volt_internal_batch64_trtri_bytes(B, n);
-    if (!state || !need || state_bytes < need) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    int* prog = reinterpret_cast<int*>(state);
-    const int pstride = batch64_pstride(n), nprog = B * pstride + BATCH_QWORDS;
-    int* ierr = reinterpret_cast<int*>(reinterpret_cast<char*>(state) + ((((size_t)nprog) * sizeof(int) + 255) & ~(size_t)255));
-    int blocks = (std::max(B, nprog) + 255) / 256;
-    if (blocks > 256) blocks = 256;
-    if (blocks * 256 < B) blocks = (B + 255) / 256;
-    hipLaunchKernelGGL(batch64_begin_kernel, dim3(blocks), dim3(256), 0, s, ierr, B, prog, nprog, n, pstride, B * pstride);
-    const bool local = (B & 7) == 0 && tunables().batch_local != 0 && tunables().xccs == 8;
+    if (!state.p || !need || state.bytes < need) return 0;
+    int* ierr = reinterpret_cast<int*>(reinterpret_cast<char*>(state.p) + batch64_prog_bytes(B, n));
     const int64_t npieces = (int64_t)B * n * (n + 1) / 2;
-    if (npieces > 0x7fffffff) return 0;
-    const unsigned grid = (unsigned)std::min<int64_t>(npieces, tunables().batch_pullers > 0 ? (int64_t)tunables().cus * tunables().batch_pullers : npieces);
     const KSource64 src{nullptr, 0, 0, nullptr, 0.0, Np};
-    const Batch64Args args{const_cast<double*>(A), const_cast<double*>(Winv), Y, ierr, Np, B, prog, pstride, src, g_batch64_stamps, (int)npieces, 1};
-    const int xskew = tunables().batch_xskew, xdrop = tunables().batch_xdrop;
-    hipError_t e;
-    if (local) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(batch64_step_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, BATCH64_LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(batch64_step_kernel<true>, dim3(grid), dim3(256), BATCH64_LDS_BYTES, s, args, xskew, xdrop);
-    } else {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(batch64_step_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, BATCH64_LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(batch64_step_kernel<false>, dim3(grid), dim3(256), BATCH64_LDS_BYTES, s, args, xskew, xdrop);
-    }
-    e = hipGetLastError();
-    return e != hipSuccess ? (int)e : 1;
+    const Batch64Args args{const_cast<double*>(A), const_cast<double*>(Winv), Y, ierr, Np, B, reinterpret_cast<int*>(state.p), batch64_pstride(n), src, g_batch64_stamps, (int)npieces, 1};
+    return batch64_launch(args, npieces, n, (hipStream_t)stream);
 }
 
 extern "C" {

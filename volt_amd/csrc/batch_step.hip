@@ -384,10 +384,10 @@ static int batch_lad(int B) {
 }
 
 static size_t batch_table_bytes(int B, int n, bool has_y) {
-    return ((size_t)(BATCH_HDR + batch_count(B, n, has_y)) * sizeof(BatchItem) + 255) & ~(size_t)255;
+    return al256((size_t)(BATCH_HDR + batch_count(B, n, has_y)) * sizeof(BatchItem));
 }
 static size_t batch_prog_bytes(int B, int n) {                 // progress words of every matrix, then the queue words
-    return (((size_t)B * batch_pstride(n) + BATCH_QWORDS) * sizeof(int) + 255) & ~(size_t)255;
+    return al256(((size_t)B * batch_pstride(n) + BATCH_QWORDS) * sizeof(int));
 }
 
 size_t volt_internal_batch_bytes(int B, int n, int has_y) {
@@ -448,39 +448,32 @@ static const BatchTable* get_batch_table(int B, int n, bool has_y) {
     return bt;
 }
 
-int volt_internal_batch_install(void* state, size_t bytes, int B, int n, int has_y, void* stream) {
-    if (!state || bytes < volt_internal_batch_bytes(B, n, has_y) || !volt_internal_batch_applies(B, n, has_y)) return 0;
+int volt_internal_batch_install(Region state, int B, int n, int has_y, void* stream) {
+    if (!state.p || state.bytes < volt_internal_batch_bytes(B, n, has_y) || !volt_internal_batch_applies(B, n, has_y)) return 0;
     const BatchTable* bt = get_batch_table(B, n, has_y != 0);
     if (!bt) return (int)hipErrorOutOfMemory;
-    hipError_t e = hipMemcpyAsync(state, bt->items, bt->bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
+    hipError_t e = hipMemcpyAsync(state.p, bt->items, bt->bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
     return e != hipSuccess ? (int)e : 0;
 }
 
-// One step: clear the hand-off words, then the one launch.  K != nullptr: tiles read their input from K (A receives L);
-// K == nullptr: A holds the input (volt_potrf_f32).  Y == nullptr: the factorisation alone.  e0 / e1 (optional): events
+// One step: clear the hand-off words, then the one launch.  src.K != nullptr: tiles read their input from K (A receives L);
+// src.K == nullptr: A holds the input (volt_potrf_f32).  m.Y == nullptr: the factorisation alone.  e0 / e1 (optional): events
 // recorded around the step kernel on `stream` (bench.py's roofline leg).  Returns 1 when the step was enqueued, 0 when
 // the shape is not this schedule's (nothing enqueued), a HIP error otherwise.
-int volt_internal_batch_step(const float* K, int64_t ldk, int64_t bsk, const float* sigma2, float jitter, float* A,
-                             float* Winv, float* Y, int* info, const float* rpad, float* zpart, float* frob, int B, int N,
-                             float* z, float* apart, void* state, size_t state_bytes, void* stream, hipEvent_t e0,
-                             hipEvent_t e1) {
-    const int Np = volt_padded_n(N), n = Np / TS;
-    const bool has_y = Y != nullptr;
-    if (!state || !volt_internal_batch_applies(B, n, has_y) || state_bytes < volt_internal_batch_bytes(B, n, has_y)) return 0;
-    if (has_y && (!z || !apart)) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const int4* tab = reinterpret_cast<const int4*>(state);
-    int* prog = reinterpret_cast<int*>(reinterpret_cast<char*>(state) + batch_table_bytes(B, n, has_y));
+int volt_internal_batch_step(const StepMats& m, const KSource& src, const TriReduce& red_in, const StepTail& t, Region state,
+                             hipEvent_t e0, hipEvent_t e1) {
+    const int B = m.B, Np = volt_padded_n(m.N), n = Np / TS;
+    const bool has_y = m.Y != nullptr;
+    if (!state.p || !volt_internal_batch_applies(B, n, has_y) || state.bytes < volt_internal_batch_bytes(B, n, has_y)) return 0;
+    if (has_y && (!t.z || !t.apart)) return 0;
+    hipStream_t s = m.stream;
+    const int4* tab = reinterpret_cast<const int4*>(state.p);
+    int* prog = reinterpret_cast<int*>(reinterpret_cast<char*>(state.p) + batch_table_bytes(B, n, has_y));
     const int pstride = batch_pstride(n), nprog = B * pstride + BATCH_QWORDS, nflags = B * n;
-    int blocks = (std::max(std::max(nflags, B), nprog) + 255) / 256;
-    if (blocks > 256) blocks = 256;
-    if (blocks * 256 < std::max(nflags, B)) blocks = (std::max(nflags, B) + 255) / 256;
-    hipLaunchKernelGGL(batch_begin_kernel, dim3(blocks), dim3(256), 0, s, Winv, nflags, info, B, prog, nprog);
+    hipLaunchKernelGGL(batch_begin_kernel, dim3(begin_grid(std::max(nflags, B), nprog)), dim3(256), 0, s, m.Winv, nflags, m.info, B, prog, nprog);
     const int check = batch_check_word(B, n, has_y);
-    // eight queues, one per XCD, when the matrices divide among them evenly (the pullers read their XCC id: batch_step_kernel)
-    const bool local = (B & 7) == 0 && tunables().batch_local != 0 && tunables().xccs == 8;
-    const KSource src{K, ldk, bsk, sigma2, jitter, N};
-    const TriReduce red{has_y ? rpad : nullptr, zpart, frob, N};
+    const bool local = batch_local_handoffs(B);
+    const TriReduce red{has_y ? red_in.rpad : nullptr, red_in.zpart, red_in.frob, m.N};
     const int64_t npieces = batch_count(B, n, has_y);
     // Few matrices: ONE workgroup per CU (16 KB of dynamic LDS padding).  With two, the diagonal tile -- the latency chain a
     // block column waits for -- shares its CU's LDS and issue slots with a tile in its K loop and takes 80 us instead of 32
@@ -492,13 +485,13 @@ int volt_internal_batch_step(const float* K, int64_t ldk, int64_t bsk, const flo
     // further on, or dry)
     const int64_t slots = (int64_t)tunables().cus * (pad ? 1 : 2) * std::max(1, tunables().batch_pullers);
     const unsigned grid = (unsigned)std::min<int64_t>(npieces, tunables().batch_pullers > 0 ? slots : npieces);
-    const BatchArgs args{A, Winv, Y, info, Np, B, src, red, tab, prog, pstride, z, apart, g_batch_stamps};
+    const BatchArgs args{m.A, m.Winv, m.Y, m.info, Np, B, src, red, tab, prog, pstride, t.z, t.apart, g_batch_stamps};
     const int xskew = tunables().batch_xskew, xdrop = tunables().batch_xdrop;
     if (e0 && hipEventRecord(e0, s) != hipSuccess) return (int)hipGetLastError();
 #define VOLT_BATCH_LAUNCH(FK, LC) \
     hipLaunchKernelGGL((batch_step_kernel<FK, LC>), dim3(grid), dim3(256), pad, s, args, check, (int)npieces, xskew, xdrop)
-    if (K && local) VOLT_BATCH_LAUNCH(true, true);
-    else if (K) VOLT_BATCH_LAUNCH(true, false);
+    if (src.K && local) VOLT_BATCH_LAUNCH(true, true);
+    else if (src.K) VOLT_BATCH_LAUNCH(true, false);
     else if (local) VOLT_BATCH_LAUNCH(false, true);
     else VOLT_BATCH_LAUNCH(false, false);
 #undef VOLT_BATCH_LAUNCH

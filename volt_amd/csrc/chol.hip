@@ -422,14 +422,6 @@ __global__ void tune_empty_kernel(float* A) { if (A == nullptr) A[0] = 0.f; }
 
 using namespace volt;
 
-// batch_step.hip: the whole factorisation in one launch
-size_t volt_internal_batch_bytes(int B, int n, int has_y);
-int volt_internal_batch_install(void* state, size_t bytes, int B, int n, int has_y, void* stream);
-int volt_internal_batch_step(const float* K, int64_t ldk, int64_t bsk, const float* sigma2, float jitter, float* A,
-                             float* Winv, float* Y, int* info, const float* rpad, float* zpart, float* frob, int B, int N,
-                             float* z, float* apart, void* state, size_t state_bytes, void* stream, hipEvent_t e0,
-                             hipEvent_t e1);
-
 static Tunables read_env(Tunables t) {                       // VOLT_TUNE=1 processes only
     auto geti = [](const char* name, int& v) { if (const char* e = getenv(name)) v = atoi(e); };
         geti("VOLT_GROUPS", t.groups);
@@ -473,6 +465,10 @@ static Tunables read_env(Tunables t) {                       // VOLT_TUNE=1 proc
         geti("VOLT_BATCH64", t.batch64);
         geti("VOLT_BATCH64_MAX", t.batch64_max);
         geti("VOLT_BATCH64_MAX_STEP", t.batch64_max_step);
+        geti("VOLT_F64_LOOKAHEAD", t.f64_lookahead);
+        geti("VOLT_F64_TRTRI_LOOKAHEAD", t.f64_trtri_lookahead);
+        geti("VOLT_F64_SPREAD", t.f64_spread);
+        geti("VOLT_F64_SPLIT_TARGET", t.f64_split_target);
         if (const char* e = getenv("VOLT_SCHED_FRAC")) t.sched_frac = (float)atof(e);
         geti("VOLT_FAKE_CUS", t.cus);                        // tests: plan as if the device had this many CUs / XCDs
         geti("VOLT_FAKE_XCCS", t.xccs);
@@ -788,10 +784,7 @@ static void enqueue_step(const Group& g, int Np, int k, LaunchTimer* tm) {
 // info = 0 and every W block's ready flag cleared, on the caller's stream before anything forks from it
 static int begin_factor(float* Winv, int* info, int B, int n, hipStream_t s, int* sk_count = nullptr) {
     const int nflags = B * n, ncount = sk_count ? (n + 1) * (n + 1) * B : 0;   // counters: [n+1 launches][B (n+1) tiles]
-    int blocks = (std::max(std::max(nflags, B), ncount) + 255) / 256;
-    if (blocks > 256) blocks = 256;
-    if (blocks * 256 < std::max(nflags, B)) blocks = (std::max(nflags, B) + 255) / 256;
-    hipLaunchKernelGGL(begin_factor_kernel, dim3(blocks), dim3(256), 0, s, Winv, nflags, info, B, sk_count, ncount);
+    hipLaunchKernelGGL(begin_factor_kernel, dim3(begin_grid(std::max(nflags, B), ncount)), dim3(256), 0, s, Winv, nflags, info, B, sk_count, ncount);
     return 0;
 }
 
@@ -832,13 +825,8 @@ static StreamPool* stream_pool() {
     return pools[dev].ok ? &pools[dev] : nullptr;
 }
 
-// chol64.hip runs its look-ahead on the same pool: one auxiliary stream, the fork event and five of the join events,
-// under the pool's mutex while it enqueues -- like run_factor_groups below.
-struct VoltAux {
-    hipStream_t aux, aux2, aux3, aux4;
-    hipEvent_t fork, ev[12];
-    std::mutex* mu;
-};
+// chol64.hip runs its look-ahead on the same pool (VoltAux, host.h), under the pool's mutex while it enqueues -- like
+// run_factor_groups below.
 bool volt_internal_aux(VoltAux* out) {
     StreamPool* p = stream_pool();
     if (!p) return false;
@@ -856,8 +844,6 @@ static int pick_groups(const StreamPool* pool, int B, int force) {
     while (want > 1 && (B % want != 0 || B / want < 8)) want >>= 1;   // keep whole-XCD groups of >= 8 matrices
     return want;
 }
-
-typedef void (*volt_group_post_fn)(void* ctx, int b0, int Bg, hipStream_t s);
 
 #define VOLT_TRY(call)                              \
     do {                                            \
@@ -994,47 +980,41 @@ static int run_trtri(const float* A, const float* Winv, float* Y, int B, int Np,
 // of at most B diagonal items + 4 slices of B (n + 1) tiles.
 size_t volt_internal_sched_bytes(int B, int n) {
     if (B < 3 || B > 64 || n < 8) return 0;
-    return ((((size_t)(n + 1) * B * (1 + 4 * (size_t)(n + 1)) + SCHED_HDR) * sizeof(SchedItem)) + 255) & ~(size_t)255;
+    return al256(((size_t)(n + 1) * B * (1 + 4 * (size_t)(n + 1)) + SCHED_HDR) * sizeof(SchedItem));
 }
 
 // used by mll.hip (volt_mll_workspace_init_f32)
-int volt_internal_sched_install(void* tab, size_t tab_bytes, int B, int n, int has_y, int cap, void* stream) {
-    return sched_install(tab, tab_bytes, B, n, has_y != 0, cap, (hipStream_t)stream);
+int volt_internal_sched_install(Region tab, int B, int n, int has_y, int cap, void* stream) {
+    return sched_install(tab.p, tab.bytes, B, n, has_y != 0, cap, (hipStream_t)stream);
+}
+
+// block column 0 (its diagonal tile is factored straight out of A) is copied; everything else is read from K
+static FactorOpts factor_from_k(const StepMats& m, const KSource& src, const TriReduce& red, const SplitScratch& sk) {
+    const int Np = volt_padded_n(m.N);
+    hipLaunchKernelGGL(prepare_kernel, dim3(Np / TS, m.B), dim3(256), 0, m.stream, src.K, src.ldk, src.bsk, src.sigma2, src.jitter,
+                       m.A, m.N, Np, 1);
+    return FactorOpts{src, m.Y, red, SplitK{sk.slab, sk.count, 1, 1, sk.rows, (int4*)sk.tab.p, sk.tab.bytes}};
 }
 
 // used by mll.hip
-int volt_internal_factor(const float* K, int64_t ldk, int64_t bsk, const float* sigma2, float jitter, float* A,
-                         float* Winv, float* Y, int* info, const float* rpad, float* zpart, float* frob, int B, int N,
-                         void* stream, volt_group_post_fn post, void* post_ctx, float* sk_slab, int* sk_count, int sk_rows,
-                         void* tab, size_t tab_bytes) {
-    const int Np = volt_padded_n(N), n = Np / TS;
-    hipStream_t s = (hipStream_t)stream;
-    // block column 0 (its diagonal tile is factored straight out of A) is copied; everything else is read from K
-    hipLaunchKernelGGL(prepare_kernel, dim3(n, B), dim3(256), 0, s, K, ldk, bsk, sigma2, jitter, A, N, Np, 1);
-    FactorOpts o{KSource{K, ldk, bsk, sigma2, jitter, N}, Y, TriReduce{rpad, zpart, frob, N},
-                 SplitK{sk_slab, sk_count, 1, 1, sk_rows, (int4*)tab, tab_bytes}};
-    return run_factor_groups(A, Winv, info, B, Np, s, o, post, post_ctx);
+int volt_internal_factor(const StepMats& m, const KSource& src, const TriReduce& red, const SplitScratch& sk,
+                         volt_group_post_fn post, void* post_ctx) {
+    const FactorOpts o = factor_from_k(m, src, red, sk);
+    return run_factor_groups(m.A, m.Winv, m.info, m.B, volt_padded_n(m.N), m.stream, o, post, post_ctx);
 }
 
 // The same, with every launch bracketed by HIP events on its own stream (bench.py's roofline leg through
 // volt_profile_step_f32 in mll.hip): identical buffers, reductions and scratch, so the profiled launches ARE the
 // timed step's -- including, through `post`, the O(N^2) tail each group runs on its own stream beside the other groups'
 // factor launches (it is not timed itself, but it shares the GPU with the launches that are).  Synchronises the stream.
-int volt_internal_profile(const float* K, int64_t ldk, int64_t bsk, const float* sigma2, float* A, float* Winv, float* Y,
-                          int* info, const float* rpad, float* zpart, float* frob, int B, int N, int groups, void* stream,
-                          float* sk_slab, int* sk_count, int sk_rows, void* tab, size_t tab_bytes, volt_group_post_fn post,
-                          void* post_ctx, float* ms_sum_host, float* ms_union_host, int* launches_host,
-                          float* per_launch_host) {
+int volt_internal_profile(const StepMats& m, const KSource& src, const TriReduce& red, const SplitScratch& sk, int groups,
+                          volt_group_post_fn post, void* post_ctx, const ProfileOut& out) {
     if (groups < 0 || groups > MAX_GROUPS) return -11;
-    const int Np = volt_padded_n(N), n = Np / TS;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(prepare_kernel, dim3(n, B), dim3(256), 0, s, K, ldk, bsk, sigma2, 0.f, A, N, Np, 1);
-    FactorOpts o{KSource{K, ldk, bsk, sigma2, 0.f, N}, Y, TriReduce{rpad, zpart, frob, N},
-                 SplitK{sk_slab, sk_count, 1, 1, sk_rows, (int4*)tab, tab_bytes}};
+    const FactorOpts o = factor_from_k(m, src, red, sk);
     LaunchTimer tm;
-    const int rc = run_factor_groups(A, Winv, info, B, Np, s, o, post, post_ctx, &tm, groups);
-    hipError_t e = hipStreamSynchronize(s);            // the groups have joined into s
-    tm.collect(ms_sum_host, ms_union_host, launches_host, 2, per_launch_host);
+    const int rc = run_factor_groups(m.A, m.Winv, m.info, m.B, volt_padded_n(m.N), m.stream, o, post, post_ctx, &tm, groups);
+    hipError_t e = hipStreamSynchronize(m.stream);     // the groups have joined into s
+    tm.collect(out.ms_sum, out.ms_union, out.launches, 2, out.per_launch);
     if (rc) return rc;
     if (e != hipSuccess) return (int)e;
     return tm.err != hipSuccess ? (int)tm.err : 0;
@@ -1114,42 +1094,77 @@ int volt_tune_diag_f32(float* A, float* Winv, int* info, int B, int Np, int k, l
 // launch has only B (n - k + 1) tiles, so even 64 matrices leave CUs idle in the late block columns: up to 31 matrices
 // get the 64 rows the MLL step's workspace has, 32..64 get 128 (two slices per tile for 64 matrices).
 static int potrf_ws_rows(int B) { return B < 32 ? VOLT_SPLITK_SLABS : (B <= 64 ? 2 * VOLT_SPLITK_SLABS : 0); }
-static size_t potrf_ws_slab_bytes(int B, int Np) {
-    return (((size_t)potrf_ws_rows(B) * (Np / TS + 1) * TS * TS * sizeof(float)) + 255) & ~(size_t)255;
+
+// The scratch of B matrices of size Np (a multiple of 128): slabs | counters | balanced tables -- the launch-per-column
+// schedules' -- then the table + progress words of the one-launch factorisation.  ws == nullptr: the sizes alone.
+struct PotrfWs {
+    SplitScratch sk;         // rows == 0: none (more than 64 matrices fill the chip with whole tiles; below three block columns no product is long enough to be cut: slices are >= 2 K-blocks)
+    Region batch;
+    size_t bytes;
+};
+static PotrfWs carve_potrf(void* ws, int B, int Np) {
+    const size_t n = (size_t)Np / TS;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        void* p = ws && bytes ? reinterpret_cast<char*>(ws) + off : nullptr;
+        off += bytes;
+        return Region{p, bytes};
+    };
+    PotrfWs w;
+    w.sk.rows = n < 3 ? 0 : potrf_ws_rows(B);
+    w.sk.slab = reinterpret_cast<float*>(take(w.sk.rows ? al256((size_t)w.sk.rows * (n + 1) * TS * TS * sizeof(float)) : 0).p);
+    w.sk.count = reinterpret_cast<int*>(take(w.sk.rows ? al256((n + 1) * (n + 1) * B * sizeof(int)) : 0).p);
+    w.sk.tab = take(w.sk.rows ? volt_internal_sched_bytes(B, (int)n) : 0);
+    w.batch = take(volt_internal_batch_bytes(B, (int)n, 0));
+    w.bytes = off;
+    return w;
 }
 
-static size_t potrf_ws_count_bytes(int B, int Np) {
-    const size_t n = (size_t)Np / TS;
-    return (((n + 1) * (n + 1) * B * sizeof(int)) + 255) & ~(size_t)255;
-}
-// scratch of the launch-per-column schedules (slabs, counters, balanced tables) ...
-static size_t potrf_ws_sched_bytes(int B, int Np) {
-    if (B < 1 || potrf_ws_rows(B) == 0 || Np < TS || Np % TS) return 0;   // more than 64 matrices fill the chip with whole tiles
-    if (Np / TS < 3) return 0;               // k <= 1: no product is long enough to be cut (slices are >= 2 K-blocks)
-    return potrf_ws_slab_bytes(B, Np) + potrf_ws_count_bytes(B, Np) + volt_internal_sched_bytes(B, Np / TS);
-}
-// ... followed by the table + progress words of the one-launch factorisation (volt_potrf_k_f32 only: tiles read from K)
 size_t volt_potrf_workspace_bytes(int B, int Np) {
     if (B < 1 || Np < TS || Np % TS) return 0;
-    return potrf_ws_sched_bytes(B, Np) + volt_internal_batch_bytes(B, Np / TS, 0);
+    return carve_potrf(nullptr, B, Np).bytes;
 }
 
 int volt_potrf_workspace_init_f32(void* ws, size_t ws_bytes, int B, int Np, void* stream) {
     if (B < 1) return -3;
     if (Np < TS || Np % TS) return -4;
-    const size_t need = volt_potrf_workspace_bytes(B, Np);
-    if (!need) return 0;
+    if (!volt_potrf_workspace_bytes(B, Np)) return 0;
     if (!ws || ((uintptr_t)ws & 255)) return -1;
-    if (ws_bytes < need) return -2;
-    const size_t bb = volt_internal_batch_bytes(B, Np / TS, 0);
-    if (bb) {
-        const int rc = volt_internal_batch_install(reinterpret_cast<char*>(ws) + potrf_ws_sched_bytes(B, Np), bb, B, Np / TS, 0, stream);
+    const PotrfWs w = carve_potrf(ws, B, Np);
+    if (ws_bytes < w.bytes) return -2;
+    if (w.batch.p) {
+        const int rc = volt_internal_batch_install(w.batch, B, Np / TS, 0, stream);
         if (rc) return rc;
     }
-    const size_t tb = potrf_ws_sched_bytes(B, Np) ? volt_internal_sched_bytes(B, Np / TS) : 0;
-    if (!tb) return 0;
-    return sched_install(reinterpret_cast<char*>(ws) + potrf_ws_slab_bytes(B, Np) + potrf_ws_count_bytes(B, Np), tb, B, Np / TS,
-                         false, potrf_ws_rows(B), (hipStream_t)stream);
+    if (!w.sk.tab.p) return 0;
+    return sched_install(w.sk.tab.p, w.sk.tab.bytes, B, Np / TS, false, w.sk.rows, (hipStream_t)stream);
+}
+
+// The body of volt_potrf_ws_f32 (src.K == nullptr: A holds the input, N = Np) and volt_potrf_k_f32 (tiles straight from K).
+// err: the entry's code for a misaligned scratch; err - 1: scratch too small; err - 2: the one-launch step refused its arguments.
+static int potrf_with_scratch(const KSource& src, const StepMats& m, void* ws, size_t ws_bytes, int ws_flags, int err) {
+    const int Np = volt_padded_n(m.N);
+    const bool ready = (ws_flags & VOLT_WS_INITIALISED) != 0;
+    SplitScratch sk{nullptr, nullptr, 0, {}};
+    if (ws) {
+        if (((uintptr_t)ws & 255) != 0) return err;
+        const PotrfWs w = carve_potrf(ws, m.B, Np);
+        if (ws_bytes < w.bytes) return err - 1;
+        // the whole factorisation in one launch (batch_step.hip), on the caller's word that the init ran on this scratch -- with
+        // the tiles read from A itself the same schedule, and so the same bits, as straight from K on the same matrix
+        if (w.batch.p && ready) {
+            KSource bsrc = src;
+            bsrc.N = m.N;
+            const int rc = volt_internal_batch_step(m, bsrc, TriReduce{nullptr, nullptr, nullptr, 0}, StepTail{}, w.batch);
+            if (rc == 1) return 0;
+            if (rc) return rc > 0 ? rc : err - 2;
+        }
+        sk = w.sk;                                           // K-slices and the balanced schedule
+        if (!ready) sk.tab.p = nullptr;                      // the table region is followed only on the caller's word that the init ran on this scratch
+    }
+    if (src.K) return volt_internal_factor(m, src, TriReduce{nullptr, nullptr, nullptr, 0}, sk, nullptr, nullptr);
+    const FactorOpts o{src, nullptr, TriReduce{nullptr, nullptr, nullptr, 0}, SplitK{sk.slab, sk.count, 1, 1, sk.rows, (int4*)sk.tab.p, sk.tab.bytes}};
+    return run_factor_groups(m.A, m.Winv, m.info, m.B, Np, m.stream, o);
 }
 
 int volt_potrf_ws_f32(float* A, float* Winv, int* info, int B, int Np, void* ws, size_t ws_bytes, int ws_flags, void* stream) {
@@ -1159,34 +1174,8 @@ int volt_potrf_ws_f32(float* A, float* Winv, int* info, int B, int Np, void* ws,
     if (B < 0) return -4;
     if (Np < TS || Np % TS) return -5;
     if (B == 0) return 0;
-    SplitK sk{nullptr, nullptr, 1, 1, 0, nullptr, 0};
-    const size_t need = volt_potrf_workspace_bytes(B, Np);
-    if (ws) {
-        if (((uintptr_t)ws & 255) != 0) return -6;
-        if (ws_bytes < need) return -7;
-        // the whole factorisation in one launch (batch_step.hip: the tiles read their input from A itself), on the caller's word
-        // that the init ran on this scratch -- the same schedule, and so the same bits, as volt_potrf_k_f32 on the same matrix
-        const size_t bb = volt_internal_batch_bytes(B, Np / TS, 0);
-        if (bb && (ws_flags & VOLT_WS_INITIALISED)) {
-            const int rc = volt_internal_batch_step(nullptr, 0, 0, nullptr, 0.f, A, Winv, nullptr, info, nullptr, nullptr, nullptr, B, Np,
-                                                    nullptr, nullptr, reinterpret_cast<char*>(ws) + potrf_ws_sched_bytes(B, Np), bb,
-                                                    stream, nullptr, nullptr);
-            if (rc == 1) return 0;
-            if (rc) return rc > 0 ? rc : -8;
-        }
-        if (potrf_ws_sched_bytes(B, Np)) {                       // K-slices and the balanced schedule
-            sk.slab = reinterpret_cast<float*>(ws);
-            sk.count = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + potrf_ws_slab_bytes(B, Np));
-            sk.cap = potrf_ws_rows(B);
-            sk.tab_bytes = volt_internal_sched_bytes(B, Np / TS);
-            // the table region is followed only on the caller's word that volt_potrf_workspace_init_f32 ran on this scratch
-            sk.tab = (sk.tab_bytes && (ws_flags & VOLT_WS_INITIALISED))
-                         ? reinterpret_cast<int4*>(reinterpret_cast<char*>(ws) + potrf_ws_slab_bytes(B, Np) + potrf_ws_count_bytes(B, Np))
-                         : nullptr;
-        }
-    }
-    FactorOpts o{KSource{nullptr, 0, 0, nullptr, 0.f, 0}, nullptr, TriReduce{nullptr, nullptr, nullptr, 0}, sk};
-    return run_factor_groups(A, Winv, info, B, Np, (hipStream_t)stream, o);
+    return potrf_with_scratch(KSource{nullptr, 0, 0, nullptr, 0.f, 0}, StepMats{A, Winv, nullptr, info, B, Np, (hipStream_t)stream}, ws,
+                              ws_bytes, ws_flags, -6);
 }
 
 int volt_potrf_f32(float* A, float* Winv, int* info, int B, int Np, void* stream) {
@@ -1206,36 +1195,8 @@ int volt_potrf_k_f32(const float* K, int64_t ldk, int64_t bsk, const float* sigm
     if (B < 0 || B > 65535) return -9;
     if (N < 1) return -10;
     if (B == 0) return 0;
-    const int Np = volt_padded_n(N), n = Np / TS;
-    SplitK sk{nullptr, nullptr, 1, 1, 0, nullptr, 0};
-    const size_t need = volt_potrf_workspace_bytes(B, Np);
-    if (ws) {
-        if (((uintptr_t)ws & 255) != 0) return -11;
-        if (ws_bytes < need) return -12;
-        // the whole factorisation in one launch (batch_step.hip), on the caller's word that the init ran on this scratch
-        const size_t bb = volt_internal_batch_bytes(B, n, 0);
-        if (bb && (ws_flags & VOLT_WS_INITIALISED)) {
-            const int rc = volt_internal_batch_step(K, ldk, bsk, sigma2, jitter, A, Winv, nullptr, info, nullptr, nullptr, nullptr, B, N,
-                                                    nullptr, nullptr, reinterpret_cast<char*>(ws) + potrf_ws_sched_bytes(B, Np), bb,
-                                                    stream, nullptr, nullptr);
-            if (rc == 1) return 0;
-            if (rc) return rc > 0 ? rc : -13;
-        }
-        if (potrf_ws_sched_bytes(B, Np)) {
-            sk.slab = reinterpret_cast<float*>(ws);
-            sk.count = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + potrf_ws_slab_bytes(B, Np));
-            sk.cap = potrf_ws_rows(B);
-            sk.tab_bytes = volt_internal_sched_bytes(B, Np / TS);
-            // the table region is followed only on the caller's word that volt_potrf_workspace_init_f32 ran on this scratch
-            sk.tab = (sk.tab_bytes && (ws_flags & VOLT_WS_INITIALISED))
-                         ? reinterpret_cast<int4*>(reinterpret_cast<char*>(ws) + potrf_ws_slab_bytes(B, Np) + potrf_ws_count_bytes(B, Np))
-                         : nullptr;
-        }
-    }
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(prepare_kernel, dim3(n, B), dim3(256), 0, s, K, ldk, bsk, sigma2, jitter, A, N, Np, 1);
-    FactorOpts o{KSource{K, ldk, bsk, sigma2, jitter, N}, nullptr, TriReduce{nullptr, nullptr, nullptr, 0}, sk};
-    return run_factor_groups(A, Winv, info, B, Np, s, o);
+    return potrf_with_scratch(KSource{K, ldk, bsk, sigma2, jitter, N}, StepMats{A, Winv, nullptr, info, B, N, (hipStream_t)stream}, ws,
+                              ws_bytes, ws_flags, -11);
 }
 
 int volt_trtri_f32(const float* A, const float* Winv, float* Y, int B, int Np, void* stream) {

@@ -216,22 +216,6 @@ __global__ __launch_bounds__(256, 2) void trtri64_p2_kernel(const double* __rest
 
 using namespace volt;
 
-// chol.hip: the library's stream pool (one auxiliary stream, fork event, two more events, the enqueue mutex)
-struct VoltAux {
-    hipStream_t aux, aux2, aux3, aux4;
-    hipEvent_t fork, ev[12];
-    std::mutex* mu;
-};
-bool volt_internal_aux(VoltAux* out);
-
-// Experiment knobs: compiled-in defaults unless the process was started with VOLT_TUNE=1 (like tunables() in chol.hip)
-static int tune_int(const char* name, int dflt) {
-    static const bool on = [] { const char* t = getenv("VOLT_TUNE"); return t && atoi(t) != 0; }();
-    if (!on) return dflt;
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 #define VOLT_TRY64(call)                            \
     do {                                            \
         hipError_t e__ = (call);                    \
@@ -247,12 +231,10 @@ static int tune_int(const char* name, int dflt) {
 // (slot-count gates are for the full chip: scaled with the device's CU count, host.h)
 static int per_chip(int v) { return (int)((int64_t)v * tunables().cus / 256); }
 static unsigned spread64(int workgroups) {
-    static const int lim = per_chip(tune_int("VOLT_F64_SPREAD", 512));
-    return workgroups <= lim ? 16 * 1024 : 0;
+    return workgroups <= per_chip(tunables().f64_spread) ? 16 * 1024 : 0;
 }
 static int trtri64_slices(int i, int B) {                       // row i: i B tiles of 1 .. i K blocks
-    static const int target = per_chip(tune_int("VOLT_F64_SPLIT_TARGET", 512));
-    int S = target / (i * B);
+    int S = per_chip(tunables().f64_split_target) / (i * B);
     if (S > (i + 1) / 2) S = (i + 1) / 2;
     if (S > 16) S = 16;
     return S < 1 ? 1 : S;
@@ -262,7 +244,7 @@ static int trtri64_slices(int i, int B) {                       // row i: i B ti
 // B <= 4 -1 %, B = 8 10.3 -> 12.0, 16: 17.6 -> 20.3 (from 8 matrices on the inverse is bound by the 128x128 fp64 core's
 // throughput, not by its chain, and one more stream only gets in the factorisation's way): up to 4 matrices.
 static bool trtri64_lookahead(int B) {
-    static const int env = tune_int("VOLT_F64_TRTRI_LOOKAHEAD", -1);
+    const int env = tunables().f64_trtri_lookahead;
     return env >= 0 ? env != 0 : B <= 4;
 }
 static void trtri64_begin(double* Y, int B, int Np, hipStream_t s, bool lookahead = false) {
@@ -292,18 +274,7 @@ static void trtri64_finish(const double* A, const double* Winv, double* Y, int B
     hipLaunchKernelGGL(trtri64_p2_kernel, dim3((i + 1) * B), dim3(256), spread64((i + 1) * B), s, Winv, Y, Np, i, B);
 }
 
-// Factorisation (+ optional triangular inverse Y = L^-T, row k-1 riding on a THIRD stream beside block column k: at
-// small batches the latency chain of the factorisation leaves most CUs idle, and the inverse fills them).
-int volt_internal_factor_f64(double* A, double* Winv, int* info, double* Y, int B, int Np, void* stream, void* state = nullptr,
-                             size_t state_bytes = 0);
-// batch64_step.hip: the one-launch schedule of small batches (state: the progress words, caller scratch)
-bool volt_internal_batch64_applies(int B, int n, int has_y);
-size_t volt_internal_batch64_bytes(int B, int n, int has_y);
-size_t volt_internal_batch64_trtri_bytes(int B, int n);
-int volt_internal_batch64_trtri(const double* A, const double* Winv, double* Y, int B, int Np, void* state, size_t state_bytes,
-                                void* stream);
-int volt_internal_batch64_step(double* A, double* Winv, int* info, double* Y, int B, int Np, void* state, size_t state_bytes,
-                               void* stream, const volt::KSource64* ksrc = nullptr);
+// (volt_internal_factor_f64 below; the one-launch schedule of small batches: batch64_step.hip)
 
 extern "C" {
 
@@ -392,7 +363,7 @@ int volt_trtri_ws_f64(const double* A, const double* Winv, double* Y, int B, int
     if (ws && ((uintptr_t)ws & 255)) return -6;
     if (B == 0) return 0;
     if (ws) {                                                // the whole inverse in one launch (batch64_step.hip)
-        const int rc = volt_internal_batch64_trtri(A, Winv, Y, B, Np, ws, ws_bytes, stream);
+        const int rc = volt_internal_batch64_trtri(A, Winv, Y, B, Np, Region{ws, ws_bytes}, stream);
         if (rc == 1) return 0;
         if (rc != 0) return rc;
     }
@@ -400,7 +371,7 @@ int volt_trtri_ws_f64(const double* A, const double* Winv, double* Y, int B, int
 }
 
 int volt_potrf_f64(double* A, double* Winv, int* info, int B, int Np, void* stream) {
-    return volt_internal_factor_f64(A, Winv, info, nullptr, B, Np, stream);
+    return volt_internal_factor_f64(StepMats64{A, Winv, nullptr, info, B, Np, (hipStream_t)stream});
 }
 
 size_t volt_potrf_workspace_bytes_f64(int B, int Np) {
@@ -410,7 +381,7 @@ size_t volt_potrf_workspace_bytes_f64(int B, int Np) {
 
 int volt_potrf_ws_f64(double* A, double* Winv, int* info, int B, int Np, void* ws, size_t ws_bytes, void* stream) {
     if (ws && ((uintptr_t)ws & 255)) return -6;
-    return volt_internal_factor_f64(A, Winv, info, nullptr, B, Np, stream, ws, ws_bytes);
+    return volt_internal_factor_f64(StepMats64{A, Winv, nullptr, info, B, Np, (hipStream_t)stream}, Region{ws, ws_bytes});
 }
 
 int volt_potrf_k_f64(const double* K, int64_t ldk, int64_t bsk, const double* sigma2, double jitter, double* A, double* Winv,
@@ -424,31 +395,35 @@ int volt_potrf_k_f64(const double* K, int64_t ldk, int64_t bsk, const double* si
     if (N < 1) return -10;
     if (ws && ((uintptr_t)ws & 255)) return -11;
     if (B == 0) return 0;
-    const int Np = volt_padded_n(N);
+    const StepMats64 m{A, Winv, nullptr, info, B, volt_padded_n(N), (hipStream_t)stream};
     if (ws) {                                                         // one launch, the tiles straight from K
         const KSource64 src{K, ldk, bsk, sigma2, jitter, N};
-        const int rc = volt_internal_batch64_step(A, Winv, info, nullptr, B, Np, ws, ws_bytes, stream, &src);
+        const int rc = volt_internal_batch64_step(m, Region{ws, ws_bytes}, &src);
         if (rc != 0) return rc == 1 ? 0 : rc;
     }
     const int rc = volt_prepare_f64(K, ldk, bsk, sigma2, jitter, A, B, N, stream);
     if (rc) return rc;
-    return volt_internal_factor_f64(A, Winv, info, nullptr, B, Np, stream, ws, ws_bytes);
+    return volt_internal_factor_f64(m, Region{ws, ws_bytes});
 }
 
 }  // extern "C"
 
-int volt_internal_factor_f64(double* A, double* Winv, int* info, double* Y, int B, int Np, void* stream, void* state,
-                             size_t state_bytes) {
+// Factorisation (+ optional triangular inverse Y = L^-T, row k-1 riding on a THIRD stream beside block column k: at
+// small batches the latency chain of the factorisation leaves most CUs idle, and the inverse fills them).
+int volt_internal_factor_f64(const StepMats64& m, Region state) {
+    double *const A = m.A, *const Winv = m.Winv, *const Y = m.Y;
+    int* const info = m.info;
+    const int B = m.B, Np = m.Np;
     if (!A) return -1;
     if (!Winv) return -2;
     if (!info) return -3;
     if (B < 0) return -4;
     if (Np < TS || Np % TS) return -5;
     if (B == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = m.stream;
     const int n = Np / TS;
-    if (state) {                                                      // a small batch: the whole schedule as one launch
-        const int rc = volt_internal_batch64_step(A, Winv, info, Y, B, Np, state, state_bytes, stream);
+    if (state.p) {                                                    // a small batch: the whole schedule as one launch
+        const int rc = volt_internal_batch64_step(m, state);
         if (rc != 0) return rc == 1 ? 0 : rc;
     }
     hipError_t e = hipMemsetAsync(info, 0, sizeof(int) * (size_t)B, s);
@@ -467,9 +442,9 @@ int volt_internal_factor_f64(double* A, double* Winv, int* info, double* Y, int 
     // look-ahead depth: 0 = one stream, 1 = one column, 2 = two columns.  Measured (N = 4096, potrf / MLL step, ms, depth 1 ->
     // depth 2): B = 8 6.55 -> 5.87 / 10.6 -> 10.2, B = 16 11.6 -> 9.7 / 19.2 -> 17.6, 32 x 2048 3.81 -> 3.28 / 6.82 -> 6.54; B <= 4
     // potrf +-2 % and the step 1 - 5 % SLOWER (the third stream competes with the rows of the inverse): depth 2 from B = 6
-    static const int look_env = tune_int("VOLT_F64_LOOKAHEAD", -1);
+    const int look_env = tunables().f64_lookahead;
     const int look = look_env >= 0 ? look_env : (B >= 6 ? 2 : 1);
-    static const int target = per_chip(tune_int("VOLT_F64_SPLIT_TARGET", 512));
+    const int target = per_chip(tunables().f64_split_target);
     auto slices = [&](int tiles, int kblocks) {
         int S = tiles > 0 ? target / tiles : 1;
         if (S > kblocks / 2) S = kblocks / 2;                          // a slice is at least two K blocks long

@@ -359,7 +359,6 @@ __global__ __launch_bounds__(256) void gpcv_scalars_kernel(const float* __restri
     }
 }
 
-static inline size_t al256g(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct GpcvWs {
     float *LqT, *W, *Tt, *G, *P, *mllout, *beta, *rowstat, *frobT, *frobG, *cvpart;
@@ -371,10 +370,10 @@ struct GpcvWs {
 // the "exp" layout is a prefix of the "cv" one.
 static GpcvWs carve_gpcv(void* base, int B, int N, int want_dk, int Kc = 0) {
     const size_t Np = (size_t)volt_padded_n(N), n = Np / TS;
-    size_t off = al256g(volt_mll_workspace_bytes(B, N, 1));
+    size_t off = al256(volt_mll_workspace_bytes(B, N, 1));
     auto take = [&](size_t floats) {
         float* p = base ? reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) : nullptr;
-        off += al256g(floats * sizeof(float));
+        off += al256(floats * sizeof(float));
         return p;
     };
     GpcvWs w;

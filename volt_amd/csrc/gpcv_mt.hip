@@ -464,7 +464,6 @@ __global__ __launch_bounds__(256) void mt_dk_kernel(const float* __restrict__ P1
     gK[(int64_t)i * N + j] = -0.5f * wk * (P1[p] - tsc[0] * P2[p]);
 }
 
-static inline size_t al256m(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct MtWs {
     float *LxT, *W, *Tt, *G, *P1, *P2, *Bm, *Rt, *V, *At, *mllout, *beta, *vx, *logd, *rowred, *gm, *colpart, *ellpart,
@@ -476,10 +475,10 @@ struct MtWs {
 
 static MtWs carve_mt(void* base, int N, int T, int want_dk) {
     const size_t Np = (size_t)volt_padded_n(N), n = Np / TS;
-    size_t off = al256m(volt_mll_workspace_bytes(1, N, 1));
+    size_t off = al256(volt_mll_workspace_bytes(1, N, 1));
     auto take = [&](size_t floats) {
         float* p = base ? reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) : nullptr;
-        off += al256m(floats * sizeof(float));
+        off += al256(floats * sizeof(float));
         return p;
     };
     MtWs w;

@@ -3,6 +3,7 @@
 // these are their host-side launchers.
 #pragma once
 #include "common.h"
+#include "host.h"
 
 namespace volt {
 
@@ -26,5 +27,3 @@ int launch_transpose_tri(const float* src, int64_t lds, int64_t bss, float* dst,
                          hipStream_t s);
 
 }  // namespace volt
-
-const float* volt_internal_mll_y(void* workspace, int B, int N);      // mll.hip

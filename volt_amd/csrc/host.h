@@ -1,12 +1,15 @@
-// Host-side internals shared by the translation units of libvolt_hip.so (not part of the C ABI).
+// Host-side internals shared by the translation units of libvolt_hip.so (not part of the C ABI): the tuning table, the
+// argument bundles, and EVERY function that crosses a translation unit -- declared here once, defined in the file named
+// beside it, declared nowhere else.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <mutex>
 
 // Schedule parameters: compiled-in defaults (measured on MI355X).  A deployment reads NO environment:
 // only a process started with VOLT_TUNE=1 (the experiment scripts) may override them through the VOLT_* variables listed in
-// include/volt_hip_tune.h -- read ONCE, here and in chol64.hip's tune_int, nowhere else.
+// include/volt_hip_tune.h -- read ONCE, by read_env in chol.hip when tunables() is first called, nowhere else.
 struct Tunables {
     int groups = 2;                  // stream groups of a large batch (2 >= 4 > 8 with one launch per block column)
     int splitk_target = 512, splitk_minl = 2, splitk_maxs = 8, splitk_groups = 2, splitk_maxb = 22;
@@ -38,6 +41,131 @@ struct Tunables {
     int long_pullers = 1;                      // one long series: this many times the resident workgroups pull its pieces by ticket (0: a workgroup per piece -- they take tickets all the same)
     int rollout_lane = 1;                      // rollouts: one lane per path where the mean's window fits the LDS ring (0: a wave per path everywhere -- the tests compare the two)
     int batch_xskew = 0, batch_xdrop = 0;      // ... tests only: the queues of the XCDs shifted by this many (the map is nobody's assumption); bit x set = the pullers on XCD x leave at once (an XCD a CU mask emptied: its queue is adopted)
+    // ---- chol64.hip's launch-per-column schedules.  The two slot counts are for the full chip: scaled with the CU count where they are used
+    int f64_lookahead = -1;                    // columns of look-ahead: -1 by batch size (one below 6 matrices, two from 6 on), 0 one stream
+    int f64_trtri_lookahead = -1;              // one-row look-ahead of the inverse: -1 up to 4 matrices, 0 off, 1 on
+    int f64_spread = 512;                      // launches of up to this many workgroups run one workgroup per CU
+    int f64_split_target = 512;                // K-sliced launches aim at this many workgroups
 };
-// (the struct continues: what the device looks like, and what follows from it)
-const Tunables& tunables();                    // chol.hip: read once per process (VOLT_TUNE=1 only)
+const Tunables& tunables();                    // chol.hip: the table above after the environment (VOLT_TUNE=1 only) and the device's topology, made once per process
+
+namespace volt {
+
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }   // every region of a workspace starts on a 256-byte boundary
+
+// ---- what the tile bodies read their input from, and the reductions fused into the inverse (plain data: no device code)
+// C tiles of block columns >= 1 come straight from the caller's K (+ sigma2/jitter on the diagonal, identity in the
+// padding) instead of a prepared copy in A, which removes the K -> A copy pass for every block column but the first.
+struct KSource {
+    const float* K;          // nullptr: the working matrix A already holds the input (volt_potrf_f32)
+    int64_t ldk, bsk;
+    const float* sigma2;
+    float jitter;
+    int N;
+};
+// Where the fp64 one-launch step reads a tile of its input from (batch64_step.hip): K == nullptr -- the prepared copy A; else the
+// caller's K (+ sigma2[b] + jitter on the diagonal, identity in the padding): no copy-in pass ahead of the factorisation.
+struct KSource64 {
+    const double* K;
+    int64_t ldk, bsk;
+    const double* sigma2;
+    double jitter;
+    int N;
+};
+// Optional reductions fused into the trtri epilogue (the MLL step needs z = Y'r and ||Y||_F^2; doing
+// them here saves a full pass over Y): zpart[b][j][i*128 + r] = sum_c Y[j*128+c][i*128+r] rvec[j*128+c],
+// frob[b][tile(j,i)] = sum of squares over rows < N.  Deterministic, no atomics.
+struct TriReduce {
+    const float* rpad;   // [B,Np] residual, zero padded; nullptr = no reductions
+    float* zpart;        // [B,n,Np]
+    float* frob;         // [B,n(n+1)/2]
+    int N;
+};
+
+// ---- argument bundles of the functions below (host only; none of them is a kernel argument)
+struct StepMats {            // the matrices of an fp32 step
+    float *A, *Winv, *Y;     // Y == nullptr: the factorisation alone
+    int* info;
+    int B, N;                // N: the series' length (the padded size where A holds the input)
+    hipStream_t stream;
+};
+struct StepMats64 {          // ... of an fp64 one (always padded)
+    double *A, *Winv, *Y;
+    int* info;
+    int B, Np;
+    hipStream_t stream;
+};
+struct StepTail {            // the vectors of a step's O(N^2) tail
+    const float* resid;
+    float *rpad, *z, *apad, *apart, *out, *alpha;
+};
+struct Region {              // a state region of the caller's workspace
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+struct SplitScratch {        // scratch of the K-sliced / balanced launch-per-column schedules
+    float* slab;
+    int* count;
+    int rows;
+    Region tab;              // the balanced schedule's tables (p == nullptr: the workspace was not declared initialised)
+};
+struct ProfileOut {          // volt_profile_step_f32's host outputs
+    float *ms_sum, *ms_union;
+    int* launches;
+    float* per_launch;
+};
+
+// "hand-offs through the XCD's L2": eight queues, one per XCD, when the matrices divide among them evenly (the pullers read their XCC id)
+inline bool batch_local_handoffs(int B) { return (B & 7) == 0 && tunables().batch_local != 0 && tunables().xccs == 8; }
+// grid of a begin kernel (256 threads): a thread of its own for each of the first `direct` words, at most 256 workgroups striding over the rest
+inline int begin_grid(int direct, int strided) {
+    int blocks = ((direct > strided ? direct : strided) + 255) / 256;
+    if (blocks > 256) blocks = 256;
+    if (blocks * 256 < direct) blocks = (direct + 255) / 256;
+    return blocks;
+}
+
+}  // namespace volt
+
+// ---- chol.hip: the launch-per-column schedules, the stream pool
+// runs the factorisation group by group on the library's streams and calls `post` on each group's stream when that
+// group's factor (+ inverse) is enqueued, so the O(N^2) tail of one group overlaps the other groups' MFMA work
+typedef void (*volt_group_post_fn)(void* ctx, int b0, int Bg, hipStream_t s);
+struct VoltAux {             // chol64.hip runs its look-ahead on the pool: auxiliary streams, the fork event, twelve more, the enqueue mutex
+    hipStream_t aux, aux2, aux3, aux4;
+    hipEvent_t fork, ev[12];
+    std::mutex* mu;
+};
+bool volt_internal_aux(VoltAux* out);
+size_t volt_internal_sched_bytes(int B, int n);
+int volt_internal_sched_install(volt::Region tab, int B, int n, int has_y, int cap, void* stream);
+int volt_internal_factor(const volt::StepMats& m, const volt::KSource& src, const volt::TriReduce& red, const volt::SplitScratch& sk,
+                         volt_group_post_fn post, void* post_ctx);
+int volt_internal_profile(const volt::StepMats& m, const volt::KSource& src, const volt::TriReduce& red, const volt::SplitScratch& sk,
+                          int groups, volt_group_post_fn post, void* post_ctx, const volt::ProfileOut& out);
+// ---- one_launch.hip: short series / one long series in one launch.  A step returns 1: enqueued, 0: not this shape's, else a HIP error
+size_t volt_internal_small_bytes(int B, int n);
+int volt_internal_small_install(volt::Region state, int B, int n, void* stream);
+int volt_internal_small_step(const volt::StepMats& m, const volt::KSource& src, const volt::TriReduce& red, const volt::StepTail& t,
+                             volt::Region state);
+size_t volt_internal_long_bytes(int B, int n);
+size_t volt_internal_long_slab_floats(int B, int n);
+int volt_internal_long_install(volt::Region state, int B, int n, void* stream);
+int volt_internal_long_step(const volt::StepMats& m, const volt::KSource& src, const volt::TriReduce& red, const volt::StepTail& t,
+                            float* eslab, volt::Region state);
+// ---- batch_step.hip: the whole batched step in one launch (e0 / e1: events recorded around the step kernel)
+bool volt_internal_batch_applies(int B, int n, int has_y);
+size_t volt_internal_batch_bytes(int B, int n, int has_y);
+bool volt_internal_batch_first();
+int volt_internal_batch_install(volt::Region state, int B, int n, int has_y, void* stream);
+int volt_internal_batch_step(const volt::StepMats& m, const volt::KSource& src, const volt::TriReduce& red, const volt::StepTail& t,
+                             volt::Region state, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// ---- chol64.hip, batch64_step.hip: the fp64 factorisation (+ inverse) launch per column / in one launch (state: its progress words)
+int volt_internal_factor_f64(const volt::StepMats64& m, volt::Region state = {});
+bool volt_internal_batch64_applies(int B, int n, int has_y);
+size_t volt_internal_batch64_bytes(int B, int n, int has_y);
+int volt_internal_batch64_step(const volt::StepMats64& m, volt::Region state, const volt::KSource64* ksrc = nullptr);
+size_t volt_internal_batch64_trtri_bytes(int B, int n);
+int volt_internal_batch64_trtri(const double* A, const double* Winv, double* Y, int B, int Np, volt::Region state, void* stream);
+// ---- mll.hip: gpcv.hip continues from the factor and Y = L^-T the step leaves in its workspace
+const float* volt_internal_mll_y(void* workspace, int B, int N);

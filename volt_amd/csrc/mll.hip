@@ -4,6 +4,7 @@
 // The O(N^2) passes here are HBM-bound streams over Y = L^-T (upper triangle only); the first of them
 // (z = Y'r partials, Frobenius partials) is fused into the trtri epilogue in chol.hip.
 #include "common.h"
+#include "host.h"
 #include "../../include/volt_hip.h"
 #include "../../include/volt_hip_tune.h"
 #include <math.h>
@@ -227,47 +228,14 @@ __global__ __launch_bounds__(256) void refine_finish_kernel(const float* __restr
 }
 
 struct MllWs {
-    float *A, *Winv, *Y, *rpad, *z, *scratch, *apad, *zpart, *frob, *sk_slab, *apart;
-    int sk_rows;
-    int* sk_count;
-    void* tab;               // the balanced schedule's item tables (chol.hip), tab_bytes long
-    size_t tab_bytes;
-    void* small;             // state of the one-launch step for short series (chol.hip), small_bytes long
-    size_t small_bytes;
-    void* lng;               // state of the one-launch step for one long series (chol.hip), lng_bytes long
-    size_t lng_bytes;
+    float *A, *Winv, *Y, *rpad, *z, *scratch, *apad, *zpart, *frob, *apart;
+    SplitScratch sk;         // slab rows, arrival counters and item tables of the K-sliced / balanced schedules (chol.hip)
+    Region small;            // state of the one-launch step for short series (one_launch.hip)
+    Region lng;              // state of the one-launch step for one long series (one_launch.hip)
     float* eslab;            // ... and the slabs of its early-part slices
-    void* batch;             // table + progress words of the one-launch batched step (batch_step.hip), batch_bytes long
-    size_t batch_bytes;
+    Region batch;            // table + progress words of the one-launch batched step (batch_step.hip)
     size_t bytes;
 };
-
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-}  // namespace volt
-size_t volt_internal_sched_bytes(int B, int n);   // chol.hip
-int volt_internal_sched_install(void* tab, size_t tab_bytes, int B, int n, int has_y, int cap, void* stream);
-size_t volt_internal_small_bytes(int B, int n);
-int volt_internal_small_install(void* state, size_t bytes, int B, int n, void* stream);
-int volt_internal_small_step(const float* K, int64_t ldk, int64_t bsk, const float* resid, const float* sigma2,
-                             float jitter, float* A, float* Winv, float* Y, int* info, float* rpad, float* zpart,
-                             float* frob, float* z, float* apad, float* apart, float* out, float* alpha, void* state,
-                             int B, int N, void* stream);
-size_t volt_internal_long_bytes(int B, int n);
-size_t volt_internal_long_slab_floats(int B, int n);
-int volt_internal_long_install(void* state, size_t bytes, int B, int n, void* stream);
-int volt_internal_long_step(const float* K, int64_t ldk, int64_t bsk, const float* resid, const float* sigma2,
-                            float jitter, float* A, float* Winv, float* Y, int* info, float* rpad, float* zpart,
-                            float* frob, float* z, float* apad, float* apart, float* eslab, float* out, float* alpha,
-                            void* state, int B, int N, void* stream);
-size_t volt_internal_batch_bytes(int B, int n, int has_y);   // batch_step.hip
-bool volt_internal_batch_first();
-int volt_internal_batch_install(void* state, size_t bytes, int B, int n, int has_y, void* stream);
-int volt_internal_batch_step(const float* K, int64_t ldk, int64_t bsk, const float* sigma2, float jitter, float* A,
-                             float* Winv, float* Y, int* info, const float* rpad, float* zpart, float* frob, int B, int N,
-                             float* z, float* apart, void* state, size_t state_bytes, void* stream, hipEvent_t e0,
-                             hipEvent_t e1);
-namespace volt {
 
 static MllWs carve(void* base, int B, int N, int want_grad) {
     const size_t Np = (size_t)volt_padded_n(N), n = Np / TS;
@@ -294,24 +262,17 @@ static MllWs carve(void* base, int B, int N, int want_grad) {
     // scratch of the small-batch / balanced schedules (chol.hip): slab rows of (n+1) tiles + arrival counters.  64 rows
     // below 32 matrices; the forward-only step has no trtri rows to fill the late launches with, so it gets 128 rows up to
     // 64 matrices (two slices per tile at 64)
-    w.sk_rows = B < 32 ? 64 : (!want_grad && B <= 64 ? 128 : 0);
-    if (w.sk_rows) {
-        w.sk_slab = take((size_t)w.sk_rows * (n + 1) * TS * TS);
-        w.sk_count = reinterpret_cast<int*>(take((size_t)(n + 1) * (n + 1) * B));
-    } else {
-        w.sk_slab = nullptr;
-        w.sk_count = nullptr;
-    }
-    w.tab_bytes = w.sk_rows ? volt_internal_sched_bytes(B, (int)n) : 0;
-    w.tab = w.tab_bytes ? take(w.tab_bytes / sizeof(float)) : nullptr;
-    w.small_bytes = want_grad ? volt_internal_small_bytes(B, (int)n) : 0;
-    w.small = w.small_bytes ? take(w.small_bytes / sizeof(float)) : nullptr;
-    w.lng_bytes = want_grad ? volt_internal_long_bytes(B, (int)n) : 0;
-    w.lng = w.lng_bytes ? take(w.lng_bytes / sizeof(float)) : nullptr;
-    w.eslab = w.lng_bytes ? take(volt_internal_long_slab_floats(B, (int)n)) : nullptr;
-    w.batch_bytes = volt_internal_batch_bytes(B, (int)n, want_grad);
-    w.apart = (w.small_bytes || w.lng_bytes || (want_grad && w.batch_bytes)) ? take((size_t)B * n * Np) : nullptr;   // alpha's partial sums, per row of the inverse
-    w.batch = w.batch_bytes ? take(w.batch_bytes / sizeof(float)) : nullptr;
+    w.sk.rows = B < 32 ? 64 : (!want_grad && B <= 64 ? 128 : 0);
+    w.sk.slab = w.sk.rows ? take((size_t)w.sk.rows * (n + 1) * TS * TS) : nullptr;
+    w.sk.count = w.sk.rows ? reinterpret_cast<int*>(take((size_t)(n + 1) * (n + 1) * B)) : nullptr;
+    auto region = [&](size_t bytes) { return Region{bytes ? take(bytes / sizeof(float)) : nullptr, bytes}; };
+    w.sk.tab = region(w.sk.rows ? volt_internal_sched_bytes(B, (int)n) : 0);
+    w.small = region(want_grad ? volt_internal_small_bytes(B, (int)n) : 0);
+    w.lng = region(want_grad ? volt_internal_long_bytes(B, (int)n) : 0);
+    w.eslab = w.lng.bytes ? take(volt_internal_long_slab_floats(B, (int)n)) : nullptr;
+    const size_t batch_bytes = volt_internal_batch_bytes(B, (int)n, want_grad);
+    w.apart = (w.small.bytes || w.lng.bytes || (want_grad && batch_bytes)) ? take((size_t)B * n * Np) : nullptr;   // alpha's partial sums, per row of the inverse
+    w.batch = region(batch_bytes);
     w.bytes = off;
     return w;
 }
@@ -319,21 +280,6 @@ static MllWs carve(void* base, int B, int N, int want_grad) {
 }  // namespace volt
 
 using namespace volt;
-
-// chol.hip: runs the factorisation group by group on the library's streams and calls `post` on each group's
-// stream when that group's factor (+ inverse) is enqueued, so the O(N^2) tail of one group overlaps the other
-// groups' MFMA work instead of running after the join.
-typedef void (*volt_group_post_fn)(void* ctx, int b0, int Bg, hipStream_t s);
-int volt_internal_factor(const float* K, int64_t ldk, int64_t bsk, const float* sigma2, float jitter, float* A,
-                         float* Winv, float* Y, int* info, const float* rpad, float* zpart, float* frob, int B, int N,
-                         void* stream, volt_group_post_fn post, void* post_ctx, float* sk_slab, int* sk_count, int sk_rows,
-                         void* tab, size_t tab_bytes);
-
-int volt_internal_profile(const float* K, int64_t ldk, int64_t bsk, const float* sigma2, float* A, float* Winv, float* Y,
-                          int* info, const float* rpad, float* zpart, float* frob, int B, int N, int groups, void* stream,
-                          float* sk_slab, int* sk_count, int sk_rows, void* tab, size_t tab_bytes, volt_group_post_fn post,
-                          void* post_ctx, float* ms_sum_host, float* ms_union_host, int* launches_host,
-                          float* per_launch_host);
 
 namespace {
 struct TailCtx {
@@ -377,6 +323,29 @@ void batch_tail(TailCtx& c, int B, hipStream_t s) {
     hipLaunchKernelGGL(mll_scalars_kernel, dim3(B), dim3(256), 0, s, c.w.A, c.w.z, c.w.apad, c.w.frob, c.sigma2, c.jitter, c.out,
                        c.alpha, c.N, c.Np, 1);
 }
+
+// a step's argument bundles (host.h), straight from the carved workspace
+struct StepArgs {
+    StepMats m;
+    KSource src;
+    TriReduce red;
+    StepTail t;
+};
+StepArgs step_args(const TailCtx& c, const float* K, int64_t ldk, int64_t bsk, const float* resid, int* info, int B, hipStream_t s) {
+    const volt::MllWs& w = c.w;                              // (w.Y, w.zpart, w.frob: nullptr in a forward-only workspace)
+    return {StepMats{w.A, w.Winv, w.Y, info, B, c.N, s}, KSource{K, ldk, bsk, c.sigma2, c.jitter, c.N},
+            TriReduce{w.rpad, w.zpart, w.frob, c.N}, StepTail{resid, w.rpad, w.z, w.apad, w.apart, c.out, c.alpha}};
+}
+void pad_resid(const StepArgs& a, const TailCtx& c) {
+    hipLaunchKernelGGL(pad_resid_kernel, dim3((c.Np + 255) / 256, a.m.B), dim3(256), 0, a.m.stream, a.t.resid, a.t.rpad, c.N, c.Np);
+}
+// batches of longer series: the whole step in one launch (batch_step.hip), then its tail.  1: enqueued, 0: not this shape's
+int try_batch_step(const StepArgs& a, TailCtx& c, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+    pad_resid(a, c);
+    const int rc = volt_internal_batch_step(a.m, a.src, a.red, a.t, c.w.batch, e0, e1);
+    if (rc == 1) batch_tail(c, a.m.B, a.m.stream);
+    return rc;
+}
 }  // namespace
 
 // gpcv.hip continues from the factor and Y = L^-T this step leaves in its workspace
@@ -395,20 +364,12 @@ int volt_mll_workspace_init_f32(void* workspace, int B, int N, int want_grad, vo
     if (N < 1) return -3;
     MllWs w = carve(workspace, B, N, want_grad);
     const int n = volt_padded_n(N) / TS;
-    if (w.small) {
-        const int rc = volt_internal_small_install(w.small, w.small_bytes, B, n, stream);
-        if (rc) return rc;
-    }
-    if (w.lng) {
-        const int rc = volt_internal_long_install(w.lng, w.lng_bytes, B, n, stream);
-        if (rc) return rc;
-    }
-    if (w.batch) {
-        const int rc = volt_internal_batch_install(w.batch, w.batch_bytes, B, n, want_grad, stream);
-        if (rc) return rc;
-    }
-    if (!w.tab) return 0;
-    return volt_internal_sched_install(w.tab, w.tab_bytes, B, n, want_grad, w.sk_rows, stream);
+    int rc;
+    if (w.small.p && (rc = volt_internal_small_install(w.small, B, n, stream))) return rc;
+    if (w.lng.p && (rc = volt_internal_long_install(w.lng, B, n, stream))) return rc;
+    if (w.batch.p && (rc = volt_internal_batch_install(w.batch, B, n, want_grad, stream))) return rc;
+    if (!w.sk.tab.p) return 0;
+    return volt_internal_sched_install(w.sk.tab, B, n, want_grad, w.sk.rows, stream);
 }
 
 int volt_mll_step_f32(const float* K, int64_t ldk, int64_t bsk, const float* resid, const float* sigma2, float jitter,
@@ -430,53 +391,27 @@ int volt_mll_step_f32(const float* K, int64_t ldk, int64_t bsk, const float* res
     if (B == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int Np = volt_padded_n(N);
-    MllWs w = carve(workspace, B, N, want_grad);
-    int rc;
-    bool done = false;
-    if (ready && w.batch && volt_internal_batch_first()) {                          // batches of longer series: the whole step in one launch (batch_step.hip)
-        hipLaunchKernelGGL(pad_resid_kernel, dim3((Np + 255) / 256, B), dim3(256), 0, s, resid, w.rpad, N, Np);
-        rc = volt_internal_batch_step(K, ldk, bsk, sigma2, jitter, w.A, w.Winv, want_grad ? w.Y : nullptr, info, w.rpad, w.zpart,
-                                      w.frob, B, N, w.z, w.apart, w.batch, w.batch_bytes, stream, nullptr, nullptr);
-        if (rc == 1) {
-            TailCtx ctx{w, sigma2, jitter, out, alpha, N, Np, want_grad};
-            batch_tail(ctx, B, s);
-            done = true;
-        } else if (rc) {
-            return rc > 0 ? rc : -1;
-        }
+    TailCtx ctx{carve(workspace, B, N, want_grad), sigma2, jitter, out, alpha, N, Np, want_grad};
+    const MllWs& w = ctx.w;
+    const StepArgs a = step_args(ctx, K, ldk, bsk, resid, info, B, s);
+    int rc = 0;                                              // 1: a one-launch step has been enqueued
+    if (ready && w.batch.p && volt_internal_batch_first()) rc = try_batch_step(a, ctx);
+    if (rc == 0 && ready && want_grad && w.lng.p && w.apart && w.eslab)   // one long series: one launch with sliced early parts (one_launch.hip)
+        rc = volt_internal_long_step(a.m, a.src, a.red, a.t, w.eslab, w.lng);
+    if (rc == 0 && ready && want_grad && w.small.p && w.apart)            // short series: the whole step in one launch (one_launch.hip)
+        rc = volt_internal_small_step(a.m, a.src, a.red, a.t, w.small);
+    if (rc == 0 && ready && w.batch.p) rc = try_batch_step(a, ctx);
+    if (rc == 0) {                                           // a launch per block column (chol.hip), the tail group by group
+        pad_resid(a, ctx);
+        TriReduce red = a.red;
+        if (!want_grad) red.rpad = nullptr;
+        SplitScratch sk = w.sk;
+        if (!ready) sk.tab.p = nullptr;
+        rc = volt_internal_factor(a.m, a.src, red, sk, mll_tail, &ctx);
+    } else if (rc == 1) {
+        rc = 0;
     }
-    if (!done && ready && want_grad && w.lng && w.apart && w.eslab) {  // one long series: one launch with sliced early parts (chol.hip)
-        rc = volt_internal_long_step(K, ldk, bsk, resid, sigma2, jitter, w.A, w.Winv, w.Y, info, w.rpad, w.zpart, w.frob,
-                                     w.z, w.apad, w.apart, w.eslab, out, alpha, w.lng, B, N, stream);
-        if (rc == 1) done = true;
-        else if (rc) return rc > 0 ? rc : -1;
-    }
-    if (!done && ready && want_grad && w.small && w.apart) {   // short series: the whole step in one launch (chol.hip)
-        rc = volt_internal_small_step(K, ldk, bsk, resid, sigma2, jitter, w.A, w.Winv, w.Y, info, w.rpad, w.zpart, w.frob,
-                                      w.z, w.apad, w.apart, out, alpha, w.small, B, N, stream);
-        if (rc == 1) done = true;
-        else if (rc) return rc > 0 ? rc : -1;
-    }
-    if (!done && ready && w.batch) {                          // batches of longer series: the whole step in one launch (batch_step.hip)
-        hipLaunchKernelGGL(pad_resid_kernel, dim3((Np + 255) / 256, B), dim3(256), 0, s, resid, w.rpad, N, Np);
-        rc = volt_internal_batch_step(K, ldk, bsk, sigma2, jitter, w.A, w.Winv, want_grad ? w.Y : nullptr, info, w.rpad, w.zpart,
-                                      w.frob, B, N, w.z, w.apart, w.batch, w.batch_bytes, stream, nullptr, nullptr);
-        if (rc == 1) {
-            TailCtx ctx{w, sigma2, jitter, out, alpha, N, Np, want_grad};
-            batch_tail(ctx, B, s);
-            done = true;
-        } else if (rc) {
-            return rc > 0 ? rc : -1;
-        }
-    }
-    if (!done) {
-        hipLaunchKernelGGL(pad_resid_kernel, dim3((Np + 255) / 256, B), dim3(256), 0, s, resid, w.rpad, N, Np);
-        TailCtx ctx{w, sigma2, jitter, out, alpha, N, Np, want_grad};
-        if ((rc = volt_internal_factor(K, ldk, bsk, sigma2, jitter, w.A, w.Winv, want_grad ? w.Y : nullptr, info,
-                                       want_grad ? w.rpad : nullptr, w.zpart, w.frob, B, N, stream, mll_tail, &ctx, w.sk_slab,
-                                       w.sk_count, w.sk_rows, ready ? w.tab : nullptr, w.tab_bytes)))
-            return rc > 0 ? rc : -1;
-    }
+    if (rc) return rc > 0 ? rc : -1;
     if (want_grad && (flags & VOLT_REFINE_ALPHA)) {
         // one step of iterative refinement (opt-in): fp64-accumulated residual against K, correction through the factor
         hipLaunchKernelGGL(refine_resid_kernel, dim3((Np + 3) / 4, B), dim3(256), 0, s, K, ldk, bsk, resid, alpha, sigma2, jitter,
@@ -504,19 +439,15 @@ int volt_profile_step_f32(const float* K, int64_t ldk, int64_t bsk, const float*
     if (!ms_sum_host) return -14;
     if (!ms_union_host) return -15;
     if (!launches_host) return -16;
-    const int Np = volt_padded_n(N);
-    MllWs w = carve(workspace, B, N, 1);
-    hipLaunchKernelGGL(pad_resid_kernel, dim3((Np + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, resid, w.rpad, N, Np);
-    TailCtx ctx{w, sigma2, 0.f, out, alpha, N, Np, 1};
-    if (groups == 0 && w.batch) {
+    TailCtx ctx{carve(workspace, B, N, 1), sigma2, 0.f, out, alpha, N, volt_padded_n(N), 1};
+    const StepArgs a = step_args(ctx, K, ldk, bsk, resid, info, B, (hipStream_t)stream);
+    if (groups == 0 && ctx.w.batch.p) {
         // the one-launch batched step (batch_step.hip) is what this shape runs: class 0 = that one launch (factorisation AND
         // inverse: the whole step's 2 N^3 / 3), class 1 empty
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return (int)hipGetLastError();
-        int rc = volt_internal_batch_step(K, ldk, bsk, sigma2, 0.f, w.A, w.Winv, w.Y, info, w.rpad, w.zpart, w.frob, B, N, w.z,
-                                          w.apart, w.batch, w.batch_bytes, stream, e0, e1);
+        int rc = try_batch_step(a, ctx, e0, e1);
         if (rc == 1) {
-            batch_tail(ctx, B, (hipStream_t)stream);
             hipError_t e = hipStreamSynchronize((hipStream_t)stream);
             float ms = 0.f;
             if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
@@ -534,9 +465,9 @@ int volt_profile_step_f32(const float* K, int64_t ldk, int64_t bsk, const float*
         return rc;
     }
     // groups > 0 forces that many stream groups and (like the round-2 hook) switches the small-batch schedules off
-    return volt_internal_profile(K, ldk, bsk, sigma2, w.A, w.Winv, w.Y, info, w.rpad, w.zpart, w.frob, B, N, groups, stream,
-                                 w.sk_slab, w.sk_count, w.sk_rows, w.tab, w.tab_bytes, mll_tail, &ctx, ms_sum_host,
-                                 ms_union_host, launches_host, per_launch_host);
+    pad_resid(a, ctx);
+    return volt_internal_profile(a.m, a.src, a.red, ctx.w.sk, groups, mll_tail, &ctx,
+                                 ProfileOut{ms_sum_host, ms_union_host, launches_host, per_launch_host});
 }
 
 }  // extern "C"

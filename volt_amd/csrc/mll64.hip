@@ -6,10 +6,9 @@
 // The O(N^2) passes are HBM streams; the O(N^3) work runs on v_mfma_f64_16x16x4_f64 (chol64.hip).
 #include "common.h"
 #include "tiles64.h"
+#include "host.h"
 #include "../../include/volt_hip.h"
 #include <math.h>
-
-size_t volt_internal_batch64_bytes(int B, int n, int has_y);   // batch64_step.hip
 
 namespace volt {
 
@@ -106,10 +105,9 @@ __global__ __launch_bounds__(256) void mll_scalars64_kernel(const double* __rest
 
 struct Mll64Ws {
     double *A, *Winv, *Y, *rpad, *z, *scratch, *apad, *frob;
-    void* prog;                      // progress words of the one-launch schedule (batch64_step.hip), if the shape is its
-    size_t prog_bytes, bytes;
+    Region prog;                     // progress words of the one-launch schedule (batch64_step.hip), if the shape is its
+    size_t bytes;
 };
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 static Mll64Ws carve64(void* base, int B, int N, int want_grad) {
     const size_t Np = (size_t)volt_padded_n(N), n = Np / TS;
     size_t off = 0;
@@ -127,8 +125,8 @@ static Mll64Ws carve64(void* base, int B, int N, int want_grad) {
     w.apad = take((size_t)B * Np);
     w.Y = want_grad ? take((size_t)B * Np * Np) : nullptr;
     w.frob = want_grad ? take((size_t)B * n * (n + 1) / 2) : nullptr;
-    w.prog_bytes = volt_internal_batch64_bytes(B, (int)n, want_grad);
-    w.prog = w.prog_bytes ? take(w.prog_bytes / sizeof(double)) : nullptr;
+    w.prog.bytes = volt_internal_batch64_bytes(B, (int)n, want_grad);
+    w.prog.p = w.prog.bytes ? take(w.prog.bytes / sizeof(double)) : nullptr;
     w.bytes = off;
     return w;
 }
@@ -136,11 +134,6 @@ static Mll64Ws carve64(void* base, int B, int N, int want_grad) {
 }  // namespace volt
 
 using namespace volt;
-
-int volt_internal_factor_f64(double* A, double* Winv, int* info, double* Y, int B, int Np, void* stream, void* state,
-                             size_t state_bytes);   // chol64.hip
-int volt_internal_batch64_step(double* A, double* Winv, int* info, double* Y, int B, int Np, void* state, size_t state_bytes,
-                               void* stream, const volt::KSource64* ksrc);   // batch64_step.hip
 
 extern "C" {
 
@@ -168,11 +161,12 @@ int volt_mll_step_f64(const double* K, int64_t ldk, int64_t bsk, const double* r
     hipLaunchKernelGGL(pad_resid64_kernel, dim3((Np + 255) / 256, B), dim3(256), 0, s, resid, w.rpad, N, Np);
     // small / medium batches: factorisation (+ inverse) as ONE launch that reads its tiles straight from K (batch64_step.hip)
     const KSource64 src{K, ldk, bsk, sigma2, jitter, N};
-    rc = w.prog ? volt_internal_batch64_step(w.A, w.Winv, info, want_grad ? w.Y : nullptr, B, Np, w.prog, w.prog_bytes, stream, &src) : 0;
+    const StepMats64 m{w.A, w.Winv, w.Y, info, B, Np, s};         // (w.Y: nullptr in a forward-only workspace)
+    rc = w.prog.p ? volt_internal_batch64_step(m, w.prog, &src) : 0;
     if (rc != 0 && rc != 1) return rc > 0 ? rc : -1;
     // otherwise a prepared copy, then factorisation and (gradient step) the triangular inverse in one multi-stream schedule (chol64.hip)
     if (rc == 0 && (rc = volt_prepare_f64(K, ldk, bsk, sigma2, jitter, w.A, B, N, stream))) return rc > 0 ? rc : -1;
-    if (rc == 0 && (rc = volt_internal_factor_f64(w.A, w.Winv, info, want_grad ? w.Y : nullptr, B, Np, stream, w.prog, w.prog_bytes))) return rc > 0 ? rc : -1;
+    if (rc == 0 && (rc = volt_internal_factor_f64(m, w.prog))) return rc > 0 ? rc : -1;
     if ((rc = volt_trsv_lower_f64(w.A, w.Winv, w.rpad, w.z, w.scratch, B, Np, stream))) return rc > 0 ? rc : -1;
     if (want_grad) {
         if ((rc = volt_trsv_lower_t_f64(w.A, w.Winv, w.z, w.apad, w.scratch, B, Np, stream))) return rc > 0 ? rc : -1;

@@ -1096,35 +1096,30 @@ static bool small_applies(int B, int n) {
 }
 size_t volt_internal_small_bytes(int B, int n) {
     if (!small_applies(B, n)) return 0;
-    return (((size_t)SMALL_HDR + (size_t)B * small_stride(n)) * sizeof(int) + 255) & ~(size_t)255;
+    return al256(((size_t)SMALL_HDR + (size_t)B * small_stride(n)) * sizeof(int));
 }
 static long long* g_small_stamps = nullptr;    // volt_tune_small_stamps
-int volt_internal_small_install(void* state, size_t bytes, int B, int n, void* stream) {
-    if (!state || !small_applies(B, n) || bytes < volt_internal_small_bytes(B, n)) return 0;
+int volt_internal_small_install(Region state, int B, int n, void* stream) {
+    if (!state.p || !small_applies(B, n) || state.bytes < volt_internal_small_bytes(B, n)) return 0;
     const int count = SMALL_HDR + B * small_stride(n);
-    hipLaunchKernelGGL(small_init_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, (int*)state, count, B, n);
+    hipLaunchKernelGGL(small_init_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, (int*)state.p, count, B, n);
     VOLT_LAUNCH_CHECK();
     return 0;
 }
 // 1: the step has been enqueued (one launch);  0: not applicable here (the caller runs the launch-per-column path)
-int volt_internal_small_step(const float* K, int64_t ldk, int64_t bsk, const float* resid, const float* sigma2,
-                             float jitter, float* A, float* Winv, float* Y, int* info, float* rpad, float* zpart,
-                             float* frob, float* z, float* apad, float* apart, float* out, float* alpha, void* state,
-                             int B, int N, void* stream) {
-    const int Np = volt_padded_n(N), n = Np / TS;
-    if (!state || !Y || !apart || !small_applies(B, n)) return 0;    // (state: only passed for a workspace declared initialised)
-    int* base = (int*)state;
+int volt_internal_small_step(const StepMats& m, const KSource& src, const TriReduce& red, const StepTail& t, Region state) {
+    const int B = m.B, Np = volt_padded_n(m.N), n = Np / TS;
+    if (!state.p || !m.Y || !t.apart || !small_applies(B, n)) return 0;    // (state: only passed for a workspace declared initialised)
+    int* base = (int*)state.p;
     const SmallState st{base, base + SMALL_HDR, small_stride(n), g_small_stamps};
-    const KSource src{K, ldk, bsk, sigma2, jitter, N};
-    const TriReduce red{rpad, zpart, frob, N};
-    const SmallTail tl{resid, rpad, z, apad, apart, sigma2, jitter, out, alpha, N};
+    const SmallTail tl{t.resid, t.rpad, t.z, t.apad, t.apart, src.sigma2, src.jitter, t.out, t.alpha, m.N};
     // A pivot chain that shares its CU with another piece's MFMA / LDS traffic runs two to three times slower (64 x 399:
     // 71 us per diagonal block against 22): while every series can still have ~8 pieces resident, a workgroup gets a CU
     // to itself (16 KB of dynamic LDS on top of the 72 KB: one workgroup per 160 KB CU)
     const unsigned pad = B <= tunables().small_pad_maxb ? 16 * 1024 : 0;
     const int grid = B * small_pieces(n);
     const int tickets = grid > tunables().cus * (pad ? 1 : 2);     // more workgroups than the chip holds at once: pieces by ticket
-    hipLaunchKernelGGL(small_step_kernel, dim3(grid), dim3(256), pad, (hipStream_t)stream, A, Winv, Y, info, Np,
+    hipLaunchKernelGGL(small_step_kernel, dim3(grid), dim3(256), pad, m.stream, m.A, m.Winv, m.Y, m.info, Np,
                        B, src, red, st, tl, tickets);
     VOLT_LAUNCH_CHECK();
     return 1;
@@ -1197,7 +1192,7 @@ size_t volt_internal_long_bytes(int B, int n) {
     size_t items;
     int nslabs, ncnt;
     long_sizes(n, items, nslabs, ncnt);
-    return ((long_flag_ints(n, ncnt) * sizeof(int) + 255) & ~(size_t)255) + (((items + n) * sizeof(int4) + 255) & ~(size_t)255);
+    return al256(long_flag_ints(n, ncnt) * sizeof(int)) + al256((items + n) * sizeof(int4));
 }
 size_t volt_internal_long_slab_floats(int B, int n) {
     if (!long_applies(B, n)) return 0;
@@ -1206,33 +1201,29 @@ size_t volt_internal_long_slab_floats(int B, int n) {
     long_sizes(n, items, nslabs, ncnt);
     return (size_t)nslabs * TS * TS;
 }
-int volt_internal_long_install(void* state, size_t bytes, int B, int n, void* stream) {
-    if (!state || !long_applies(B, n) || bytes < volt_internal_long_bytes(B, n)) return 0;
+int volt_internal_long_install(Region state, int B, int n, void* stream) {
+    if (!state.p || !long_applies(B, n) || state.bytes < volt_internal_long_bytes(B, n)) return 0;
     const LongPlanDev* pd = get_long_plan(n, (hipStream_t)stream);
     if (!pd) return 0;
     const int count = (int)long_flag_ints(n, pd->ncnt);
-    hipLaunchKernelGGL(small_init_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, (int*)state, count, 1, n);
+    hipLaunchKernelGGL(small_init_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, (int*)state.p, count, 1, n);
     VOLT_LAUNCH_CHECK();
-    char* tab = reinterpret_cast<char*>(state) + (((size_t)count * sizeof(int) + 255) & ~(size_t)255);
+    char* tab = reinterpret_cast<char*>(state.p) + al256((size_t)count * sizeof(int));
     hipError_t e = hipMemcpyAsync(tab, pd->items, (size_t)(pd->nitems + n) * sizeof(int4), hipMemcpyHostToDevice, (hipStream_t)stream);
     return e != hipSuccess ? (int)e : 0;
 }
 // 1: enqueued (one launch);  0: not applicable (launch-per-column path)
-int volt_internal_long_step(const float* K, int64_t ldk, int64_t bsk, const float* resid, const float* sigma2,
-                            float jitter, float* A, float* Winv, float* Y, int* info, float* rpad, float* zpart,
-                            float* frob, float* z, float* apad, float* apart, float* eslab, float* out, float* alpha,
-                            void* state, int B, int N, void* stream) {
-    const int Np = volt_padded_n(N), n = Np / TS;
-    hipStream_t s = (hipStream_t)stream;
-    if (!state || !Y || !apart || !eslab || !long_applies(B, n)) return 0;   // (state: only for a workspace declared initialised)
+int volt_internal_long_step(const StepMats& m, const KSource& src, const TriReduce& red, const StepTail& t, float* eslab,
+                            Region state) {
+    const int Np = volt_padded_n(m.N), n = Np / TS;
+    hipStream_t s = m.stream;
+    if (!state.p || !m.Y || !t.apart || !eslab || !long_applies(m.B, n)) return 0;   // (state: only for a workspace declared initialised)
     const LongPlanDev* pd = get_long_plan(n, s);
     if (!pd) return 0;
-    int* base = (int*)state;
-    const size_t flag_bytes = (long_flag_ints(n, pd->ncnt) * sizeof(int) + 255) & ~(size_t)255;
-    const KSource src{K, ldk, bsk, sigma2, jitter, N};
-    const TriReduce red{rpad, zpart, frob, N};
-    const SmallTail tl{resid, rpad, z, apad, apart, sigma2, jitter, out, alpha, N};
-    const int4* tab = reinterpret_cast<const int4*>(reinterpret_cast<char*>(state) + flag_bytes);
+    int* base = (int*)state.p;
+    const size_t flag_bytes = al256(long_flag_ints(n, pd->ncnt) * sizeof(int));
+    const SmallTail tl{t.resid, t.rpad, t.z, t.apad, t.apart, src.sigma2, src.jitter, t.out, t.alpha, m.N};
+    const int4* tab = reinterpret_cast<const int4*>(reinterpret_cast<char*>(state.p) + flag_bytes);
     // (xcd_from: the spines-on-XCD-0 variant assumed the grid index -> XCD map; pieces are pulled by ticket now, so it is off)
     const LongState st{base, base + SMALL_HDR, tab, tab + pd->nitems, eslab, g_small_stamps, 0, tunables().long_split};
     // one workgroup per CU (16 KB of LDS padding): a pivot chain that shares its CU runs 1.5 - 3x slower
@@ -1240,7 +1231,7 @@ int volt_internal_long_step(const float* K, int64_t ldk, int64_t bsk, const floa
     // as many pullers as the chip holds at once (nothing depends on the number: the kernel derives its ticket base from it)
     const int pullers = std::min(pd->nitems, tunables().cus * (pad ? 1 : 2) * std::max(1, tunables().long_pullers));
     const int grid = tunables().long_pullers > 0 ? pullers : pd->nitems;
-    hipLaunchKernelGGL(long_step_kernel, dim3(grid), dim3(256), pad, s, A, Winv, Y, info, Np, src, red, st, tl, pd->nitems, 0);
+    hipLaunchKernelGGL(long_step_kernel, dim3(grid), dim3(256), pad, s, m.A, m.Winv, m.Y, m.info, Np, src, red, st, tl, pd->nitems, 0);
     VOLT_LAUNCH_CHECK();
     return 1;
 }

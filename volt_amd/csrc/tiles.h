@@ -4,19 +4,12 @@
 // short and long one-launch steps; batch_step.hip: the whole batched step in one launch).
 #pragma once
 #include "common.h"
+#include "host.h"
 
 namespace volt {
 
 // ----------------------------------------------------------------------------- panel update (diagonal tiles)
-// C tiles of block columns >= 1 come straight from the caller's K (+ sigma2/jitter on the diagonal, identity in the
-// padding) instead of a prepared copy in A, which removes the K -> A copy pass for every block column but the first.
-struct KSource {
-    const float* K;          // nullptr: the working matrix A already holds the input (volt_potrf_f32)
-    int64_t ldk, bsk;
-    const float* sigma2;
-    float jitter;
-    int N;
-};
+// (KSource: host.h)
 
 // Element (gi, gj) of the input matrix: from K (+ sigma2/jitter on the diagonal, identity in the padding), or from A.
 __device__ __forceinline__ float input_elem(const KSource& src, const float* Kb, float add, const float* Ab, int Np,
@@ -655,15 +648,7 @@ __device__ __forceinline__ void diag_body(float* __restrict__ A, float* __restri
 // -- one tri_tile_run (common.h).  grid part: (i+1) * B tiles (j = 0..i; j == i copies W_i^T).
 constexpr int WLD = TS + 4;    // 132-float rows: b128 reads of 16 rows land on 16 distinct slots
 
-// Optional reductions fused into the trtri epilogue (the MLL step needs z = Y'r and ||Y||_F^2; doing
-// them here saves a full pass over Y): zpart[b][j][i*128 + r] = sum_c Y[j*128+c][i*128+r] rvec[j*128+c],
-// frob[b][tile(j,i)] = sum of squares over rows < N.  Deterministic, no atomics.
-struct TriReduce {
-    const float* rpad;   // [B,Np] residual, zero padded; nullptr = no reductions
-    float* zpart;        // [B,n,Np]
-    float* frob;         // [B,n(n+1)/2]
-    int N;
-};
+// (TriReduce, the optional reductions fused into the trtri epilogue: host.h)
 
 // Output tiles are written once and not read again before the next launch: non-temporal stores keep them from
 // displacing the shared operand in L2 (round 2 A/B, git history: reads 1.70 -> 1.67 GB per launch, +0.2 % speed).

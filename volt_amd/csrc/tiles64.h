@@ -2,22 +2,13 @@
 // same bodies): the 128x128 fp64 MFMA core with its chunk pipeline, and the diagonal block (factor + inverse in an LDS image).
 #pragma once
 #include "common.h"
+#include "host.h"
 
 namespace volt {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4_64 __attribute__((ext_vector_type(4)));
-
-// Where the one-launch step reads a tile of its input from (batch64_step.hip): K == nullptr -- the prepared copy A; else the
-// caller's K (+ sigma2[b] + jitter on the diagonal, identity in the padding): no copy-in pass ahead of the factorisation.
-struct KSource64 {
-    const double* K;
-    int64_t ldk, bsk;
-    const double* sigma2;
-    double jitter;
-    int N;
-};
 
 constexpr int SLD64 = SLD / 2;          // 18 doubles per LDS row
 constexpr int BK64 = BK / 2;            // 16 doubles of K per chunk
