@@ -174,6 +174,58 @@ def test_gpcv_stage_refuses_cpu_tensors_and_validates_arguments():
     with pytest.raises(_lib.VoltHipError):
         LearnGPCV(x, torch.rand(51) + 1.0, train_iters=1)
 
+    # volt_gemm_nt_f32: every return code of csrc/gpcv.hip, none of which reaches a launch (the pointers are small integers).
+    # A code is minus the position of the argument it blames; bsc (11), alpha (13) and beta (14) have no condition to fail.
+    def gemm(**kw):
+        a = dict(A=256, lda=128, bsa=0, uplo_a=0, B=256, ldb=128, bsb=0, uplo_b=0, C=256, ldc=128, bsc=0, uplo_c=0,
+                 alpha=1.0, beta=0.0, batch=1, M=128, N=128, K=128, stream=None)
+        assert not set(kw) - set(a)
+        a.update(kw)
+        return L.volt_gemm_nt_f32(*a.values())
+    for code, cases in ((-1, [dict(A=None)]),
+                        (-2, [dict(lda=127), dict(K=256, lda=128), dict(lda=130), dict(A=260)]),   # < K, % 4, misaligned A
+                        (-3, [dict(bsa=2)]),
+                        (-4, [dict(uplo_a=3), dict(uplo_a=-1)]),
+                        (-5, [dict(B=None)]),
+                        (-6, [dict(ldb=124), dict(ldb=129), dict(B=264)]),
+                        (-7, [dict(bsb=6)]),
+                        (-8, [dict(uplo_b=3), dict(uplo_b=-1)]),
+                        (-9, [dict(C=None)]),
+                        (-10, [dict(ldc=127), dict(N=256, ldc=255)]),
+                        (-12, [dict(uplo_c=3), dict(uplo_c=-1)]),
+                        (-15, [dict(batch=-1)]),
+                        (-16, [dict(M=0), dict(M=100), dict(M=-128)]),
+                        (-17, [dict(N=0), dict(N=130, ldc=130)]),
+                        (-18, [dict(K=0), dict(K=64), dict(K=132, lda=132, ldb=132)])):
+        for kw in cases:
+            assert gemm(**kw) == code, (code, kw)
+    assert gemm(batch=0) == 0                                   # nothing to do: no launch
+    assert gemm(batch=0, lda=127) == -2                         # ... but validated all the same
+
+    # volt_ewma_f32(y, bs_y, w, k, out, B, N, stream)
+    def ewma(**kw):
+        a = dict(y=256, bs_y=8, w=256, k=5, out=256, B=1, N=8, stream=None)
+        assert not set(kw) - set(a)
+        a.update(kw)
+        return L.volt_ewma_f32(*a.values())
+    for code, cases in ((-1, [dict(y=None)]), (-3, [dict(w=None)]), (-4, [dict(k=0), dict(k=16385), dict(k=-1)]),
+                        (-5, [dict(out=None)]), (-6, [dict(B=65536), dict(B=-1)]), (-7, [dict(N=0)])):
+        for kw in cases:
+            assert ewma(**kw) == code, (code, kw)
+    assert ewma(B=0) == 0 and ewma(B=0, k=16384) == 0
+    assert ewma(B=0, N=0) == -7
+
+    # volt_adam_step_f32(slots, nslots, total, grad, lr, beta1, beta2, eps, state, stream)
+    def adam(**kw):
+        a = dict(slots=256, nslots=1, total=1, grad=256, lr=0.1, beta1=0.9, beta2=0.999, eps=1e-8, state=256, stream=None)
+        assert not set(kw) - set(a)
+        a.update(kw)
+        return L.volt_adam_step_f32(*a.values())
+    for code, cases in ((-1, [dict(slots=None)]), (-2, [dict(nslots=0), dict(nslots=-1)]), (-3, [dict(total=0), dict(total=-5)]),
+                        (-4, [dict(grad=None)]), (-9, [dict(state=None)])):
+        for kw in cases:
+            assert adam(**kw) == code, (code, kw)
+
 
 def test_reference_call_sites_resolve_through_the_aliases():
     """example.ipynb cells 0 and 8 and train_utils.py reach everything by name: voltron.* and gpytorch.*."""

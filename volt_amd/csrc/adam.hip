@@ -20,9 +20,18 @@ struct AdamSlot {            // one parameter tensor
 
 __global__ __launch_bounds__(256) void adam_kernel(const AdamSlot* __restrict__ slots, int nslots, long long total,
                                                   const float* __restrict__ grad, float lr, float b1, float b2, float eps, int* __restrict__ state) {
-    const int t = state[0] + 1;
-    const float bc1 = 1.f - __powf(b1, (float)t), bc2 = 1.f - __powf(b2, (float)t);
-    const float step = lr / bc1, rs2 = 1.f / sqrtf(bc2);
+    // The bias corrections 1 - b^t cancel at small t (1 - 0.999^1 keeps 10 of fp32's 24 bits, and a fast powf fewer), and
+    // every element's update is proportional to them: one thread forms them in double, as torch.optim.Adam does on the host.
+    __shared__ int t_sh;
+    __shared__ float step_sh, rs2_sh;
+    if (threadIdx.x == 0) {
+        t_sh = state[0] + 1;
+        step_sh = (float)((double)lr / (1.0 - pow((double)b1, (double)t_sh)));
+        rs2_sh = (float)(1.0 / sqrt(1.0 - pow((double)b2, (double)t_sh)));
+    }
+    __syncthreads();
+    const int t = t_sh;
+    const float step = step_sh, rs2 = rs2_sh;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
         int s = 0;
         while (s + 1 < nslots && e >= slots[s].end) ++s;
