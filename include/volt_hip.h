@@ -374,6 +374,36 @@ int volt_kron_epilogue_f64(const double* raw_vol, const double* covar_factor, co
                            const double* out, const double* alpha, const double* state, double* res, int N, int T,
                            void* stream);
 
+/* ---- Path summaries  (voltron/option_utils.py:26-52 ECDF / Pricer; the weather calibration notebook's per-step ECDF, mean and
+ * std) -- what every consumer of a rollout computes on the host after samples.cpu(), here on the device.
+ * For every series g and horizon step h the S values samples[g*bs + s*ld + h] (ld >= H: any slice of the horizon is a view)
+ * are sorted and reduced; G >= 1, 1 <= S <= VOLT_SUMMARY_MAX_S, H >= 1.  With VOLT_SUMMARY_EXP in `flags` every statistic is
+ * that of v = exp(x), the exponential taken in fp64 from the fp32 sample; without it v = x.  All arithmetic after the sort is
+ * fp64; the outputs are fp32 (counts int32) and keep H contiguous:
+ *     moments [G,4,H]  mean, unbiased standard deviation (two-pass; NaN for S = 1), min, max
+ *     quant   [G,Q,H]  for the levels q [Q] (DEVICE, fp64): pos = q (S-1), lo = floor(pos), v_(lo) + (v_(lo+1) - v_(lo)) (pos - lo)
+ *                      over the sorted column (torch.quantile's default "linear" rule, in fp64).  Q may be 0.
+ *     counts  [G,3,H]  n_nan = NaN samples;  n_lt = #{v < truth} (ECDF's numerator);  n_le = #{v <= truth}.  truth [G,H] is in
+ *                      value units and may be NULL; where it is NaN or absent n_lt = n_le = -1.
+ *     crps    [G,H]    mean |v_i - y| - S^-2 sum_i (2i - S - 1) v_(i), i 1-based over the sorted column
+ *                      (= mean |v - y| - 1/2 mean |v_i - v_j|); NaN where truth is.
+ *     call, put [G,M,H] for strikes [G,M]: mean max(v - K, 0), mean max(K - v, 0).  M may be 0.
+ * A column with any NaN sample reports n_nan, NaN in every float output and n_lt = n_le = -1.  Infinities are ordinary values
+ * of the ordering.  moments, counts and crps may be NULL (not written).
+ * scratch: volt_path_summary_scratch_bytes(G,S,H) bytes (G H round_up(S, 64) floats: the transposed samples; 0 for a shape out
+ * of range), 256-byte aligned, caller-owned.  Two launches, no host synchronisation, no allocation, no atomics: every
+ * reduction has a fixed order, results are bitwise repeatable, and the call replays from a hipGraph.
+ * Argument errors (before any launch): -1 samples NULL; -2 ld < H; -4 G < 1 (or G H beyond a grid); -5 S out of range;
+ * -6 H < 1; -7 unknown flag bits; -8 Q > 0 and q NULL; -9 Q < 0; -11 M > 0 and strikes NULL; -12 M < 0; -14 Q > 0 and quant
+ * NULL; -17 / -18 M > 0 and call / put NULL; -19 scratch NULL or not 256-byte aligned; -20 scratch_bytes too small. */
+#define VOLT_SUMMARY_MAX_S 32768
+#define VOLT_SUMMARY_EXP 1        /* flag bit of volt_path_summary_f32 */
+size_t volt_path_summary_scratch_bytes(int G, int S, int H);
+int volt_path_summary_f32(const float* samples, int64_t ld, int64_t bs, int G, int S, int H, int flags,
+                          const double* q, int Q, const float* truth, const float* strikes, int M,
+                          float* moments, float* quant, int* counts, float* crps, float* call, float* put,
+                          void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,10 +26,10 @@ def install_as_voltron(gpytorch_standin=True):
     if gpytorch_standin:
         from . import gpytorch_compat
         gpytorch_compat.install()
-    from . import kernels, likelihoods, means, models, rollout_utils, train_utils
+    from . import kernels, likelihoods, means, models, option_utils, rollout_utils, train_utils
     me = sys.modules[__name__]
     sys.modules.setdefault("voltron", me)
     for name, mod in (("kernels", kernels), ("likelihoods", likelihoods), ("means", means), ("models", models),
-                      ("rollout_utils", rollout_utils), ("train_utils", train_utils)):
+                      ("rollout_utils", rollout_utils), ("train_utils", train_utils), ("option_utils", option_utils)):
         sys.modules.setdefault("voltron." + name, mod)
     return me

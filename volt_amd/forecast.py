@@ -91,15 +91,35 @@ def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_ite
     return samples.detach()                                                              # .detach(): :118
 
 
+def _window_summary(samples, series, last_day, spec):
+    """Summary of one window's samples [B,S,H] on the device against the realised continuation series[:, e:e+H] (NaN where
+    the series ends): scoring.summarize_paths, nothing comes to the host."""
+    from . import scoring
+    B, _, H = samples.shape
+    truth = torch.full((B, H), float("nan"), device=samples.device)
+    have = max(0, min(H, series.shape[1] - last_day))
+    if have:
+        truth[:, :have] = series[:, last_day:last_day + have].float()
+    return scoring.summarize_paths(samples, q=spec.q, truth=truth, strikes=spec.strikes, exp=spec.exp)
+
+
 def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample, mean, k, gpcv_iters, vol_iters,
-                      data_iters, theta, vol_fn, generator, save, path_fn, debug=None, graph=None):
+                      data_iters, theta, vol_fn, generator, save, path_fn, debug=None, graph=None, summary=None,
+                      keep_samples=True):
     """One batched pass per window (series [B,T] prices; the window ending at index e trains on series[:, e-ntrain:e]).
     A numerical failure anywhere in the batched pass (NotPSDError / NanError after the jitter ladders) must not take the
     other series down with it: the window is then redone one series at a time, and a series that still fails gets NaN
     samples and a "Failed:" line -- what the reference's per-ticker try / except does
     (experiments/stocks/GenerateMultiMeanPreds.py:185-198).
-    ``debug`` (a dict) receives the last window's intermediates (vol, pred_vol, z, model) for tests."""
+    ``debug`` (a dict) receives the last window's intermediates (vol, pred_vol, z, model) for tests.
+    ``summary`` (a scoring.SummarySpec): every window is also summarised on the device (_window_summary) and
+    ``<sample file stem>_summary.pt`` saved next to the sample files; the return is then (last samples, [PathSummary per
+    window]).  ``keep_samples=False`` (with a summary) skips the copy of the samples to the host and the sample files and
+    returns (None, summaries)."""
+    if not keep_samples and summary is None:
+        raise ValueError("keep_samples=False leaves nothing to return without summary=")
     B = series.shape[0]
+    summaries = []
     H = test_x.numel()
     args = (nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator, graph)
     last = None
@@ -116,24 +136,37 @@ def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample,
                     samples[b] = _window_pass(train_x, test_x, train_y[b:b + 1], *args)[0]
                 except (NotPSDError, NanError):
                     print("Failed: ", names[b], mean, k)
-        last = samples.cpu()
+        if summary is not None:
+            summaries.append(_window_summary(samples, series, last_day, summary))
+        if keep_samples:
+            last = samples.cpu()
         if save:
+            host = summaries[-1].cpu() if summary is not None else None
             for b, name in enumerate(names):
                 path = path_fn(name, last_day)
                 os.makedirs(os.path.dirname(path), exist_ok=True)
-                torch.save(last[b], path)
-    return last
+                if keep_samples:
+                    torch.save(last[b], path)
+                if host is not None:
+                    torch.save({f: v[b] for f, v in host.fields().items()}, os.path.splitext(path)[0] + "_summary.pt")
+    if summary is None:
+        return last
+    return last, summaries
 
 
 def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=20, train_iters=400, nsample=1000,
                                   ntrain=400, mean="ewma", save=False, k=300, ntimes=-1, vol_fn=None,
-                                  vol_iters=None, par_dir="./saved-outputs/", generator=None, debug=None, graph=None):
+                                  vol_iters=None, par_dir="./saved-outputs/", generator=None, debug=None, graph=None,
+                                  summary=None, keep_samples=True):
     """closes [B, T] prices for B tickers on a common calendar (device tensor).  Same window schedule,
     model name and file layout as GenerateStockPredictions (GenerateMultiMeanPreds.py:69-83,128); ``mean`` in
     ewma / dewma / tewma takes the Rollouts branch (:110-112), constant / loglinear / linear the "VOLT + standard
     mean" branch (:113-119: one multi-point GeneratePrediction per path).
     Under torch.distributed each rank takes a contiguous shard of the tickers.  Returns the samples of
-    the last window, [B_local, nsample, forecast_horizon] on the CPU."""
+    the last window, [B_local, nsample, forecast_horizon] on the CPU.
+    ``summary=scoring.SummarySpec(...)``: each window's paths are summarised on the device against the realised
+    continuation and the return is (samples, [PathSummary per window]); with ``keep_samples=False`` the samples never
+    come to the host (no sample files either) and the first element is None."""
     if mean not in _MODES and mean not in _STANDARD:
         raise ValueError(f"unknown mean {mean!r}: one of {sorted(_MODES) + list(_STANDARD)}")
     dev = closes.device
@@ -154,17 +187,19 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
         date = str(last_day) if dates is None else str(dates[last_day])
         return os.path.join(par_dir, tckr, model_name + date + ".pt")                    # :128
     return _forecast_windows(tickers, closes, end_idxs.tolist(), ntrain, train_x, test_x, nsample, mean, k,
-                             train_iters, vol_iters, train_iters, None, vol_fn, generator, save, path_fn, debug, graph)
+                             train_iters, vol_iters, train_iters, None, vol_fn, generator, save, path_fn, debug, graph,
+                             summary, keep_samples)
 
 
 def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=400, n_test_times=10, nsample=1000, k=400,
                                  theta=0.01, gpcv_iters=200, vol_iters=500, data_iters=0, save=False, vol_fn=None,
-                                 par_dir="./saved-outputs/", generator=None, graph=None):
+                                 par_dir="./saved-outputs/", generator=None, graph=None, summary=None, keep_samples=True):
     """The ``--kernel volt --mean ewma`` branch of experiments/weather/GPGenerator.py:20-112 for B stations at once:
     data [B,T] wind speeds (missing = -99 -> 0, then +1 as at :47,55), dt = 1/365 (:38-41), the schedule of test
     windows of :33-34, GPCV 200 / vol model 500 / data model 0 iterations (:64-67,89-92), EWMA(k=400) mean and
     mean-reverting rollouts with theta = 0.01 (:96-102), files ``stn<idx>/volt_ema<k>_theta<theta>_<last_day>.pt``
-    (:103-106).  Stations shard across ranks like tickers.  Returns the last window's samples [B_local,S,H] (CPU)."""
+    (:103-106).  Stations shard across ranks like tickers.  Returns the last window's samples [B_local,S,H] (CPU).
+    ``summary`` / ``keep_samples``: as for GenerateStockPredictionsBatch (the truth is the shifted series, data + 1)."""
     dev = data.device
     lo, hi = shard_range(len(stations))
     stations, data = list(stations)[lo:hi], data[lo:hi].float()
@@ -179,4 +214,5 @@ def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=40
         return os.path.join(par_dir, "stn" + str(stn), "volt_ema" + str(k) + "_theta" + str(theta) + "_" +
                             str(last_day) + ".pt")
     return _forecast_windows(stations, data, end_idxs, ntrain, train_x, test_x, nsample, "ewma", k, gpcv_iters,
-                             vol_iters, data_iters, theta, vol_fn, generator, save, path_fn, None, graph)
+                             vol_iters, data_iters, theta, vol_fn, generator, save, path_fn, None, graph, summary,
+                             keep_samples)

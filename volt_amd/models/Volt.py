@@ -55,10 +55,21 @@ class Volt(VolGP):
         params = _train_noise_and_mean(self, self.likelihood)    # noise (+ the constant mean), Volt.py:110-127
         _fit_exact(self, self.likelihood, x, self.train_y, params, LR_DATA, data_mod_iters, display)
 
-    def Forecast(self, test_x, nsample=50, return_vol=False, mean_revert=False, theta=0.05, **rollout_kw):
+    def Forecast(self, test_x, nsample=50, return_vol=False, mean_revert=False, theta=0.05, summary=None,
+                 keep_samples=True, **rollout_kw):
+        """``summary`` (a scoring.SummarySpec) / ``keep_samples``: as in the batch drivers of forecast.py -- the return
+        becomes (samples or None, PathSummary), without a truth (a forecast has no realised continuation yet).  Rollouts'
+        own return is unchanged (log-price samples on the CPU), so the [nsample, H] paths go back up for the summary."""
         if self.vol_model is not None:
             self.vol_model.eval()
         self.eval()
         prices = torch.cat((self.train_targets[..., :1], self.train_targets.squeeze())).exp()   # Rollouts drops [0]
-        return Rollouts(self.train_inputs[0].squeeze(), prices, test_x, self, nsample=nsample,
-                        theta=theta if mean_revert else None, **rollout_kw)
+        samples = Rollouts(self.train_inputs[0].squeeze(), prices, test_x, self, nsample=nsample,
+                           theta=theta if mean_revert else None, **rollout_kw)
+        if summary is None:
+            if not keep_samples:
+                raise ValueError("keep_samples=False leaves nothing to return without summary=")
+            return samples
+        from ..scoring import summarize_paths
+        s = summarize_paths(samples.to(test_x.device), q=summary.q, strikes=summary.strikes, exp=summary.exp)
+        return (samples if keep_samples else None), s

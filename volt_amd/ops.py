@@ -599,3 +599,83 @@ def kron_mll_step(params, x: torch.Tensor, Y: torch.Tensor, M: torch.Tensor, ws:
                   ws.resid.data_ptr(), out.data_ptr(), alpha.data_ptr(), ws.state.data_ptr(), ws.res.data_ptr(), N, T,
                   _lib.stream_ptr()), "volt_kron_epilogue")
     return ws.res, info, ws.eig_info, ws
+
+
+# ---- path summaries (volt_path_summary_f32) ---------------------------------------------------------------------------
+SUMMARY_MAX_S = _lib.SUMMARY_MAX_S
+_SUMMARY_SCRATCH = {}
+_SUMMARY_LEVELS = {}
+
+
+def _summary_scratch(G: int, S: int, H: int, device):
+    """Caller-owned scratch of volt_path_summary_f32 (the transposed samples), one buffer per (device, stream, shape),
+    reused across calls; calls that share a buffer are ordered by their stream.  Returns (aligned pointer, bytes)."""
+    nbytes = int(_lib.lib().volt_path_summary_scratch_bytes(G, S, H))
+    key = (device.index, _lib.stream_ptr(), G, S, H)
+    buf = _SUMMARY_SCRATCH.get(key)
+    if buf is None:
+        if len(_SUMMARY_SCRATCH) >= 8:                          # a handful of shapes is what a run has; drop the oldest
+            _SUMMARY_SCRATCH.pop(next(iter(_SUMMARY_SCRATCH)))
+        buf = _SUMMARY_SCRATCH[key] = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    return ((buf.data_ptr() + 255) // 256) * 256, nbytes
+
+
+def _summary_levels(q, device) -> torch.Tensor:
+    """The quantile levels as a device fp64 tensor, cached per (levels, device): a host-to-device copy per call would
+    keep the entry out of a captured iteration."""
+    if torch.is_tensor(q):
+        return q.to(device=device, dtype=torch.float64).reshape(-1).contiguous()
+    key = (tuple(float(v) for v in q), str(device))
+    if key not in _SUMMARY_LEVELS:
+        if any(not 0.0 <= v <= 1.0 for v in key[0]):
+            raise ValueError("quantile levels must lie in [0, 1]")
+        _SUMMARY_LEVELS[key] = torch.tensor(key[0], dtype=torch.float64, device=device)
+    return _SUMMARY_LEVELS[key]
+
+
+def path_summary(samples: torch.Tensor, q=(), truth: torch.Tensor | None = None, strikes: torch.Tensor | None = None,
+                 exp: bool = False):
+    """volt_path_summary_f32 on samples [G,S,H] (fp32; any view with a contiguous last dimension, a row stride >= H and a
+    batch stride is read in place, anything else is copied first).  q: levels (sequence or tensor); truth [G,H] in value
+    units; strikes [G,M].  Returns (moments [G,4,H], quant [G,Q,H], counts [G,3,H] int32, crps [G,H], call [G,M,H],
+    put [G,M,H]) on the device; no host synchronisation."""
+    if samples.ndim != 3:
+        raise ValueError("samples must be [G,S,H]")
+    G, S, H = samples.shape
+    if S > SUMMARY_MAX_S:
+        raise ValueError(f"path_summary sorts a column in one workgroup: S = {S} > {SUMMARY_MAX_S}")
+    if min(G, S, H) < 1:
+        raise ValueError("samples must not be empty")
+    _need_gpu(samples, truth, strikes)
+    if samples.dtype != torch.float32:
+        samples = samples.float()
+    sg, ss, sh = samples.stride()
+    if (H > 1 and sh != 1) or (S > 1 and ss < H) or (G > 1 and sg < 0):
+        samples = samples.contiguous()
+        sg, ss, sh = samples.stride()
+    ld = ss if S > 1 else H
+    dev = samples.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    qd = _summary_levels(q, dev)
+    Q = qd.numel()
+    M = 0
+    if strikes is not None:
+        strikes = strikes.to(torch.float32).reshape(G, -1).contiguous()
+        M = strikes.shape[1]
+    if truth is not None:
+        truth = truth.to(torch.float32).reshape(G, H).contiguous()
+    moments = torch.empty(G, 4, H, **f32)
+    quant = torch.empty(G, Q, H, **f32)
+    counts = torch.empty(G, 3, H, dtype=torch.int32, device=dev)
+    crps = torch.empty(G, H, **f32)
+    call = torch.empty(G, M, H, **f32)
+    put = torch.empty(G, M, H, **f32)
+    wp, nbytes = _summary_scratch(G, S, H, dev)
+
+    def P(t, n=1):
+        return None if t is None or n == 0 else t.data_ptr()
+    _lib.check(_lib.lib().volt_path_summary_f32(
+        samples.data_ptr(), ld, sg if G > 1 else 0, G, S, H, _lib.SUMMARY_EXP if exp else 0, P(qd, Q), Q, P(truth),
+        P(strikes, M), M, moments.data_ptr(), P(quant, Q), counts.data_ptr(), crps.data_ptr(), P(call, M), P(put, M), wp,
+        nbytes, _lib.stream_ptr()), "volt_path_summary")
+    return moments, quant, counts, crps, call, put
