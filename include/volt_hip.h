@@ -404,6 +404,37 @@ int volt_path_summary_f32(const float* samples, int64_t ld, int64_t bs, int G, i
                           float* moments, float* quant, int* counts, float* crps, float* call, float* put,
                           void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Linear-time Brownian-motion solver  (BMGP, voltron/models/BMGP.py:9-28, with solver="linear": the vol forecaster's
+ * MLL step and posterior solve without any N x N matrix).  K = v M, M = min(x_i, x_k) over a grid 0 <= x_0 < x_1 < ..
+ * shared by the batch.  With D the first-difference operator D M D' = diag(delta) (delta_0 = x_0, delta_i = x_i - x_{i-1}),
+ * so A = v M + s I = D^-1 T D^-T with T = v diag(delta) + s D D' tridiagonal and SPD whenever s > 0 (also at x_0 = 0,
+ * where M itself is singular).  Two O(N) sweeps over T = L diag(d) L' give everything the dense step returns
+ * (csrc/bm.hip has the recurrences); the arithmetic is fp64 whatever the I/O type.
+ *     volt_bm_step_*:  x [N], vol [B] (v > 0), sigma2 [B] (s > 0), resid [B,N]  ->  out [B,8], alpha [B,N], info [B]
+ *         out[b,0..5] exactly as volt_mll_step_*: mll, d mll / d sigma2, r'A^-1 r, logdet, tr A^-1, alpha'alpha;
+ *         out[b,6] = sigma2[b], out[b,7] = vol[b] (the parameters the step used).  `flags`: VOLT_WANT_GRAD -- without it the backward sweep is skipped and
+ *         out[b,1], out[b,4], out[b,5] and alpha are not written (workspace and alpha may then be NULL).
+ *     volt_bm_solve_*: X [B,N,H] = A_b^-1 R_b for R [B,N,H], H contiguous (the posterior's solve: R = K_t*).
+ * info[b]: 0, or i + 1 for the first pivot d_i that is not a positive finite number (s = 0 at x_0 = 0, a NaN parameter);
+ * logdet and mll are then NaN.  A NaN in resid leaves info at 0 and comes out as NaN in out and alpha.
+ * workspace: volt_bm_workspace_bytes(B,N,H) bytes (the step: H = 1), 256-byte aligned: (1 + H) B N doubles, the pivots'
+ * reciprocals and the forward sweep's z.  Nothing is O(N^2).  The step is ONE launch, the solve two; no host
+ * synchronisation, no allocation, no atomics: every sum has a fixed order, results are bitwise repeatable, and the calls
+ * replay from a hipGraph.  Any B >= 1, N >= 1, H >= 1; indices are 64-bit.
+ * Argument errors (before any launch, checked in the order of their numbers), step: -1 x, -2 vol, -3 sigma2, -4 resid, -5 out NULL; -6 alpha NULL with
+ * VOLT_WANT_GRAD; -7 info NULL; -8 workspace NULL or not 256-byte aligned with VOLT_WANT_GRAD; -9 B < 1; -10 N < 1;
+ * -11 unknown flag bits.  Solve: -1 x, -2 vol, -3 sigma2, -4 R, -5 X, -6 info NULL; -7 workspace NULL or misaligned;
+ * -8 B < 1; -9 N < 1; -10 H < 1 (or B H beyond a grid). */
+size_t volt_bm_workspace_bytes(int B, int N, int H);
+int volt_bm_step_f32(const float* x, const float* vol, const float* sigma2, const float* resid, float* out /*[B,8]*/,
+                     float* alpha /*[B,N]*/, int* info, void* workspace, int B, int N, int flags, void* stream);
+int volt_bm_step_f64(const double* x, const double* vol, const double* sigma2, const double* resid, double* out /*[B,8]*/,
+                     double* alpha /*[B,N]*/, int* info, void* workspace, int B, int N, int flags, void* stream);
+int volt_bm_solve_f32(const float* x, const float* vol, const float* sigma2, const float* R /*[B,N,H]*/,
+                      float* X /*[B,N,H]*/, int* info, void* workspace, int B, int N, int H, void* stream);
+int volt_bm_solve_f64(const double* x, const double* vol, const double* sigma2, const double* R /*[B,N,H]*/,
+                      double* X /*[B,N,H]*/, int* info, void* workspace, int B, int N, int H, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

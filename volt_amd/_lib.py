@@ -73,6 +73,11 @@ _SIGS = {
     "volt_path_summary_scratch_bytes": (_sz, [_i32, _i32, _i32]),
     "volt_path_summary_f32": (C.c_int, [_ptr, _i64, _i64, _i32, _i32, _i32, _i32, _ptr, _i32, _ptr, _ptr, _i32] + [_ptr] * 7
                               + [_sz, _ptr]),
+    "volt_bm_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "volt_bm_step_f32": (C.c_int, [_ptr] * 8 + [_i32, _i32, _i32, _ptr]),
+    "volt_bm_step_f64": (C.c_int, [_ptr] * 8 + [_i32, _i32, _i32, _ptr]),
+    "volt_bm_solve_f32": (C.c_int, [_ptr] * 7 + [_i32, _i32, _i32, _ptr]),
+    "volt_bm_solve_f64": (C.c_int, [_ptr] * 7 + [_i32, _i32, _i32, _ptr]),
 }
 SUMMARY_MAX_S, SUMMARY_EXP = 32768, 1                   # include/volt_hip.h: VOLT_SUMMARY_MAX_S, VOLT_SUMMARY_EXP
 

@@ -1,0 +1,409 @@
+// Linear-time solver for the Brownian-motion prior of the vol forecaster (models/BMGP.py, solver="linear").
+//
+// K = v M, M = min(x_i, x_k) over a grid 0 <= x_0 < x_1 < ...  With D the first-difference operator (unit lower bidiagonal)
+// D M D' = diag(delta), delta_0 = x_0, delta_i = x_i - x_{i-1}, so A = v M + s I = D^-1 T D^-T with the SPD tridiagonal
+// T = v diag(delta) + s D D' (D D': diagonal 1, 2, 2, .., off-diagonals -1).  T = L diag(d) L' with L unit lower bidiagonal,
+// L_{i,i-1} = -c_i:
+//     d_0 = v delta_0 + s,   c_i = s / d_{i-1},   d_i = v delta_i + 2 s - s c_i
+//     forward   u = D r,  z_i = u_i + c_i z_{i-1}                     logdet = sum log d_i,  r'A^-1 r = sum z_i^2 / d_i
+//     backward  w_i = z_i / d_i + (s / d_i) w_{i+1},  alpha = D'w     (alpha_i = w_i - w_{i+1})
+//     trace     G = T^-1:  G_ii = 1/d_i + (s/d_i)^2 G_{i+1,i+1},  G_{i,i+1} = (s/d_i) G_{i+1,i+1},
+//               tr A^-1 = tr(D'G D) = sum_i (1 + [i>0]) G_ii - 2 sum_i G_{i,i+1}
+// All arithmetic is fp64 whatever the I/O type; nothing is O(N^2); no atomics, every sum has a fixed order.
+//
+//   bm_step_kernel    one lane per series, ONE wave per workgroup (B > 64 spreads over CUs).  resid [B,N] is staged through
+//                     LDS in transposed tiles of 64 series x 64 steps (whole 256 / 512-byte rows from global memory, a
+//                     conflict-free column per lane out of LDS); the next tile's rows are requested into registers before the
+//                     current tile's chain runs.  1/d_i and z_i go to the workspace series-fastest for the backward sweep,
+//                     which reads them sixteen steps ahead and sends alpha back through the same LDS tile.
+//                     The chain: d_i = fma(-s^2, 1/d_{i-1}, v delta_i + 2 s), then v_rcp_f64 + two Newton steps -- one
+//                     reciprocal and one FMA; the log (a running product of v_frexp mantissas and a sum of exponents: ONE
+//                     log per series), the z chain and the sums hang off it.
+//   bm_factor_kernel  the d chain alone, 1/d_i -> workspace (the solve's factorisation, once per series).
+//   bm_solve_kernel   one lane per (series, right-hand side): R [B,N,H] with H contiguous, so the lanes of a series load and
+//                     store whole rows.  Forward z -> workspace, backward X = D'w.  Its chains are one FMA per step.
+#include "common.h"
+#include "host.h"
+#include "../../include/volt_hip.h"
+
+namespace volt {
+
+constexpr int BM_T = 64;                   // tile edge: series per workgroup, steps per staged tile
+constexpr int BM_LD = BM_T + 1;            // LDS row stride (doubles): a column read by 64 lanes touches every bank pair once
+constexpr int BM_PF = 16;                  // steps per register-prefetched block of the workspace sweeps
+constexpr int BM_FB = 8;                   // steps per block of the step kernel's forward chain (divides BM_T)
+constexpr double BM_LN2 = 0.693147180559945309417232121458;
+constexpr double BM_LOG_2PI = 1.837877066409345483560659472811;
+
+// 1 / d: v_rcp_f64 and two Newton steps (d is a positive normal number wherever info stays 0; anything else comes out as
+// NaN / inf and is reported through info)
+__device__ __forceinline__ double bm_rcp(double d) {
+    double r = __builtin_amdgcn_rcp(d);
+    double e = __builtin_fma(-d, r, 1.0);
+    r = __builtin_fma(r, e, r);
+    e = __builtin_fma(-d, r, 1.0);
+    return __builtin_fma(r, e, r);
+}
+__device__ __forceinline__ bool bm_pivot_ok(double d) { return d > 0.0 && d < __builtin_inf(); }     // false for NaN
+
+template <typename T>
+struct BmStepParams {
+    const T *x, *vol, *sigma2, *resid;
+    T *out, *alpha;
+    int* info;
+    double *inv, *zs;                      // [N][B], series-fastest
+    int64_t B, N;
+};
+
+// rows r < nb of the tile that starts at step i0 (lane = step), and the lane's grid points x_i, x_{i-1}
+template <typename T>
+__device__ __forceinline__ void bm_fetch(const BmStepParams<T>& p, int64_t b0, int nb, int64_t i0, T (&pre)[BM_T], T& px, T& pxm) {
+    const int64_t i = i0 + threadIdx.x;
+    const bool in = i < p.N;
+#pragma unroll
+    for (int r = 0; r < BM_T; ++r) {
+        T val = (T)0;
+        if (r < nb && in) val = p.resid[(b0 + r) * p.N + i];
+        pre[r] = val;
+    }
+    px = (T)0;
+    pxm = (T)0;
+    if (in) px = p.x[i];
+    if (in && i > 0) pxm = p.x[i - 1];
+}
+template <typename T>
+__device__ __forceinline__ void bm_commit(double* tile, double* dl, int nb, const T (&pre)[BM_T], T px, T pxm) {
+#pragma unroll
+    for (int r = 0; r < BM_T; ++r)
+        if (r < nb) tile[r * BM_LD + threadIdx.x] = (double)pre[r];
+    dl[threadIdx.x] = (double)px - (double)pxm;
+}
+
+template <typename T, bool GRAD>
+__global__ __launch_bounds__(BM_T) void bm_step_kernel(BmStepParams<T> p) {
+    __shared__ double tile[BM_T * BM_LD];
+    __shared__ double dl[BM_T];
+    const int lane = threadIdx.x;
+    const int64_t N = p.N, B = p.B;
+    const int64_t b0 = (int64_t)blockIdx.x * BM_T;
+    const int nb = (int)(B - b0 < BM_T ? B - b0 : BM_T);              // series of this workgroup (wave-uniform)
+    const bool act = lane < nb;
+    const int64_t b = b0 + lane;
+    const double v = act ? (double)p.vol[b] : 1.0, s = act ? (double)p.sigma2[b] : 1.0;
+    const double ss = s * s, s2 = 2.0 * s;
+
+    // ---- forward sweep
+    T pre[BM_T], px, pxm;
+    bm_fetch(p, b0, nb, 0, pre, px, pxm);
+    double inv_prev = 0.0, zprev = 0.0, rprev = 0.0, quad = 0.0, P = 1.0;
+    int64_t E = 0;
+    int info = 0;
+    for (int64_t i0 = 0; i0 < N; i0 += BM_T) {
+        bm_commit(tile, dl, nb, pre, px, pxm);
+        __syncthreads();
+        if (i0 + BM_T < N) bm_fetch(p, b0, nb, i0 + BM_T, pre, px, pxm);      // in flight while this tile's chain runs
+        const int cnt = (int)(N - i0 < BM_T ? N - i0 : BM_T);
+        int e = 0;
+        // blocks of BM_FB steps: their LDS reads first (one wait), the chain in one basic block (a step past the tile's end --
+        // last tile only -- reads stale LDS and is discarded by selects, not branches), then the block's stores
+        for (int j0 = 0; j0 < cnt; j0 += BM_FB) {
+            double rr[BM_FB], dd[BM_FB], iv[BM_FB], zz[BM_FB];
+#pragma unroll
+            for (int u = 0; u < BM_FB; ++u) {
+                rr[u] = tile[lane * BM_LD + j0 + u];
+                dd[u] = dl[j0 + u];
+            }
+#pragma unroll
+            for (int u = 0; u < BM_FB; ++u) {
+                const int64_t i = i0 + j0 + u;
+                const bool on = j0 + u < cnt;
+                const double base = __builtin_fma(v, dd[u], i == 0 ? s : s2);
+                const double d = __builtin_fma(-ss, inv_prev, base);           // the chain: this FMA and the reciprocal
+                const double c = s * inv_prev;
+                const double inv = bm_rcp(d);
+                const double z = __builtin_fma(c, zprev, rr[u] - rprev);
+                quad = on ? __builtin_fma(z * z, inv, quad) : quad;
+                P = on ? P * __builtin_amdgcn_frexp_mant(d) : P;
+                e += on ? __builtin_amdgcn_frexp_exp(d) : 0;
+                if (on && !bm_pivot_ok(d) && info == 0) info = (int)(i + 1 < 0x7fffffff ? i + 1 : 0x7fffffff);
+                iv[u] = inv;
+                zz[u] = z;
+                inv_prev = on ? inv : inv_prev;
+                zprev = on ? z : zprev;
+                rprev = on ? rr[u] : rprev;
+            }
+            if (GRAD && act) {
+#pragma unroll
+                for (int u = 0; u < BM_FB; ++u)
+                    if (j0 + u < cnt) {
+                        const int64_t i = i0 + j0 + u;
+                        p.inv[i * B + b] = iv[u];
+                        p.zs[i * B + b] = zz[u];
+                    }
+            }
+        }
+        e += __builtin_amdgcn_frexp_exp(P);                                    // (at most 64 mantissas in [1/2, 1) since the last time)
+        P = __builtin_amdgcn_frexp_mant(P);
+        E += e;
+        __syncthreads();
+    }
+    const double logdet = info ? __builtin_nan("") : log(P) + (double)E * BM_LN2;
+    const double nd = (double)N;
+    if (act) {
+        T* o = p.out + b * 8;
+        o[0] = (T)(-0.5 * (quad + logdet + nd * BM_LOG_2PI) / nd);
+        o[2] = (T)quad;
+        o[3] = (T)logdet;
+        o[6] = (T)s;
+        o[7] = (T)v;
+        p.info[b] = info;
+    }
+    if constexpr (!GRAD) return;
+
+    // ---- backward sweep: blocks of BM_PF steps from the end, the block below already requested
+    double ci[BM_PF], cz[BM_PF], ni[BM_PF], nz[BM_PF];
+    auto request = [&](int64_t q) {
+#pragma unroll
+        for (int j = 0; j < BM_PF; ++j) {
+            const int64_t i = q * BM_PF + j;
+            double a = 0.0, c = 0.0;
+            if (act && i < N) {
+                a = p.inv[i * B + b];
+                c = p.zs[i * B + b];
+            }
+            ni[j] = a;
+            nz[j] = c;
+        }
+    };
+    double wn = 0.0, gn = 0.0, aa = 0.0, tr = 0.0;
+    const int64_t qlast = (N - 1) / BM_PF;
+    request(qlast);
+    for (int64_t q = qlast; q >= 0; --q) {
+#pragma unroll
+        for (int j = 0; j < BM_PF; ++j) ci[j] = ni[j], cz[j] = nz[j];
+        if (q > 0) request(q - 1);
+#pragma unroll
+        for (int j = BM_PF - 1; j >= 0; --j) {
+            // no guard: a step past the end (first block only, where wn = gn = 0) was requested as 1/d = z = 0 and so gives
+            // w = g = alpha = 0, adds nothing to the sums, and lands in a tile column that is never sent out
+            const int64_t i = q * BM_PF + j;
+            const double inv = ci[j], e = s * inv;
+            const double w = __builtin_fma(e, wn, cz[j] * inv);
+            const double a = w - wn;
+            aa = __builtin_fma(a, a, aa);
+            const double g = __builtin_fma(e * e, gn, inv);
+            tr += __builtin_fma(-2.0 * e, gn, (i > 0 ? 2.0 : 1.0) * g);
+            tile[lane * BM_LD + (int)(i & (BM_T - 1))] = a;
+            wn = w;
+            gn = g;
+        }
+        if ((q & (BM_T / BM_PF - 1)) == 0) {                                   // a tile of alpha is complete: rows go out whole
+            __syncthreads();
+            const int64_t i = q * BM_PF + lane;
+            if (i < N) {
+#pragma unroll 8
+                for (int r = 0; r < nb; ++r) p.alpha[(b0 + r) * N + i] = (T)tile[r * BM_LD + lane];
+            }
+            __syncthreads();
+        }
+    }
+    if (act) {
+        T* o = p.out + b * 8;
+        o[1] = (T)(0.5 * (aa - tr) / nd);
+        o[4] = (T)tr;
+        o[5] = (T)aa;
+    }
+}
+
+template <typename T>
+struct BmSolveParams {
+    const T *x, *vol, *sigma2, *R;
+    T* X;
+    int* info;
+    double *inv, *zs;                      // [N][B] and [N][B H]
+    int64_t B, N, H;
+};
+
+// the d chain alone: one lane per series
+template <typename T>
+__global__ __launch_bounds__(BM_T) void bm_factor_kernel(BmSolveParams<T> p) {
+    const int64_t b = (int64_t)blockIdx.x * BM_T + threadIdx.x;
+    const int64_t N = p.N, B = p.B;
+    const bool act = b < B;
+    const double v = act ? (double)p.vol[b] : 1.0, s = act ? (double)p.sigma2[b] : 1.0;
+    const double ss = s * s, s2 = 2.0 * s;
+    double inv_prev = 0.0, xprev = 0.0;
+    int info = 0;
+    for (int64_t i0 = 0; i0 < N; i0 += BM_PF) {
+        double xs[BM_PF];
+#pragma unroll
+        for (int j = 0; j < BM_PF; ++j) xs[j] = i0 + j < N ? (double)p.x[i0 + j] : 0.0;     // (uniform: scalar loads)
+#pragma unroll
+        for (int j = 0; j < BM_PF; ++j) {
+            const int64_t i = i0 + j;
+            if (i < N) {
+                const double base = __builtin_fma(v, xs[j] - xprev, i == 0 ? s : s2);
+                const double d = __builtin_fma(-ss, inv_prev, base);
+                const double inv = bm_rcp(d);
+                if (!bm_pivot_ok(d) && info == 0) info = (int)(i + 1 < 0x7fffffff ? i + 1 : 0x7fffffff);
+                if (act) p.inv[i * B + b] = inv;
+                inv_prev = inv;
+                xprev = xs[j];
+            }
+        }
+    }
+    if (act) p.info[b] = info;
+}
+
+template <typename T>
+__global__ __launch_bounds__(BM_T) void bm_solve_kernel(BmSolveParams<T> p) {
+    const int64_t g = (int64_t)blockIdx.x * BM_T + threadIdx.x;
+    const int64_t N = p.N, B = p.B, H = p.H, BH = B * H;
+    const bool act = g < BH;
+    const int64_t b = act ? g / H : 0, h = act ? g % H : 0;
+    const double s = act ? (double)p.sigma2[b] : 1.0;
+    const T* R = p.R + b * N * H + h;
+    T* X = p.X + b * N * H + h;
+    const int64_t nq = (N + BM_PF - 1) / BM_PF;
+
+    // ---- forward: z_i = (r_i - r_{i-1}) + s / d_{i-1} z_{i-1}
+    double cr[BM_PF], ci[BM_PF], nr[BM_PF], ni[BM_PF];
+    auto request_f = [&](int64_t q) {
+#pragma unroll
+        for (int j = 0; j < BM_PF; ++j) {
+            const int64_t i = q * BM_PF + j;
+            double r = 0.0, a = 0.0;
+            if (act && i < N) {
+                r = (double)R[i * H];
+                if (i > 0) a = p.inv[(i - 1) * B + b];
+            }
+            nr[j] = r;
+            ni[j] = a;
+        }
+    };
+    double zprev = 0.0, rprev = 0.0;
+    request_f(0);
+    for (int64_t q = 0; q < nq; ++q) {
+#pragma unroll
+        for (int j = 0; j < BM_PF; ++j) cr[j] = nr[j], ci[j] = ni[j];
+        if (q + 1 < nq) request_f(q + 1);
+#pragma unroll
+        for (int j = 0; j < BM_PF; ++j) {
+            const int64_t i = q * BM_PF + j;
+            if (i < N) {
+                const double z = __builtin_fma(s * ci[j], zprev, cr[j] - rprev);
+                if (act) p.zs[i * BH + g] = z;
+                zprev = z;
+                rprev = cr[j];
+            }
+        }
+    }
+
+    // ---- backward: w_i = z_i / d_i + s / d_i w_{i+1},  X_i = w_i - w_{i+1}   (this lane reads back its own z)
+    auto request_b = [&](int64_t q) {
+#pragma unroll
+        for (int j = 0; j < BM_PF; ++j) {
+            const int64_t i = q * BM_PF + j;
+            double z = 0.0, a = 0.0;
+            if (act && i < N) {
+                z = p.zs[i * BH + g];
+                a = p.inv[i * B + b];
+            }
+            nr[j] = z;
+            ni[j] = a;
+        }
+    };
+    double wn = 0.0;
+    request_b(nq - 1);
+    for (int64_t q = nq - 1; q >= 0; --q) {
+#pragma unroll
+        for (int j = 0; j < BM_PF; ++j) cr[j] = nr[j], ci[j] = ni[j];
+        if (q > 0) request_b(q - 1);
+#pragma unroll
+        for (int j = BM_PF - 1; j >= 0; --j) {
+            const int64_t i = q * BM_PF + j;
+            if (i < N) {
+                const double w = __builtin_fma(s * ci[j], wn, cr[j] * ci[j]);
+                if (act) X[i * H] = (T)(w - wn);
+                wn = w;
+            }
+        }
+    }
+}
+
+inline size_t bm_inv_bytes(int64_t B, int64_t N) { return al256((size_t)B * (size_t)N * sizeof(double)); }
+
+template <typename T>
+int bm_step(const T* x, const T* vol, const T* sigma2, const T* resid, T* out, T* alpha, int* info, void* workspace, int B,
+            int N, int flags, void* stream) {
+    if (!x) return -1;
+    if (!vol) return -2;
+    if (!sigma2) return -3;
+    if (!resid) return -4;
+    if (!out) return -5;
+    const bool grad = (flags & VOLT_WANT_GRAD) != 0;
+    if (grad && !alpha) return -6;
+    if (!info) return -7;
+    if (grad && (!workspace || ((uintptr_t)workspace & 255))) return -8;
+    if (B < 1) return -9;
+    if (N < 1) return -10;
+    if (flags & ~VOLT_WANT_GRAD) return -11;
+    BmStepParams<T> p{x, vol, sigma2, resid, out, alpha, info, (double*)workspace,
+                      (double*)((char*)workspace + (grad ? bm_inv_bytes(B, N) : 0)), B, N};
+    const dim3 grid((unsigned)((B + BM_T - 1) / BM_T));
+    if (grad) hipLaunchKernelGGL((bm_step_kernel<T, true>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((bm_step_kernel<T, false>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
+    VOLT_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename T>
+int bm_solve(const T* x, const T* vol, const T* sigma2, const T* R, T* X, int* info, void* workspace, int B, int N, int H,
+             void* stream) {
+    if (!x) return -1;
+    if (!vol) return -2;
+    if (!sigma2) return -3;
+    if (!R) return -4;
+    if (!X) return -5;
+    if (!info) return -6;
+    if (!workspace || ((uintptr_t)workspace & 255)) return -7;
+    if (B < 1) return -8;
+    if (N < 1) return -9;
+    if (H < 1) return -10;
+    const int64_t waves = ((int64_t)B * H + BM_T - 1) / BM_T;
+    if (waves > 0x7fffffff) return -10;
+    BmSolveParams<T> p{x, vol, sigma2, R, X, info, (double*)workspace, (double*)((char*)workspace + bm_inv_bytes(B, N)), B, N, H};
+    hipLaunchKernelGGL((bm_factor_kernel<T>), dim3((unsigned)((B + BM_T - 1) / BM_T)), dim3(BM_T), 0, (hipStream_t)stream, p);
+    VOLT_LAUNCH_CHECK();
+    hipLaunchKernelGGL((bm_solve_kernel<T>), dim3((unsigned)waves), dim3(BM_T), 0, (hipStream_t)stream, p);
+    VOLT_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace volt
+
+extern "C" {
+
+size_t volt_bm_workspace_bytes(int B, int N, int H) {
+    if (B < 1 || N < 1 || H < 1) return 0;
+    return volt::bm_inv_bytes(B, N) + volt::al256((size_t)B * (size_t)N * (size_t)H * sizeof(double));
+}
+
+int volt_bm_step_f32(const float* x, const float* vol, const float* sigma2, const float* resid, float* out, float* alpha,
+                     int* info, void* workspace, int B, int N, int flags, void* stream) {
+    return volt::bm_step<float>(x, vol, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
+}
+int volt_bm_step_f64(const double* x, const double* vol, const double* sigma2, const double* resid, double* out, double* alpha,
+                     int* info, void* workspace, int B, int N, int flags, void* stream) {
+    return volt::bm_step<double>(x, vol, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
+}
+int volt_bm_solve_f32(const float* x, const float* vol, const float* sigma2, const float* R, float* X, int* info,
+                      void* workspace, int B, int N, int H, void* stream) {
+    return volt::bm_solve<float>(x, vol, sigma2, R, X, info, workspace, B, N, H, stream);
+}
+int volt_bm_solve_f64(const double* x, const double* vol, const double* sigma2, const double* R, double* X, int* info,
+                      void* workspace, int B, int N, int H, void* stream) {
+    return volt::bm_solve<double>(x, vol, sigma2, R, X, info, workspace, B, N, H, stream);
+}
+
+}  // extern "C"

@@ -169,3 +169,4 @@ size_t volt_internal_batch64_trtri_bytes(int B, int n);
 int volt_internal_batch64_trtri(const double* A, const double* Winv, double* Y, int B, int Np, volt::Region state, void* stream);
 // ---- mll.hip: gpcv.hip continues from the factor and Y = L^-T the step leaves in its workspace
 const float* volt_internal_mll_y(void* workspace, int B, int N);
+// ---- bm.hip: nothing internal -- its entries (volt_bm_*) are the C ABI's, declared and documented in include/volt_hip.h

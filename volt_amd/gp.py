@@ -238,6 +238,24 @@ class _ScaledDense(_Evaluated):
         return self.base.shape
 
 
+class _BrownianPrior(_ScaledDense):
+    """Lazy prior covariance of BMGP(solver="linear"): K = scale * min(x, x') over the 1-D grid ``x``, never formed --
+    ExactMarginalLogLikelihood hands (scale, x) to the linear-time step (_BMChainMLL, csrc/bm.hip).  min(x, x') is
+    materialised only when ``.evaluate()`` / ``.to_dense()`` (or ``.base``) is asked for."""
+
+    def __init__(self, scale, x):
+        self.scale, self.x = scale, x
+
+    @property
+    def base(self):
+        return torch.minimum(self.x.unsqueeze(-1), self.x.unsqueeze(-2))
+
+    @property
+    def shape(self):
+        n = self.x.shape[-1]
+        return torch.Size((n, n))
+
+
 def _dense(c):
     return c.evaluate() if isinstance(c, _Evaluated) else c
 
@@ -681,13 +699,61 @@ class _ExactMLL(torch.autograd.Function):
         if ctx.want_dk:
             gK, rest = g.reshape(-1, 1, 1) * rest[0], rest[1:]
         if ctx.has_scale:
-            # K = c M  =>  a'Ma = (r'a - s2 a'a)/c  and  tr(K_s^-1 M) = (N - s2 tr K_s^-1)/c
-            q, noise, c = rest
-            quad, tr, aa = q[:, 0], q[:, 2], q[:, 3]
-            gscale = (g * 0.5 * ((quad - noise * aa) - (ctx.n - noise * tr)) / (ctx.n * c.reshape(-1))).reshape(c.shape)
-            if gscale.shape != c.shape:
-                gscale = gscale.sum().reshape(c.shape)
+            gscale = _scale_grad(g, *rest, ctx.n)
         return gK, gm, g * dsig, -gm, None, gscale
+
+
+def _scale_grad(g, q, noise, c, n):
+    """g * d mll / d c for K = c M from the step's scalars q = (quad, logdet, tr K_s^-1, a'a) [B,4]:
+    a'Ma = (r'a - s2 a'a)/c  and  tr(K_s^-1 M) = (N - s2 tr K_s^-1)/c."""
+    quad, tr, aa = q[:, 0], q[:, 2], q[:, 3]
+    gscale = (g * 0.5 * ((quad - noise * aa) - (n - noise * tr)) / (n * c.reshape(-1))).reshape(c.shape)
+    if gscale.shape != c.shape:
+        gscale = gscale.sum().reshape(c.shape)
+    return gscale
+
+
+class _BMChainMLL(torch.autograd.Function):
+    """_ExactMLL for the Brownian-motion prior K_b = scale_b min(x, x') without K: the linear-time step (ops.bm_step,
+    csrc/bm.hip; fp64 arithmetic, two O(N) sweeps).  Same value, same gradients -- d/d mean = a/N, d/d target = -a/N,
+    d/d s2, and d/d scale from the closed form shared with _ExactMLL (_scale_grad).  No jitter ladder: the tridiagonal the
+    step factors is SPD whenever s2 > 0, so a failed pivot is a NaN (NanError) or a non-positive noise (NotPSDError)."""
+
+    @staticmethod
+    def forward(ctx, mean, noise, target, holder, scale, x):
+        B, n = mean.shape
+        need_grad = any(ctx.needs_input_grad[:3]) or ctx.needs_input_grad[4]
+        dt = torch.float64 if mean.dtype == torch.float64 else torch.float32
+        ws = holder.bm_workspace(B, n, x.device, dt)
+        resid = (target - mean).to(dt)
+        noise = noise.to(dt)
+        out, alpha, info = ops.bm_step(x, scale.detach(), noise, resid, ws, want_grad=need_grad)
+        chk = deferred_checks.deferring()
+        if chk is not None:
+            chk.note(info)
+        else:
+            if deferred_checks._active is not None:
+                deferred_checks._active.reserve(info)
+            bad = int((info != 0).sum().item())
+            if bad:
+                if torch.isnan(resid).any() or torch.isnan(noise).any() or torch.isnan(scale).any() or torch.isnan(x).any():
+                    raise NanError("Brownian-motion MLL: NaN in the grid, the scale, the noise or the residual")
+                raise NotPSDError(f"vol min(x, x') + sigma^2 I not positive definite for {bad} of {B} series "
+                                  f"(first failing pivot {int(info[info != 0][0].item())}): the noise must be positive")
+        ctx.n = n
+        if need_grad:
+            pk = torch.cat((out, alpha), dim=1)          # the ONE saved tensor: [B, 8 + N], the scalars and alpha
+            ctx.save_for_backward(pk)
+            ctx.scale_shape = scale.shape if scale.numel() == B else torch.Size((B,))
+            return pk[:, 0]
+        return out[:, 0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (pk,) = ctx.saved_tensors                    # out[:, 6] = the noise, out[:, 7] = the scale the step used
+        gm = g.unsqueeze(-1) * pk[:, 8:] / ctx.n
+        gscale = _scale_grad(g, pk[:, 2:6], pk[:, 6], pk[:, 7].reshape(ctx.scale_shape), ctx.n) if ctx.needs_input_grad[4] else None
+        return gm, g * pk[:, 1], -gm, None, gscale, None
 
 
 class _KronMLL(torch.autograd.Function):
@@ -753,6 +819,12 @@ class ExactMarginalLogLikelihood(Module):
             self._ws = ws = ops.MllWorkspace(B, n, want_grad, device, dtype)
         return ws
 
+    def bm_workspace(self, B, n, device, dtype=torch.float32):
+        ws = getattr(self, "_bws", None)
+        if ws is None or not ws.fits(B, n, dtype) or ws.buf.device != device:
+            self._bws = ws = ops.BmWorkspace(B, n, device, dtype)
+        return ws
+
     def kron_workspace(self, n, T, device, dtype=torch.float32):
         ws = getattr(self, "_kws", None)
         if ws is None or not ws.fits(n, T, dtype) or ws.state.device != device:
@@ -779,6 +851,26 @@ class ExactMarginalLogLikelihood(Module):
             res = res + prior_.log_prob(closure(module)).sum() / num_data
         return res
 
+    def _bm_forward(self, function_dist, target):
+        """BMGP(solver="linear")'s prior: the linear-time step (_BMChainMLL), in the mean's dtype."""
+        mean, prior = function_dist.mean, function_dist.lazy_covariance_matrix
+        if not prior.x.is_cuda or not target.is_cuda:
+            raise ops._lib.VoltHipError("ExactMarginalLogLikelihood: tensors must live on the MI355X; no CPU fallback")
+        batched = mean.ndim > 1
+        n = mean.shape[-1]
+        mean2, t2 = mean.reshape(-1, n), target.reshape(-1, n)
+        B = mean2.shape[0]
+        noise = self.likelihood.noise.reshape(-1)
+        noise = noise.expand(B) if noise.numel() == 1 else noise
+        scale = prior.scale.expand(B) if prior.scale.numel() == 1 and B > 1 else prior.scale
+        dt = torch.float64 if mean.dtype == torch.float64 else torch.float32
+        res = _BMChainMLL.apply(mean2.to(dt), noise.to(dt), t2.to(dt), self, scale, prior.x)
+        res = res.reshape(mean.shape[:-1]) if batched else res.reshape(())
+        priors = self.model.named_priors() if isinstance(self.model, Module) else ()
+        for _, module, prior_, closure in priors:
+            res = res + prior_.log_prob(closure(module)).sum() / n
+        return res
+
     def forward(self, function_dist, target):
         if isinstance(function_dist, MultitaskMultivariateNormal) and isinstance(function_dist.lazy_covariance_matrix,
                                                                                  _KroneckerPrior):
@@ -786,6 +878,8 @@ class ExactMarginalLogLikelihood(Module):
         mean = function_dist.mean
         lazy = function_dist.lazy_covariance_matrix
         scale = None
+        if isinstance(lazy, _BrownianPrior):
+            return self._bm_forward(function_dist, target)
         if isinstance(lazy, _ScaledDense):
             scale = lazy.scale
             K = lazy._product(lazy.scale.detach())

@@ -13,32 +13,104 @@ parameter, noise and posterior) -- what the batched forecast driver trains inste
 import torch
 
 from .. import ops
-from ..gp import ExactGP, MultitaskMultivariateNormal, MultivariateNormal, _KroneckerPrior, _safe_factor, same_values
+from ..gp import (ExactGP, MultitaskMultivariateNormal, MultivariateNormal, NanError, NotPSDError, _BrownianPrior, _KroneckerPrior,
+                  _safe_factor, same_values)
 from ..kernels.BMKernel import BMKernel
 from ..kernels.FBMKernel import FBMKernel
 from ..kernels.MultitaskKernel import MultitaskKernel
 
 
 class BMGP(ExactGP):
-    def __init__(self, train_x, train_y, likelihood, kernel="bm"):
+    """``solver="dense"`` (default): the N x N machinery of the data model.  ``solver="linear"`` (kernel "bm" only): Brownian
+    motion is Markov, so the MLL step and the posterior solve run in O(N) on csrc/bm.hip (fp64 arithmetic, no N x N matrix
+    anywhere) -- ``forward`` returns a lazy prior, ``posterior_call`` goes through ops.bm_step / ops.bm_solve.
+    The training grid is validated ONCE here (one host read): 1-D, x_0 >= 0, strictly increasing."""
+    SOLVERS = ("dense", "linear")
+    _POST_CHUNK = 4096                        # rows of K_t* per fp64 product of the linear posterior (bounds its temporaries)
+
+    def __init__(self, train_x, train_y, likelihood, kernel="bm", solver="dense"):
+        if solver not in self.SOLVERS:
+            raise ValueError(f"BMGP: solver must be one of {self.SOLVERS}, got {solver!r}")
+        if solver == "linear" and kernel != "bm":
+            raise ValueError(f"BMGP: solver='linear' needs kernel='bm' (Brownian motion is Markov; kernel {kernel!r} is not)")
+        if solver == "linear":
+            if train_x.ndim != 1:
+                raise ValueError(f"BMGP(solver='linear'): the grid must be 1-D [N], got shape {tuple(train_x.shape)}")
+            if train_x.shape[0] > 1:
+                first_ok, increasing = torch.stack([train_x[0] >= 0, (train_x[1:] > train_x[:-1]).all()]).tolist()
+            else:
+                first_ok, increasing = bool(train_x[0] >= 0), True
+            if not first_ok:
+                raise ValueError("BMGP(solver='linear'): the grid must start at x[0] >= 0")
+            if not increasing:
+                raise ValueError("BMGP(solver='linear'): the grid must be strictly increasing")
         super().__init__(train_x, train_y, likelihood)
         kw = {"batch_shape": train_y.shape[:-1]} if train_y.ndim > 1 else {}
         if kernel == "bm":
             self.covar_module = BMKernel(**kw).to(train_x.device)
         elif kernel == "fbm":
             self.covar_module = FBMKernel(**kw).to(train_x.device)      # BMGP.py:15-16; dense d mll / d K path
+        self.solver = solver
         self.scaling = (train_x[1] - train_x[0])
 
     def mean_module(self, x):
         return -0.5 * self.covar_module.vol.pow(2.0) * x.squeeze()        # BMGP.py:20-21
 
     def forward(self, x):
+        if self.solver == "linear":
+            stored = self.train_inputs[0]
+            if not same_values(x, stored) and not (x.ndim >= 2 and x.shape[-2:] == stored.shape
+                                                   and torch.equal(x, stored.expand_as(x))):
+                raise ValueError("BMGP(solver='linear'): the prior is over the training grid validated at construction")
+            return MultivariateNormal(self.mean_module(x), _BrownianPrior(self.covar_module.vol, self.train_inputs[0][:, 0]))
         return MultivariateNormal(self.mean_module(x), self.covar_module(x))
+
+    def _posterior_linear(self, x):
+        """mean* = m(x*) + K_*t alpha and cov = K_** - K_*t A^-1 K_t* with alpha from the linear-time step (fp64) and
+        A^-1 K_t* from the linear-time solve in the model's dtype (R = K_t* [T,N,H]); the two products over N are
+        accumulated in fp64, a block of rows at a time.  Returned in the model's dtype."""
+        with torch.no_grad():
+            xt = self.train_inputs[0][:, 0]
+            y = self.train_targets
+            batched = y.ndim > 1
+            T = y.shape[0] if batched else 1
+            n = xt.shape[0]
+            xs = x[:, 0] if x.ndim > 1 else x
+            H = xs.shape[0]
+            dt = torch.float64 if y.dtype == torch.float64 else torch.float32
+            vol = self.covar_module.vol.reshape(-1).expand(T)
+            noise = self.likelihood.noise.reshape(-1).expand(T)
+            resid = (y - self.mean_module(xt)).reshape(T, n)
+            # alpha in fp64 (the residual upcast) and K_*t rebuilt in fp64 block by block below: K_*t alpha sums N terms of
+            # either sign, so an fp32 rounding of alpha or of K_*t would come back multiplied by sum |alpha_i| K_i
+            x64, xs64, vol64 = xt.double(), xs.double(), vol.double().reshape(T, 1, 1)
+            # (the workspaces, (1 + H) T N doubles, live for this call only: a forecast takes one posterior per fit)
+            _, alpha, info = ops.bm_step(x64, vol, noise, resid.double())
+            if int((info != 0).sum().item()):
+                if not bool(torch.isfinite(vol).all()) or not bool(torch.isfinite(noise).all()):
+                    raise NanError("BMGP posterior: NaN / inf in the kernel's vol or the noise")
+                raise NotPSDError("BMGP posterior: vol min(x, x') + sigma^2 I is not positive definite (the noise must be positive)")
+            Kts = vol.to(dt).reshape(T, 1, 1) * torch.minimum(xt.to(dt).unsqueeze(-1), xs.to(dt).unsqueeze(-2))     # [T,N,H]
+            X, _ = ops.bm_solve(xt, vol, noise, Kts)
+            mean_c = torch.zeros(T, H, dtype=torch.float64, device=xt.device)
+            S = torch.zeros(T, H, H, dtype=torch.float64, device=xt.device)
+            for lo in range(0, n, self._POST_CHUNK):
+                Kc = vol64 * torch.minimum(x64[lo:lo + self._POST_CHUNK].unsqueeze(-1), xs64.unsqueeze(-2))    # [T,c,H]
+                mean_c += torch.einsum("tnh,tn->th", Kc, alpha[:, lo:lo + self._POST_CHUNK])
+                S += Kc.mT @ X[:, lo:lo + self._POST_CHUNK].double()
+            Kss = vol64 * torch.minimum(xs64.unsqueeze(-1), xs64.unsqueeze(-2))
+            mean = (self.mean_module(x).double().reshape(T, H) + mean_c).to(dt)
+            cov = (Kss - S).to(dt)
+            if not batched:
+                mean, cov = mean[0], cov[0]
+            return MultivariateNormal(mean, cov)
 
     def posterior_call(self, x):
         """Exact-GP posterior at the test points: K_s = L L' on the HIP potrf, K_s^-1 = Y Y' with Y = L^-T from the HIP
         triangular inverse, every product on the library GEMM.  One series -> MultivariateNormal(mean [H], cov [H,H]);
-        T series over the shared grid -> (mean [T,H], cov [T,H,H])."""
+        T series over the shared grid -> (mean [T,H], cov [T,H,H]).  solver="linear": _posterior_linear."""
+        if self.solver == "linear":
+            return self._posterior_linear(x)
         with torch.no_grad():
             from ..gp import _dense
             xt = self.train_inputs[0]

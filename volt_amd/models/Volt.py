@@ -21,7 +21,7 @@ _MEAN_CLASSES = {"ewma": EWMAMean, "dewma": DEWMAMean, "tewma": TEWMAMean}
 
 
 class Volt(VolGP):
-    def __init__(self, train_x, log_data, mean='constant', vol_path=None, k=25, *, multitask_vol=False):
+    def __init__(self, train_x, log_data, mean='constant', vol_path=None, k=25, *, multitask_vol=False, vol_solver="dense"):
         # The reference builds the ExactGP on [1:] but keeps the FULL train_x / log_data as attributes (Volt.py:52-62);
         # with a vol_path of length N-1 its own train_cov line is then shape-inconsistent.  The [1:] view is kept
         # everywhere here, so that train_cov matches train_inputs.
@@ -34,7 +34,7 @@ class Volt(VolGP):
             self.mean_module = _MEAN_CLASSES[name](x, y, k).to(train_x.device)
         else:
             raise ValueError("ERROR: Mean not implemented")      # the reference prints this and fails on the next line
-        self._init_vol_state(x, y, vol_path, multitask_vol)
+        self._init_vol_state(x, y, vol_path, multitask_vol, vol_solver)
         self._full_x, self._full_log_data = train_x, log_data    # Train's GPCV stage starts from the prices
 
     def Train(self, gpcv_iters=400, vol_mod_iters=1000, data_mod_iters=400, display=False, vol=None,
@@ -49,7 +49,7 @@ class Volt(VolGP):
                                           "and pass it as vol= (the reference's GPCV + MultitaskBMGP stage is not wired into "
                                           "batched Train; TrainVolModelMultitask fits the multitask vol model)")
             vol = LearnGPCV(self._full_x[1:], self._full_log_data.exp(), gpcv_iters, printing=display)
-            vol_model, vol_lh = TrainVolModel(self._full_x[1:], vol, vol_mod_iters, printing=display)
+            vol_model, vol_lh = TrainVolModel(self._full_x[1:], vol, vol_mod_iters, printing=display, solver=self.vol_solver)
         self.UpdateVolPath(vol)
         _attach_vol(self, vol_model, vol_lh, x.device)
         params = _train_noise_and_mean(self, self.likelihood)    # noise (+ the constant mean), Volt.py:110-127

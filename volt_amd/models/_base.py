@@ -11,7 +11,7 @@ from .BMGP import BMGP, MultitaskBMGP
 
 
 class VolGP(ExactGP):
-    def _init_vol_state(self, x, y, vol_path, multitask_vol=False):
+    def _init_vol_state(self, x, y, vol_path, multitask_vol=False, vol_solver="dense"):
         """x [N], y [N] or [T,N] (batched layout: one shared input grid, T target / vol rows), vol_path like y or None.
         Call after ``mean_module`` is set so that the modules register in the reference's order.  ``multitask_vol`` (batched
         models only): the reference's own vol forecaster, a MultitaskBMGP over the [N,T] log-vol paths with a
@@ -26,7 +26,13 @@ class VolGP(ExactGP):
         self.train_cov = self.covar_module(self.train_x.unsqueeze(-1), self.log_vol_path.exp().unsqueeze(-1)).detach()
         # vol forecaster: one BM-GP per series by default.  (The reference's batched models use botorch's Kronecker multitask
         # GP there: MultitaskBMGP, opt-in with multitask_vol=True; the default batched BMGP -- T independent vol models over
-        # the shared grid -- leaves out the cross-series correlation.)
+        # the shared grid -- leaves out the cross-series correlation.)  ``vol_solver="linear"``: that BM-GP on the linear-time
+        # solver (BMGP(solver="linear"), csrc/bm.hip); MultitaskBMGP keeps its dense path.
+        if vol_solver not in BMGP.SOLVERS:
+            raise ValueError(f"vol_solver must be one of {BMGP.SOLVERS}, got {vol_solver!r}")
+        self.vol_solver = vol_solver          # Volt.Train refits the vol forecaster: with the solver the model was built with
+        if multitask_vol and vol_solver != "dense":
+            raise ValueError("vol_solver='linear' is for the per-series BMGP; MultitaskBMGP (multitask_vol=True) has the dense path only")
         if multitask_vol:
             if not len(batch_shape) or self.log_vol_path.shape[:-1] != batch_shape:
                 raise ValueError("multitask_vol=True needs a batched model with a [T,N] vol_path")
@@ -35,7 +41,7 @@ class VolGP(ExactGP):
             self.vol_model = MultitaskBMGP(x, self.log_vol_path.t(), self.vol_lh)   # [N] inputs, [N,T] targets
             return
         self.vol_lh = GaussianLikelihood(batch_shape=batch_shape).to(dev)
-        self.vol_model = BMGP(x, self.log_vol_path, self.vol_lh) if self.log_vol_path.shape[:-1] == batch_shape else None
+        self.vol_model = BMGP(x, self.log_vol_path, self.vol_lh, solver=vol_solver) if self.log_vol_path.shape[:-1] == batch_shape else None
 
     def UpdateVolPath(self, vol_path):
         self.log_vol_path = vol_path.log()

@@ -284,6 +284,77 @@ def mll_step(K: torch.Tensor, resid: torch.Tensor, sigma2: torch.Tensor, ws: Mll
     return ws.out, ws.alpha, ws.info
 
 
+# ------------------------------------------------------------------ linear-time Brownian-motion solver (csrc/bm.hip)
+class BmWorkspace:
+    """Caller-owned scratch and outputs of volt_bm_step_* / volt_bm_solve_*, reusable across calls of the same
+    (B, N, H, dtype): (1 + H) B N doubles, nothing O(N^2).  H = 0: the step alone (out, alpha); H >= 1 adds X [B,N,H]."""
+
+    def __init__(self, B: int, N: int, device, dtype=torch.float32, H: int = 0):
+        self.B, self.N, self.H, self.dtype = B, N, H, dtype
+        nbytes = int(_lib.lib().volt_bm_workspace_bytes(B, N, max(H, 1)))
+        self.buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+        self.ptr = (self.buf.data_ptr() + 255) // 256 * 256
+        self.info = torch.empty(B, dtype=torch.int32, device=device)
+        if H == 0:
+            self.out = torch.empty(B, 8, dtype=dtype, device=device)
+            self.alpha = torch.empty(B, N, dtype=dtype, device=device)
+        else:
+            self.X = torch.empty(B, N, H, dtype=dtype, device=device)
+
+    def fits(self, B, N, dtype=torch.float32, H=0):
+        return self.B == B and self.N == N and self.H == H and self.dtype == dtype
+
+
+def _bm_args(x, vol, sigma2, B, dt):
+    if x.ndim != 1:
+        raise ValueError("the Brownian-motion grid x must be 1-D [N], shared by the batch")
+    return x.to(dt).contiguous(), vol.to(dt).reshape(-1).expand(B).contiguous(), sigma2.to(dt).reshape(-1).expand(B).contiguous()
+
+
+def bm_step(x: torch.Tensor, vol: torch.Tensor, sigma2: torch.Tensor, resid: torch.Tensor, ws: BmWorkspace | None = None,
+            want_grad: bool = True):
+    """One MLL(+grad) evaluation of the Brownian-motion prior K = vol * min(x, x') + sigma2 I in O(N) (volt_bm_step_f32 /
+    _f64 by resid's dtype; the arithmetic is fp64 either way).  x [N] (0 <= x_0 < x_1 < ..), vol [B], sigma2 [B],
+    resid [B,N].  Returns (out [B,8], alpha [B,N], info [B]) with the meaning of `mll_step`'s; they live in ``ws``."""
+    _need_gpu(x, vol, sigma2, resid)
+    dt = torch.float64 if resid.dtype == torch.float64 else torch.float32
+    if resid.ndim != 2:
+        raise ValueError("resid must be [B,N]")
+    B, n = resid.shape
+    if x.shape[-1] != n:
+        raise ValueError("x and resid disagree on N")
+    x, vol, sigma2 = _bm_args(x, vol, sigma2, B, dt)
+    resid = resid.to(dt).contiguous()
+    if ws is None or not ws.fits(B, n, dt):
+        ws = BmWorkspace(B, n, resid.device, dt)
+    fn = _lib.lib().volt_bm_step_f32 if dt == torch.float32 else _lib.lib().volt_bm_step_f64
+    with torch.cuda.device(resid.device):
+        _lib.check(fn(x.data_ptr(), vol.data_ptr(), sigma2.data_ptr(), resid.data_ptr(), ws.out.data_ptr(), ws.alpha.data_ptr(),
+                      ws.info.data_ptr(), ws.ptr, B, n, _lib.WANT_GRAD if want_grad else 0, _lib.stream_ptr()), "volt_bm_step")
+    return ws.out, ws.alpha, ws.info
+
+
+def bm_solve(x: torch.Tensor, vol: torch.Tensor, sigma2: torch.Tensor, R: torch.Tensor, ws: BmWorkspace | None = None):
+    """X = (vol_b min(x, x') + sigma2_b I)^-1 R_b in O(N H) per series (volt_bm_solve_f32 / _f64 by R's dtype).
+    R [B,N,H].  Returns (X [B,N,H], info [B]); they live in ``ws``."""
+    _need_gpu(x, vol, sigma2, R)
+    dt = torch.float64 if R.dtype == torch.float64 else torch.float32
+    if R.ndim != 3:
+        raise ValueError("R must be [B,N,H]")
+    B, n, H = R.shape
+    if x.shape[-1] != n:
+        raise ValueError("x and R disagree on N")
+    x, vol, sigma2 = _bm_args(x, vol, sigma2, B, dt)
+    R = R.to(dt).contiguous()
+    if ws is None or not ws.fits(B, n, dt, H):
+        ws = BmWorkspace(B, n, R.device, dt, H)
+    fn = _lib.lib().volt_bm_solve_f32 if dt == torch.float32 else _lib.lib().volt_bm_solve_f64
+    with torch.cuda.device(R.device):
+        _lib.check(fn(x.data_ptr(), vol.data_ptr(), sigma2.data_ptr(), R.data_ptr(), ws.X.data_ptr(), ws.info.data_ptr(), ws.ptr,
+                      B, n, H, _lib.stream_ptr()), "volt_bm_solve")
+    return ws.X, ws.info
+
+
 # ------------------------------------------------------------------ GPCV stage (SURVEY 8(f) row 4)
 def gemm_nt(A: torch.Tensor, B: torch.Tensor, uplo_a: int = 0, uplo_b: int = 0) -> torch.Tensor:
     """A @ B.mT on the library's fp32 MFMA GEMM.  A [T,M,K], B [T,N,K] (or 2-D); uplo_* = 1 / 2 declare an

@@ -212,7 +212,7 @@ def _capture_pays(target, n3_coeff=2.0 / 3.0):
     return batch * n3_coeff * npad ** 3 / 110e12 * 1e3 < CAPTURE_BELOW_MS
 
 
-def _auto_graph(graph, target, distributed=False, n3_coeff=2.0 / 3.0):
+def _auto_graph(graph, target, distributed=False, n3_coeff=2.0 / 3.0, launch_bound=False):
     """``graph=None`` (the default of every training loop here, as no reference call site passes it --
     voltron/train_utils.py:15,69,98,192): capture where it pays, on a CUDA device, outside an ongoing capture, single
     process.  An explicit True / False is honoured.
@@ -224,6 +224,8 @@ def _auto_graph(graph, target, distributed=False, n3_coeff=2.0 / 3.0):
         return bool(graph)
     if distributed or not target.is_cuda or torch.cuda.is_current_stream_capturing():
         return False
+    if launch_bound:         # a step that is launch-bound at EVERY N (the linear-time BM solver): the N^3 cost model does not apply
+        return True
     return _capture_pays(target, n3_coeff)
 
 
@@ -364,28 +366,29 @@ def LearnGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kerne
 
 
 # ------------------------------------------------------------------------------------------------ (f)1: vol forecaster
-def _vol_model(train_x, vol_path, kernel, batch_shape):
+def _vol_model(train_x, vol_path, kernel, batch_shape, solver="dense"):
     from .models import BMGP
     vol_lh = GaussianLikelihood(batch_shape=batch_shape).to(train_x.device)
     # (the reference's `vol_lh.noise.data = 1e-2` at :71 writes to a temporary: the noise starts at softplus(0) + 1e-4)
-    return BMGP(train_x, vol_path.log(), vol_lh, kernel=kernel).to(train_x.device), vol_lh
+    return BMGP(train_x, vol_path.log(), vol_lh, kernel=kernel, solver=solver).to(train_x.device), vol_lh
 
 
-def TrainVolModel(train_x, vol_path, train_iters=1000, printing=False, kernel="bm", graph=None):
+def TrainVolModel(train_x, vol_path, train_iters=1000, printing=False, kernel="bm", graph=None, solver="dense"):
     """voltron/train_utils.py:69-95: the Brownian-motion GP over log-vol that supplies pred_vol to Rollouts.  The MLL
     and its gradient wrt the kernel's `vol` and the noise run on the HIP step (K = vol * min(x,x') keeps d mll / d vol
-    in closed form, gp._ExactMLL)."""
-    vol_model, vol_lh = _vol_model(train_x, vol_path, kernel, torch.Size())
+    in closed form, gp._ExactMLL).  ``solver="linear"``: the O(N) step of csrc/bm.hip (gp._BMChainMLL) instead of the dense
+    one; launch-bound at every N, so ``graph=None`` captures wherever capturing is possible."""
+    vol_model, vol_lh = _vol_model(train_x, vol_path, kernel, torch.Size(), solver)
     _fit_exact(vol_model, vol_lh, train_x, vol_path.log(), list(vol_model.parameters()), LR_VOL, train_iters, printing,
-               _auto_graph(graph, vol_path))
+               _auto_graph(graph, vol_path, launch_bound=solver == "linear"))
     return vol_model, vol_lh
 
 
-def TrainVolModelBatch(train_x, vol_path, train_iters=1000, printing=False, kernel="bm", graph=None):
+def TrainVolModelBatch(train_x, vol_path, train_iters=1000, printing=False, kernel="bm", graph=None, solver="dense"):
     """TrainVolModel for T series at once: vol_path [T,N] -> one batched BMGP (per-series kernel parameter and noise)."""
     T = vol_path.shape[0]
-    vol_model, vol_lh = _vol_model(train_x, vol_path, kernel, torch.Size([T]))
-    graph = _auto_graph(graph, vol_path)
+    vol_model, vol_lh = _vol_model(train_x, vol_path, kernel, torch.Size([T]), solver)
+    graph = _auto_graph(graph, vol_path, launch_bound=solver == "linear")
     _fit_exact(vol_model, vol_lh, train_x, vol_path.log(), list(vol_model.parameters()), LR_VOL, train_iters, printing, graph,
                defer=not graph, batched=True, scale=1.0 / T)
     return vol_model, vol_lh
