@@ -435,6 +435,31 @@ int volt_bm_solve_f32(const float* x, const float* vol, const float* sigma2, con
 int volt_bm_solve_f64(const double* x, const double* vol, const double* sigma2, const double* R /*[B,N,H]*/,
                       double* X /*[B,N,H]*/, int* info, void* workspace, int B, int N, int H, void* stream);
 
+/* ---- GPCV ELBO step for the Brownian-motion prior in O(N^2)  (SingleTaskVariationalGP(prior_solver="linear"): LearnGPCV's
+ * default prior, K = vol min(x, x'), without the N x N factorisation).  The step of volt_gpcv_step_f32 / volt_gpcv_cv_step_f32
+ * with K given as (x [N], vol [B]) over a grid 0 <= x_0 < x_1 < .. shared by the batch:  A = K + jitter I = D^-1 T D^-T with T
+ * tridiagonal (volt_bm_*, above), so G = A^-1 Lq is one O(N) chain solve per column of Lq and every scalar of the KL follows
+ * from the same sweeps (csrc/gpcv_bm.hip has the recurrences).  Chain arithmetic fp64, I/O fp32.
+ *     abc == NULL (and Kc == 0): the "exp" likelihood;  abc [B,3,Kc], 1 <= Kc <= VOLT_GPCV_CV_K_MAX: the "cv" one.
+ *     out[b,0..11], grad_m, grad_mu [B,N], grad_Lq [B,N,N] (zero above the diagonal), grad_abc [B,3,Kc]: exactly as
+ *     volt_gpcv_step_f32 / volt_gpcv_cv_step_f32 document them.  There is no grad_K: the prior's only parameter is vol, and
+ *     dF/dvol follows from out[b,2..8] in closed form.  Elements of Lq above the diagonal are never read.
+ * info[b]: 0, or i + 1 for the first pivot d_i that is not a positive finite number (as volt_bm_step_*: jitter = 0 at
+ * x_0 = 0, a NaN vol); the outputs of that series are then NaN.
+ * workspace: volt_gpcv_bm_workspace_bytes(B, N, Kc) bytes (0 for a shape out of range), 256-byte aligned: one row-packed fp64
+ * lower triangle per series for the forward sweep's z (4 B N (N + 1) bytes) plus O(B N).  It needs no initialisation call.
+ * No host synchronisation, no allocation, no atomics: every reduction has a fixed order, results are bitwise repeatable, and
+ * the launch sequence replays from a hipGraph.  1 <= B <= 65535, N >= 1; indices are 64-bit.
+ * Argument errors (before any launch, checked in the order of their numbers): -1 x, -2 vol, -4 resid, -5 m, -6 Lq, -7 y NULL;
+ * -9 Kc out of range with abc, or Kc != 0 without; -10 gh_x, -11 gh_w NULL; -12 Q outside 1 .. 1024; -17 out, -18 grad_m,
+ * -19 grad_mu, -20 grad_Lq NULL; -21 grad_abc NULL with abc; -22 info NULL; -23 workspace NULL or not 256-byte aligned;
+ * -24 B outside 1 .. 65535; -25 N < 1. */
+size_t volt_gpcv_bm_workspace_bytes(int B, int N, int Kc);
+int volt_gpcv_bm_step_f32(const float* x, const float* vol, float jitter, const float* resid, const float* m, const float* Lq,
+                          const float* y, const float* abc, int Kc, const float* gh_x, const float* gh_w, int Q, float min_var,
+                          float min_scale, float w_ell, float w_kl, float* out, float* grad_m, float* grad_mu, float* grad_Lq,
+                          float* grad_abc, int* info, void* workspace, int B, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,9 @@ _SIGS = {
     "volt_bm_step_f64": (C.c_int, [_ptr] * 8 + [_i32, _i32, _i32, _ptr]),
     "volt_bm_solve_f32": (C.c_int, [_ptr] * 7 + [_i32, _i32, _i32, _ptr]),
     "volt_bm_solve_f64": (C.c_int, [_ptr] * 7 + [_i32, _i32, _i32, _ptr]),
+    "volt_gpcv_bm_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "volt_gpcv_bm_step_f32": (C.c_int, [_ptr, _ptr, _f32] + [_ptr] * 5 + [_i32, _ptr, _ptr, _i32, _f32, _f32, _f32, _f32]
+                              + [_ptr] * 7 + [_i32, _i32, _ptr]),
 }
 SUMMARY_MAX_S, SUMMARY_EXP = 32768, 1                   # include/volt_hip.h: VOLT_SUMMARY_MAX_S, VOLT_SUMMARY_EXP
 

@@ -51,7 +51,7 @@ struct BmStepParams {
     const T *x, *vol, *sigma2, *resid;
     T *out, *alpha;
     int* info;
-    double *inv, *zs;                      // [N][B], series-fastest
+    double *inv, *zs;                      // [N][B], series-fastest (inv: volt_internal_bm_inv hands it to gpcv_bm.hip)
     int64_t B, N;
 };
 
@@ -381,6 +381,9 @@ int bm_solve(const T* x, const T* vol, const T* sigma2, const T* R, T* X, int* i
 }
 
 }  // namespace volt
+
+// 1/d_i of the last volt_bm_step_* (VOLT_WANT_GRAD) on this workspace: fp64, [N][B] series-fastest (host.h; gpcv_bm.hip reads it)
+const double* volt_internal_bm_inv(const void* workspace) { return static_cast<const double*>(workspace); }
 
 extern "C" {
 

@@ -464,6 +464,31 @@ static int gpcv_step_impl(const float* K, int64_t ldk, int64_t bsk, float jitter
 
 using namespace volt;
 
+// The step's likelihood rows and its scalars for gpcv_bm.hip (host.h): the same kernels, launched on the caller's buffers.
+int volt_internal_gpcv_rows(const float* m, const float* Lq, const float* y, const float* abc, int Kc, const float* gh_x,
+                            const float* gh_w, int Q, float min_var, float min_scale, float w_ell, float* rowstat, float* cvpart,
+                            float* grad_abc, int B, int N, hipStream_t s) {
+    if (abc) {
+        GpcvWs w{};
+        w.rowstat = rowstat;
+        w.cvpart = cvpart;
+        launch_cv_rows(m, Lq, y, abc, Kc, gh_x, gh_w, Q, min_var, min_scale, w_ell, w, grad_abc, B, N, s);
+    } else {
+        hipLaunchKernelGGL(gh_ell_kernel, dim3((N + 3) / 4, B), dim3(256), 0, s, m, Lq, y, gh_x, gh_w, Q, min_var, min_scale,
+                           rowstat, N);
+    }
+    VOLT_LAUNCH_CHECK();
+    return 0;
+}
+
+int volt_internal_gpcv_scalars(const float* rowstat, const float* mllout, const float* frobT, const float* frobG, float jitter,
+                               float* out, int B, int N, int ntiles, float w_ell, float w_kl, hipStream_t s) {
+    hipLaunchKernelGGL(gpcv_scalars_kernel, dim3(B), dim3(256), 0, s, rowstat, mllout, frobT, frobG, jitter, out, N, ntiles,
+                       w_ell, w_kl);
+    VOLT_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" {
 
 int volt_gemm_nt_f32(const float* A, int64_t lda, int64_t bsa, int uplo_a, const float* Bm, int64_t ldb, int64_t bsb,

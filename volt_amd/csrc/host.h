@@ -169,4 +169,14 @@ size_t volt_internal_batch64_trtri_bytes(int B, int n);
 int volt_internal_batch64_trtri(const double* A, const double* Winv, double* Y, int B, int Np, volt::Region state, void* stream);
 // ---- mll.hip: gpcv.hip continues from the factor and Y = L^-T the step leaves in its workspace
 const float* volt_internal_mll_y(void* workspace, int B, int N);
-// ---- bm.hip: nothing internal -- its entries (volt_bm_*) are the C ABI's, declared and documented in include/volt_hip.h
+// ---- gpcv.hip: the variational step's likelihood rows ("exp": abc == nullptr, else "cv" + the fixed-order reduction into
+// grad_abc; rowstat [B,N,4], cvpart [B, ceil(N/4), 3 Kc]) and its scalars (out [B,12] from rowstat, an MLL-style out [B,8] and
+// per-series "tile" sums of tr(K^-1 S) and |G|_F^2), for gpcv_bm.hip
+int volt_internal_gpcv_rows(const float* m, const float* Lq, const float* y, const float* abc, int Kc, const float* gh_x,
+                            const float* gh_w, int Q, float min_var, float min_scale, float w_ell, float* rowstat, float* cvpart,
+                            float* grad_abc, int B, int N, hipStream_t s);
+int volt_internal_gpcv_scalars(const float* rowstat, const float* mllout, const float* frobT, const float* frobG, float jitter,
+                               float* out, int B, int N, int ntiles, float w_ell, float w_kl, hipStream_t s);
+// ---- bm.hip: its entries (volt_bm_*) are the C ABI's, declared and documented in include/volt_hip.h.  gpcv_bm.hip continues from
+// the pivots' reciprocals 1/d_i that volt_bm_step_* (VOLT_WANT_GRAD) leaves in its workspace: fp64, [N][B] series-fastest
+const double* volt_internal_bm_inv(const void* workspace);

@@ -61,13 +61,13 @@ def _standard_mean_prediction(model, train_x, log_y, vol, test_x, pred_vol, z):
 
 
 def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator,
-                 graph, vol_solver="dense", debug=None):
+                 graph, vol_solver="dense", gpcv_solver="dense", debug=None):
     """One window for the series in train_y [b, ntrain] (prices): GPCV -> data model -> vol forecasters -> rollouts,
     every stage for all b series at once.  Returns samples [b, S, H] on the device."""
     dev = train_y.device
     b, H = train_y.shape[0], test_x.numel()
     if vol_fn is None:
-        vol = LearnGPCV(train_x, train_y, train_iters=gpcv_iters, graph=graph)           # all series at once
+        vol = LearnGPCV(train_x, train_y, train_iters=gpcv_iters, graph=graph, solver=gpcv_solver)   # all series at once
     else:
         vol = vol_fn(train_x, train_y)                                                   # [b, ntrain-1]
     # the shards are independent series and the ranks may run different numbers of fits (a failed window is redone series
@@ -105,7 +105,7 @@ def _window_summary(samples, series, last_day, spec):
 
 def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample, mean, k, gpcv_iters, vol_iters,
                       data_iters, theta, vol_fn, generator, save, path_fn, debug=None, graph=None, summary=None,
-                      keep_samples=True, vol_solver="dense"):
+                      keep_samples=True, vol_solver="dense", gpcv_solver="dense"):
     """One batched pass per window (series [B,T] prices; the window ending at index e trains on series[:, e-ntrain:e]).
     A numerical failure anywhere in the batched pass (NotPSDError / NanError after the jitter ladders) must not take the
     other series down with it: the window is then redone one series at a time, and a series that still fails gets NaN
@@ -121,7 +121,7 @@ def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample,
     B = series.shape[0]
     summaries = []
     H = test_x.numel()
-    args = (nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator, graph, vol_solver)
+    args = (nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator, graph, vol_solver, gpcv_solver)
     last = None
     for last_day in end_idxs:
         train_y = series[:, last_day - ntrain:last_day].float()                          # [B, ntrain] prices
@@ -157,7 +157,7 @@ def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample,
 def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=20, train_iters=400, nsample=1000,
                                   ntrain=400, mean="ewma", save=False, k=300, ntimes=-1, vol_fn=None,
                                   vol_iters=None, par_dir="./saved-outputs/", generator=None, debug=None, graph=None,
-                                  summary=None, keep_samples=True, vol_solver="dense"):
+                                  summary=None, keep_samples=True, vol_solver="dense", gpcv_solver="dense"):
     """closes [B, T] prices for B tickers on a common calendar (device tensor).  Same window schedule,
     model name and file layout as GenerateStockPredictions (GenerateMultiMeanPreds.py:69-83,128); ``mean`` in
     ewma / dewma / tewma takes the Rollouts branch (:110-112), constant / loglinear / linear the "VOLT + standard
@@ -168,7 +168,9 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
     continuation and the return is (samples, [PathSummary per window]); with ``keep_samples=False`` the samples never
     come to the host (no sample files either) and the first element is None.
     ``vol_solver="linear"``: the vol forecaster's fit and posterior on the linear-time Brownian-motion solver
-    (TrainVolModelBatch(solver=...), csrc/bm.hip); the default "dense" changes nothing."""
+    (TrainVolModelBatch(solver=...), csrc/bm.hip); the default "dense" changes nothing.
+    ``gpcv_solver="linear"``: the GPCV stage's ELBO step in O(N^2) (LearnGPCV(solver=...), csrc/gpcv_bm.hip); independent of
+    ``vol_solver``, ignored with a ``vol_fn``, and "dense" changes nothing."""
     if mean not in _MODES and mean not in _STANDARD:
         raise ValueError(f"unknown mean {mean!r}: one of {sorted(_MODES) + list(_STANDARD)}")
     dev = closes.device
@@ -190,19 +192,19 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
         return os.path.join(par_dir, tckr, model_name + date + ".pt")                    # :128
     return _forecast_windows(tickers, closes, end_idxs.tolist(), ntrain, train_x, test_x, nsample, mean, k,
                              train_iters, vol_iters, train_iters, None, vol_fn, generator, save, path_fn, debug, graph,
-                             summary, keep_samples, vol_solver)
+                             summary, keep_samples, vol_solver, gpcv_solver)
 
 
 def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=400, n_test_times=10, nsample=1000, k=400,
                                  theta=0.01, gpcv_iters=200, vol_iters=500, data_iters=0, save=False, vol_fn=None,
                                  par_dir="./saved-outputs/", generator=None, graph=None, summary=None, keep_samples=True,
-                                 vol_solver="dense"):
+                                 vol_solver="dense", gpcv_solver="dense"):
     """The ``--kernel volt --mean ewma`` branch of experiments/weather/GPGenerator.py:20-112 for B stations at once:
     data [B,T] wind speeds (missing = -99 -> 0, then +1 as at :47,55), dt = 1/365 (:38-41), the schedule of test
     windows of :33-34, GPCV 200 / vol model 500 / data model 0 iterations (:64-67,89-92), EWMA(k=400) mean and
     mean-reverting rollouts with theta = 0.01 (:96-102), files ``stn<idx>/volt_ema<k>_theta<theta>_<last_day>.pt``
     (:103-106).  Stations shard across ranks like tickers.  Returns the last window's samples [B_local,S,H] (CPU).
-    ``summary`` / ``keep_samples`` / ``vol_solver``: as for GenerateStockPredictionsBatch (the truth is the shifted series,
+    ``summary`` / ``keep_samples`` / ``vol_solver`` / ``gpcv_solver``: as for GenerateStockPredictionsBatch (the truth is the shifted series,
     data + 1)."""
     dev = data.device
     lo, hi = shard_range(len(stations))
@@ -219,4 +221,4 @@ def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=40
                             str(last_day) + ".pt")
     return _forecast_windows(stations, data, end_idxs, ntrain, train_x, test_x, nsample, "ewma", k, gpcv_iters,
                              vol_iters, data_iters, theta, vol_fn, generator, save, path_fn, None, graph, summary,
-                             keep_samples, vol_solver)
+                             keep_samples, vol_solver, gpcv_solver)

@@ -8,17 +8,27 @@ factorisations of ``initialize_variational_parameters`` -- runs through the HIP 
 import torch
 
 from .. import ops
-from ..gp import ConstantMean, EqualMemo, Module, MultivariateNormal, _dense, _safe_factor
+from ..gp import ConstantMean, EqualMemo, Module, MultivariateNormal, _BrownianPrior, _dense, _safe_factor
+from ..kernels.BMKernel import BMKernel
 from ..likelihoods import VolatilityGaussianLikelihood  # noqa: F401  (re-exported like the reference's module namespace)
 from ..variational import CholeskyVariationalDistribution, UnwhitenedVariationalStrategy, VariationalLatent
 
 
 class SingleTaskVariationalGP(Module):
+    """``prior_solver="dense"`` (default): the prior is ``covar_module(x)`` and the ELBO step factors it (csrc/gpcv.hip).
+    ``prior_solver="linear"`` (``covar_module`` a BMKernel only): ``forward`` returns the lazy ``gp._BrownianPrior`` and
+    VariationalELBO runs the O(N^2) step of csrc/gpcv_bm.hip.  The inducing grid is validated ONCE here (one
+    host read): x_0 >= 0, strictly increasing.  The start-up values (``initialize_variational_parameters``) are dense
+    either way."""
+    PRIOR_SOLVERS = ("dense", "linear")
+
     def __init__(self, init_points=None, likelihood=None, learn_inducing_locations=True, covar_module=None,
                  mean_module=None, use_piv_chol_init=True, num_inducing=None, use_whitened_var_strat=True,
                  init_targets=None, train_inputs=None, train_targets=None, outcome_transform=None,
-                 input_transform=None):
+                 input_transform=None, *, prior_solver="dense"):
         super().__init__()
+        if prior_solver not in self.PRIOR_SOLVERS:
+            raise ValueError(f"SingleTaskVariationalGP: prior_solver must be one of {self.PRIOR_SOLVERS}, got {prior_solver!r}")
         if use_whitened_var_strat:
             raise NotImplementedError("use_whitened_var_strat=True is outside the accelerated path: LearnGPCV uses the "
                                       "unwhitened strategy (train_utils.py:30)")
@@ -26,7 +36,24 @@ class SingleTaskVariationalGP(Module):
             raise NotImplementedError("botorch input/outcome transforms are not used by LearnGPCV")
         if covar_module is None:
             raise NotImplementedError("pass covar_module (BMKernel / FBMKernel, train_utils.py:22-25)")
+        if prior_solver == "linear" and not isinstance(covar_module, BMKernel):
+            raise ValueError("SingleTaskVariationalGP: prior_solver='linear' needs covar_module=BMKernel (Brownian motion is "
+                             f"Markov; {type(covar_module).__name__} is not)")
         inducing_points = init_points.detach().clone()
+        if prior_solver == "linear":
+            grid = inducing_points.reshape(-1)
+            if inducing_points.ndim > 2 or (inducing_points.ndim == 2 and inducing_points.shape[-1] != 1):
+                raise ValueError("SingleTaskVariationalGP(prior_solver='linear'): the inducing grid must be [N] or [N,1], got "
+                                 f"shape {tuple(inducing_points.shape)}")
+            if grid.shape[0] > 1:
+                first_ok, increasing = torch.stack([grid[0] >= 0, (grid[1:] > grid[:-1]).all()]).tolist()
+            else:
+                first_ok, increasing = bool(grid[0] >= 0), True
+            if not first_ok:
+                raise ValueError("SingleTaskVariationalGP(prior_solver='linear'): the grid must start at x[0] >= 0")
+            if not increasing:
+                raise ValueError("SingleTaskVariationalGP(prior_solver='linear'): the grid must be strictly increasing")
+        self.prior_solver = prior_solver
         variational_distribution = CholeskyVariationalDistribution(inducing_points.shape[-2])
         self.variational_strategy = UnwhitenedVariationalStrategy(
             self, inducing_points, variational_distribution, learn_inducing_locations=learn_inducing_locations)
@@ -44,7 +71,13 @@ class SingleTaskVariationalGP(Module):
         return 1
 
     def forward(self, x):
-        """The prior at x (single_task_variational_gp.py:117-121)."""
+        """The prior at x (single_task_variational_gp.py:117-121); prior_solver="linear": lazily, over the inducing grid."""
+        if self.prior_solver == "linear":
+            Z = self.variational_strategy.inducing_points
+            if x is not Z and not (x.numel() == Z.numel() and torch.equal(x.reshape(-1), Z.reshape(-1))):
+                raise ValueError("SingleTaskVariationalGP(prior_solver='linear'): the prior is over the inducing grid validated "
+                                 "at construction")
+            return MultivariateNormal(self.mean_module(x), _BrownianPrior(self.covar_module.vol, Z[:, 0]))
         return MultivariateNormal(self.mean_module(x), self.covar_module(x))
 
     def __call__(self, x):

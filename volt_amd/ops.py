@@ -472,6 +472,66 @@ def gpcv_cv_step(K, resid, m, Lq, y, abc, gh_x, gh_w, ws: GpcvWorkspace | None =
     return ws
 
 
+class GpcvBmWorkspace:
+    """Caller-owned scratch and outputs of volt_gpcv_bm_step_f32, reusable across steps of the same (B, N, Kc): one packed
+    fp64 triangle per series plus O(B N); no initialisation call.  Kc > 0 adds .grad_abc [B,3,Kc] (the "cv" likelihood)."""
+
+    def __init__(self, B: int, N: int, device, Kc: int = 0):
+        self.B, self.N, self.Kc = B, N, int(Kc)
+        if Kc < 0 or Kc > GPCV_CV_K_MAX:
+            raise _lib.VoltHipError(f'the "cv" GPCV step takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms (got Kc = {Kc})')
+        nbytes = int(_lib.lib().volt_gpcv_bm_workspace_bytes(B, N, int(Kc)))
+        self.buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+        self.ptr = (self.buf.data_ptr() + 255) // 256 * 256
+        f32 = dict(dtype=torch.float32, device=device)
+        self.out = torch.empty(B, 12, **f32)
+        self.grad_m = torch.empty(B, N, **f32)
+        self.grad_mu = torch.empty(B, N, **f32)
+        self.grad_Lq = torch.empty(B, N, N, **f32)
+        self.grad_abc = torch.empty(B, 3, Kc, **f32) if Kc else None
+        self.info = torch.empty(B, dtype=torch.int32, device=device)
+
+    def fits(self, B, N, Kc=0):
+        return self.B == B and self.N == N and self.Kc == Kc
+
+
+def gpcv_bm_step(x, vol, resid, m, Lq, y, gh_x, gh_w, ws: GpcvBmWorkspace | None = None, abc=None, jitter: float = 1e-3,
+                 min_var: float = 1e-6, min_scale: float = 1e-3, w_ell: float = 1.0, w_kl: float = 1.0):
+    """``gpcv_step`` / ``gpcv_cv_step`` (abc [B,3,Kc] given) for the Brownian-motion prior K = vol min(x, x') in O(N^2)
+    (include/volt_hip.h, volt_gpcv_bm_step_f32): x [N] the grid (0 <= x_0 < x_1 < ..), vol [B] (or one value for all series).
+    Returns the workspace: .out [B,12], .grad_m, .grad_mu, .grad_Lq (.grad_abc with abc), .info -- there is no grad_K;
+    d/dvol follows from .out[:, 2:9] (variational._dkl_dscale_grad)."""
+    _need_gpu(x, vol, resid, m, Lq, y, gh_x, gh_w)
+    if Lq.ndim != 3:
+        raise ValueError("Lq must be [B,N,N]")
+    B, n, _ = Lq.shape
+    if x.shape[-1] != n:
+        raise ValueError("x and Lq disagree on N")
+    x, vol, _ = _bm_args(x, vol, vol, B, torch.float32)
+    c = lambda t, shape: t.reshape(shape).to(torch.float32).contiguous()
+    resid, m, y, Lq = c(resid, (B, n)), c(m, (B, n)), c(y, (B, n)), c(Lq, (B, n, n))
+    gh_x, gh_w = gh_x.to(torch.float32).contiguous(), gh_w.to(torch.float32).contiguous()
+    Kc = 0
+    if abc is not None:
+        if abc.ndim != 3 or abc.shape[0] != B or abc.shape[1] != 3:
+            raise ValueError("abc must be [B,3,Kc]")
+        Kc = abc.shape[2]
+        abc = c(abc, (B, 3, Kc))
+    if abc is not None and not 1 <= Kc <= GPCV_CV_K_MAX:      # no workspace can be sized: let the entry name the argument
+        ws = None
+    elif ws is None or not ws.fits(B, n, Kc):
+        ws = GpcvBmWorkspace(B, n, Lq.device, Kc)
+    o = lambda name: getattr(ws, name).data_ptr() if ws is not None and getattr(ws, name) is not None else None
+    with torch.cuda.device(Lq.device):
+        _lib.check(_lib.lib().volt_gpcv_bm_step_f32(
+            x.data_ptr(), vol.data_ptr(), float(jitter), resid.data_ptr(), m.data_ptr(), Lq.data_ptr(), y.data_ptr(),
+            abc.data_ptr() if abc is not None else None, Kc, gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var),
+            float(min_scale), float(w_ell), float(w_kl), o("out"), o("grad_m"), o("grad_mu"), o("grad_Lq"), o("grad_abc"),
+            o("info"), ws.ptr if ws is not None else None, B, n,
+            _lib.stream_ptr()), "volt_gpcv_bm_step")
+    return ws
+
+
 GPCV_MT_T_MAX = 64                 # include/volt_hip.h: volt_gpcv_mt_step_f32 takes 1 <= T <= 64 series
 
 

@@ -254,13 +254,26 @@ def _fit_exact(model, lh, train_x, target, params, lr, train_iters, printing, gr
 
 
 # ------------------------------------------------------------------------------------------------ (f)4: GPCV
+GPCV_SOLVERS = ("dense", "linear")
+
+
+def _check_gpcv_solver(solver, kernel):
+    if solver not in GPCV_SOLVERS:
+        raise ValueError(f"GPCV: solver must be one of {GPCV_SOLVERS}, got {solver!r}")
+    if solver == "linear" and kernel != "bm":
+        raise ValueError(f"GPCV: solver='linear' needs kernel='bm' (Brownian motion is Markov; kernel {kernel!r} is not)")
+
+
 def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None, *, param="exp", K=1,
-            train_likelihood=False):
+            train_likelihood=False, solver="dense"):
     """The fit inside LearnGPCV (train_utils.py:15-58), returning what it builds: (model, likelihood, losses).
     ``param="cv"`` fits the copula-process likelihood with K warp terms (volatility_likelihood.py:43-51; the start-up
     values exist for K = 1 only, as in the reference); ``train_likelihood=True`` adds its raw_a, raw_b, raw_c to the one
     Adam group at LR_GPCV (the reference's loop trains the model's parameters only, :37-43; its commented-out
-    likelihood group is not reference behaviour).  The defaults are the reference's loop."""
+    likelihood group is not reference behaviour).  The defaults are the reference's loop.
+    ``solver="linear"`` (kernel "bm" only): the ELBO step of csrc/gpcv_bm.hip, O(N^2) instead of the dense step's O(N^3)
+    (``SingleTaskVariationalGP(prior_solver="linear")``; the start-up values stay dense)."""
+    _check_gpcv_solver(solver, kernel)
     from .kernels import BMKernel, FBMKernel
     from .likelihoods import VolatilityGaussianLikelihood
     from .models import SingleTaskVariationalGP
@@ -275,7 +288,7 @@ def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", gra
     covar_module = {"bm": BMKernel, "fbm": FBMKernel}[kernel](**kw)
     model = SingleTaskVariationalGP(init_points=train_x.view(-1, 1), likelihood=likelihood, use_piv_chol_init=False,
                                     mean_module=gp.ConstantMean(**kw), covar_module=covar_module,
-                                    learn_inducing_locations=False, use_whitened_var_strat=False)
+                                    learn_inducing_locations=False, use_whitened_var_strat=False, prior_solver=solver)
     model.initialize_variational_parameters(likelihood, train_x, y=yy)
     model.train()
     likelihood.train()
@@ -304,14 +317,17 @@ def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", gra
 
 
 def LearnGPCV(train_x, train_y, train_iters=1000, printing=False, early_stopping=False, kernel="bm", graph=None, *,
-              param="exp", K=1, train_likelihood=False):
+              param="exp", K=1, train_likelihood=False, solver="dense"):
     """voltron/train_utils.py:15-67: the volatility path of a price series from a variational GP (BM or FBM prior over
     log-vol, ``y | f ~ N(0, exp f)``) fitted to the scaled returns; one HIP ELBO step per iteration.
     train_y [N+1] prices -> pred_scale [N]; train_y [T,N+1] fits T series at once (batched parameters).
-    ``param``, ``K``, ``train_likelihood``: the copula-process likelihood, see FitGPCV."""
-    graph = _auto_graph(graph, train_y[..., 1:], n3_coeff=5.0 / 3.0)   # (only the fitted scale is returned: nothing per-iteration is lost)
+    ``param``, ``K``, ``train_likelihood``: the copula-process likelihood, see FitGPCV.  ``solver="linear"``: the O(N^2) step
+    (FitGPCV); until its capture gate has been measured it is treated like the linear BM step (``launch_bound=True``)."""
+    _check_gpcv_solver(solver, kernel)
+    # (only the fitted scale is returned: nothing per-iteration is lost by capturing)
+    graph = _auto_graph(graph, train_y[..., 1:], n3_coeff=5.0 / 3.0, launch_bound=solver == "linear")
     model, likelihood, _ = FitGPCV(train_x, train_y, train_iters=train_iters, printing=printing, kernel=kernel, graph=graph,
-                                   param=param, K=K, train_likelihood=train_likelihood)
+                                   param=param, K=K, train_likelihood=train_likelihood, solver=solver)
     return likelihood(model(train_x), return_gaussian=False).scale.mean(0).detach()      # :60-67
 
 

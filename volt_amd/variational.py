@@ -1,5 +1,6 @@
 """Variational-GP plumbing of the GPCV stage, backed by volt_gpcv_step_f32 ("exp" likelihood),
-volt_gpcv_cv_step_f32 ("cv") and volt_gpcv_mt_step_f32 (the multi-task model).
+volt_gpcv_cv_step_f32 ("cv"), volt_gpcv_bm_step_f32 (either likelihood under the lazy Brownian-motion prior of
+``SingleTaskVariationalGP(prior_solver="linear")``) and volt_gpcv_mt_step_f32 (the multi-task model).
 
 The reference builds this stage from gpytorch parts (voltron/train_utils.py:20-44,
 voltron/models/single_task_variational_gp.py:69-122): ``CholeskyVariationalDistribution`` +
@@ -25,7 +26,7 @@ import torch
 from torch import nn
 
 from . import gp, ops
-from .gp import Module, MultivariateNormal, NotPSDError, NanError, _ScaledDense, _dense
+from .gp import Module, MultivariateNormal, NotPSDError, NanError, _BrownianPrior, _ScaledDense, _dense
 
 PRIOR_JITTER = 1e-3        # LazyTensor.add_jitter() default on the inducing prior
 MIN_VARIANCE = 1e-6        # gpytorch.settings.min_variance for fp32
@@ -231,6 +232,56 @@ class _GPCVCvElbo(torch.autograd.Function):
         return g1 * gm, g2 * gL, g1 * gmu, gK, None, ga, gb, gc, None, gscale, None, None, None
 
 
+class _GPCVBmElbo(torch.autograd.Function):
+    """``_GPCVElbo`` / ``_GPCVCvElbo`` (raw_a, raw_b, raw_c given) under the lazy Brownian-motion prior K = scale min(x, x'):
+    the O(N^2) step of csrc/gpcv_bm.hip.  No dense K and no dF/dK: the prior's only parameter is ``scale``, whose gradient is
+    the closed form both dense functions use (``_dkl_dscale_grad``)."""
+
+    @staticmethod
+    def forward(ctx, m, Lq, mean, scale, x, y, raw_a, raw_b, raw_c, holder, num_gh, w_ell, w_kl):
+        B, n = m.shape
+        gh_x, gh_w = _gauss_hermite(num_gh, m.device)
+        cv = raw_a is not None
+        Kc = raw_a.shape[-1] if cv else 0
+        ws = holder.bm_workspace(B, n, m.device, Kc)
+        abc = jac = None
+        if cv:
+            sa, sb, sc = torch.sigmoid(raw_a.detach()), torch.sigmoid(raw_b.detach()), torch.sigmoid(raw_c.detach())
+            abc = torch.stack([torch.nn.functional.softplus(raw_a.detach()), 3.0 * sb, 6.0 * sc - 3.0], -2)     # [..., 3, Kc]
+            jac = torch.stack([sa, 3.0 * sb * (1.0 - sb), 6.0 * sc * (1.0 - sc)], -2)
+            abc = abc.to(torch.float32).expand(B, 3, Kc)
+        ops.gpcv_bm_step(x, scale.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y, gh_x, gh_w, ws, abc=abc,
+                         jitter=PRIOR_JITTER, min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
+        chk = gp.deferred_checks.deferring()
+        if chk is None and gp.deferred_checks._active is not None:
+            gp.deferred_checks._active.reserve(ws.info)
+        if chk is not None:
+            chk.note(ws.info)
+        elif bool((ws.info != 0).any().item()):
+            _raise_step_failure("GPCV step (linear prior)", ws.info, (scale, m, Lq) + ((abc,) if cv else ()),
+                                "prior covariance K + 1e-3 I")
+        ctx.n, ctx.w_kl, ctx.cv = n, w_kl, cv
+        saved = [ws.grad_m.clone(), ws.grad_Lq.clone(), ws.grad_mu.clone(), ws.out[:, 2:9].clone(), scale.detach().clone()]
+        if cv:
+            ctx.shared, ctx.raw_shape = raw_a.ndim == 1, raw_a.shape
+            saved.append(ws.grad_abc * jac)
+        ctx.save_for_backward(*saved)
+        return ws.out[:, 9].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        sv = list(ctx.saved_tensors)
+        gm, gL, gmu, o, scale = sv[:5]
+        g1, g2 = g.reshape(-1, 1), g.reshape(-1, 1, 1)
+        gscale = _dkl_dscale_grad(o, scale, ctx.n, ctx.w_kl, g)
+        ga = gb = gc = None
+        if ctx.cv:
+            graw = g2 * sv[5]                                             # [B,3,Kc]
+            graw = graw.sum(0) if ctx.shared else graw.transpose(0, 1)    # [3,Kc] / [3,B,Kc]
+            ga, gb, gc = (graw[i].reshape(ctx.raw_shape) for i in range(3))
+        return g1 * gm, g2 * gL, g1 * gmu, gscale, None, None, ga, gb, gc, None, None, None, None
+
+
 class MultitaskVariationalLatent(MultivariateNormal):
     """What ``MultitaskVariationalGP(inducing_points)`` returns: q(F) = N(M, S_x (x) S_t) itself (event shape [N,T]), tied
     to its model so the ELBO can reach the prior."""
@@ -357,6 +408,13 @@ class VariationalELBO(Module):
         self.num_data, self.beta = float(num_data), float(beta)
         self._ws = None
         self._mt_ws = None
+        self._bm_ws = None
+
+    def bm_workspace(self, B, n, device, Kc=0):
+        ws = self._bm_ws
+        if ws is None or not ws.fits(B, n, Kc) or ws.buf.device != device:
+            self._bm_ws = ws = ops.GpcvBmWorkspace(B, n, device, Kc)
+        return ws
 
     def workspace(self, B, n, want_dk, device, Kc=0):
         ws = self._ws
@@ -392,6 +450,17 @@ class VariationalELBO(Module):
                                  K.to(torch.float32), target.to(torch.float32), self, scale,
                                  num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data)
 
+    @staticmethod
+    def _cv_raws(lik, B, m):
+        Kc = lik.raw_a.shape[-1]
+        raws = [lik.raw_a, lik.raw_b, lik.raw_c]
+        if lik.raw_a.ndim > 1:                                       # batched likelihood: one parameter set per series
+            if lik.raw_a.numel() != B * Kc:
+                raise ValueError(f"VariationalELBO: the likelihood's batch shape {tuple(lik.raw_a.shape[:-1])} does not "
+                                 f"match the model's {tuple(m.shape[:-1])}")
+            raws = [r.reshape(B, Kc) for r in raws]
+        return raws
+
     def forward(self, approximate_dist_f, target):
         if isinstance(approximate_dist_f, MultitaskVariationalLatent):
             return self._forward_multitask(approximate_dist_f, target)
@@ -409,21 +478,22 @@ class VariationalELBO(Module):
         B = m2.shape[0]
         mean2 = prior.mean.expand(m.shape).reshape(-1, n)
         lazy = prior.lazy_covariance_matrix
+        lik = self.likelihood
+        if isinstance(lazy, _BrownianPrior):                           # prior_solver="linear": no dense K anywhere
+            raws = [None, None, None]
+            if getattr(lik, "param", "exp") == "cv":
+                raws = self._cv_raws(lik, B, m)
+            res = _GPCVBmElbo.apply(m2.to(torch.float32), L3.to(torch.float32), mean2.to(torch.float32), lazy.scale, lazy.x, y2,
+                                    *raws, self, num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data)
+            return res.reshape(m.shape[:-1]) if batched else res.reshape(())
         scale = None
         if isinstance(lazy, _ScaledDense):
             scale = lazy.scale
             K3 = (scale.detach().reshape(-1, 1, 1) * lazy.base).expand(B, n, n)
         else:
             K3 = _dense(lazy).expand(B, n, n) if _dense(lazy).ndim == 2 else _dense(lazy).reshape(-1, n, n)
-        lik = self.likelihood
         if getattr(lik, "param", "exp") == "cv":
-            Kc = lik.raw_a.shape[-1]
-            raws = [lik.raw_a, lik.raw_b, lik.raw_c]
-            if lik.raw_a.ndim > 1:                                   # batched likelihood: one parameter set per series
-                if lik.raw_a.numel() != B * Kc:
-                    raise ValueError(f"VariationalELBO: the likelihood's batch shape {tuple(lik.raw_a.shape[:-1])} does not "
-                                     f"match the model's {tuple(m.shape[:-1])}")
-                raws = [r.reshape(B, Kc) for r in raws]
+            raws = self._cv_raws(lik, B, m)
             res = _GPCVCvElbo.apply(m2.to(torch.float32), L3.to(torch.float32), mean2.to(torch.float32), K3, y2, *raws, self,
                                     scale, num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data)
             return res.reshape(m.shape[:-1]) if batched else res.reshape(())
