@@ -430,6 +430,21 @@ int volt_bm_step_f32(const float* x, const float* vol, const float* sigma2, cons
                      float* alpha /*[B,N]*/, int* info, void* workspace, int B, int N, int flags, void* stream);
 int volt_bm_step_f64(const double* x, const double* vol, const double* sigma2, const double* resid, double* out /*[B,8]*/,
                      double* alpha /*[B,N]*/, int* info, void* workspace, int B, int N, int flags, void* stream);
+
+/* The same step for the volatility-kernel data model (VoltronGP / VoltMagpie / Volt with data_solver="linear"):
+ * K_b[i,k] = V_b[min(i,k)], every series on its OWN grid V_b = CumTrapz(vol_b^2, x), scale 1.  V [B,N] with batch stride
+ * `bsv` in elements (bsv >= N, or bsv = 0: one grid [N] shared by the batch); each row non-decreasing with V_0 >= 0 (the
+ * caller's contract, not checked per step; an increment of 0 is legal, T stays SPD through sigma2 > 0).  delta_i =
+ * V_i - V_{i-1} is formed in fp64 from the values as stored, so the step factors exactly the matrix a dense step on
+ * volt_fill_*(V) factors.  out[b,0..6], alpha, info, flags and the workspace (volt_bm_workspace_bytes(B, N, 1)) mean what
+ * they mean for volt_bm_step_*; out[b,7] = 1.  One launch, fp64 arithmetic, no atomics, bitwise repeatable, replays from
+ * a hipGraph, 64-bit indices, nothing O(N^2).
+ * Argument errors: -1 V NULL; -2 bsv < 0 or 0 < bsv < N; -3 sigma2, -4 resid, -5 out NULL; -6 alpha NULL with VOLT_WANT_GRAD;
+ * -7 info NULL; -8 workspace NULL or not 256-byte aligned with VOLT_WANT_GRAD; -9 B < 1; -10 N < 1; -11 unknown flag bits. */
+int volt_vk_step_f32(const float* V, int64_t bsv, const float* sigma2, const float* resid, float* out /*[B,8]*/,
+                     float* alpha /*[B,N]*/, int* info, void* workspace, int B, int N, int flags, void* stream);
+int volt_vk_step_f64(const double* V, int64_t bsv, const double* sigma2, const double* resid, double* out /*[B,8]*/,
+                     double* alpha /*[B,N]*/, int* info, void* workspace, int B, int N, int flags, void* stream);
 int volt_bm_solve_f32(const float* x, const float* vol, const float* sigma2, const float* R /*[B,N,H]*/,
                       float* X /*[B,N,H]*/, int* info, void* workspace, int B, int N, int H, void* stream);
 int volt_bm_solve_f64(const double* x, const double* vol, const double* sigma2, const double* R /*[B,N,H]*/,

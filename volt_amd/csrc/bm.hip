@@ -19,6 +19,11 @@
 //                     The chain: d_i = fma(-s^2, 1/d_{i-1}, v delta_i + 2 s), then v_rcp_f64 + two Newton steps -- one
 //                     reciprocal and one FMA; the log (a running product of v_frexp mantissas and a sum of exponents: ONE
 //                     log per series), the z chain and the sums hang off it.
+//                     VK = true (volt_vk_step_*, the volatility-kernel data model: K_b = V_b[min(i,k)], v = 1): every series
+//                     has its OWN grid V_b, staged like resid through a second transposed LDS tile; the lane carries
+//                     V_{b,i-1} and forms delta in fp64.  Both arrays then travel in tiles of BM_VT = 32 steps (two rows per
+//                     load: the half-waves take neighbouring series), so that the two register prefetches together are as
+//                     deep as the one of the shared-grid kernel.  Chain, sums and the backward sweep are the same code.
 //   bm_factor_kernel  the d chain alone, 1/d_i -> workspace (the solve's factorisation, once per series).
 //   bm_solve_kernel   one lane per (series, right-hand side): R [B,N,H] with H contiguous, so the lanes of a series load and
 //                     store whole rows.  Forward z -> workspace, backward X = D'w.  Its chains are one FMA per step.
@@ -29,6 +34,8 @@
 namespace volt {
 
 constexpr int BM_T = 64;                   // tile edge: series per workgroup, steps per staged tile
+constexpr int BM_VT = 32;                  // steps per staged tile of the per-series-grid step (VK): resid and V, half as deep each
+constexpr int BM_VLD = BM_VT + 1;          // LDS row stride of its V tile
 constexpr int BM_LD = BM_T + 1;            // LDS row stride (doubles): a column read by 64 lanes touches every bank pair once
 constexpr int BM_PF = 16;                  // steps per register-prefetched block of the workspace sweeps
 constexpr int BM_FB = 8;                   // steps per block of the step kernel's forward chain (divides BM_T)
@@ -48,61 +55,83 @@ __device__ __forceinline__ bool bm_pivot_ok(double d) { return d > 0.0 && d < __
 
 template <typename T>
 struct BmStepParams {
-    const T *x, *vol, *sigma2, *resid;
+    const T *x, *vol, *sigma2, *resid;     // x: the shared grid [N], or (VK) the per-series grids [B,N] with batch stride bsx; vol NULL: 1
     T *out, *alpha;
     int* info;
     double *inv, *zs;                      // [N][B], series-fastest (inv: volt_internal_bm_inv hands it to gpcv_bm.hip)
-    int64_t B, N;
+    int64_t B, N, bsx;
 };
 
-// rows r < nb of the tile that starts at step i0 (lane = step), and the lane's grid points x_i, x_{i-1}
+// A staged tile of TS steps x BM_T series of src [B,N] (batch stride bs) that starts at step i0: BM_T / TS rows per load, the
+// lanes of a row on consecutive steps, TS registers per lane.  Rows r >= nb and steps >= N come as 0.
+template <typename T, int TS>
+__device__ __forceinline__ void bm_fetch_rows(const T* src, int64_t bs, int64_t b0, int nb, int64_t i0, int64_t N, T (&pre)[TS]) {
+    constexpr int RP = BM_T / TS;
+    const int sub = RP == 1 ? 0 : threadIdx.x / TS;                    // (RP == 1: r < nb stays wave-uniform)
+    const int64_t i = i0 + (RP == 1 ? threadIdx.x : threadIdx.x % TS);
+    const bool in = i < N;
+#pragma unroll
+    for (int k = 0; k < TS; ++k) {
+        const int r = k * RP + sub;
+        const int64_t row = (b0 + k * RP) * bs;                          // (wave-uniform; the half-wave picks its row)
+        T val = (T)0;
+        if (r < nb && in) val = src[(sub ? row + bs : row) + i];
+        pre[k] = val;
+    }
+}
+template <typename T, int TS>
+__device__ __forceinline__ void bm_commit_rows(double* tile, int ld, int nb, const T (&pre)[TS]) {
+    constexpr int RP = BM_T / TS;
+    const int sub = RP == 1 ? 0 : threadIdx.x / TS, st = RP == 1 ? threadIdx.x : threadIdx.x % TS;
+#pragma unroll
+    for (int k = 0; k < TS; ++k) {
+        const int r = k * RP + sub;
+        if (r < nb) tile[r * ld + st] = (double)pre[k];
+    }
+}
+// the shared grid's points x_i, x_{i-1} of the tile that starts at step i0 (lane = step)
 template <typename T>
-__device__ __forceinline__ void bm_fetch(const BmStepParams<T>& p, int64_t b0, int nb, int64_t i0, T (&pre)[BM_T], T& px, T& pxm) {
+__device__ __forceinline__ void bm_fetch_grid(const BmStepParams<T>& p, int64_t i0, T& px, T& pxm) {
     const int64_t i = i0 + threadIdx.x;
     const bool in = i < p.N;
-#pragma unroll
-    for (int r = 0; r < BM_T; ++r) {
-        T val = (T)0;
-        if (r < nb && in) val = p.resid[(b0 + r) * p.N + i];
-        pre[r] = val;
-    }
     px = (T)0;
     pxm = (T)0;
     if (in) px = p.x[i];
     if (in && i > 0) pxm = p.x[i - 1];
 }
-template <typename T>
-__device__ __forceinline__ void bm_commit(double* tile, double* dl, int nb, const T (&pre)[BM_T], T px, T pxm) {
-#pragma unroll
-    for (int r = 0; r < BM_T; ++r)
-        if (r < nb) tile[r * BM_LD + threadIdx.x] = (double)pre[r];
-    dl[threadIdx.x] = (double)px - (double)pxm;
-}
 
-template <typename T, bool GRAD>
+template <typename T, bool GRAD, bool VK>
 __global__ __launch_bounds__(BM_T) void bm_step_kernel(BmStepParams<T> p) {
+    constexpr int TS = VK ? BM_VT : BM_T;                               // steps per staged tile of the forward sweep
     __shared__ double tile[BM_T * BM_LD];
-    __shared__ double dl[BM_T];
+    __shared__ double gl[VK ? BM_T * BM_VLD : BM_T];                    // VK: the V tile [series][step]; else delta of the tile's steps
     const int lane = threadIdx.x;
     const int64_t N = p.N, B = p.B;
     const int64_t b0 = (int64_t)blockIdx.x * BM_T;
     const int nb = (int)(B - b0 < BM_T ? B - b0 : BM_T);              // series of this workgroup (wave-uniform)
     const bool act = lane < nb;
     const int64_t b = b0 + lane;
-    const double v = act ? (double)p.vol[b] : 1.0, s = act ? (double)p.sigma2[b] : 1.0;
+    const double v = act && !VK ? (double)p.vol[b] : 1.0, s = act ? (double)p.sigma2[b] : 1.0;
     const double ss = s * s, s2 = 2.0 * s;
 
     // ---- forward sweep
-    T pre[BM_T], px, pxm;
-    bm_fetch(p, b0, nb, 0, pre, px, pxm);
-    double inv_prev = 0.0, zprev = 0.0, rprev = 0.0, quad = 0.0, P = 1.0;
+    T pre[TS], pg[VK ? TS : 2];                                        // pg: (VK) the V tile's rows; else x_i, x_{i-1} of this lane's step
+    auto fetch = [&](int64_t i0) {
+        bm_fetch_rows<T, TS>(p.resid, N, b0, nb, i0, N, pre);
+        if constexpr (VK) bm_fetch_rows<T, TS>(p.x, p.bsx, b0, nb, i0, N, pg);
+        else bm_fetch_grid(p, i0, pg[0], pg[1]);
+    };
+    fetch(0);
+    double inv_prev = 0.0, zprev = 0.0, rprev = 0.0, gprev = 0.0, quad = 0.0, P = 1.0;
     int64_t E = 0;
     int info = 0;
-    for (int64_t i0 = 0; i0 < N; i0 += BM_T) {
-        bm_commit(tile, dl, nb, pre, px, pxm);
+    for (int64_t i0 = 0; i0 < N; i0 += TS) {
+        bm_commit_rows<T, TS>(tile, BM_LD, nb, pre);
+        if constexpr (VK) bm_commit_rows<T, TS>(gl, BM_VLD, nb, pg);
+        else gl[lane] = (double)pg[0] - (double)pg[1];
         __syncthreads();
-        if (i0 + BM_T < N) bm_fetch(p, b0, nb, i0 + BM_T, pre, px, pxm);      // in flight while this tile's chain runs
-        const int cnt = (int)(N - i0 < BM_T ? N - i0 : BM_T);
+        if (i0 + TS < N) fetch(i0 + TS);                                       // in flight while this tile's chain runs
+        const int cnt = (int)(N - i0 < TS ? N - i0 : TS);
         int e = 0;
         // blocks of BM_FB steps: their LDS reads first (one wait), the chain in one basic block (a step past the tile's end --
         // last tile only -- reads stale LDS and is discarded by selects, not branches), then the block's stores
@@ -111,7 +140,15 @@ __global__ __launch_bounds__(BM_T) void bm_step_kernel(BmStepParams<T> p) {
 #pragma unroll
             for (int u = 0; u < BM_FB; ++u) {
                 rr[u] = tile[lane * BM_LD + j0 + u];
-                dd[u] = dl[j0 + u];
+                dd[u] = VK ? gl[lane * BM_VLD + j0 + u] : gl[j0 + u];
+            }
+            if constexpr (VK) {                                                // delta_i = V_i - V_{i-1} (V_{-1} = 0), exact in fp64
+#pragma unroll
+                for (int u = 0; u < BM_FB; ++u) {
+                    const double g = dd[u];
+                    dd[u] = g - gprev;
+                    gprev = j0 + u < cnt ? g : gprev;
+                }
             }
 #pragma unroll
             for (int u = 0; u < BM_FB; ++u) {
@@ -142,7 +179,7 @@ __global__ __launch_bounds__(BM_T) void bm_step_kernel(BmStepParams<T> p) {
                     }
             }
         }
-        e += __builtin_amdgcn_frexp_exp(P);                                    // (at most 64 mantissas in [1/2, 1) since the last time)
+        e += __builtin_amdgcn_frexp_exp(P);                                    // (at most BM_T mantissas in [1/2, 1) since the last time)
         P = __builtin_amdgcn_frexp_mant(P);
         E += e;
         __syncthreads();
@@ -349,10 +386,35 @@ int bm_step(const T* x, const T* vol, const T* sigma2, const T* resid, T* out, T
     if (N < 1) return -10;
     if (flags & ~VOLT_WANT_GRAD) return -11;
     BmStepParams<T> p{x, vol, sigma2, resid, out, alpha, info, (double*)workspace,
-                      (double*)((char*)workspace + (grad ? bm_inv_bytes(B, N) : 0)), B, N};
+                      (double*)((char*)workspace + (grad ? bm_inv_bytes(B, N) : 0)), B, N, 0};
     const dim3 grid((unsigned)((B + BM_T - 1) / BM_T));
-    if (grad) hipLaunchKernelGGL((bm_step_kernel<T, true>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((bm_step_kernel<T, false>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
+    if (grad) hipLaunchKernelGGL((bm_step_kernel<T, true, false>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((bm_step_kernel<T, false, false>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
+    VOLT_LAUNCH_CHECK();
+    return 0;
+}
+
+// the step for K_b = V_b[min(i,k)]: per-series grids V [B,N] with batch stride bsv (0: one grid for all), v = 1
+template <typename T>
+int vk_step(const T* V, int64_t bsv, const T* sigma2, const T* resid, T* out, T* alpha, int* info, void* workspace, int B, int N,
+            int flags, void* stream) {
+    if (!V) return -1;
+    if (bsv < 0 || (bsv > 0 && bsv < N)) return -2;
+    if (!sigma2) return -3;
+    if (!resid) return -4;
+    if (!out) return -5;
+    const bool grad = (flags & VOLT_WANT_GRAD) != 0;
+    if (grad && !alpha) return -6;
+    if (!info) return -7;
+    if (grad && (!workspace || ((uintptr_t)workspace & 255))) return -8;
+    if (B < 1) return -9;
+    if (N < 1) return -10;
+    if (flags & ~VOLT_WANT_GRAD) return -11;
+    BmStepParams<T> p{V, nullptr, sigma2, resid, out, alpha, info, (double*)workspace,
+                      (double*)((char*)workspace + (grad ? bm_inv_bytes(B, N) : 0)), B, N, bsv};
+    const dim3 grid((unsigned)((B + BM_T - 1) / BM_T));
+    if (grad) hipLaunchKernelGGL((bm_step_kernel<T, true, true>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((bm_step_kernel<T, false, true>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
     VOLT_LAUNCH_CHECK();
     return 0;
 }
@@ -399,6 +461,14 @@ int volt_bm_step_f32(const float* x, const float* vol, const float* sigma2, cons
 int volt_bm_step_f64(const double* x, const double* vol, const double* sigma2, const double* resid, double* out, double* alpha,
                      int* info, void* workspace, int B, int N, int flags, void* stream) {
     return volt::bm_step<double>(x, vol, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
+}
+int volt_vk_step_f32(const float* V, int64_t bsv, const float* sigma2, const float* resid, float* out, float* alpha, int* info,
+                     void* workspace, int B, int N, int flags, void* stream) {
+    return volt::vk_step<float>(V, bsv, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
+}
+int volt_vk_step_f64(const double* V, int64_t bsv, const double* sigma2, const double* resid, double* out, double* alpha,
+                     int* info, void* workspace, int B, int N, int flags, void* stream) {
+    return volt::vk_step<double>(V, bsv, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
 }
 int volt_bm_solve_f32(const float* x, const float* vol, const float* sigma2, const float* R, float* X, int* info,
                       void* workspace, int B, int N, int H, void* stream) {

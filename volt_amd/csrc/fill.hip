@@ -41,6 +41,45 @@ __global__ __launch_bounds__(256) void cumtrapz_kernel(const T* __restrict__ vol
     for (int i = threadIdx.x; i < N; i += blockDim.x) out[i] = prod[i];
 }
 
+// The same for a series that does not fit in LDS (N * sizeof(T) > 160 KB: the linear-time data solver has no N x N matrix to
+// cap N): chunks of CUMTRAPZ_CHUNK elements pass through LDS, lane 0 carries the fp64 accumulator from chunk to chunk.  The
+// same products, the same order of additions, the same roundings: bit-identical to one pass.
+constexpr int CUMTRAPZ_CHUNK = 8192;
+template <typename T>
+__global__ __launch_bounds__(256) void cumtrapz_long_kernel(const T* __restrict__ vol, int64_t bs_vol,
+                                                            const T* __restrict__ x, int64_t bs_x,
+                                                            T* __restrict__ V, int N, int square) {
+    __shared__ T prod[CUMTRAPZ_CHUNK];
+    const int b = blockIdx.x;
+    const T* v = vol + (int64_t)b * bs_vol;
+    const T* xb = x + (int64_t)b * bs_x;
+    T* out = V + (int64_t)b * N;
+    const T dx = xb[1] - xb[0];
+    const T half = dx * T(0.5);
+    double acc = 0.0;                                // (lane 0's is the running sum)
+    for (int c0 = 0; c0 < N; c0 += CUMTRAPZ_CHUNK) {
+        const int cnt = N - c0 < CUMTRAPZ_CHUNK ? N - c0 : CUMTRAPZ_CHUNK;
+        for (int j = threadIdx.x; j < cnt; j += blockDim.x) {
+            const int i = c0 + j;
+            T y = v[i];
+            if (square) y = y * y;
+            const T w = (i == 0 || i == N - 1) ? half : dx;
+            if constexpr (sizeof(T) == 4) prod[j] = __fmul_rn(w, y);
+            else prod[j] = __dmul_rn(w, y);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int j = 0; j < cnt; ++j) {
+                acc += (double)prod[j];
+                prod[j] = (T)acc;
+            }
+        }
+        __syncthreads();
+        for (int j = threadIdx.x; j < cnt; j += blockDim.x) out[c0 + j] = prod[j];
+        __syncthreads();
+    }
+}
+
 // K[b,i,j] = V[b,min(i,j)].  Pure HBM-write stream: 4*N^2 bytes out, 4*N in (L2-resident).
 // Workgroup = 16 rows x 256 columns; a thread owns one 16-byte column quad and walks 4 rows, so
 // every store instruction of a wave writes 64 x 16 B = 1 KiB contiguous.  Rows per thread measured at 64 x 4096^2
@@ -87,8 +126,14 @@ static int launch_cumtrapz(const T* vol, int64_t bs_vol, const T* x, int64_t bs_
     if (!x) return -3;
     if (!V) return -5;
     if (B < 0) return -6;
-    if (N < 2 || (size_t)N * sizeof(T) > 160 * 1024) return -7;   // x[1]-x[0] needs N >= 2
+    if (N < 2) return -7;                         // x[1]-x[0] needs N >= 2
     if (B == 0) return 0;
+    if ((size_t)N * sizeof(T) > 160 * 1024) {     // longer than LDS: the chunked kernel
+        hipLaunchKernelGGL(cumtrapz_long_kernel<T>, dim3(B), dim3(256), 0, (hipStream_t)stream, vol, bs_vol, x, bs_x, V, N,
+                           square);
+        VOLT_LAUNCH_CHECK();
+        return 0;
+    }
     if ((size_t)N * sizeof(T) > 48 * 1024) {      // large dynamic LDS has to be opted into
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cumtrapz_kernel<T>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)N * sizeof(T)));

@@ -256,6 +256,37 @@ class _BrownianPrior(_ScaledDense):
         return torch.Size((n, n))
 
 
+class _VolPrior(_Evaluated):
+    """Lazy covariance of the data model with ``data_solver="linear"`` (models/_base.py): K[.., i, j] = V[.., min(i, j)] over
+    the integrated squared vol path ``x`` = V ([N] or [B,N]), never formed -- ExactMarginalLogLikelihood hands V to the
+    linear-time step (_VKChainMLL, csrc/bm.hip).  K is filled only when ``.evaluate()`` / ``.to_dense()`` is asked for."""
+
+    def __init__(self, V):
+        self.x = V
+
+    @property
+    def tensor(self):
+        return ops.fill(self.x)
+
+    @tensor.setter
+    def tensor(self, v):
+        raise AttributeError("read-only")
+
+    def evaluate(self):
+        return ops.fill(self.x)
+
+    def to_dense(self):
+        return ops.fill(self.x)
+
+    def detach(self):
+        return ops.fill(self.x.detach())
+
+    @property
+    def shape(self):
+        n = self.x.shape[-1]
+        return torch.Size((*self.x.shape[:-1], n, n))
+
+
 def _dense(c):
     return c.evaluate() if isinstance(c, _Evaluated) else c
 
@@ -756,6 +787,47 @@ class _BMChainMLL(torch.autograd.Function):
         return gm, g * pk[:, 1], -gm, None, gscale, None
 
 
+class _VKChainMLL(torch.autograd.Function):
+    """_ExactMLL for the volatility-kernel data model K_b = V_b[min(i, j)] without K: the linear-time step on per-series grids
+    (ops.vk_step, csrc/bm.hip; fp64 arithmetic, two O(N) sweeps).  Same value, same gradients -- d/d mean = a/N,
+    d/d target = -a/N, d/d s2; the vol path is frozen (no gradient with respect to V, no scale).  No jitter ladder, as in
+    _BMChainMLL: a failed pivot is a NaN (NanError) or a non-positive noise (NotPSDError)."""
+
+    @staticmethod
+    def forward(ctx, mean, noise, target, holder, V):
+        B, n = mean.shape
+        need_grad = any(ctx.needs_input_grad[:3])
+        dt = torch.float64 if mean.dtype == torch.float64 else torch.float32
+        ws = holder.bm_workspace(B, n, V.device, dt)
+        resid = (target - mean).to(dt)
+        noise = noise.to(dt)
+        out, alpha, info = ops.vk_step(V.detach(), noise, resid, ws, want_grad=need_grad)
+        chk = deferred_checks.deferring()
+        if chk is not None:
+            chk.note(info)
+        else:
+            if deferred_checks._active is not None:
+                deferred_checks._active.reserve(info)
+            bad = int((info != 0).sum().item())
+            if bad:
+                if torch.isnan(resid).any() or torch.isnan(noise).any() or torch.isnan(V).any():
+                    raise NanError("volatility-kernel MLL: NaN in the integrated vol path, the noise or the residual")
+                raise NotPSDError(f"V[min(i, j)] + sigma^2 I not positive definite for {bad} of {B} series "
+                                  f"(first failing pivot {int(info[info != 0][0].item())}): the noise must be positive")
+        ctx.n = n
+        if need_grad:
+            pk = torch.cat((out, alpha), dim=1)          # the ONE saved tensor: [B, 8 + N], the scalars and alpha
+            ctx.save_for_backward(pk)
+            return pk[:, 0]
+        return out[:, 0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (pk,) = ctx.saved_tensors
+        gm = g.unsqueeze(-1) * pk[:, 8:] / ctx.n
+        return gm, g * pk[:, 1], -gm, None, None
+
+
 class _KronMLL(torch.autograd.Function):
     """mll = log N(vec Y; vec mu, K_x (x) K_t + I (x) D) / (N T) of MultitaskBMGP and its gradient wrt the five raw
     parameters, from ONE prologue -> batched step (B = T over the shared M) -> epilogue sequence (ops.kron_mll_step,
@@ -871,6 +943,30 @@ class ExactMarginalLogLikelihood(Module):
             res = res + prior_.log_prob(closure(module)).sum() / n
         return res
 
+    def _vk_forward(self, function_dist, target):
+        """The data model's prior with data_solver="linear": the linear-time step on per-series grids (_VKChainMLL), in the
+        integrated vol path's dtype (the dense step computes in the covariance's, which is V's)."""
+        mean, prior = function_dist.mean, function_dist.lazy_covariance_matrix
+        if not prior.x.is_cuda or not target.is_cuda:
+            raise ops._lib.VoltHipError("ExactMarginalLogLikelihood: tensors must live on the MI355X; no CPU fallback")
+        batched = mean.ndim > 1
+        n = mean.shape[-1]
+        mean2, t2 = mean.reshape(-1, n), target.reshape(-1, n)
+        B = mean2.shape[0]
+        V = prior.x.reshape(-1, n)
+        V = V[0] if V.shape[0] == 1 else V               # [N]: one grid for all series
+        if V.ndim == 2 and V.shape[0] != B:
+            raise ValueError(f"ExactMarginalLogLikelihood: {V.shape[0]} vol paths for {B} series")
+        noise = self.likelihood.noise.reshape(-1)
+        noise = noise.expand(B) if noise.numel() == 1 else noise
+        dt = torch.float64 if V.dtype == torch.float64 else torch.float32
+        res = _VKChainMLL.apply(mean2.to(dt), noise.to(dt), t2.to(dt), self, V)
+        res = res.reshape(mean.shape[:-1]) if batched else res.reshape(())
+        priors = self.model.named_priors() if isinstance(self.model, Module) else ()
+        for _, module, prior_, closure in priors:
+            res = res + prior_.log_prob(closure(module)).sum() / n
+        return res
+
     def forward(self, function_dist, target):
         if isinstance(function_dist, MultitaskMultivariateNormal) and isinstance(function_dist.lazy_covariance_matrix,
                                                                                  _KroneckerPrior):
@@ -878,6 +974,8 @@ class ExactMarginalLogLikelihood(Module):
         mean = function_dist.mean
         lazy = function_dist.lazy_covariance_matrix
         scale = None
+        if isinstance(lazy, _VolPrior):
+            return self._vk_forward(function_dist, target)
         if isinstance(lazy, _BrownianPrior):
             return self._bm_forward(function_dist, target)
         if isinstance(lazy, _ScaledDense):

@@ -1,29 +1,38 @@
 """What VoltronGP, VoltMagpie and Volt share (voltron/models/{VoltronGP,VoltMagpie,Volt}.py): an exact GP whose
 covariance is the volatility kernel of a stored vol path, filled ONCE on the device (``train_cov``) and reused by every
-training step, plus a Brownian-motion GP over the log-vol path that forecasts it.  Attribute names are the reference's
+training step (``data_solver="linear"``: kept as its integrated vol path V, gp._VolPrior, and never filled), plus a Brownian-motion GP over the log-vol path that forecasts it.  Attribute names are the reference's
 (rollout_utils.py:7-32,81-86 and train_utils.py:222-224 read and write them); the subclasses only choose the mean."""
 import torch
 
+from .. import ops
 from ..gp import (ExactGP, ExactMarginalLogLikelihood, GaussianLikelihood, MultitaskGaussianLikelihood, MultivariateNormal,
-                  same_values)
+                  _VolPrior, same_values)
 from ..kernels import VolatilityKernel
 from .BMGP import BMGP, MultitaskBMGP
 
 
 class VolGP(ExactGP):
-    def _init_vol_state(self, x, y, vol_path, multitask_vol=False, vol_solver="dense"):
+    def _init_vol_state(self, x, y, vol_path, multitask_vol=False, vol_solver="dense", data_solver="dense"):
         """x [N], y [N] or [T,N] (batched layout: one shared input grid, T target / vol rows), vol_path like y or None.
         Call after ``mean_module`` is set so that the modules register in the reference's order.  ``multitask_vol`` (batched
         models only): the reference's own vol forecaster, a MultitaskBMGP over the [N,T] log-vol paths with a
         MultitaskGaussianLikelihood(T) at noise 1e-3 (VoltMagpie.py:51-55) -- the T forecasts are then jointly drawn and
-        correlated; without it T independent BM-GPs (the batched BMGP)."""
+        correlated; without it T independent BM-GPs (the batched BMGP).  ``data_solver="linear"``: ``train_cov`` is the lazy
+        _VolPrior over V = CumTrapz(vol^2, x) instead of the N x N fill, and the MLL of the training inputs runs on the linear-time
+        step (gp._VKChainMLL, csrc/bm.hip); the default "dense" is the filled matrix and the dense step."""
+        if data_solver not in BMGP.SOLVERS:
+            raise ValueError(f"data_solver must be one of {BMGP.SOLVERS}, got {data_solver!r}")
+        self.data_solver = data_solver        # Volt.Train fits the data model with the solver the model was built with
         dev = x.device
         batch_shape = y.shape[:-1]
         self.covar_module = VolatilityKernel().to(dev)
         self.train_x = x.unsqueeze(0).repeat(*batch_shape, 1) if len(batch_shape) else x
         self.train_y = y
         self.log_vol_path = vol_path.log() if vol_path is not None else -torch.ones(x.shape[0], device=dev)
-        self.train_cov = self.covar_module(self.train_x.unsqueeze(-1), self.log_vol_path.exp().unsqueeze(-1)).detach()
+        if data_solver == "linear":
+            self.train_cov = self._vol_prior(self.train_x.squeeze(), self.log_vol_path.exp().squeeze())   # (the kernel's squeeze()s)
+        else:
+            self.train_cov = self.covar_module(self.train_x.unsqueeze(-1), self.log_vol_path.exp().unsqueeze(-1)).detach()
         # vol forecaster: one BM-GP per series by default.  (The reference's batched models use botorch's Kronecker multitask
         # GP there: MultitaskBMGP, opt-in with multitask_vol=True; the default batched BMGP -- T independent vol models over
         # the shared grid -- leaves out the cross-series correlation.)  ``vol_solver="linear"``: that BM-GP on the linear-time
@@ -43,8 +52,17 @@ class VolGP(ExactGP):
         self.vol_lh = GaussianLikelihood(batch_shape=batch_shape).to(dev)
         self.vol_model = BMGP(x, self.log_vol_path, self.vol_lh, solver=vol_solver) if self.log_vol_path.shape[:-1] == batch_shape else None
 
+    @staticmethod
+    def _vol_prior(x, vol):
+        """The linear data solver's covariance: V = CumTrapz(vol^2, x) as VolatilityKernel.forward forms it, not filled."""
+        return _VolPrior(ops.cumtrapz(vol, x, square=True).detach())
+
     def UpdateVolPath(self, vol_path):
         self.log_vol_path = vol_path.log()
+        if self.data_solver == "linear":
+            self.train_cov = self._vol_prior(self.train_inputs[0].squeeze(-1) if self.train_x.ndim == 1 else self.train_x,
+                                             self.log_vol_path.exp())
+            return
         self.train_cov = self.covar_module(self.train_inputs[0].squeeze(-1) if self.train_x.ndim == 1 else self.train_x,
                                            self.log_vol_path.exp())
 
@@ -79,7 +97,7 @@ class VolGP(ExactGP):
     def forward(self, x):
         mean_x = self.mean_module(x)
         if same_values(x, self.train_inputs[0]):          # torch.equal without the device sync when aliased
-            covar_x = self.train_cov                      # the cached fill
+            covar_x = self.train_cov                      # the cached fill (data_solver="linear": the lazy _VolPrior)
         else:
             covar_x = self.covar_module(x, self.log_vol_path.exp())
         return MultivariateNormal(mean_x, covar_x)

@@ -334,6 +334,35 @@ def bm_step(x: torch.Tensor, vol: torch.Tensor, sigma2: torch.Tensor, resid: tor
     return ws.out, ws.alpha, ws.info
 
 
+def vk_step(V: torch.Tensor, sigma2: torch.Tensor, resid: torch.Tensor, ws: BmWorkspace | None = None, want_grad: bool = True):
+    """One MLL(+grad) evaluation of the volatility-kernel data model K_b = V_b[min(i, j)] + sigma2_b I in O(N) (volt_vk_step_f32 /
+    _f64 by resid's dtype; the arithmetic is fp64 either way), without K.  V [N] (one grid for all series) or [B,N] (each
+    series its own: non-decreasing rows, V_0 >= 0 -- what `cumtrapz(vol, x, square=True)` returns), sigma2 [B] (or one
+    value), resid [B,N].  Returns (out [B,8], alpha [B,N], info [B]) with the meaning of `mll_step`'s; they live in ``ws``."""
+    _need_gpu(V, sigma2, resid)
+    dt = torch.float64 if resid.dtype == torch.float64 else torch.float32
+    if resid.ndim != 2:
+        raise ValueError("resid must be [B,N]")
+    B, n = resid.shape
+    if V.ndim not in (1, 2) or V.shape[-1] != n:
+        raise ValueError("V must be [N] or [B,N] with resid's N")
+    if V.ndim == 2 and V.shape[0] != B:
+        raise ValueError("V [B,N] and resid disagree on B")
+    V = V.to(dt)
+    if V.stride(-1) != 1 or (V.ndim == 2 and B > 1 and V.stride(0) < n):
+        V = V.contiguous()
+    bsv = 0 if V.ndim == 1 or B == 1 else V.stride(0)
+    sigma2 = sigma2.to(dt).reshape(-1).expand(B).contiguous()
+    resid = resid.to(dt).contiguous()
+    if ws is None or not ws.fits(B, n, dt):
+        ws = BmWorkspace(B, n, resid.device, dt)
+    fn = _lib.lib().volt_vk_step_f32 if dt == torch.float32 else _lib.lib().volt_vk_step_f64
+    with torch.cuda.device(resid.device):
+        _lib.check(fn(V.data_ptr(), bsv, sigma2.data_ptr(), resid.data_ptr(), ws.out.data_ptr(), ws.alpha.data_ptr(),
+                      ws.info.data_ptr(), ws.ptr, B, n, _lib.WANT_GRAD if want_grad else 0, _lib.stream_ptr()), "volt_vk_step")
+    return ws.out, ws.alpha, ws.info
+
+
 def bm_solve(x: torch.Tensor, vol: torch.Tensor, sigma2: torch.Tensor, R: torch.Tensor, ws: BmWorkspace | None = None):
     """X = (vol_b min(x, x') + sigma2_b I)^-1 R_b in O(N H) per series (volt_bm_solve_f32 / _f64 by R's dtype).
     R [B,N,H].  Returns (X [B,N,H], info [B]); they live in ``ws``."""

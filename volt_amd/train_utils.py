@@ -438,37 +438,50 @@ def _attach_vol(model, vol_model, vol_lh, dev):
         model.vol_model = vol_model.to(dev)
 
 
-def TrainDataModel(train_x, train_y, vol_model, vol_lh, vol_path, train_iters=1000, printing=False, graph=None):
-    """voltron/train_utils.py:98-144: VoltronGP with a log-linear mean; noise, slope and intercept train."""
+def _check_data_solver(solver):
+    from .models import BMGP
+    if solver not in BMGP.SOLVERS:
+        raise ValueError(f"data model: solver must be one of {BMGP.SOLVERS}, got {solver!r}")
+
+
+def TrainDataModel(train_x, train_y, vol_model, vol_lh, vol_path, train_iters=1000, printing=False, graph=None, solver="dense"):
+    """voltron/train_utils.py:98-144: VoltronGP with a log-linear mean; noise, slope and intercept train.
+    ``solver="linear"``: the O(N) step of csrc/bm.hip on the integrated vol path (gp._VKChainMLL) instead of the N x N fill and
+    the dense step; the iteration is then launch-bound at every N and captured by default."""
+    _check_data_solver(solver)
     dev = train_x.device
     log_y = train_y.log()
     lh = GaussianLikelihood().to(dev)
-    model = VoltronGP(train_x, log_y, lh, vol_path)
+    model = VoltronGP(train_x, log_y, lh, vol_path, data_solver=solver)
     _set_mean(model, "loglinear", train_x, log_y)
     _attach_vol(model, vol_model, vol_lh, dev)
     params = _train_noise_and_mean(model, lh)
-    _fit_exact(model, lh, train_x, log_y, params, LR_DATA, train_iters, printing, _auto_graph(graph, log_y))
+    _fit_exact(model, lh, train_x, log_y, params, LR_DATA, train_iters, printing,
+               _auto_graph(graph, log_y, launch_bound=solver == "linear"))
     return model, lh
 
 
 def TrainVoltMagpieModel(train_x, train_y, vol_model, vol_lh, vol_path, train_iters=1000, printing=False, k=25,
-                         theta=0.5, mean_func="ewma", graph=None):
+                         theta=0.5, mean_func="ewma", graph=None, solver="dense"):
     """voltron/train_utils.py:192-257: VoltMagpie with the chosen mean; the noise (and a constant / (log)linear mean's
-    parameters) train, the vol forecaster rides along frozen."""
+    parameters) train, the vol forecaster rides along frozen.  ``solver``: as in TrainDataModel."""
+    _check_data_solver(solver)
     dev = train_x.device
     log_y = train_y.log()
     lh = GaussianLikelihood().to(dev)
-    model = VoltMagpie(train_x, log_y, lh, vol_path, k=k).to(dev)
+    model = VoltMagpie(train_x, log_y, lh, vol_path, k=k, data_solver=solver).to(dev)
     if mean_func.lower() != "ewma":                                   # VoltMagpie's own mean is the EWMA
         _set_mean(model, mean_func, train_x, log_y, k, theta)
     _attach_vol(model, vol_model, vol_lh, dev)
     params = _train_noise_and_mean(model, lh)
-    _fit_exact(model, lh, train_x, log_y, params, LR_DATA, train_iters, printing, _auto_graph(graph, log_y))
+    _fit_exact(model, lh, train_x, log_y, params, LR_DATA, train_iters, printing,
+               _auto_graph(graph, log_y, launch_bound=solver == "linear"))
     return model, lh
 
 
 def TrainVoltMagpieBatch(train_x, train_y, vol_path, train_iters=1000, k=25, printing=False, process_group=None,
-                         shared_noise=False, mean_func="ewma", theta=0.5, graph=None, defer=True, reduce_across_ranks=True):
+                         shared_noise=False, mean_func="ewma", theta=0.5, graph=None, defer=True, reduce_across_ranks=True,
+                         solver="dense"):
     """B independent series in one batched model (train_y [B,N] raw prices[1:], vol_path [B,N]).  Per-series raw_noise
     by default (each series is its own GP, as in the reference's loop over tickers); ``shared_noise`` ties one
     likelihood across series AND ranks, whose gradient is then all-reduced.  ``mean_func`` as in
@@ -480,13 +493,15 @@ def TrainVoltMagpieBatch(train_x, train_y, vol_path, train_iters=1000, k=25, pri
     With ``reduce_across_ranks`` EVERY rank of the group must call this with the same ``train_iters``, ``defer`` and ``graph``
     (each stretch of the loop ends in a collective "replay?" decision, and a rank whose jitter ladder is exhausted raises
     only after that decision has been taken by all -- see ``agree``): checked once, up front, with an all-gather.
+    ``solver``: as in TrainDataModel (each series steps on its own integrated vol path).
     Returns (model, likelihood, last per-series losses)."""
     from . import distributed as vdist
+    _check_data_solver(solver)
     B = train_y.shape[0]
     dev = train_x.device
     log_y = train_y.log()
     lh = GaussianLikelihood(batch_shape=torch.Size() if shared_noise else torch.Size([B])).to(dev)
-    model = VoltMagpie(train_x, log_y, lh, vol_path, k=k).to(dev)
+    model = VoltMagpie(train_x, log_y, lh, vol_path, k=k, data_solver=solver).to(dev)
     if mean_func.lower() != "ewma":
         _set_mean(model, mean_func, train_x, log_y, k, theta, torch.Size([B]))
     params = _train_noise_and_mean(model, lh)
@@ -498,7 +513,7 @@ def TrainVoltMagpieBatch(train_x, train_y, vol_path, train_iters=1000, k=25, pri
         warnings.warn("TrainVoltMagpieBatch: graph=True is for single-process runs (the all-reduce stays eager); running the "
                       "eager loop with the deferred check", RuntimeWarning, stacklevel=2)
         graph = False
-    graph = _auto_graph(graph, log_y, distributed)
+    graph = _auto_graph(graph, log_y, distributed, launch_bound=solver == "linear")
     count = torch.tensor(float(B), device=dev)
 
     def reduce(loss):                                     # the path's one collective: summed loss (and a shared gradient)
