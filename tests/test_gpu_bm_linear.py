@@ -258,7 +258,7 @@ def test_bmgp_linear_saves_one_packed_tensor_and_defers_checks():
     mll = gp.ExactMarginalLogLikelihood(lh, m)
     val = mll(m(m.train_inputs[0][:, 0]), m.train_targets)
     fn = val.grad_fn
-    while fn is not None and "BMChainMLL" not in type(fn).__name__:
+    while fn is not None and "ChainMLL" not in type(fn).__name__:
         fn = fn.next_functions[0][0] if fn.next_functions else None
     assert fn is not None and len(fn.saved_tensors) == 1 and tuple(fn.saved_tensors[0].shape) == (1, 8 + n)
     assert isinstance(m(m.train_inputs[0][:, 0]).lazy_covariance_matrix, gp._BrownianPrior)

@@ -1,5 +1,5 @@
 """The linear-time step of the volatility-kernel data model on the MI355X (volt_vk_step_*, csrc/bm.hip; ops.vk_step,
-gp._VolPrior / _VKChainMLL, VoltronGP / VoltMagpie / Volt(data_solver="linear"), the data-model trainers' solver="linear")
+gp._VolPrior / _ChainMLL, VoltronGP / VoltMagpie / Volt(data_solver="linear"), the data-model trainers' solver="linear")
 against the fp64 restatement of its recurrences (tests/vk_chain_ref.py, itself checked against the oracle and dense fp64
 LAPACK in tests/test_vk_chain_host.py), against the dense path and against the fp64 oracle.
 
@@ -335,7 +335,7 @@ def test_linear_data_model_saves_one_packed_tensor_and_defers_checks():
     mll = gp.ExactMarginalLogLikelihood(lh, m)
     val = mll(m(tx), y)
     fn = val.grad_fn
-    while fn is not None and "VKChainMLL" not in type(fn).__name__:
+    while fn is not None and "ChainMLL" not in type(fn).__name__:
         fn = fn.next_functions[0][0] if fn.next_functions else None
     assert fn is not None and len(fn.saved_tensors) == 1 and tuple(fn.saved_tensors[0].shape) == (1, 8 + n)
     # a forward for any other x fills densely, as before

@@ -111,6 +111,17 @@ class deferred_checks:
         acc, flat = self._slot(info)
         acc.bitwise_or_(flat)                            # one launch per step; non-zero once any step failed
 
+    @classmethod
+    def settle(cls, *infos) -> bool:
+        """The protocol every step follows once its ``info`` words are on the device.  While deferring: OR each into its
+        accumulator and return False -- no allocation and no host read, so the step can be captured.  Otherwise: size the
+        accumulators if a context is active (``immediate``) and return True -- the caller reads ``info`` on the host now."""
+        chk = cls._active
+        if chk is not None:
+            for info in infos:
+                (chk.reserve if chk.immediate else chk.note)(info)
+        return chk is None or chk.immediate
+
     def clear(self):
         for acc in self._acc.values():
             acc.zero_()
@@ -240,7 +251,7 @@ class _ScaledDense(_Evaluated):
 
 class _BrownianPrior(_ScaledDense):
     """Lazy prior covariance of BMGP(solver="linear"): K = scale * min(x, x') over the 1-D grid ``x``, never formed --
-    ExactMarginalLogLikelihood hands (scale, x) to the linear-time step (_BMChainMLL, csrc/bm.hip).  min(x, x') is
+    ExactMarginalLogLikelihood hands (scale, x) to the linear-time step (_ChainMLL, csrc/bm.hip).  min(x, x') is
     materialised only when ``.evaluate()`` / ``.to_dense()`` (or ``.base``) is asked for."""
 
     def __init__(self, scale, x):
@@ -256,10 +267,23 @@ class _BrownianPrior(_ScaledDense):
         return torch.Size((n, n))
 
 
+def check_grid(x, who):
+    """What the linear-time solvers (csrc/bm.hip, csrc/gpcv_bm.hip) need of their 1-D grid ``x``, checked once with ONE host
+    read: x[0] >= 0 and strictly increasing.  ``who`` names the caller in the message."""
+    if x.shape[0] > 1:
+        first_ok, increasing = torch.stack([x[0] >= 0, (x[1:] > x[:-1]).all()]).tolist()
+    else:
+        first_ok, increasing = bool(x[0] >= 0), True
+    if not first_ok:
+        raise ValueError(f"{who}: the grid must start at x[0] >= 0")
+    if not increasing:
+        raise ValueError(f"{who}: the grid must be strictly increasing")
+
+
 class _VolPrior(_Evaluated):
     """Lazy covariance of the data model with ``data_solver="linear"`` (models/_base.py): K[.., i, j] = V[.., min(i, j)] over
     the integrated squared vol path ``x`` = V ([N] or [B,N]), never formed -- ExactMarginalLogLikelihood hands V to the
-    linear-time step (_VKChainMLL, csrc/bm.hip).  K is filled only when ``.evaluate()`` / ``.to_dense()`` is asked for."""
+    linear-time step (_ChainMLL, csrc/bm.hip).  K is filled only when ``.evaluate()`` / ``.to_dense()`` is asked for."""
 
     def __init__(self, V):
         self.x = V
@@ -669,14 +693,7 @@ class _ExactMLL(torch.autograd.Function):
         # gpytorch factors through psd_safe_cholesky: plain first, then jitter 1e-6 * 10^i (fp32 default) with a
         # NumericalWarning, then NotPSDError.  Same ladder here; the jitter is added inside the fused step.
         out, alpha, info = ops.mll_step(K, resid, noise, ws, want_grad=need_grad, jitter=0.0, refine_alpha=refine_alpha.active())
-        chk = deferred_checks.deferring()
-        if chk is not None:
-            chk.note(info)
-            bad = 0
-        else:
-            bad = int((info != 0).sum().item())
-            if deferred_checks._active is not None:
-                deferred_checks._active.reserve(info)
+        bad = int((info != 0).sum().item()) if deferred_checks.settle(info) else 0
         if bad and ops.info_internal(info):
             # NOT "not positive definite": a one-launch step's hand-off timed out or its workspace table is not what the init
             # wrote (include/volt_hip.h: info <= INT_MIN + 1).  gpytorch's ladder is for pivots; this is re-run ONCE on the
@@ -744,38 +761,45 @@ def _scale_grad(g, q, noise, c, n):
     return gscale
 
 
-class _BMChainMLL(torch.autograd.Function):
-    """_ExactMLL for the Brownian-motion prior K_b = scale_b min(x, x') without K: the linear-time step (ops.bm_step,
-    csrc/bm.hip; fp64 arithmetic, two O(N) sweeps).  Same value, same gradients -- d/d mean = a/N, d/d target = -a/N,
-    d/d s2, and d/d scale from the closed form shared with _ExactMLL (_scale_grad).  No jitter ladder: the tridiagonal the
-    step factors is SPD whenever s2 > 0, so a failed pivot is a NaN (NanError) or a non-positive noise (NotPSDError)."""
+class _ChainMLL(torch.autograd.Function):
+    """_ExactMLL without K, on the linear-time step of csrc/bm.hip (fp64 arithmetic, two O(N) sweeps), for the two covariances
+    that are Markov chains over a grid:
+      * ``scale`` given: the Brownian-motion prior K_b = scale_b min(x, x'), ``grid`` = x [N] (ops.bm_step);
+      * ``scale`` None: the volatility-kernel data model K_b = V_b[min(i, j)], ``grid`` = V, [N] or [B,N] (ops.vk_step); the vol
+        path is frozen (no gradient with respect to V, no scale).
+    Same value, same gradients -- d/d mean = a/N, d/d target = -a/N, d/d s2, and d/d scale from the closed form shared with
+    _ExactMLL (_scale_grad).  No jitter ladder: the tridiagonal the step factors is SPD whenever s2 > 0, so a failed pivot is
+    a NaN (NanError) or a non-positive noise (NotPSDError)."""
 
     @staticmethod
-    def forward(ctx, mean, noise, target, holder, scale, x):
+    def forward(ctx, mean, noise, target, holder, grid, scale):
         B, n = mean.shape
-        need_grad = any(ctx.needs_input_grad[:3]) or ctx.needs_input_grad[4]
+        need_grad = any(ctx.needs_input_grad[:3]) or ctx.needs_input_grad[5]
         dt = torch.float64 if mean.dtype == torch.float64 else torch.float32
-        ws = holder.bm_workspace(B, n, x.device, dt)
+        ws = holder.bm_workspace(B, n, grid.device, dt)
         resid = (target - mean).to(dt)
         noise = noise.to(dt)
-        out, alpha, info = ops.bm_step(x, scale.detach(), noise, resid, ws, want_grad=need_grad)
-        chk = deferred_checks.deferring()
-        if chk is not None:
-            chk.note(info)
+        if scale is None:
+            out, alpha, info = ops.vk_step(grid.detach(), noise, resid, ws, want_grad=need_grad)
         else:
-            if deferred_checks._active is not None:
-                deferred_checks._active.reserve(info)
+            out, alpha, info = ops.bm_step(grid, scale.detach(), noise, resid, ws, want_grad=need_grad)
+        if deferred_checks.settle(info):
             bad = int((info != 0).sum().item())
             if bad:
-                if torch.isnan(resid).any() or torch.isnan(noise).any() or torch.isnan(scale).any() or torch.isnan(x).any():
-                    raise NanError("Brownian-motion MLL: NaN in the grid, the scale, the noise or the residual")
-                raise NotPSDError(f"vol min(x, x') + sigma^2 I not positive definite for {bad} of {B} series "
+                if scale is None:
+                    what, K, inputs = "volatility-kernel", "V[min(i, j)]", "the integrated vol path"
+                else:
+                    what, K, inputs = "Brownian-motion", "vol min(x, x')", "the grid, the scale"
+                if any(torch.isnan(t).any() for t in (resid, noise, grid) + (() if scale is None else (scale,))):
+                    raise NanError(f"{what} MLL: NaN in {inputs}, the noise or the residual")
+                raise NotPSDError(f"{K} + sigma^2 I not positive definite for {bad} of {B} series "
                                   f"(first failing pivot {int(info[info != 0][0].item())}): the noise must be positive")
         ctx.n = n
         if need_grad:
             pk = torch.cat((out, alpha), dim=1)          # the ONE saved tensor: [B, 8 + N], the scalars and alpha
             ctx.save_for_backward(pk)
-            ctx.scale_shape = scale.shape if scale.numel() == B else torch.Size((B,))
+            if scale is not None:
+                ctx.scale_shape = scale.shape if scale.numel() == B else torch.Size((B,))
             return pk[:, 0]
         return out[:, 0].clone()
 
@@ -783,49 +807,8 @@ class _BMChainMLL(torch.autograd.Function):
     def backward(ctx, g):
         (pk,) = ctx.saved_tensors                    # out[:, 6] = the noise, out[:, 7] = the scale the step used
         gm = g.unsqueeze(-1) * pk[:, 8:] / ctx.n
-        gscale = _scale_grad(g, pk[:, 2:6], pk[:, 6], pk[:, 7].reshape(ctx.scale_shape), ctx.n) if ctx.needs_input_grad[4] else None
-        return gm, g * pk[:, 1], -gm, None, gscale, None
-
-
-class _VKChainMLL(torch.autograd.Function):
-    """_ExactMLL for the volatility-kernel data model K_b = V_b[min(i, j)] without K: the linear-time step on per-series grids
-    (ops.vk_step, csrc/bm.hip; fp64 arithmetic, two O(N) sweeps).  Same value, same gradients -- d/d mean = a/N,
-    d/d target = -a/N, d/d s2; the vol path is frozen (no gradient with respect to V, no scale).  No jitter ladder, as in
-    _BMChainMLL: a failed pivot is a NaN (NanError) or a non-positive noise (NotPSDError)."""
-
-    @staticmethod
-    def forward(ctx, mean, noise, target, holder, V):
-        B, n = mean.shape
-        need_grad = any(ctx.needs_input_grad[:3])
-        dt = torch.float64 if mean.dtype == torch.float64 else torch.float32
-        ws = holder.bm_workspace(B, n, V.device, dt)
-        resid = (target - mean).to(dt)
-        noise = noise.to(dt)
-        out, alpha, info = ops.vk_step(V.detach(), noise, resid, ws, want_grad=need_grad)
-        chk = deferred_checks.deferring()
-        if chk is not None:
-            chk.note(info)
-        else:
-            if deferred_checks._active is not None:
-                deferred_checks._active.reserve(info)
-            bad = int((info != 0).sum().item())
-            if bad:
-                if torch.isnan(resid).any() or torch.isnan(noise).any() or torch.isnan(V).any():
-                    raise NanError("volatility-kernel MLL: NaN in the integrated vol path, the noise or the residual")
-                raise NotPSDError(f"V[min(i, j)] + sigma^2 I not positive definite for {bad} of {B} series "
-                                  f"(first failing pivot {int(info[info != 0][0].item())}): the noise must be positive")
-        ctx.n = n
-        if need_grad:
-            pk = torch.cat((out, alpha), dim=1)          # the ONE saved tensor: [B, 8 + N], the scalars and alpha
-            ctx.save_for_backward(pk)
-            return pk[:, 0]
-        return out[:, 0].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        (pk,) = ctx.saved_tensors
-        gm = g.unsqueeze(-1) * pk[:, 8:] / ctx.n
-        return gm, g * pk[:, 1], -gm, None, None
+        gscale = _scale_grad(g, pk[:, 2:6], pk[:, 6], pk[:, 7].reshape(ctx.scale_shape), ctx.n) if ctx.needs_input_grad[5] else None
+        return gm, g * pk[:, 1], -gm, None, None, gscale
 
 
 class _KronMLL(torch.autograd.Function):
@@ -841,15 +824,8 @@ class _KronMLL(torch.autograd.Function):
         n, T = target.shape
         ws = holder.kron_workspace(n, T, M.device, M.dtype)
         res, info, eig_info, _ = ops.kron_mll_step(params, x, target, M, ws)
-        chk = deferred_checks.deferring()
         eig_bad = eig_info.clamp(max=0)                       # sweeps used >= 0; -1: the eigensolver hit its sweep cap
-        if chk is not None:
-            chk.note(info)
-            chk.note(eig_bad)
-        else:
-            if deferred_checks._active is not None:
-                deferred_checks._active.reserve(info)
-                deferred_checks._active.reserve(eig_bad)
+        if deferred_checks.settle(info, eig_bad):
             nbad, ebad, internal = torch.stack([(info != 0).sum(), (eig_bad != 0).sum(),
                                                 (info <= ops._lib.INFO_INTERNAL_MAX).sum()]).tolist()
             if ebad:
@@ -886,22 +862,20 @@ class ExactMarginalLogLikelihood(Module):
         self._ws = None
 
     def workspace(self, B, n, want_grad, device, dtype=torch.float32):
-        ws = self._ws
-        if ws is None or not ws.fits(B, n, want_grad, dtype) or ws.buf.device != device:
-            self._ws = ws = ops.MllWorkspace(B, n, want_grad, device, dtype)
-        return ws
+        return ops.cached_workspace(self, "_ws", ops.MllWorkspace, B, n, want_grad, device, dtype)
 
     def bm_workspace(self, B, n, device, dtype=torch.float32):
-        ws = getattr(self, "_bws", None)
-        if ws is None or not ws.fits(B, n, dtype) or ws.buf.device != device:
-            self._bws = ws = ops.BmWorkspace(B, n, device, dtype)
-        return ws
+        return ops.cached_workspace(self, "_bws", ops.BmWorkspace, B, n, device, dtype)
 
     def kron_workspace(self, n, T, device, dtype=torch.float32):
-        ws = getattr(self, "_kws", None)
-        if ws is None or not ws.fits(n, T, dtype) or ws.state.device != device:
-            self._kws = ws = ops.KronWorkspace(n, T, device, dtype)
-        return ws
+        return ops.cached_workspace(self, "_kws", ops.KronWorkspace, n, T, device, dtype)
+
+    def _add_log_priors(self, res, num_data):
+        """gpytorch: + sum log p(theta) / num_data over the model's registered priors."""
+        priors = self.model.named_priors() if isinstance(self.model, Module) else ()
+        for _, module, prior, closure in priors:
+            res = res + prior.log_prob(closure(module)).sum() / num_data
+        return res
 
     def _kron_forward(self, function_dist, target):
         """MultitaskBMGP's prior: the Kronecker step (_KronMLL).  ``target`` has the model's layout, [N, T]."""
@@ -917,86 +891,50 @@ class ExactMarginalLogLikelihood(Module):
         f64 = any(t.dtype == torch.float64 for t in (prior.x, target, *params))
         dt = torch.float64 if f64 else torch.float32           # torch's promotion of the reference's own arithmetic
         res = _KronMLL.apply(*params, prior.x, target.to(dt), prior.M.to(dt), self)
-        num_data = target.numel()                              # gpytorch: the MultitaskMultivariateNormal's event size
-        priors = self.model.named_priors() if isinstance(self.model, Module) else ()
-        for _, module, prior_, closure in priors:
-            res = res + prior_.log_prob(closure(module)).sum() / num_data
-        return res
-
-    def _bm_forward(self, function_dist, target):
-        """BMGP(solver="linear")'s prior: the linear-time step (_BMChainMLL), in the mean's dtype."""
-        mean, prior = function_dist.mean, function_dist.lazy_covariance_matrix
-        if not prior.x.is_cuda or not target.is_cuda:
-            raise ops._lib.VoltHipError("ExactMarginalLogLikelihood: tensors must live on the MI355X; no CPU fallback")
-        batched = mean.ndim > 1
-        n = mean.shape[-1]
-        mean2, t2 = mean.reshape(-1, n), target.reshape(-1, n)
-        B = mean2.shape[0]
-        noise = self.likelihood.noise.reshape(-1)
-        noise = noise.expand(B) if noise.numel() == 1 else noise
-        scale = prior.scale.expand(B) if prior.scale.numel() == 1 and B > 1 else prior.scale
-        dt = torch.float64 if mean.dtype == torch.float64 else torch.float32
-        res = _BMChainMLL.apply(mean2.to(dt), noise.to(dt), t2.to(dt), self, scale, prior.x)
-        res = res.reshape(mean.shape[:-1]) if batched else res.reshape(())
-        priors = self.model.named_priors() if isinstance(self.model, Module) else ()
-        for _, module, prior_, closure in priors:
-            res = res + prior_.log_prob(closure(module)).sum() / n
-        return res
-
-    def _vk_forward(self, function_dist, target):
-        """The data model's prior with data_solver="linear": the linear-time step on per-series grids (_VKChainMLL), in the
-        integrated vol path's dtype (the dense step computes in the covariance's, which is V's)."""
-        mean, prior = function_dist.mean, function_dist.lazy_covariance_matrix
-        if not prior.x.is_cuda or not target.is_cuda:
-            raise ops._lib.VoltHipError("ExactMarginalLogLikelihood: tensors must live on the MI355X; no CPU fallback")
-        batched = mean.ndim > 1
-        n = mean.shape[-1]
-        mean2, t2 = mean.reshape(-1, n), target.reshape(-1, n)
-        B = mean2.shape[0]
-        V = prior.x.reshape(-1, n)
-        V = V[0] if V.shape[0] == 1 else V               # [N]: one grid for all series
-        if V.ndim == 2 and V.shape[0] != B:
-            raise ValueError(f"ExactMarginalLogLikelihood: {V.shape[0]} vol paths for {B} series")
-        noise = self.likelihood.noise.reshape(-1)
-        noise = noise.expand(B) if noise.numel() == 1 else noise
-        dt = torch.float64 if V.dtype == torch.float64 else torch.float32
-        res = _VKChainMLL.apply(mean2.to(dt), noise.to(dt), t2.to(dt), self, V)
-        res = res.reshape(mean.shape[:-1]) if batched else res.reshape(())
-        priors = self.model.named_priors() if isinstance(self.model, Module) else ()
-        for _, module, prior_, closure in priors:
-            res = res + prior_.log_prob(closure(module)).sum() / n
-        return res
+        return self._add_log_priors(res, target.numel())       # gpytorch: the MultitaskMultivariateNormal's event size
 
     def forward(self, function_dist, target):
-        if isinstance(function_dist, MultitaskMultivariateNormal) and isinstance(function_dist.lazy_covariance_matrix,
-                                                                                 _KroneckerPrior):
+        lazy = function_dist.lazy_covariance_matrix
+        if isinstance(function_dist, MultitaskMultivariateNormal) and isinstance(lazy, _KroneckerPrior):
             return self._kron_forward(function_dist, target)
         mean = function_dist.mean
-        lazy = function_dist.lazy_covariance_matrix
-        scale = None
-        if isinstance(lazy, _VolPrior):
-            return self._vk_forward(function_dist, target)
-        if isinstance(lazy, _BrownianPrior):
-            return self._bm_forward(function_dist, target)
-        if isinstance(lazy, _ScaledDense):
-            scale = lazy.scale
-            K = lazy._product(lazy.scale.detach())
-        else:
-            K = function_dist.covariance_matrix
-        batched = mean.ndim > 1
         n = mean.shape[-1]
-        mean2, K3, t2 = mean.reshape(-1, n), K.reshape(-1, n, n), target.reshape(-1, n)
-        if not K3.is_cuda:
+        mean2, t2 = mean.reshape(-1, n), target.reshape(-1, n)
+        B = mean2.shape[0]
+        # the three priors differ in what stands for the covariance, the function applied to it and the dtype rule
+        if isinstance(lazy, _VolPrior):
+            # the data model with data_solver="linear": the linear-time step on per-series grids, in the integrated vol
+            # path's dtype (the dense step computes in the covariance's, which is V's)
+            V = lazy.x.reshape(-1, n)
+            cov = V = V[0] if V.shape[0] == 1 else V         # [N]: one grid for all series
+            if V.ndim == 2 and V.shape[0] != B:
+                raise ValueError(f"ExactMarginalLogLikelihood: {V.shape[0]} vol paths for {B} series")
+            f64 = V.dtype == torch.float64
+            step = lambda *mean_noise_target: _ChainMLL.apply(*mean_noise_target, self, V, None)
+        elif isinstance(lazy, _BrownianPrior):
+            # BMGP(solver="linear"): the linear-time step, in the mean's dtype
+            cov = lazy.x
+            scale = lazy.scale.expand(B) if lazy.scale.numel() == 1 and B > 1 else lazy.scale
+            f64 = mean.dtype == torch.float64
+            step = lambda *mean_noise_target: _ChainMLL.apply(*mean_noise_target, self, lazy.x, scale)
+        else:
+            scale = None
+            if isinstance(lazy, _ScaledDense):
+                scale = lazy.scale
+                K = lazy._product(lazy.scale.detach())
+            else:
+                K = function_dist.covariance_matrix
+            cov = K.reshape(-1, n, n)
+            f64 = cov.dtype == torch.float64                 # computed in the covariance's dtype
+            step = lambda *mean_noise_target: _ExactMLL.apply(cov, *mean_noise_target, self, scale)
+        if not cov.is_cuda or not target.is_cuda:
             raise ops._lib.VoltHipError("ExactMarginalLogLikelihood: tensors must live on the MI355X; no CPU fallback")
         noise = self.likelihood.noise.reshape(-1)
-        noise = noise.expand(mean2.shape[0]) if noise.numel() == 1 else noise
-        dt = torch.float64 if K3.dtype == torch.float64 else torch.float32      # computed in the covariance's dtype
-        res = _ExactMLL.apply(K3, mean2.to(dt), noise.to(dt), t2.to(dt), self, scale)
-        res = res.reshape(mean.shape[:-1]) if batched else res.reshape(())
-        priors = self.model.named_priors() if isinstance(self.model, Module) else ()
-        for _, module, prior, closure in priors:                          # gpytorch: + sum log p(theta) / num_data
-            res = res + prior.log_prob(closure(module)).sum() / n
-        return res
+        noise = noise.expand(B) if noise.numel() == 1 else noise
+        dt = torch.float64 if f64 else torch.float32
+        res = step(mean2.to(dt), noise.to(dt), t2.to(dt))
+        res = res.reshape(mean.shape[:-1]) if mean.ndim > 1 else res.reshape(())
+        return self._add_log_priors(res, n)
 
 
 # -------------------------------------------------------------------------- psd_safe_cholesky

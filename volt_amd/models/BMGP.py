@@ -14,7 +14,7 @@ import torch
 
 from .. import ops
 from ..gp import (ExactGP, MultitaskMultivariateNormal, MultivariateNormal, NanError, NotPSDError, _BrownianPrior, _KroneckerPrior,
-                  _safe_factor, same_values)
+                  _safe_factor, check_grid, same_values)
 from ..kernels.BMKernel import BMKernel
 from ..kernels.FBMKernel import FBMKernel
 from ..kernels.MultitaskKernel import MultitaskKernel
@@ -36,14 +36,7 @@ class BMGP(ExactGP):
         if solver == "linear":
             if train_x.ndim != 1:
                 raise ValueError(f"BMGP(solver='linear'): the grid must be 1-D [N], got shape {tuple(train_x.shape)}")
-            if train_x.shape[0] > 1:
-                first_ok, increasing = torch.stack([train_x[0] >= 0, (train_x[1:] > train_x[:-1]).all()]).tolist()
-            else:
-                first_ok, increasing = bool(train_x[0] >= 0), True
-            if not first_ok:
-                raise ValueError("BMGP(solver='linear'): the grid must start at x[0] >= 0")
-            if not increasing:
-                raise ValueError("BMGP(solver='linear'): the grid must be strictly increasing")
+            check_grid(train_x, "BMGP(solver='linear')")
         super().__init__(train_x, train_y, likelihood)
         kw = {"batch_shape": train_y.shape[:-1]} if train_y.ndim > 1 else {}
         if kernel == "bm":

@@ -19,7 +19,7 @@ class VolGP(ExactGP):
         MultitaskGaussianLikelihood(T) at noise 1e-3 (VoltMagpie.py:51-55) -- the T forecasts are then jointly drawn and
         correlated; without it T independent BM-GPs (the batched BMGP).  ``data_solver="linear"``: ``train_cov`` is the lazy
         _VolPrior over V = CumTrapz(vol^2, x) instead of the N x N fill, and the MLL of the training inputs runs on the linear-time
-        step (gp._VKChainMLL, csrc/bm.hip); the default "dense" is the filled matrix and the dense step."""
+        step (gp._ChainMLL, csrc/bm.hip); the default "dense" is the filled matrix and the dense step."""
         if data_solver not in BMGP.SOLVERS:
             raise ValueError(f"data_solver must be one of {BMGP.SOLVERS}, got {data_solver!r}")
         self.data_solver = data_solver        # Volt.Train fits the data model with the solver the model was built with

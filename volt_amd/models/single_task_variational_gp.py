@@ -8,7 +8,7 @@ factorisations of ``initialize_variational_parameters`` -- runs through the HIP 
 import torch
 
 from .. import ops
-from ..gp import ConstantMean, EqualMemo, Module, MultivariateNormal, _BrownianPrior, _dense, _safe_factor
+from ..gp import ConstantMean, EqualMemo, Module, MultivariateNormal, _BrownianPrior, _dense, _safe_factor, check_grid
 from ..kernels.BMKernel import BMKernel
 from ..likelihoods import VolatilityGaussianLikelihood  # noqa: F401  (re-exported like the reference's module namespace)
 from ..variational import CholeskyVariationalDistribution, UnwhitenedVariationalStrategy, VariationalLatent
@@ -41,18 +41,10 @@ class SingleTaskVariationalGP(Module):
                              f"Markov; {type(covar_module).__name__} is not)")
         inducing_points = init_points.detach().clone()
         if prior_solver == "linear":
-            grid = inducing_points.reshape(-1)
             if inducing_points.ndim > 2 or (inducing_points.ndim == 2 and inducing_points.shape[-1] != 1):
                 raise ValueError("SingleTaskVariationalGP(prior_solver='linear'): the inducing grid must be [N] or [N,1], got "
                                  f"shape {tuple(inducing_points.shape)}")
-            if grid.shape[0] > 1:
-                first_ok, increasing = torch.stack([grid[0] >= 0, (grid[1:] > grid[:-1]).all()]).tolist()
-            else:
-                first_ok, increasing = bool(grid[0] >= 0), True
-            if not first_ok:
-                raise ValueError("SingleTaskVariationalGP(prior_solver='linear'): the grid must start at x[0] >= 0")
-            if not increasing:
-                raise ValueError("SingleTaskVariationalGP(prior_solver='linear'): the grid must be strictly increasing")
+            check_grid(inducing_points.reshape(-1), "SingleTaskVariationalGP(prior_solver='linear')")
         self.prior_solver = prior_solver
         variational_distribution = CholeskyVariationalDistribution(inducing_points.shape[-2])
         self.variational_strategy = UnwhitenedVariationalStrategy(

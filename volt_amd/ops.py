@@ -104,25 +104,38 @@ class CholeskyFactor:
         return torch.tril(self.A[:, : self.n, : self.n])
 
 
+def _scratch(nbytes: int, device, buf: torch.Tensor | None = None):
+    """The one rule for scratch handed to the library: ``buf`` is nbytes + 256 bytes of uint8 and ``ptr`` the first
+    256-byte-aligned address inside it.  Returns (buf, ptr); a ``buf`` made here earlier (the per-shape caches) is kept."""
+    if buf is None:
+        buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    return buf, (buf.data_ptr() + 255) // 256 * 256
+
+
+def _cached_scratch(cache: dict, key, nbytes: int, device):
+    """Scratch kept in ``cache`` under ``key`` and reused across calls; calls that share a buffer are ordered by their
+    stream.  Returns (aligned pointer, whether the buffer is new)."""
+    fresh = key not in cache
+    if fresh and len(cache) >= 8:                               # a handful of shapes is what a run has; drop the oldest
+        cache.pop(next(iter(cache)))
+    cache[key], ptr = _scratch(nbytes, device, cache.get(key))
+    return ptr, fresh
+
+
 _POTRF_WS = {}
 
 
 def _potrf_workspace(B: int, Np: int, device):
     """Caller-owned scratch of volt_potrf_ws_f32, one buffer per (device, stream, B, Np), reused across calls -- the
-    jitter ladder and the many small-matrix call sites would otherwise allocate up to 277 MB per call.  Calls that
-    share a buffer are ordered by their stream.  Returns (aligned pointer or None, bytes)."""
+    jitter ladder and the many small-matrix call sites would otherwise allocate up to 277 MB per call.  Returns
+    (aligned pointer or None, bytes)."""
     nbytes = int(_lib.lib().volt_potrf_workspace_bytes(B, Np))
     if not nbytes:
         return None, 0
-    key = (device.index, _lib.stream_ptr(), B, Np)
-    buf = _POTRF_WS.get(key)
-    if buf is None:
-        if len(_POTRF_WS) >= 8:                                 # a handful of shapes is what a run has; drop the oldest
-            _POTRF_WS.pop(next(iter(_POTRF_WS)))
-        buf = _POTRF_WS[key] = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-        _lib.check(_lib.lib().volt_potrf_workspace_init_f32(((buf.data_ptr() + 255) // 256) * 256, nbytes, B, Np,
-                                                            _lib.stream_ptr()), "volt_potrf_workspace_init")
-    return ((buf.data_ptr() + 255) // 256) * 256, nbytes
+    ptr, fresh = _cached_scratch(_POTRF_WS, (device.index, _lib.stream_ptr(), B, Np), nbytes, device)
+    if fresh:
+        _lib.check(_lib.lib().volt_potrf_workspace_init_f32(ptr, nbytes, B, Np, _lib.stream_ptr()), "volt_potrf_workspace_init")
+    return ptr, nbytes
 
 
 def _potrf_ws_f64(B: int, Np: int, device):
@@ -131,13 +144,7 @@ def _potrf_ws_f64(B: int, Np: int, device):
     nbytes = int(_lib.lib().volt_potrf_workspace_bytes_f64(B, Np))
     if not nbytes:
         return None, 0
-    key = (device.index, _lib.stream_ptr(), B, Np, "f64")
-    buf = _POTRF_WS.get(key)
-    if buf is None:
-        if len(_POTRF_WS) >= 8:
-            _POTRF_WS.pop(next(iter(_POTRF_WS)))
-        buf = _POTRF_WS[key] = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    return ((buf.data_ptr() + 255) // 256) * 256, nbytes
+    return _cached_scratch(_POTRF_WS, (device.index, _lib.stream_ptr(), B, Np, "f64"), nbytes, device)[0], nbytes
 
 
 def potrf_f64_inplace(A: torch.Tensor, Winv: torch.Tensor, info: torch.Tensor) -> None:
@@ -227,10 +234,19 @@ def trtri(f: CholeskyFactor) -> torch.Tensor:
     else:
         # a few KB of progress words let the whole inverse run as one launch (csrc/batch64_step.hip); 0 bytes: launch per row
         nbytes = int(L.volt_trtri_workspace_bytes_f64(B, Np))
-        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=f.A.device) if nbytes else None
-        wp = (ws.data_ptr() + 255) // 256 * 256 if nbytes else None
+        ws, wp = _scratch(nbytes, f.A.device) if nbytes else (None, None)
         _lib.check(L.volt_trtri_ws_f64(f.A.data_ptr(), f.Winv.data_ptr(), Y.data_ptr(), B, Np, wp, nbytes, _lib.stream_ptr()), "volt_trtri")
     return torch.triu(Y[:, : f.n, : f.n])
+
+
+def cached_workspace(holder, attr: str, cls, *shape):
+    """``holder.<attr>`` if it ``fits(*shape)`` -- the constructor's own arguments, the device among them --, else a new
+    ``cls(*shape)`` kept there: how the MLL and ELBO objects carry one workspace of each kind from iteration to iteration."""
+    ws = getattr(holder, attr, None)
+    if ws is None or not ws.fits(*shape):
+        ws = cls(*shape)
+        setattr(holder, attr, ws)
+    return ws
 
 
 class MllWorkspace:
@@ -241,8 +257,7 @@ class MllWorkspace:
         L = _lib.lib()
         query = L.volt_mll_workspace_bytes if dtype == torch.float32 else L.volt_mll_workspace_bytes_f64
         nbytes = query(B, N, int(want_grad))
-        self.buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-        self.ptr = (self.buf.data_ptr() + 255) // 256 * 256
+        self.buf, self.ptr = _scratch(nbytes, device)
         self.flags = int(bool(want_grad)) * _lib.WANT_GRAD
         if dtype == torch.float32:                      # the launch-schedule table of this shape, once (mid-size batches)
             with torch.cuda.device(self.buf.device):
@@ -252,8 +267,8 @@ class MllWorkspace:
         self.alpha = torch.empty(B, N, dtype=dtype, device=device)
         self.info = torch.empty(B, dtype=torch.int32, device=device)
 
-    def fits(self, B, N, want_grad, dtype=torch.float32):
-        return self.B == B and self.N == N and self.want_grad == bool(want_grad) and self.dtype == dtype
+    def fits(self, B, N, want_grad, device, dtype=torch.float32):
+        return ((self.B, self.N, self.want_grad, self.buf.device, self.dtype) == (B, N, bool(want_grad), device, dtype))
 
 
 def mll_step(K: torch.Tensor, resid: torch.Tensor, sigma2: torch.Tensor, ws: MllWorkspace | None = None,
@@ -273,7 +288,7 @@ def mll_step(K: torch.Tensor, resid: torch.Tensor, sigma2: torch.Tensor, ws: Mll
         K = K.contiguous()
     resid = resid.reshape(B, n).to(dt).contiguous()
     s2 = sigma2.to(dt).expand(B).contiguous()
-    if ws is None or not ws.fits(B, n, want_grad, dt):
+    if ws is None or not ws.fits(B, n, want_grad, K.device, dt):
         ws = MllWorkspace(B, n, want_grad, K.device, dt)
     fn = _lib.lib().volt_mll_step_f32 if dt == torch.float32 else _lib.lib().volt_mll_step_f64
     _lib.check(fn(K.data_ptr(), K.stride(1), K.stride(0), resid.data_ptr(), s2.data_ptr(), float(jitter), ws.out.data_ptr(),
@@ -292,8 +307,7 @@ class BmWorkspace:
     def __init__(self, B: int, N: int, device, dtype=torch.float32, H: int = 0):
         self.B, self.N, self.H, self.dtype = B, N, H, dtype
         nbytes = int(_lib.lib().volt_bm_workspace_bytes(B, N, max(H, 1)))
-        self.buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-        self.ptr = (self.buf.data_ptr() + 255) // 256 * 256
+        self.buf, self.ptr = _scratch(nbytes, device)
         self.info = torch.empty(B, dtype=torch.int32, device=device)
         if H == 0:
             self.out = torch.empty(B, 8, dtype=dtype, device=device)
@@ -301,8 +315,8 @@ class BmWorkspace:
         else:
             self.X = torch.empty(B, N, H, dtype=dtype, device=device)
 
-    def fits(self, B, N, dtype=torch.float32, H=0):
-        return self.B == B and self.N == N and self.H == H and self.dtype == dtype
+    def fits(self, B, N, device, dtype=torch.float32, H=0):
+        return (self.B, self.N, self.buf.device, self.dtype, self.H) == (B, N, device, dtype, H)
 
 
 def _bm_args(x, vol, sigma2, B, dt):
@@ -324,14 +338,7 @@ def bm_step(x: torch.Tensor, vol: torch.Tensor, sigma2: torch.Tensor, resid: tor
     if x.shape[-1] != n:
         raise ValueError("x and resid disagree on N")
     x, vol, sigma2 = _bm_args(x, vol, sigma2, B, dt)
-    resid = resid.to(dt).contiguous()
-    if ws is None or not ws.fits(B, n, dt):
-        ws = BmWorkspace(B, n, resid.device, dt)
-    fn = _lib.lib().volt_bm_step_f32 if dt == torch.float32 else _lib.lib().volt_bm_step_f64
-    with torch.cuda.device(resid.device):
-        _lib.check(fn(x.data_ptr(), vol.data_ptr(), sigma2.data_ptr(), resid.data_ptr(), ws.out.data_ptr(), ws.alpha.data_ptr(),
-                      ws.info.data_ptr(), ws.ptr, B, n, _lib.WANT_GRAD if want_grad else 0, _lib.stream_ptr()), "volt_bm_step")
-    return ws.out, ws.alpha, ws.info
+    return _chain_step("volt_bm_step", (x.data_ptr(), vol.data_ptr()), sigma2, resid, dt, ws, want_grad)
 
 
 def vk_step(V: torch.Tensor, sigma2: torch.Tensor, resid: torch.Tensor, ws: BmWorkspace | None = None, want_grad: bool = True):
@@ -353,13 +360,20 @@ def vk_step(V: torch.Tensor, sigma2: torch.Tensor, resid: torch.Tensor, ws: BmWo
         V = V.contiguous()
     bsv = 0 if V.ndim == 1 or B == 1 else V.stride(0)
     sigma2 = sigma2.to(dt).reshape(-1).expand(B).contiguous()
+    return _chain_step("volt_vk_step", (V.data_ptr(), bsv), sigma2, resid, dt, ws, want_grad)
+
+
+def _chain_step(entry, grid_args, sigma2, resid, dt, ws, want_grad):
+    """What `bm_step` and `vk_step` share once their own arguments are checked and marshalled: the residual, the workspace
+    and the call of ``entry``_f32 / _f64, whose leading arguments ``grid_args`` are all the two entries differ in."""
+    B, n = resid.shape
     resid = resid.to(dt).contiguous()
-    if ws is None or not ws.fits(B, n, dt):
+    if ws is None or not ws.fits(B, n, resid.device, dt):
         ws = BmWorkspace(B, n, resid.device, dt)
-    fn = _lib.lib().volt_vk_step_f32 if dt == torch.float32 else _lib.lib().volt_vk_step_f64
+    fn = getattr(_lib.lib(), entry + ("_f32" if dt == torch.float32 else "_f64"))
     with torch.cuda.device(resid.device):
-        _lib.check(fn(V.data_ptr(), bsv, sigma2.data_ptr(), resid.data_ptr(), ws.out.data_ptr(), ws.alpha.data_ptr(),
-                      ws.info.data_ptr(), ws.ptr, B, n, _lib.WANT_GRAD if want_grad else 0, _lib.stream_ptr()), "volt_vk_step")
+        _lib.check(fn(*grid_args, sigma2.data_ptr(), resid.data_ptr(), ws.out.data_ptr(), ws.alpha.data_ptr(),
+                      ws.info.data_ptr(), ws.ptr, B, n, _lib.WANT_GRAD if want_grad else 0, _lib.stream_ptr()), entry)
     return ws.out, ws.alpha, ws.info
 
 
@@ -375,7 +389,7 @@ def bm_solve(x: torch.Tensor, vol: torch.Tensor, sigma2: torch.Tensor, R: torch.
         raise ValueError("x and R disagree on N")
     x, vol, sigma2 = _bm_args(x, vol, sigma2, B, dt)
     R = R.to(dt).contiguous()
-    if ws is None or not ws.fits(B, n, dt, H):
+    if ws is None or not ws.fits(B, n, R.device, dt, H):
         ws = BmWorkspace(B, n, R.device, dt, H)
     fn = _lib.lib().volt_bm_solve_f32 if dt == torch.float32 else _lib.lib().volt_bm_solve_f64
     with torch.cuda.device(R.device):
@@ -423,11 +437,9 @@ class GpcvWorkspace:
             if Kc < 1 or Kc > GPCV_CV_K_MAX:
                 raise _lib.VoltHipError(f'the "cv" GPCV step takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms (got Kc = {Kc})')
             nbytes = _lib.lib().volt_gpcv_cv_workspace_bytes(B, N, int(want_dk), int(Kc))
-            self.grad_abc = torch.empty(B, 3, Kc, dtype=torch.float32, device=device)
         else:
             nbytes = _lib.lib().volt_gpcv_workspace_bytes(B, N, int(want_dk))
-        self.buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-        self.ptr = (self.buf.data_ptr() + 255) // 256 * 256
+        self.buf, self.ptr = _scratch(nbytes, device)
         with torch.cuda.device(self.buf.device):        # it begins with an MLL workspace: the schedule table of that step
             _lib.check(_lib.lib().volt_mll_workspace_init_f32(self.ptr, B, N, 1, _lib.stream_ptr()), "volt_mll_workspace_init")
         f32 = dict(dtype=torch.float32, device=device)
@@ -436,7 +448,11 @@ class GpcvWorkspace:
         self.grad_mu = torch.empty(B, N, **f32)
         self.grad_Lq = torch.empty(B, N, N, **f32)
         self.grad_K = torch.empty(B, N, N, **f32) if want_dk else None
+        self.grad_abc = torch.empty(B, 3, Kc, **f32) if Kc else None
         self.info = torch.empty(B, dtype=torch.int32, device=device)
+
+    def fits(self, B, N, want_dk, device, Kc=0):
+        return (self.B, self.N, self.want_dk, self.buf.device, self.Kc) == (B, N, bool(want_dk), device, Kc)
 
 
 def gpcv_step(K, resid, m, Lq, y, gh_x, gh_w, ws: GpcvWorkspace | None = None, want_dk: bool = False,
@@ -446,24 +462,7 @@ def gpcv_step(K, resid, m, Lq, y, gh_x, gh_w, ws: GpcvWorkspace | None = None, w
     K [B,N,N] prior covariance without jitter; resid = m - prior mean, m, y [B,N]; Lq [B,N,N].
     Gradients are those of F = w_ell * ell - w_kl * KL (out[:, 9]).
     Returns the workspace: .out [B,12], .grad_m, .grad_mu, .grad_Lq (.grad_K if want_dk), .info."""
-    _need_gpu(K, resid, m, Lq, y, gh_x, gh_w)
-    if K.ndim != 3 or K.dtype != torch.float32:
-        raise ValueError("K must be [B,N,N] fp32")
-    B, n, _ = K.shape
-    if K.stride(-1) != 1:
-        K = K.contiguous()
-    c = lambda t, shape: t.reshape(shape).to(torch.float32).contiguous()
-    resid, m, y, Lq = c(resid, (B, n)), c(m, (B, n)), c(y, (B, n)), c(Lq, (B, n, n))
-    gh_x, gh_w = gh_x.to(torch.float32).contiguous(), gh_w.to(torch.float32).contiguous()
-    if ws is None or ws.B != B or ws.N != n or ws.want_dk != bool(want_dk):
-        ws = GpcvWorkspace(B, n, want_dk, K.device)
-    _lib.check(_lib.lib().volt_gpcv_step_f32(
-        K.data_ptr(), K.stride(1), K.stride(0), float(jitter), resid.data_ptr(), m.data_ptr(), Lq.data_ptr(),
-        y.data_ptr(), gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var), float(min_scale), float(w_ell), float(w_kl),
-        ws.out.data_ptr(), ws.grad_m.data_ptr(), ws.grad_mu.data_ptr(), ws.grad_Lq.data_ptr(),
-        ws.grad_K.data_ptr() if want_dk else None, ws.info.data_ptr(), ws.ptr, B, n, _lib.WS_INITIALISED, _lib.stream_ptr()),
-        "volt_gpcv_step")
-    return ws
+    return _gpcv_dense_step(K, resid, m, Lq, y, None, gh_x, gh_w, ws, want_dk, jitter, min_var, min_scale, w_ell, w_kl)
 
 
 def gpcv_cv_step(K, resid, m, Lq, y, abc, gh_x, gh_w, ws: GpcvWorkspace | None = None, want_dk: bool = False,
@@ -472,32 +471,42 @@ def gpcv_cv_step(K, resid, m, Lq, y, abc, gh_x, gh_w, ws: GpcvWorkspace | None =
     """``gpcv_step`` for the copula-process ("cv") likelihood, scale(f) = sum_k a_k softplus(b_k f + c_k)
     (include/volt_hip.h, volt_gpcv_cv_step_f32).  abc [B,3,Kc]: the TRANSFORMED a, b, c of every series.
     Returns the workspace: what ``gpcv_step`` returns plus .grad_abc [B,3,Kc] = dF/d(a,b,c)."""
+    return _gpcv_dense_step(K, resid, m, Lq, y, abc, gh_x, gh_w, ws, want_dk, jitter, min_var, min_scale, w_ell, w_kl)
+
+
+def _gpcv_dense_step(K, resid, m, Lq, y, abc, gh_x, gh_w, ws, want_dk, jitter, min_var, min_scale, w_ell, w_kl):
+    """`gpcv_step` (``abc`` None: volt_gpcv_step_f32) and `gpcv_cv_step` (volt_gpcv_cv_step_f32, which takes abc, Kc and
+    grad_abc besides)."""
     _need_gpu(K, resid, m, Lq, y, abc, gh_x, gh_w)
     if K.ndim != 3 or K.dtype != torch.float32:
         raise ValueError("K must be [B,N,N] fp32")
     B, n, _ = K.shape
-    if abc.ndim != 3 or abc.shape[0] != B or abc.shape[1] != 3:
-        raise ValueError("abc must be [B,3,Kc]")
-    Kc = abc.shape[2]
+    Kc = 0
+    if abc is not None:
+        if abc.ndim != 3 or abc.shape[0] != B or abc.shape[1] != 3:
+            raise ValueError("abc must be [B,3,Kc]")
+        Kc = abc.shape[2]
     if K.stride(-1) != 1:
         K = K.contiguous()
     c = lambda t, shape: t.reshape(shape).to(torch.float32).contiguous()
-    resid, m, y, Lq, abc = c(resid, (B, n)), c(m, (B, n)), c(y, (B, n)), c(Lq, (B, n, n)), c(abc, (B, 3, Kc))
+    resid, m, y, Lq = c(resid, (B, n)), c(m, (B, n)), c(y, (B, n)), c(Lq, (B, n, n))
+    if abc is not None:
+        abc = c(abc, (B, 3, Kc))
     gh_x, gh_w = gh_x.to(torch.float32).contiguous(), gh_w.to(torch.float32).contiguous()
-    if Kc < 1 or Kc > GPCV_CV_K_MAX:                  # no workspace can be sized: let the entry name the argument
-        _lib.check(_lib.lib().volt_gpcv_cv_step_f32(
-            K.data_ptr(), K.stride(1), K.stride(0), float(jitter), resid.data_ptr(), m.data_ptr(), Lq.data_ptr(),
-            y.data_ptr(), abc.data_ptr(), Kc, gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var), float(min_scale),
-            float(w_ell), float(w_kl), None, None, None, None, None, None, None, None, B, n, 0, _lib.stream_ptr()),
-            "volt_gpcv_cv_step")
-    if ws is None or ws.B != B or ws.N != n or ws.want_dk != bool(want_dk) or ws.Kc != Kc:
-        ws = GpcvWorkspace(B, n, want_dk, K.device, Kc=Kc)
-    _lib.check(_lib.lib().volt_gpcv_cv_step_f32(
-        K.data_ptr(), K.stride(1), K.stride(0), float(jitter), resid.data_ptr(), m.data_ptr(), Lq.data_ptr(),
-        y.data_ptr(), abc.data_ptr(), Kc, gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var), float(min_scale),
-        float(w_ell), float(w_kl), ws.out.data_ptr(), ws.grad_m.data_ptr(), ws.grad_mu.data_ptr(), ws.grad_Lq.data_ptr(),
-        ws.grad_K.data_ptr() if want_dk else None, ws.grad_abc.data_ptr(), ws.info.data_ptr(), ws.ptr, B, n,
-        _lib.WS_INITIALISED, _lib.stream_ptr()), "volt_gpcv_cv_step")
+    if abc is not None and not 1 <= Kc <= GPCV_CV_K_MAX:      # no workspace can be sized: let the entry name the argument
+        ws = None
+    elif ws is None or not ws.fits(B, n, want_dk, K.device, Kc):
+        ws = GpcvWorkspace(B, n, want_dk, K.device, Kc)
+    o = lambda name: getattr(ws, name).data_ptr() if ws is not None and getattr(ws, name) is not None else None
+    prior = (K.data_ptr(), K.stride(1), K.stride(0), float(jitter), resid.data_ptr(), m.data_ptr(), Lq.data_ptr(), y.data_ptr())
+    quad = (gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var), float(min_scale), float(w_ell), float(w_kl))
+    grads = (o("out"), o("grad_m"), o("grad_mu"), o("grad_Lq"), o("grad_K"))
+    tail = (o("info"), ws.ptr if ws is not None else None, B, n, _lib.WS_INITIALISED if ws is not None else 0, _lib.stream_ptr())
+    if abc is None:
+        _lib.check(_lib.lib().volt_gpcv_step_f32(*prior, *quad, *grads, *tail), "volt_gpcv_step")
+    else:
+        _lib.check(_lib.lib().volt_gpcv_cv_step_f32(*prior, abc.data_ptr(), Kc, *quad, *grads, o("grad_abc"), *tail),
+                   "volt_gpcv_cv_step")
     return ws
 
 
@@ -510,8 +519,7 @@ class GpcvBmWorkspace:
         if Kc < 0 or Kc > GPCV_CV_K_MAX:
             raise _lib.VoltHipError(f'the "cv" GPCV step takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms (got Kc = {Kc})')
         nbytes = int(_lib.lib().volt_gpcv_bm_workspace_bytes(B, N, int(Kc)))
-        self.buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-        self.ptr = (self.buf.data_ptr() + 255) // 256 * 256
+        self.buf, self.ptr = _scratch(nbytes, device)
         f32 = dict(dtype=torch.float32, device=device)
         self.out = torch.empty(B, 12, **f32)
         self.grad_m = torch.empty(B, N, **f32)
@@ -520,8 +528,8 @@ class GpcvBmWorkspace:
         self.grad_abc = torch.empty(B, 3, Kc, **f32) if Kc else None
         self.info = torch.empty(B, dtype=torch.int32, device=device)
 
-    def fits(self, B, N, Kc=0):
-        return self.B == B and self.N == N and self.Kc == Kc
+    def fits(self, B, N, device, Kc=0):
+        return (self.B, self.N, self.buf.device, self.Kc) == (B, N, device, Kc)
 
 
 def gpcv_bm_step(x, vol, resid, m, Lq, y, gh_x, gh_w, ws: GpcvBmWorkspace | None = None, abc=None, jitter: float = 1e-3,
@@ -548,7 +556,7 @@ def gpcv_bm_step(x, vol, resid, m, Lq, y, gh_x, gh_w, ws: GpcvBmWorkspace | None
         abc = c(abc, (B, 3, Kc))
     if abc is not None and not 1 <= Kc <= GPCV_CV_K_MAX:      # no workspace can be sized: let the entry name the argument
         ws = None
-    elif ws is None or not ws.fits(B, n, Kc):
+    elif ws is None or not ws.fits(B, n, Lq.device, Kc):
         ws = GpcvBmWorkspace(B, n, Lq.device, Kc)
     o = lambda name: getattr(ws, name).data_ptr() if ws is not None and getattr(ws, name) is not None else None
     with torch.cuda.device(Lq.device):
@@ -573,8 +581,7 @@ class GpcvMtWorkspace:
             raise ValueError(f"the multi-task GPCV step takes 1 <= T <= {GPCV_MT_T_MAX} series (got T = {T})")
         self.N, self.T, self.want_dk = N, T, bool(want_dk)
         nbytes = _lib.lib().volt_gpcv_mt_workspace_bytes(N, T, int(want_dk))
-        self.buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-        self.ptr = (self.buf.data_ptr() + 255) // 256 * 256
+        self.buf, self.ptr = _scratch(nbytes, device)
         with torch.cuda.device(self.buf.device):        # it begins with an MLL workspace for ONE series
             _lib.check(_lib.lib().volt_mll_workspace_init_f32(self.ptr, 1, N, 1, _lib.stream_ptr()), "volt_mll_workspace_init")
         f32 = dict(dtype=torch.float32, device=device)
@@ -587,6 +594,9 @@ class GpcvMtWorkspace:
         self.grad_raw_var = torch.empty(T, **f32)
         self.grad_K = torch.empty(N, N, **f32) if want_dk else None
         self.info = torch.empty(3, dtype=torch.int32, device=device)
+
+    def fits(self, N, T, want_dk, device):
+        return (self.N, self.T, self.want_dk, self.buf.device) == (N, T, bool(want_dk), device)
 
 
 def gpcv_mt_step(K, M, c, Lx, Lt, covar_factor, raw_var, y, gh_x, gh_w, ws: GpcvMtWorkspace | None = None,
@@ -608,7 +618,7 @@ def gpcv_mt_step(K, M, c, Lx, Lt, covar_factor, raw_var, y, gh_x, gh_w, ws: Gpcv
     M, y, Lx, Lt = f(M, (n, T)), f(y, (n, T)), f(Lx, (n, n)), f(Lt, (T, T))
     c, cf, rv = f(c, (T,)), f(covar_factor, (T,)), f(raw_var, (T,))
     gh_x, gh_w = gh_x.to(torch.float32).contiguous(), gh_w.to(torch.float32).contiguous()
-    if ws is None or ws.N != n or ws.T != T or ws.want_dk != bool(want_dk) or ws.buf.device != K.device:
+    if ws is None or not ws.fits(n, T, want_dk, K.device):
         ws = GpcvMtWorkspace(n, T, want_dk, K.device)
     _lib.check(_lib.lib().volt_gpcv_mt_step_f32(
         K.data_ptr(), K.stride(0), float(jitter), M.data_ptr(), c.data_ptr(), Lx.data_ptr(), Lt.data_ptr(), cf.data_ptr(),
@@ -681,8 +691,8 @@ class KronWorkspace:
         self.mll = MllWorkspace(T, N, True, device, dtype)
         self._K = None
 
-    def fits(self, N, T, dtype):
-        return self.N == N and self.T == T and self.dtype == dtype
+    def fits(self, N, T, device, dtype=torch.float32):
+        return (self.N, self.T, self.state.device, self.dtype) == (N, T, device, dtype)
 
     def shared_k(self, M: torch.Tensor) -> torch.Tensor:
         """M as the step's [T,N,N] operand: batch stride 0 (KRON_SHARED_K), or T copies made once per M."""
@@ -745,7 +755,7 @@ def kron_mll_step(params, x: torch.Tensor, Y: torch.Tensor, M: torch.Tensor, ws:
     dt = torch.float64 if M.dtype == torch.float64 else torch.float32
     N, T = Y.shape
     _check_tasks(T)
-    if ws is None or not ws.fits(N, T, dt) or ws.state.device != M.device:
+    if ws is None or not ws.fits(N, T, M.device, dt):
         ws = KronWorkspace(N, T, M.device, dt)
     M = M.to(dt)
     if M.stride(-1) != 1:
@@ -771,13 +781,7 @@ def _summary_scratch(G: int, S: int, H: int, device):
     """Caller-owned scratch of volt_path_summary_f32 (the transposed samples), one buffer per (device, stream, shape),
     reused across calls; calls that share a buffer are ordered by their stream.  Returns (aligned pointer, bytes)."""
     nbytes = int(_lib.lib().volt_path_summary_scratch_bytes(G, S, H))
-    key = (device.index, _lib.stream_ptr(), G, S, H)
-    buf = _SUMMARY_SCRATCH.get(key)
-    if buf is None:
-        if len(_SUMMARY_SCRATCH) >= 8:                          # a handful of shapes is what a run has; drop the oldest
-            _SUMMARY_SCRATCH.pop(next(iter(_SUMMARY_SCRATCH)))
-        buf = _SUMMARY_SCRATCH[key] = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    return ((buf.data_ptr() + 255) // 256) * 256, nbytes
+    return _cached_scratch(_SUMMARY_SCRATCH, (device.index, _lib.stream_ptr(), G, S, H), nbytes, device)[0], nbytes
 
 
 def _summary_levels(q, device) -> torch.Tensor:

@@ -392,7 +392,7 @@ def _vol_model(train_x, vol_path, kernel, batch_shape, solver="dense"):
 def TrainVolModel(train_x, vol_path, train_iters=1000, printing=False, kernel="bm", graph=None, solver="dense"):
     """voltron/train_utils.py:69-95: the Brownian-motion GP over log-vol that supplies pred_vol to Rollouts.  The MLL
     and its gradient wrt the kernel's `vol` and the noise run on the HIP step (K = vol * min(x,x') keeps d mll / d vol
-    in closed form, gp._ExactMLL).  ``solver="linear"``: the O(N) step of csrc/bm.hip (gp._BMChainMLL) instead of the dense
+    in closed form, gp._ExactMLL).  ``solver="linear"``: the O(N) step of csrc/bm.hip (gp._ChainMLL) instead of the dense
     one; launch-bound at every N, so ``graph=None`` captures wherever capturing is possible."""
     vol_model, vol_lh = _vol_model(train_x, vol_path, kernel, torch.Size(), solver)
     _fit_exact(vol_model, vol_lh, train_x, vol_path.log(), list(vol_model.parameters()), LR_VOL, train_iters, printing,
@@ -446,7 +446,7 @@ def _check_data_solver(solver):
 
 def TrainDataModel(train_x, train_y, vol_model, vol_lh, vol_path, train_iters=1000, printing=False, graph=None, solver="dense"):
     """voltron/train_utils.py:98-144: VoltronGP with a log-linear mean; noise, slope and intercept train.
-    ``solver="linear"``: the O(N) step of csrc/bm.hip on the integrated vol path (gp._VKChainMLL) instead of the N x N fill and
+    ``solver="linear"``: the O(N) step of csrc/bm.hip on the integrated vol path (gp._ChainMLL) instead of the N x N fill and
     the dense step; the iteration is then launch-bound at every N and captured by default."""
     _check_data_solver(solver)
     dev = train_x.device

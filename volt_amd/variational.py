@@ -134,37 +134,56 @@ def _dkl_dscale_grad(o, c, n, w_kl, g):
     return (-w_kl * g * dkl).reshape(c.shape) if c.numel() == g.numel() else (-w_kl * g * dkl).sum().reshape(c.shape)
 
 
+def _cv_transform(raw_a, raw_b, raw_c, B):
+    """The "cv" likelihood's constraints, a = softplus(raw_a), b = 3 sigmoid(raw_b), c = 6 sigmoid(raw_c) - 3
+    (volatility_likelihood.py:24-26), as the step's abc [B,3,Kc], and their Jacobian [..., 3, Kc]:
+    d a / d raw_a = sigmoid(raw_a);  d b / d raw_b = 3 s (1 - s);  d c / d raw_c = 6 s (1 - s)."""
+    sa, sb, sc = torch.sigmoid(raw_a.detach()), torch.sigmoid(raw_b.detach()), torch.sigmoid(raw_c.detach())
+    abc = torch.stack([torch.nn.functional.softplus(raw_a.detach()), 3.0 * sb, 6.0 * sc - 3.0], -2)     # [..., 3, Kc]
+    jac = torch.stack([sa, 3.0 * sb * (1.0 - sb), 6.0 * sc * (1.0 - sc)], -2)
+    return abc.to(torch.float32).expand(B, 3, raw_a.shape[-1]), jac
+
+
+def _cv_raw_grads(g2, graw, raw_shape):
+    """The gradients of raw_a, raw_b, raw_c from graw = dF/d(a,b,c) * Jacobian [B,3,Kc]: raws of shape [Kc] are one
+    likelihood for every series (the gradient sums over them), [B,Kc] one per series."""
+    graw = g2 * graw                                                   # [B,3,Kc]
+    graw = graw.sum(0) if len(raw_shape) == 1 else graw.transpose(0, 1)     # [3,Kc] / [3,B,Kc]
+    return tuple(graw[i].reshape(raw_shape) for i in range(3))
+
+
 class _GPCVElbo(torch.autograd.Function):
-    """F[b] = w_ell ell_b - w_kl KL_b with the analytic gradient the HIP step returns."""
+    """F[b] = w_ell ell_b - w_kl KL_b over a dense prior K, with the analytic gradient the HIP step returns.  raw_a, raw_b,
+    raw_c None: the "exp" likelihood (ops.gpcv_step); given ([Kc] or [B,Kc]): the copula-process ("cv") likelihood,
+    scale(f) = sum_k a_k softplus(b_k f + c_k) (ops.gpcv_cv_step) -- the step returns dF/d(a,b,c), the constraints' chain
+    rule is applied here."""
 
     @staticmethod
-    def forward(ctx, m, Lq, mean, K, y, holder, scale, num_gh, w_ell, w_kl):
+    def forward(ctx, m, Lq, mean, K, y, raw_a, raw_b, raw_c, holder, scale, num_gh, w_ell, w_kl):
         B, n = m.shape
         want_dk = bool(ctx.needs_input_grad[3])
         gh_x, gh_w = _gauss_hermite(num_gh, m.device)
-        ws = holder.workspace(B, n, want_dk, m.device)
-        ops.gpcv_step(K.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y, gh_x, gh_w, ws, want_dk=want_dk,
-                      jitter=PRIOR_JITTER, min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
-        chk = gp.deferred_checks.deferring()
-        if chk is None and gp.deferred_checks._active is not None:
-            gp.deferred_checks._active.reserve(ws.info)
-        if chk is not None:
-            chk.note(ws.info)
-        elif bool((ws.info != 0).any().item()):
-            if ops.info_internal(ws.info):       # a hand-off time-out / workspace table: not a statement about K
-                raise ops._lib.VoltHipError(f"volt_gpcv_step_f32: internal error, info = {ws.info.tolist()[:8]}")
-            if torch.isnan(K).any() or torch.isnan(m).any() or torch.isnan(Lq).any():
-                raise NanError("GPCV step: NaN in the prior covariance or the variational parameters")
-            raise NotPSDError("GPCV step: prior covariance K + 1e-3 I is not positive definite")
-        ctx.n, ctx.w_kl, ctx.has_scale = n, w_kl, scale is not None
+        cv = raw_a is not None
+        ws = holder.workspace(B, n, want_dk, m.device, Kc=raw_a.shape[-1] if cv else 0)
+        step_args = dict(ws=ws, want_dk=want_dk, jitter=PRIOR_JITTER, min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
+        if cv:
+            abc, jac = _cv_transform(raw_a, raw_b, raw_c, B)
+            ops.gpcv_cv_step(K.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y, abc, gh_x, gh_w, **step_args)
+        else:
+            ops.gpcv_step(K.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y, gh_x, gh_w, **step_args)
+        if gp.deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
+            _raise_step_failure("GPCV cv step" if cv else "GPCV step", ws.info, (K, m, Lq) + ((abc,) if cv else ()),
+                                "prior covariance K + 1e-3 I")
+        ctx.n, ctx.w_kl, ctx.has_scale, ctx.want_dk, ctx.cv = n, w_kl, scale is not None, want_dk, cv
         saved = [ws.grad_m.clone(), ws.grad_Lq.clone(), ws.grad_mu.clone()]
+        if cv:
+            ctx.raw_shape = raw_a.shape
+            saved.append(ws.grad_abc * jac)
         if want_dk:
             saved.append(ws.grad_K.clone())
         if scale is not None:
             saved += [ws.out[:, 2:9].clone(), scale.detach().clone()]
-        ctx.want_dk = want_dk
         ctx.save_for_backward(*saved)
-        ctx.mark_non_differentiable()
         return ws.out[:, 9].clone()
 
     @staticmethod
@@ -172,98 +191,36 @@ class _GPCVElbo(torch.autograd.Function):
         sv = list(ctx.saved_tensors)
         gm, gL, gmu = sv[:3]
         g1, g2 = g.reshape(-1, 1), g.reshape(-1, 1, 1)
-        gK = g2 * sv[3] if ctx.want_dk else None
+        gK = g2 * sv[4 if ctx.cv else 3] if ctx.want_dk else None
         gscale = None
         if ctx.has_scale:
             gscale = _dkl_dscale_grad(sv[-2], sv[-1], ctx.n, ctx.w_kl, g)
-        return g1 * gm, g2 * gL, g1 * gmu, gK, None, None, gscale, None, None, None
-
-
-class _GPCVCvElbo(torch.autograd.Function):
-    """``_GPCVElbo`` for the copula-process ("cv") likelihood: F[b] = w_ell ell_b - w_kl KL_b with
-    scale(f) = sum_k a_k softplus(b_k f + c_k), a = softplus(raw_a), b = 3 sigmoid(raw_b), c = 6 sigmoid(raw_c) - 3
-    (volatility_likelihood.py:24-26).  The HIP step returns dF/d(a,b,c); the constraints' chain rule is applied here.
-    raw_a, raw_b, raw_c are [Kc] (one likelihood for every series: its gradient sums over them) or [B,Kc]."""
-
-    @staticmethod
-    def forward(ctx, m, Lq, mean, K, y, raw_a, raw_b, raw_c, holder, scale, num_gh, w_ell, w_kl):
-        B, n = m.shape
-        want_dk = bool(ctx.needs_input_grad[3])
-        gh_x, gh_w = _gauss_hermite(num_gh, m.device)
-        Kc = raw_a.shape[-1]
-        ws = holder.workspace(B, n, want_dk, m.device, Kc=Kc)
-        sa, sb, sc = torch.sigmoid(raw_a.detach()), torch.sigmoid(raw_b.detach()), torch.sigmoid(raw_c.detach())
-        abc = torch.stack([torch.nn.functional.softplus(raw_a.detach()), 3.0 * sb, 6.0 * sc - 3.0], -2)     # [..., 3, Kc]
-        ops.gpcv_cv_step(K.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y,
-                         abc.to(torch.float32).expand(B, 3, Kc), gh_x, gh_w, ws, want_dk=want_dk, jitter=PRIOR_JITTER,
-                         min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
-        chk = gp.deferred_checks.deferring()
-        if chk is None and gp.deferred_checks._active is not None:
-            gp.deferred_checks._active.reserve(ws.info)
-        if chk is not None:
-            chk.note(ws.info)
-        elif bool((ws.info != 0).any().item()):
-            _raise_step_failure("GPCV cv step", ws.info, (K, m, Lq, abc), "prior covariance K + 1e-3 I")
-        ctx.n, ctx.w_kl, ctx.has_scale, ctx.want_dk = n, w_kl, scale is not None, want_dk
-        ctx.shared = raw_a.ndim == 1
-        ctx.raw_shape = raw_a.shape
-        # d a / d raw_a = sigmoid(raw_a);  d b / d raw_b = 3 s (1 - s);  d c / d raw_c = 6 s (1 - s)
-        jac = torch.stack([sa, 3.0 * sb * (1.0 - sb), 6.0 * sc * (1.0 - sc)], -2)
-        saved = [ws.grad_m.clone(), ws.grad_Lq.clone(), ws.grad_mu.clone(), ws.grad_abc * jac]
-        if want_dk:
-            saved.append(ws.grad_K.clone())
-        if scale is not None:
-            saved += [ws.out[:, 2:9].clone(), scale.detach().clone()]
-        ctx.save_for_backward(*saved)
-        return ws.out[:, 9].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        sv = list(ctx.saved_tensors)
-        gm, gL, gmu, graw = sv[:4]
-        g1, g2 = g.reshape(-1, 1), g.reshape(-1, 1, 1)
-        gK = g2 * sv[4] if ctx.want_dk else None
-        gscale = None
-        if ctx.has_scale:
-            gscale = _dkl_dscale_grad(sv[-2], sv[-1], ctx.n, ctx.w_kl, g)
-        graw = g2 * graw                                              # [B,3,Kc]
-        graw = graw.sum(0) if ctx.shared else graw.transpose(0, 1)    # [3,Kc] / [3,B,Kc]
-        ga, gb, gc = (graw[i].reshape(ctx.raw_shape) for i in range(3))
+        ga, gb, gc = _cv_raw_grads(g2, sv[3], ctx.raw_shape) if ctx.cv else (None, None, None)
         return g1 * gm, g2 * gL, g1 * gmu, gK, None, ga, gb, gc, None, gscale, None, None, None
 
 
 class _GPCVBmElbo(torch.autograd.Function):
-    """``_GPCVElbo`` / ``_GPCVCvElbo`` (raw_a, raw_b, raw_c given) under the lazy Brownian-motion prior K = scale min(x, x'):
-    the O(N^2) step of csrc/gpcv_bm.hip.  No dense K and no dF/dK: the prior's only parameter is ``scale``, whose gradient is
-    the closed form both dense functions use (``_dkl_dscale_grad``)."""
+    """``_GPCVElbo`` (either likelihood: raw_a, raw_b, raw_c None or given) under the lazy Brownian-motion prior
+    K = scale min(x, x'): the O(N^2) step of csrc/gpcv_bm.hip.  No dense K and no dF/dK: the prior's only parameter is
+    ``scale``, whose gradient is the closed form the dense function uses (``_dkl_dscale_grad``).  A function of its own
+    because its inputs differ in kind (a grid and a scale for a matrix), not only in data."""
 
     @staticmethod
     def forward(ctx, m, Lq, mean, scale, x, y, raw_a, raw_b, raw_c, holder, num_gh, w_ell, w_kl):
         B, n = m.shape
         gh_x, gh_w = _gauss_hermite(num_gh, m.device)
         cv = raw_a is not None
-        Kc = raw_a.shape[-1] if cv else 0
-        ws = holder.bm_workspace(B, n, m.device, Kc)
-        abc = jac = None
-        if cv:
-            sa, sb, sc = torch.sigmoid(raw_a.detach()), torch.sigmoid(raw_b.detach()), torch.sigmoid(raw_c.detach())
-            abc = torch.stack([torch.nn.functional.softplus(raw_a.detach()), 3.0 * sb, 6.0 * sc - 3.0], -2)     # [..., 3, Kc]
-            jac = torch.stack([sa, 3.0 * sb * (1.0 - sb), 6.0 * sc * (1.0 - sc)], -2)
-            abc = abc.to(torch.float32).expand(B, 3, Kc)
+        ws = holder.bm_workspace(B, n, m.device, raw_a.shape[-1] if cv else 0)
+        abc, jac = _cv_transform(raw_a, raw_b, raw_c, B) if cv else (None, None)
         ops.gpcv_bm_step(x, scale.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y, gh_x, gh_w, ws, abc=abc,
                          jitter=PRIOR_JITTER, min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
-        chk = gp.deferred_checks.deferring()
-        if chk is None and gp.deferred_checks._active is not None:
-            gp.deferred_checks._active.reserve(ws.info)
-        if chk is not None:
-            chk.note(ws.info)
-        elif bool((ws.info != 0).any().item()):
+        if gp.deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
             _raise_step_failure("GPCV step (linear prior)", ws.info, (scale, m, Lq) + ((abc,) if cv else ()),
                                 "prior covariance K + 1e-3 I")
         ctx.n, ctx.w_kl, ctx.cv = n, w_kl, cv
         saved = [ws.grad_m.clone(), ws.grad_Lq.clone(), ws.grad_mu.clone(), ws.out[:, 2:9].clone(), scale.detach().clone()]
         if cv:
-            ctx.shared, ctx.raw_shape = raw_a.ndim == 1, raw_a.shape
+            ctx.raw_shape = raw_a.shape
             saved.append(ws.grad_abc * jac)
         ctx.save_for_backward(*saved)
         return ws.out[:, 9].clone()
@@ -274,11 +231,7 @@ class _GPCVBmElbo(torch.autograd.Function):
         gm, gL, gmu, o, scale = sv[:5]
         g1, g2 = g.reshape(-1, 1), g.reshape(-1, 1, 1)
         gscale = _dkl_dscale_grad(o, scale, ctx.n, ctx.w_kl, g)
-        ga = gb = gc = None
-        if ctx.cv:
-            graw = g2 * sv[5]                                             # [B,3,Kc]
-            graw = graw.sum(0) if ctx.shared else graw.transpose(0, 1)    # [3,Kc] / [3,B,Kc]
-            ga, gb, gc = (graw[i].reshape(ctx.raw_shape) for i in range(3))
+        ga, gb, gc = _cv_raw_grads(g2, sv[5], ctx.raw_shape) if ctx.cv else (None, None, None)
         return g1 * gm, g2 * gL, g1 * gmu, gscale, None, None, ga, gb, gc, None, None, None, None
 
 
@@ -352,12 +305,7 @@ class _GPCVMtElbo(torch.autograd.Function):
         ws = holder.mt_workspace(n, T, want_dk, M.device)
         ops.gpcv_mt_step(K.detach(), M, c, Lx, Lt, cf, rv, y, gh_x, gh_w, ws, want_dk=want_dk, jitter=PRIOR_JITTER,
                          min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
-        chk = gp.deferred_checks.deferring()
-        if chk is None and gp.deferred_checks._active is not None:
-            gp.deferred_checks._active.reserve(ws.info)
-        if chk is not None:
-            chk.note(ws.info)
-        elif bool((ws.info != 0).any().item()):
+        if gp.deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
             info = ws.info.cpu()
             # info[0]: K_x + jitter I (LAPACK-style or an internal code);  info[1]: a pivot of K_t;  info[2]: F not finite
             which = "prior covariance K_x + 1e-3 I" if int(info[0]) != 0 else "task covariance K_t"
@@ -411,22 +359,13 @@ class VariationalELBO(Module):
         self._bm_ws = None
 
     def bm_workspace(self, B, n, device, Kc=0):
-        ws = self._bm_ws
-        if ws is None or not ws.fits(B, n, Kc) or ws.buf.device != device:
-            self._bm_ws = ws = ops.GpcvBmWorkspace(B, n, device, Kc)
-        return ws
+        return ops.cached_workspace(self, "_bm_ws", ops.GpcvBmWorkspace, B, n, device, Kc)
 
     def workspace(self, B, n, want_dk, device, Kc=0):
-        ws = self._ws
-        if ws is None or ws.B != B or ws.N != n or ws.want_dk != bool(want_dk) or ws.buf.device != device or ws.Kc != Kc:
-            self._ws = ws = ops.GpcvWorkspace(B, n, want_dk, device, Kc=Kc)
-        return ws
+        return ops.cached_workspace(self, "_ws", ops.GpcvWorkspace, B, n, want_dk, device, Kc)
 
     def mt_workspace(self, n, T, want_dk, device):
-        ws = self._mt_ws
-        if ws is None or ws.N != n or ws.T != T or ws.want_dk != bool(want_dk) or ws.buf.device != device:
-            self._mt_ws = ws = ops.GpcvMtWorkspace(n, T, want_dk, device)
-        return ws
+        return ops.cached_workspace(self, "_mt_ws", ops.GpcvMtWorkspace, n, T, want_dk, device)
 
     def _forward_multitask(self, latent, target):
         """VariationalELBO over a MultitaskMultivariateNormal (event shape [N,T]): the likelihood term is summed over
@@ -479,24 +418,18 @@ class VariationalELBO(Module):
         mean2 = prior.mean.expand(m.shape).reshape(-1, n)
         lazy = prior.lazy_covariance_matrix
         lik = self.likelihood
+        raws = self._cv_raws(lik, B, m) if getattr(lik, "param", "exp") == "cv" else [None, None, None]
+        weights = (num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data)
         if isinstance(lazy, _BrownianPrior):                           # prior_solver="linear": no dense K anywhere
-            raws = [None, None, None]
-            if getattr(lik, "param", "exp") == "cv":
-                raws = self._cv_raws(lik, B, m)
             res = _GPCVBmElbo.apply(m2.to(torch.float32), L3.to(torch.float32), mean2.to(torch.float32), lazy.scale, lazy.x, y2,
-                                    *raws, self, num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data)
-            return res.reshape(m.shape[:-1]) if batched else res.reshape(())
-        scale = None
-        if isinstance(lazy, _ScaledDense):
-            scale = lazy.scale
-            K3 = (scale.detach().reshape(-1, 1, 1) * lazy.base).expand(B, n, n)
+                                    *raws, self, *weights)
         else:
-            K3 = _dense(lazy).expand(B, n, n) if _dense(lazy).ndim == 2 else _dense(lazy).reshape(-1, n, n)
-        if getattr(lik, "param", "exp") == "cv":
-            raws = self._cv_raws(lik, B, m)
-            res = _GPCVCvElbo.apply(m2.to(torch.float32), L3.to(torch.float32), mean2.to(torch.float32), K3, y2, *raws, self,
-                                    scale, num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data)
-            return res.reshape(m.shape[:-1]) if batched else res.reshape(())
-        res = _GPCVElbo.apply(m2.to(torch.float32), L3.to(torch.float32), mean2.to(torch.float32), K3, y2, self, scale,
-                              num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data)
+            scale = None
+            if isinstance(lazy, _ScaledDense):
+                scale = lazy.scale
+                K3 = (scale.detach().reshape(-1, 1, 1) * lazy.base).expand(B, n, n)
+            else:
+                K3 = _dense(lazy).expand(B, n, n) if _dense(lazy).ndim == 2 else _dense(lazy).reshape(-1, n, n)
+            res = _GPCVElbo.apply(m2.to(torch.float32), L3.to(torch.float32), mean2.to(torch.float32), K3, y2, *raws, self,
+                                  scale, *weights)
         return res.reshape(m.shape[:-1]) if batched else res.reshape(())
