@@ -442,3 +442,54 @@ def test_fp64_device_assembly_dpp_hazards_and_kernel_shape():
     assert len(shapes) == 2
     for name, (regs, mfma) in shapes.items():
         assert regs <= 420 and mfma == 128, (name, regs, mfma)
+
+
+def test_rollout_entries_argument_codes():
+    """Every return code of csrc/rollout.hip's two entries.  A code is minus the position of the argument it blames; none of
+    these calls reaches a launch (each has one fault, or G = 0 / S = 0: the pointers are small integers)."""
+    from volt_amd import _lib
+    L = _lib.lib()
+
+    def bordered(**kw):
+        a = dict(rho=256, tau=256, acc0=256, dx=256, hist_y=256, hist_e1=None, hist_e2=None, ema_prev=None, mr_latent=None,
+                 latent=None, w=256, pred_vol=256, z=256, samples=256, scratch=None, info=256, G=0, S=3, H=8, k=5, mean_mode=0,
+                 use_theta=0, theta=0.0, mr_theta=0.5, jitter=1e-4, stream=None)
+        assert not set(kw) - set(a)
+        a.update(kw)
+        return L.volt_rollout_bordered_f32(*a.values())
+    for code, cases in ((-1, [dict(rho=None)]), (-2, [dict(tau=None)]), (-3, [dict(acc0=None)]), (-4, [dict(dx=None)]),
+                        (-5, [dict(hist_y=None)]),
+                        (-6, [dict(mean_mode=1), dict(mean_mode=2, hist_e2=256), dict(mean_mode=4)]),     # hist_e1 missing
+                        (-7, [dict(mean_mode=2, hist_e1=256)]),
+                        (-8, [dict(mean_mode=3), dict(mean_mode=3, ema_prev=256), dict(mean_mode=3, mr_latent=256)]),
+                        (-10, [dict(use_theta=1)]),
+                        (-11, [dict(w=None)]), (-12, [dict(pred_vol=None)]), (-13, [dict(z=None)]), (-14, [dict(samples=None)]),
+                        (-16, [dict(info=None)]), (-17, [dict(G=-1)]), (-18, [dict(S=-1)]),
+                        (-19, [dict(H=0), dict(H=1025), dict(H=-1)]), (-20, [dict(k=0), dict(k=2049)]),
+                        (-21, [dict(mean_mode=-1), dict(mean_mode=5)])):
+        for kw in cases:
+            assert bordered(**kw) == code, (code, kw)
+    # nothing to do: no launch -- scratch (15) is optional, and the LDS refusal behind these checks cannot be reached from
+    # H <= 1024, k <= 2048 (12 (k + H) + k floats is 152 KB there)
+    assert bordered() == 0 and bordered(G=2, S=0) == 0 and bordered(H=1024, k=2048) == 0
+    assert bordered(mean_mode=3, ema_prev=256, mr_latent=256) == 0 and bordered(use_theta=1, latent=256) == 0
+    assert bordered(S=0, G=2, H=0) == -19                       # ... but validated all the same
+
+    def shared(**kw):
+        a = dict(hist_y=256, hist_e1=None, hist_e2=None, ema_prev=None, mr_latent=None, w=256, e=256, samples=256, G=0, S=3,
+                 H=8, k=5, mean_mode=0, mr_theta=0.5, stream=None)
+        assert not set(kw) - set(a)
+        a.update(kw)
+        return L.volt_rollout_shared_f32(*a.values())
+    for code, cases in ((-1, [dict(hist_y=None)]), (-2, [dict(mean_mode=1), dict(mean_mode=2, hist_e2=256)]),
+                        (-3, [dict(mean_mode=2, hist_e1=256)]),
+                        (-4, [dict(mean_mode=3), dict(mean_mode=3, ema_prev=256), dict(mean_mode=3, mr_latent=256)]),
+                        (-6, [dict(w=None)]), (-7, [dict(e=None)]), (-8, [dict(samples=None)]), (-9, [dict(G=-1)]),
+                        (-10, [dict(S=-1)]), (-11, [dict(H=0), dict(H=4097)]), (-12, [dict(k=0), dict(k=2049)]),
+                        (-13, [dict(mean_mode=-1), dict(mean_mode=4)]),
+                        # the LDS refusal, 12 (k + H) + k floats > 160 KB, reported against H (it sits behind the G = 0 /
+                        # S = 0 return, so it needs work to refuse: the smallest H refused at these k; nothing is launched)
+                        (-11, [dict(G=1, k=2048, H=1195), dict(G=1, k=1, H=3413)])):
+        for kw in cases:
+            assert shared(**kw) == code, (code, kw)
+    assert shared() == 0 and shared(G=2, S=0) == 0 and shared(G=0, k=2048, H=4096) == 0

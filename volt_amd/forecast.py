@@ -82,8 +82,7 @@ def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_ite
     if mean in _MODES:                                                                   # Rollouts, :110-112
         samples, info = rollout_engine.rollout_series(train_x, train_y[:, 1:].log(), vol.log(), test_x, pred_vol, z,
                                                       _MODES[mean], k, latent_mean=latent, theta=theta)
-        if bool((info < 0).any()):                      # psd_safe_cholesky(pred_cov) would have raised for these paths (:46)
-            raise NotPSDError("rollouts: predictive variance not positive after the jitter ladder")
+        rollout_engine.report_info(info)                # raises where psd_safe_cholesky(pred_cov) would have (:46), warns on a jittered pivot
     else:                                                                                # VOLT + standard mean, :113-119
         samples = _standard_mean_prediction(model, train_x, train_y[:, 1:].log(), vol, test_x, pred_vol, z)
     if debug is not None:

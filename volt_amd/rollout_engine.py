@@ -152,6 +152,24 @@ def rollout_series(train_x, log_y, log_vol_path, test_x, pred_vol, z, mean_mode,
     return samples, info
 
 
+def report_info(info):
+    """What the kernel's info codes [.., S] mean to the caller, for every route that launches the bordered engine: any
+    info < 0 (the predictive variance stayed <= 0 after the jitter ladder) raises NotPSDError, as psd_safe_cholesky(pred_cov,
+    jitter=1e-4) does at rollout_utils.py:46; otherwise any info > 0 (a non-positive pivot, a local jitter was applied) warns
+    NumericalWarning.  Both name the number of paths and the first horizon step; a clean run is silent."""
+    if not bool((info != 0).any()):
+        return
+    n = info.numel()
+    exhausted = info < 0
+    if bool(exhausted.any()):
+        raise NotPSDError(f"rollouts: predictive variance not positive after the jitter ladder for "
+                          f"{int(exhausted.sum())} of {n} sample paths (first at horizon step "
+                          f"{int((-info[exhausted]).min())})")
+    bad = info > 0
+    warnings.warn(f"rollouts: {int(bad.sum())} of {n} sample paths hit a non-positive pivot "
+                  f"(first at horizon step {int(info[bad].min())}); jitter was applied", NumericalWarning)
+
+
 def _depends_on_x_alone(mm):
     """Constant / linear / log-linear means (gp.ConstantMean, gp.LinearMean, means.LogLinearMean): parameters and the
     input, no series state."""
@@ -184,15 +202,7 @@ def rollouts_bordered(train_x, train_y, test_x, model, pred_vol, z, latent_mean,
     samples, info = rollout_series(train_x, log_y.unsqueeze(0), model.log_vol_path.unsqueeze(0), test_x,
                                    pred_vol.unsqueeze(0), z.unsqueeze(0), MODE_GIVEN if given is not None else _MODES[type(mm)],
                                    1 if given is not None else mm.k, latent_mean, theta, **kw)
-    if bool((info[0] != 0).any()):
-        exhausted = info[0] < 0
-        if bool(exhausted.any()):           # psd_safe_cholesky(pred_cov, jitter=1e-4) raises here, rollout_utils.py:46
-            raise NotPSDError(f"rollouts: predictive variance not positive after the jitter ladder for "
-                              f"{int(exhausted.sum())} of {S} sample paths (first at horizon step "
-                              f"{int((-info[0][exhausted]).min())})")
-        bad = info[0] > 0
-        warnings.warn(f"rollouts: {int(bad.sum())} of {S} sample paths hit a non-positive pivot "
-                      f"(first at horizon step {int(info[0][bad].min())}); jitter was applied", NumericalWarning)
+    report_info(info[0])
     samples = samples[0]
     # leave the model in the state the reference leaves it in (rollout_utils.py:80-86, last idx = H-1)
     if H > 1:
