@@ -4,7 +4,7 @@
  *
  * Environment knobs.  The schedule defaults below are compiled in and were measured on MI355X; a
  * deployment reads NO environment variable.  Only a process started with VOLT_TUNE=1 (the experiment scripts) may
- * override them, through ONE table read once per process (csrc/host.h `Tunables`, filled by csrc/chol.hip `tunables()`):
+ * override them, through ONE table read once per process (csrc/host.h `Tunables`, filled by csrc/runtime.hip `tunables()`):
  *   VOLT_GROUPS            stream groups for batches >= 16 (2)        VOLT_SPLITK_TARGET  workgroups per split launch (512)
  *   VOLT_SPLITK_MINL       shortest K-slice in blocks (2)            VOLT_SPLITK_MAXS    most slices per tile (8)
  *   VOLT_SPLITK_GROUPS / _MAXB   two split groups for 10 <= B < 22   VOLT_SCHED          balanced schedule on/off (1)

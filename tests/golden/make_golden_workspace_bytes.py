@@ -19,12 +19,15 @@ BS = (1, 2, 3, 7, 8, 9, 10, 16, 24, 31, 32, 40, 64, 65, 96)
 NS = (100, 128, 256, 399, 1000, 1024, 1536, 2048, 3072, 4096)
 GRADS = (0, 1)
 TASKS = (1, 4, 64)
+CV_KCS = (1, 8)
+BM_KCS = (0, 3)
 TOPOLOGIES = {"full_chip": {}, "fake_64cu_2xcd": {"VOLT_TUNE": "1", "VOLT_FAKE_CUS": "64", "VOLT_FAKE_XCCS": "2"}}
 
 
 def collect():
     """{query: nested lists in grid order}: [B][N][want_grad] for the three-argument queries, [B][N] for the (B, Np)
-    ones (asked with the padded size), [N][T][want_dk] for the multi-task GPCV step."""
+    ones (asked with the padded size), [N][T][want_dk] for the multi-task GPCV step, [B][N][want_dk][Kc] for the "cv" GPCV
+    step and [B][N][Kc] for the Brownian-motion one."""
     if ROOT not in sys.path:
         sys.path.insert(0, ROOT)
     from volt_amd import _lib
@@ -35,6 +38,8 @@ def collect():
     for q in ("volt_potrf_workspace_bytes", "volt_potrf_workspace_bytes_f64", "volt_trtri_workspace_bytes_f64"):
         t[q] = [[int(getattr(L, q)(B, L.volt_padded_n(N))) for N in NS] for B in BS]
     t["volt_gpcv_mt_workspace_bytes"] = [[[int(L.volt_gpcv_mt_workspace_bytes(N, T, g)) for g in GRADS] for T in TASKS] for N in NS]
+    t["volt_gpcv_cv_workspace_bytes"] = [[[[int(L.volt_gpcv_cv_workspace_bytes(B, N, g, k)) for k in CV_KCS] for g in GRADS] for N in NS] for B in BS]
+    t["volt_gpcv_bm_workspace_bytes"] = [[[int(L.volt_gpcv_bm_workspace_bytes(B, N, k)) for k in BM_KCS] for N in NS] for B in BS]
     return t
 
 
@@ -54,7 +59,7 @@ if __name__ == "__main__":
     if "--collect" in sys.argv:
         print(json.dumps(collect()))
     else:
-        table = {"grid": {"B": BS, "N": NS, "want_grad": GRADS, "T": TASKS}}
+        table = {"grid": {"B": BS, "N": NS, "want_grad": GRADS, "T": TASKS, "Kc_cv": CV_KCS, "Kc_bm": BM_KCS}}
         table.update({name: collect_in_child(name) for name in TOPOLOGIES})
         with open(OUT, "w") as fh:
             json.dump(table, fh, separators=(",", ":"))

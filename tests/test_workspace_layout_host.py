@@ -22,13 +22,14 @@ def test_the_table_is_for_this_grid():
     assert (tuple(g["B"]), tuple(g["N"]), tuple(g["want_grad"]), tuple(g["T"])) == (maker.BS, maker.NS, maker.GRADS, maker.TASKS)
     assert maker.BS == (1, 2, 3, 7, 8, 9, 10, 16, 24, 31, 32, 40, 64, 65, 96)
     assert maker.NS == (100, 128, 256, 399, 1000, 1024, 1536, 2048, 3072, 4096)
+    assert (tuple(g["Kc_cv"]), tuple(g["Kc_bm"])) == (maker.CV_KCS, maker.BM_KCS) == ((1, 8), (0, 3))
 
 
 @pytest.mark.parametrize("topology", list(maker.TOPOLOGIES))
 def test_workspace_bytes_are_the_recorded_ones(topology):
     # (the knobs are read once per process: the full chip is this process, the reduced device a child)
     got, want = maker.collect() if topology == "full_chip" else maker.collect_in_child(topology), TABLE[topology]
-    assert set(got) == set(want) and len(want) == 7
+    assert set(got) == set(want) and len(want) == 9
     for q in want:
         assert got[q] == want[q], q
     # the guard's effect is in the table: no state of a one-launch step on the reduced device

@@ -27,12 +27,10 @@
 #include "tiles.h"
 #include "host.h"
 #include "batch_sched.h"
+#include "table_cache.h"
 #include "../../include/volt_hip.h"
 #include "../../include/volt_hip_tune.h"
 #include <algorithm>
-#include <array>
-#include <map>
-#include <mutex>
 #include <string.h>
 #include <vector>
 
@@ -414,46 +412,32 @@ static int batch_check_word(int B, int n, bool has_y) {
     return (int)w;
 }
 
-// The table, built once per (B, n, inverse?, order) in pinned host memory and kept for the life of the library (host
-// memory only, like the balanced schedules' tables); volt_*_workspace_init copies it into the caller's scratch.
+// The table, built once per (B, n, inverse?, order) and kept for the life of the library (host memory only, like the
+// balanced schedules' tables: table_cache.h); volt_*_workspace_init copies it into the caller's scratch.
 struct BatchTable {
-    int4* items = nullptr;
-    size_t bytes = 0;
+    std::vector<int4> image;                   // BATCH_HDR header slots, then the pieces
 };
-static const BatchTable* get_batch_table(int B, int n, bool has_y) {
-    static std::mutex mu;
-    static std::map<std::array<int, 4>, BatchTable*> cache;
+using BatchCache = TableCache<BatchTable, 4>;
+static BatchCache::Table get_batch_table(int B, int n, bool has_y, hipStream_t s) {
+    static BatchCache cache;
     const int order = batch_order_for(B, n);
-    const std::array<int, 4> key{B, n, has_y ? 1 : 0, order * 16 + batch_lad(B)};
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    std::vector<BatchItem> items;
-    batch_build(B, n, has_y, order, items, batch_lad(B));
-    BatchTable* bt = new BatchTable;
-    static_assert(sizeof(BatchItem) == sizeof(int4), "items are read as int4");
-    bt->bytes = (BATCH_HDR + items.size()) * sizeof(BatchItem);
-    if ((int64_t)items.size() != batch_count(B, n, has_y) ||
-        hipHostMalloc((void**)&bt->items, bt->bytes, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        delete bt;
-        bt = nullptr;
-    } else {
-        memset(bt->items, 0, BATCH_HDR * sizeof(BatchItem));
-        bt->items[0] = int4{BATCH_MAGIC, B, n, batch_check_word(B, n, has_y)};
+    return cache.table({B, n, has_y ? 1 : 0, order * 16 + batch_lad(B)}, s, [&](BatchTable& bt) {
+        std::vector<BatchItem> items;
+        batch_build(B, n, has_y, order, items, batch_lad(B));
+        static_assert(sizeof(BatchItem) == sizeof(int4), "items are read as int4");
+        if ((int64_t)items.size() != batch_count(B, n, has_y)) return;
+        bt.image.assign(BATCH_HDR + items.size(), int4{0, 0, 0, 0});
+        bt.image[0] = int4{BATCH_MAGIC, B, n, batch_check_word(B, n, has_y)};
         for (BatchItem& it : items) it.pad = batch_check_word(B, n, has_y);
-        memcpy(bt->items + BATCH_HDR, items.data(), items.size() * sizeof(BatchItem));
-    }
-    cache[key] = bt;
-    return bt;
+        memcpy(bt.image.data() + BATCH_HDR, items.data(), items.size() * sizeof(BatchItem));
+    });
 }
 
 int volt_internal_batch_install(Region state, int B, int n, int has_y, void* stream) {
     if (!state.p || state.bytes < volt_internal_batch_bytes(B, n, has_y) || !volt_internal_batch_applies(B, n, has_y)) return 0;
-    const BatchTable* bt = get_batch_table(B, n, has_y != 0);
-    if (!bt) return (int)hipErrorOutOfMemory;
-    hipError_t e = hipMemcpyAsync(state.p, bt->items, bt->bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
-    return e != hipSuccess ? (int)e : 0;
+    const BatchCache::Table t = get_batch_table(B, n, has_y != 0, (hipStream_t)stream);
+    if (!t.plan) return (int)hipErrorOutOfMemory;
+    return install_table(state.p, t.pinned, t.plan->image.size() * sizeof(int4), (hipStream_t)stream);
 }
 
 // One step: clear the hand-off words, then the one launch.  src.K != nullptr: tiles read their input from K (A receives L);
@@ -501,23 +485,6 @@ int volt_internal_batch_step(const StepMats& m, const KSource& src, const TriRed
 }
 
 extern "C" {
-
-// What the library found the device to be, and the gates that follow from it (host.h): out[0] CUs, [1] XCDs, [2] slots the
-// balanced schedule plans for, [3] / [4] plain / split launches up to this many workgroups run one per CU, [5] launches
-// below this many workgroups run as one stream group, [6] one-launch steps enabled (short series | one long series << 1 |
-// batched << 2).  No GPU needed (a process without a device reports the full-chip defaults).
-int volt_topology_describe(int* out) {
-    if (!out) return -1;
-    const Tunables& tn = tunables();
-    out[0] = tn.cus;
-    out[1] = tn.xccs;
-    out[2] = tn.sched_g;
-    out[3] = tn.plain_spread;
-    out[4] = tn.split_spread;
-    out[5] = tn.group_gate;
-    out[6] = (tn.small_nmax > 0 ? 1 : 0) | (tn.long_on ? 2 : 0) | (tn.batch > 0 ? 4 : 0);
-    return 0;
-}
 
 int volt_tune_batch_stamps(long long* stamps) {
     g_batch_stamps = stamps;

@@ -21,13 +21,11 @@
 #include "host.h"
 #include "sched.h"
 #include "long_sched.h"
+#include "table_cache.h"
 #include "../../include/volt_hip.h"
 #include "../../include/volt_hip_tune.h"
 #include <algorithm>
-#include <array>
-#include <map>
 #include <mutex>
-#include <stdlib.h>
 #include <string.h>
 #include <utility>
 #include <vector>
@@ -422,102 +420,6 @@ __global__ void tune_empty_kernel(float* A) { if (A == nullptr) A[0] = 0.f; }
 
 using namespace volt;
 
-static Tunables read_env(Tunables t) {                       // VOLT_TUNE=1 processes only
-    auto geti = [](const char* name, int& v) { if (const char* e = getenv(name)) v = atoi(e); };
-        geti("VOLT_GROUPS", t.groups);
-        geti("VOLT_SPLITK_TARGET", t.splitk_target);
-        geti("VOLT_SPLITK_MINL", t.splitk_minl);
-        geti("VOLT_SPLITK_MAXS", t.splitk_maxs);
-        geti("VOLT_SPLITK_GROUPS", t.splitk_groups);
-        geti("VOLT_SPLITK_MAXB", t.splitk_maxb);
-        geti("VOLT_SCHED", t.sched);
-        geti("VOLT_SCHED_MINB", t.sched_minb);
-        geti("VOLT_SCHED_MAXB", t.sched_maxb);
-        geti("VOLT_SCHED_MAXB_POTRF", t.sched_maxb_potrf);
-        geti("VOLT_SCHED_G", t.sched_g);
-        geti("VOLT_SCHED_S", t.sched_s);
-        geti("VOLT_SCHED_GROUPS", t.sched_groups);
-        geti("VOLT_SCHED_KMIN", t.sched_kmin);
-        geti("VOLT_SMALL_NMAX", t.small_nmax);
-        geti("VOLT_SMALL_MAXWG", t.small_maxwg);
-        geti("VOLT_SMALL_PAD_MAXB", t.small_pad_maxb);
-        geti("VOLT_SMALL_MAXB", t.small_maxb);
-        geti("VOLT_SMALL_MAXB2", t.small_maxb2);
-        geti("VOLT_LONG", t.long_on);
-        geti("VOLT_LONG_FIRST", t.long_first);
-        geti("VOLT_LONG_EMIN", t.long_emin);
-        geti("VOLT_LONG_PAD", t.long_pad);
-        geti("VOLT_LONG_NMIN", t.long_nmin);
-        geti("VOLT_LONG_XCD", t.long_xcd);
-        geti("VOLT_LONG_SPLIT", t.long_split);
-        geti("VOLT_PLAIN_SPREAD", t.plain_spread);
-        geti("VOLT_SPLIT_SPREAD", t.split_spread);
-        geti("VOLT_BATCH", t.batch);
-        geti("VOLT_BATCH_ORDER", t.batch_order);
-        geti("VOLT_BATCH_LOCAL", t.batch_local);
-        geti("VOLT_BATCH_SPREAD", t.batch_spread);
-        geti("VOLT_BATCH_LAD", t.batch_lad);
-        geti("VOLT_BATCH_PULLERS", t.batch_pullers);
-        geti("VOLT_ROLLOUT_LANE", t.rollout_lane);
-        geti("VOLT_LONG_PULLERS", t.long_pullers);
-        geti("VOLT_BATCH_XSKEW", t.batch_xskew);
-        geti("VOLT_BATCH_XDROP", t.batch_xdrop);
-        geti("VOLT_BATCH64", t.batch64);
-        geti("VOLT_BATCH64_MAX", t.batch64_max);
-        geti("VOLT_BATCH64_MAX_STEP", t.batch64_max_step);
-        geti("VOLT_F64_LOOKAHEAD", t.f64_lookahead);
-        geti("VOLT_F64_TRTRI_LOOKAHEAD", t.f64_trtri_lookahead);
-        geti("VOLT_F64_SPREAD", t.f64_spread);
-        geti("VOLT_F64_SPLIT_TARGET", t.f64_split_target);
-        if (const char* e = getenv("VOLT_SCHED_FRAC")) t.sched_frac = (float)atof(e);
-        geti("VOLT_FAKE_CUS", t.cus);                        // tests: plan as if the device had this many CUs / XCDs
-        geti("VOLT_FAKE_XCCS", t.xccs);
-    return t;
-}
-
-// What the device looks like, and the gates that depend on it (host.h).  A process without a device (the CPU-side tests)
-// keeps the full-chip defaults.
-static void apply_topology(Tunables& t, bool faked) {
-    if (!faked) {
-        int dev = 0, cus = 0, xccs = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) {
-            t.cus = cus;
-            if (hipDeviceGetAttribute(&xccs, hipDeviceAttributeNumberOfXccs, dev) == hipSuccess && xccs > 0) t.xccs = xccs;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    if (t.cus == 256 && t.xccs == 8) return;
-    const double f = t.cus / 256.0;
-    auto scale = [f](int v, int lo) { const int r = (int)(v * f + 0.5); return r < lo ? lo : r; };
-    t.sched_g = scale(t.sched_g, 8);
-    t.plain_spread = scale(t.plain_spread, 8);
-    t.split_spread = scale(t.split_spread, 16);
-    t.splitk_target = scale(t.splitk_target, 16);
-    t.group_gate = scale(t.group_gate, 16);
-    t.batch_spread = scale(t.batch_spread, 8);
-    t.small_nmax = 0;                                        // the one-launch steps: tuned for, and (batched step) placed on, the full chip
-    t.long_on = 0;
-    t.batch = 0;
-    t.batch64 = 0;
-}
-
-const Tunables& tunables() {
-    static const Tunables tn = [] {
-        const char* tune0 = getenv("VOLT_TUNE");
-        const bool tuning = tune0 && atoi(tune0) != 0;
-        const bool faked = tuning && (getenv("VOLT_FAKE_CUS") || getenv("VOLT_FAKE_XCCS"));
-        Tunables t = [&] {
-            Tunables t;
-            if (!tuning) return t;                           // the frozen defaults
-            return read_env(t);
-        }();
-        apply_topology(t, faked);
-        return t;
-    }();
-    return tn;
-}
 // Optional per-launch timing (bench only): every launch is bracketed by two events on ITS stream; the caller
 // synchronises, and per kernel class gets the summed launch durations and the length of the UNION of the launch
 // intervals (on one stream the two agree; with the batch cut into groups on several streams the launches of a class
@@ -590,13 +492,13 @@ struct FactorOpts {
     const struct SchedDev* sched = nullptr;   // non-null: the host-balanced schedule (mid-size batches), needs sk.slab
 };
 
-// A balanced schedule: the items of all n (+1 with a triangular inverse) launches back to back, in PINNED HOST memory.
+// A balanced schedule: the items of all n (+1 with a triangular inverse) launches back to back (table_cache.h).
 // The device copy lives in the CALLER's scratch (SplitK::tab), copied there once by volt_*_workspace_init -- the library
 // owns no device memory.
 constexpr int SCHED_HDR = 16;                  // int4 slots ahead of the items: the table's identity (two are used)
 struct SchedDev {
-    int4* items = nullptr;                   // pinned host: SCHED_HDR header slots, then the items
-    size_t bytes = 0;                        // header + items
+    std::vector<int4> image;                 // SCHED_HDR header slots, then the items
+    size_t bytes = 0;                        // ... in bytes
     int4 key[2];                             // {magic, B, n, inverse?}, {G, S, 1000 frac, min_len}: what the kernels check
     std::vector<int> item_off;               // per launch: where its items start (one more entry closes the last)
     int S = 0;
@@ -604,24 +506,10 @@ struct SchedDev {
     int kmin = 0;                            // block columns below this run the plain one-tile-per-workgroup launch
 };
 
-// Built once per (device, B, n, inverse?, parameters) and kept for the life of the library, like the stream pool
-// (host memory only).  A miss while the stream is being captured into a graph returns nullptr (no allocation inside a
-// capture): the caller falls back to the schedules that need no tables.
-static const SchedDev* get_sched(int B, int n, bool has_y, const SchedParams& p, hipStream_t s) {
-    static std::mutex mu;
-    static std::map<std::array<int, 8>, SchedDev*> cache;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    const std::array<int, 8> key{dev, B, n, has_y ? 1 : 0, p.G, p.S, (int)(p.frac * 1000.f), p.min_len};
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return nullptr;
+static void sched_build(SchedDev& sd, int B, int n, bool has_y, const SchedParams& p) {
     std::vector<SchedItem> items;
-    SchedDev* sd = new SchedDev;
-    sd->S = p.S;
-    sd->pad_lds = 16 * 1024;                                 // 72 KB static + 16 KB: one workgroup per 160 KB CU
+    sd.S = p.S;
+    sd.pad_lds = 16 * 1024;                                  // 72 KB static + 16 KB: one workgroup per 160 KB CU
     // measured (N = 4096): below these block columns the plain launch is as fast or faster -- a cut tile pays ~25 us for
     // its slabs, and only the late launches (long trtri rows, k + 2 blocks against a mean of ~k / 2) are unbalanced enough
     // (ms/step at N = 4096 by first scheduled column, B = 3: 8 2.58, 12 2.57, 16 2.60; B = 6: 12 3.66, 16 3.64, 20 3.70;
@@ -629,29 +517,31 @@ static const SchedDev* get_sched(int B, int n, bool has_y, const SchedParams& p,
     const int kmin_env = tunables().sched_kmin;
     // the factorisation alone (no trtri rows; per-call ms at N = 4096 by first scheduled column, B = 16: 12 3.95, 16 4.04,
     // 20 4.28, off 4.82; B = 32: 12 6.60, 20 6.64, off 7.93; B = 64: 12 12.48, 20 12.21, 24 12.22, off 12.87)
-    sd->kmin = kmin_env >= 0 ? kmin_env : !has_y ? (B * (256 / p.G) >= 48 ? 20 : 12) : (p.G < 256 ? 16 : B <= 4 ? 12 : B <= 7 ? 16 : 20);
+    sd.kmin = kmin_env >= 0 ? kmin_env : !has_y ? (B * (256 / p.G) >= 48 ? 20 : 12) : (p.G < 256 ? 16 : B <= 4 ? 12 : B <= 7 ? 16 : 20);
     const int launches = has_y ? n + 1 : n;
     for (int k = 0; k < launches; ++k) {
-        sd->item_off.push_back((int)items.size());
+        sd.item_off.push_back((int)items.size());
         sched_build_launch(B, n, has_y, k, p, items);
     }
-    sd->item_off.push_back((int)items.size());
+    sd.item_off.push_back((int)items.size());
     static_assert(sizeof(SchedItem) == sizeof(int4), "items are read as int4");
-    sd->bytes = (SCHED_HDR + items.size()) * sizeof(SchedItem);
-    sd->key[0] = int4{0x564f4c54, B, n, has_y ? 1 : 0};
-    sd->key[1] = int4{p.G, p.S, (int)(p.frac * 1000.f), p.min_len};
-    if (hipHostMalloc((void**)&sd->items, sd->bytes, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        delete sd;
-        sd = nullptr;
-    } else {
-        memset(sd->items, 0, SCHED_HDR * sizeof(SchedItem));
-        sd->items[0] = sd->key[0];
-        sd->items[1] = sd->key[1];
-        memcpy(sd->items + SCHED_HDR, items.data(), items.size() * sizeof(SchedItem));
-    }
-    cache[key] = sd;                                         // a failure is remembered too: no retry per call
-    return sd;
+    sd.key[0] = int4{0x564f4c54, B, n, has_y ? 1 : 0};
+    sd.key[1] = int4{p.G, p.S, (int)(p.frac * 1000.f), p.min_len};
+    sd.image.assign(SCHED_HDR + items.size(), int4{0, 0, 0, 0});
+    sd.image[0] = sd.key[0];
+    sd.image[1] = sd.key[1];
+    memcpy(sd.image.data() + SCHED_HDR, items.data(), items.size() * sizeof(SchedItem));
+    sd.bytes = sd.image.size() * sizeof(int4);
+}
+
+// Built once per (device, B, n, inverse?, parameters) and kept for the life of the library, like the stream pool
+// (host memory only: table_cache.h).  A miss while the stream is being captured into a graph returns no table (no
+// allocation inside a capture): the caller falls back to the schedules that need no tables.
+using SchedCache = TableCache<SchedDev, 7>;
+static SchedCache::Table get_sched(int B, int n, bool has_y, const SchedParams& p, hipStream_t s) {
+    static SchedCache cache;
+    return cache.table({B, n, has_y ? 1 : 0, p.G, p.S, (int)(p.frac * 1000.f), p.min_len}, s,
+                       [&](SchedDev& sd) { sched_build(sd, B, n, has_y, p); });
 }
 
 // Which balanced schedule B matrices of n block columns get (false: none).  Gs = stream groups it runs in, sp = the
@@ -678,10 +568,9 @@ static int sched_install(void* tab, size_t tab_bytes, int B, int n, bool has_y, 
     int Gs = 1;
     SchedParams sp;
     if (!tab || !sched_choice(B, n, has_y, cap, Gs, sp)) return 0;
-    const SchedDev* sd = get_sched(B / Gs, n, has_y, sp, s);
-    if (!sd || sd->bytes > tab_bytes) return 0;
-    hipError_t e = hipMemcpyAsync(tab, sd->items, sd->bytes, hipMemcpyHostToDevice, s);
-    return e != hipSuccess ? (int)e : 0;
+    const SchedCache::Table t = get_sched(B / Gs, n, has_y, sp, s);
+    if (!t.plan || t.plan->bytes > tab_bytes) return 0;
+    return install_table(tab, t.pinned, t.plan->bytes, s);
 }
 
 // Everything one group of matrices needs: the batch is cut into contiguous groups that run the same
@@ -793,51 +682,9 @@ static int begin_factor(float* Winv, int* info, int B, int n, hipStream_t s, int
 // rounds of the 512 resident workgroups, and the next stage cannot start before the tail has drained.
 // Cutting the batch into G groups that run the SAME launch sequence on G streams lets one group's tail
 // overlap another group's next stage.  The auxiliary streams and the fork / join events are created once per
-// device (library-lifetime, like a BLAS handle's); a call forks from and joins back into the caller's stream
+// device (library-lifetime, like a BLAS handle's: stream_pool, runtime.hip); a call forks from and joins back into the caller's stream
 // with those events, so the caller still sees ordinary stream semantics.  Calls on one device are serialised
 // on the HOST while they enqueue (a mutex around fork .. join: the events are shared), never on the device.
-constexpr int MAX_GROUPS = 8;
-struct StreamPool {
-    hipStream_t aux[MAX_GROUPS - 1];
-    hipEvent_t fork, join[MAX_GROUPS - 1], extra[5];     // extra: chol64.hip's look-ahead schedules
-    std::mutex mu;
-    int want_groups = 2;                 // tunables().groups
-    bool ok = false;
-};
-static StreamPool* stream_pool() {
-    static StreamPool pools[16];
-    static std::once_flag once[16];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-    std::call_once(once[dev], [dev]() {
-        StreamPool& p = pools[dev];
-        bool ok = hipEventCreateWithFlags(&p.fork, hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; i < MAX_GROUPS - 1; ++i) {
-            ok = ok && hipStreamCreateWithFlags(&p.aux[i], hipStreamNonBlocking) == hipSuccess;
-            ok = ok && hipEventCreateWithFlags(&p.join[i], hipEventDisableTiming) == hipSuccess;
-        }
-        for (int i = 0; i < 5; ++i) ok = ok && hipEventCreateWithFlags(&p.extra[i], hipEventDisableTiming) == hipSuccess;
-        p.want_groups = tunables().groups;
-        if (p.want_groups < 1) p.want_groups = 1;
-        if (p.want_groups > MAX_GROUPS) p.want_groups = MAX_GROUPS;
-        p.ok = ok;
-    });
-    return pools[dev].ok ? &pools[dev] : nullptr;
-}
-
-// chol64.hip runs its look-ahead on the same pool (VoltAux, host.h), under the pool's mutex while it enqueues -- like
-// run_factor_groups below.
-bool volt_internal_aux(VoltAux* out) {
-    StreamPool* p = stream_pool();
-    if (!p) return false;
-    // (lowest-priority streams for the bulk work were tried: the chain then waits for events from a stream the hardware
-    // serves last -- one 4096^2 matrix 4.2 -> 8.1 ms)
-    *out = VoltAux{p->aux[0], p->aux[1], p->aux[2], p->aux[3], p->fork,
-                   {p->join[0], p->join[1], p->join[2], p->join[3], p->join[4], p->join[5], p->join[6], p->extra[0],
-                    p->extra[1], p->extra[2], p->extra[3], p->extra[4]}, &p->mu};
-    return true;
-}
-
 static int pick_groups(const StreamPool* pool, int B, int force) {
     int want = force > 0 ? force : (pool ? pool->want_groups : 1);
     if (want > MAX_GROUPS) want = MAX_GROUPS;
@@ -895,7 +742,7 @@ static int run_factor_groups(float* A, float* Winv, int* info, int B, int Np, hi
         // is the one get_sched returns for this shape (a pure function of it; the launches check the header on the device)
         const SchedDev* sd = nullptr;
         if (o.sk.tab && sched_choice(B, n, o.Y != nullptr, o.sk.cap, Gs, sp) && (Gs == 1 || (pool && !capturing)))
-            sd = get_sched(B / Gs, n, o.Y != nullptr, sp, s);
+            sd = get_sched(B / Gs, n, o.Y != nullptr, sp, s).plan;
         // short matrices never reach the scheduled columns; below 8 matrices the alternative is the all-split schedule,
         // which is the better one while most columns are early ones (B = 4, n = 16: 0.92 ms all-split, 1.04 hybrid)
         if (sd && sd->bytes <= o.sk.tab_bytes && n > sd->kmin + (B < 8 ? 7 : 1)) {
@@ -988,12 +835,15 @@ int volt_internal_sched_install(Region tab, int B, int n, int has_y, int cap, vo
     return sched_install(tab.p, tab.bytes, B, n, has_y != 0, cap, (hipStream_t)stream);
 }
 
+// the launch-per-column schedules' scratch as the kernels take it (S, L: set per launch)
+static SplitK split_of(const SplitScratch& sk) { return SplitK{sk.slab, sk.count, 1, 1, sk.rows, (int4*)sk.tab.p, sk.tab.bytes}; }
+
 // block column 0 (its diagonal tile is factored straight out of A) is copied; everything else is read from K
 static FactorOpts factor_from_k(const StepMats& m, const KSource& src, const TriReduce& red, const SplitScratch& sk) {
     const int Np = volt_padded_n(m.N);
     hipLaunchKernelGGL(prepare_kernel, dim3(Np / TS, m.B), dim3(256), 0, m.stream, src.K, src.ldk, src.bsk, src.sigma2, src.jitter,
                        m.A, m.N, Np, 1);
-    return FactorOpts{src, m.Y, red, SplitK{sk.slab, sk.count, 1, 1, sk.rows, (int4*)sk.tab.p, sk.tab.bytes}};
+    return FactorOpts{src, m.Y, red, split_of(sk)};
 }
 
 // used by mll.hip
@@ -1104,19 +954,14 @@ struct PotrfWs {
 };
 static PotrfWs carve_potrf(void* ws, int B, int Np) {
     const size_t n = (size_t)Np / TS;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        void* p = ws && bytes ? reinterpret_cast<char*>(ws) + off : nullptr;
-        off += bytes;
-        return Region{p, bytes};
-    };
+    Carver c{ws};
     PotrfWs w;
     w.sk.rows = n < 3 ? 0 : potrf_ws_rows(B);
-    w.sk.slab = reinterpret_cast<float*>(take(w.sk.rows ? al256((size_t)w.sk.rows * (n + 1) * TS * TS * sizeof(float)) : 0).p);
-    w.sk.count = reinterpret_cast<int*>(take(w.sk.rows ? al256((n + 1) * (n + 1) * B * sizeof(int)) : 0).p);
-    w.sk.tab = take(w.sk.rows ? volt_internal_sched_bytes(B, (int)n) : 0);
-    w.batch = take(volt_internal_batch_bytes(B, (int)n, 0));
-    w.bytes = off;
+    w.sk.slab = c.take<float>(w.sk.rows ? (size_t)w.sk.rows * (n + 1) * TS * TS : 0);
+    w.sk.count = c.take<int>(w.sk.rows ? (n + 1) * (n + 1) * B : 0);
+    w.sk.tab = c.region(w.sk.rows ? volt_internal_sched_bytes(B, (int)n) : 0);
+    w.batch = c.region(volt_internal_batch_bytes(B, (int)n, 0));
+    w.bytes = c.off;
     return w;
 }
 
@@ -1163,7 +1008,7 @@ static int potrf_with_scratch(const KSource& src, const StepMats& m, void* ws, s
         if (!ready) sk.tab.p = nullptr;                      // the table region is followed only on the caller's word that the init ran on this scratch
     }
     if (src.K) return volt_internal_factor(m, src, TriReduce{nullptr, nullptr, nullptr, 0}, sk, nullptr, nullptr);
-    const FactorOpts o{src, nullptr, TriReduce{nullptr, nullptr, nullptr, 0}, SplitK{sk.slab, sk.count, 1, 1, sk.rows, (int4*)sk.tab.p, sk.tab.bytes}};
+    const FactorOpts o{src, nullptr, TriReduce{nullptr, nullptr, nullptr, 0}, split_of(sk)};
     return run_factor_groups(m.A, m.Winv, m.info, m.B, Np, m.stream, o);
 }
 

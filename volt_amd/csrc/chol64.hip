@@ -319,27 +319,26 @@ int volt_trtri_f64(const double* A, const double* Winv, double* Y, int B, int Np
     hipStream_t s = (hipStream_t)stream;
     const int n = Np / TS;
     const bool look = trtri64_lookahead(B);
-    VoltAux ax;
+    StreamPool* ax = look && n >= 3 ? stream_pool() : nullptr;       // the look-ahead runs on the library's streams (host.h)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool two = look && n >= 3 && volt_internal_aux(&ax) && hipStreamIsCapturing(s, &cap) == hipSuccess &&
-                     cap == hipStreamCaptureStatusNone;
+    const bool two = ax && hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
     if (!two) {
         trtri64_begin(Y, B, Np, s);
         for (int i = 0; i < n; ++i) trtri64_row(A, Winv, Y, B, Np, i, s);
         VOLT_LAUNCH_CHECK();
         return 0;
     }
-    // Row i's early part (stream aux) runs beside row i-1's last block and phase 2 (the caller's stream)
-    std::lock_guard<std::mutex> lock(*ax.mu);
-    hipEvent_t ev_p2[2] = {ax.ev[7], ax.ev[8]}, ev_p1a = ax.ev[9];
+    // Row i's early part (stream aux[0]) runs beside row i-1's last block and phase 2 (the caller's stream)
+    std::lock_guard<std::mutex> lock(ax->mu);
+    hipEvent_t ev_p2[2] = {ax->extra[0], ax->extra[1]}, ev_p1a = ax->extra[2];
     trtri64_begin(Y, B, Np, s, true);
-    VOLT_TRY64(hipEventRecord(ax.fork, s));
-    VOLT_TRY64(hipStreamWaitEvent(ax.aux, ax.fork, 0));
+    VOLT_TRY64(hipEventRecord(ax->fork, s));
+    VOLT_TRY64(hipStreamWaitEvent(ax->aux[0], ax->fork, 0));
     for (int i = 0; i < n; ++i) {
         if (i >= 2) {
-            VOLT_TRY64(hipStreamWaitEvent(ax.aux, ev_p2[i & 1], 0));        // row i-2 of the inverse is out
-            trtri64_early(A, Y, B, Np, i, ax.aux);
-            VOLT_TRY64(hipEventRecord(ev_p1a, ax.aux));
+            VOLT_TRY64(hipStreamWaitEvent(ax->aux[0], ev_p2[i & 1], 0));        // row i-2 of the inverse is out
+            trtri64_early(A, Y, B, Np, i, ax->aux[0]);
+            VOLT_TRY64(hipEventRecord(ev_p1a, ax->aux[0]));
             VOLT_TRY64(hipStreamWaitEvent(s, ev_p1a, 0));
         }
         trtri64_finish(A, Winv, Y, B, Np, i, s);
@@ -451,9 +450,9 @@ int volt_internal_factor_f64(const StepMats64& m, Region state) {
         if (S > 16) S = 16;
         return S < 1 ? 1 : S;
     };
-    VoltAux ax;
+    StreamPool* ax = look && n >= 3 ? stream_pool() : nullptr;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool two = look && n >= 3 && volt_internal_aux(&ax) && hipStreamIsCapturing(s, &cap) == hipSuccess;
+    const bool two = ax && hipStreamIsCapturing(s, &cap) == hipSuccess;
     if (!two) {
         for (int k = 0; k < n; ++k) {
             if (k > 0) {
@@ -470,34 +469,34 @@ int volt_internal_factor_f64(const StepMats64& m, Region state) {
         VOLT_LAUNCH_CHECK();
         return 0;
     }
-    std::lock_guard<std::mutex> lock(*ax.mu);
-    hipEvent_t ev_a = ax.ev[0], ev_c = ax.ev[1], ev_d = ax.ev[4];
-    hipEvent_t ev_b[2] = {ax.ev[2], ax.ev[3]};
-    VOLT_TRY64(hipEventRecord(ax.fork, s));
-    VOLT_TRY64(hipStreamWaitEvent(ax.aux, ax.fork, 0));
+    std::lock_guard<std::mutex> lock(ax->mu);
+    hipEvent_t ev_a = ax->join[0], ev_c = ax->join[1], ev_d = ax->join[4];
+    hipEvent_t ev_b[2] = {ax->join[2], ax->join[3]};
+    VOLT_TRY64(hipEventRecord(ax->fork, s));
+    VOLT_TRY64(hipStreamWaitEvent(ax->aux[0], ax->fork, 0));
     // Rows of the inverse beside the factorisation, themselves with a one-row look-ahead: call k (column k-1 is complete)
-    // puts the last block + phase 2 of row k-1 on aux2 and the early part of row k -- it needs rows <= k-2 only -- on aux4
-    hipEvent_t ev_p2[2] = {ax.ev[7], ax.ev[8]}, ev_p1a = ax.ev[9];
+    // puts the last block + phase 2 of row k-1 on aux[1] and the early part of row k -- it needs rows <= k-2 only -- on aux[3]
+    hipEvent_t ev_p2[2] = {ax->extra[0], ax->extra[1]}, ev_p1a = ax->extra[2];
     // (not inside a graph capture: the fourth branch it adds crashed hipStreamEndCapture here; captured steps keep the plain rows)
     const bool tri_look = trtri64_lookahead(B) && cap == hipStreamCaptureStatusNone;
     if (Y) {
-        VOLT_TRY64(hipStreamWaitEvent(ax.aux2, ax.fork, 0));
-        if (tri_look) VOLT_TRY64(hipStreamWaitEvent(ax.aux4, ax.fork, 0));   // (a forked stream must get work that is joined: captures)
-        trtri64_begin(Y, B, Np, ax.aux2, tri_look);
+        VOLT_TRY64(hipStreamWaitEvent(ax->aux[1], ax->fork, 0));
+        if (tri_look) VOLT_TRY64(hipStreamWaitEvent(ax->aux[3], ax->fork, 0));   // (a forked stream must get work that is joined: captures)
+        trtri64_begin(Y, B, Np, ax->aux[1], tri_look);
     }
     auto tri_step = [&](int k) -> int {
-        VOLT_TRY64(hipStreamWaitEvent(ax.aux2, ev_a, 0));
+        VOLT_TRY64(hipStreamWaitEvent(ax->aux[1], ev_a, 0));
         if (!tri_look) {
-            trtri64_row(A, Winv, Y, B, Np, k - 1, ax.aux2);
+            trtri64_row(A, Winv, Y, B, Np, k - 1, ax->aux[1]);
             return 0;
         }
-        if (k - 1 >= 2) VOLT_TRY64(hipStreamWaitEvent(ax.aux2, ev_p1a, 0));
-        trtri64_finish(A, Winv, Y, B, Np, k - 1, ax.aux2);
-        VOLT_TRY64(hipEventRecord(ev_p2[(k - 1) & 1], ax.aux2));
+        if (k - 1 >= 2) VOLT_TRY64(hipStreamWaitEvent(ax->aux[1], ev_p1a, 0));
+        trtri64_finish(A, Winv, Y, B, Np, k - 1, ax->aux[1]);
+        VOLT_TRY64(hipEventRecord(ev_p2[(k - 1) & 1], ax->aux[1]));
         if (k >= 2 && k < n) {
-            VOLT_TRY64(hipStreamWaitEvent(ax.aux4, ev_p2[k & 1], 0));              // row k-2 is out
-            trtri64_early(A, Y, B, Np, k, ax.aux4);
-            VOLT_TRY64(hipEventRecord(ev_p1a, ax.aux4));
+            VOLT_TRY64(hipStreamWaitEvent(ax->aux[3], ev_p2[k & 1], 0));              // row k-2 is out
+            trtri64_early(A, Y, B, Np, k, ax->aux[3]);
+            VOLT_TRY64(hipEventRecord(ev_p1a, ax->aux[3]));
         }
         return 0;
     };
@@ -508,27 +507,27 @@ int volt_internal_factor_f64(const StepMats64& m, Region state) {
         //                     X(j):   block  m  = j-1 into the tiles below the diagonal (auxiliary stream), and the
         //                             same block into the diagonal tile on the chain itself.
         // X, Y and Z of different steps may touch one tile at the same time: all three subtract with fp64 atomics.
-        hipEvent_t ev_y = ax.ev[2], ev_z[2] = {ax.ev[3], ax.ev[5]};
-        if (n >= 4) VOLT_TRY64(hipStreamWaitEvent(ax.aux3, ax.fork, 0));     // Z(1) exists from four block columns on
+        hipEvent_t ev_y = ax->join[2], ev_z[2] = {ax->join[3], ax->join[5]};
+        if (n >= 4) VOLT_TRY64(hipStreamWaitEvent(ax->aux[2], ax->fork, 0));     // Z(1) exists from four block columns on
         for (int k = 0; k < n; ++k) {
             // the chain's waits first (they refer to what earlier iterations recorded)
             if (k >= 2) VOLT_TRY64(hipStreamWaitEvent(s, ev_y, 0));                 // Y(k-1): block k-2 is in column k
             if (k >= 3) VOLT_TRY64(hipStreamWaitEvent(s, ev_z[k & 1], 0));          // Z(k-2): blocks <= k-3 are in column k
             if (k >= 1 && k + 1 < n) {
-                VOLT_TRY64(hipStreamWaitEvent(ax.aux, ev_a, 0));                    // column k-1 complete
-                hipLaunchKernelGGL(update64_kernel, dim3((n - k - 1) * B), dim3(256), spread64((n - k - 1) * B), ax.aux, A, Np, k, k + 1, n - k - 1,
+                VOLT_TRY64(hipStreamWaitEvent(ax->aux[0], ev_a, 0));                    // column k-1 complete
+                hipLaunchKernelGGL(update64_kernel, dim3((n - k - 1) * B), dim3(256), spread64((n - k - 1) * B), ax->aux[0], A, Np, k, k + 1, n - k - 1,
                                    k - 1, k, B, 1, 1);                               // X(k)
-                VOLT_TRY64(hipEventRecord(ev_c, ax.aux));
-                hipLaunchKernelGGL(update64_kernel, dim3((n - k - 1) * B), dim3(256), spread64((n - k - 1) * B), ax.aux, A, Np, k + 1, k + 1,
+                VOLT_TRY64(hipEventRecord(ev_c, ax->aux[0]));
+                hipLaunchKernelGGL(update64_kernel, dim3((n - k - 1) * B), dim3(256), spread64((n - k - 1) * B), ax->aux[0], A, Np, k + 1, k + 1,
                                    n - k - 1, k - 1, k, B, 1, 1);                    // Y(k): block k-1 into column k+1
-                VOLT_TRY64(hipEventRecord(ev_y, ax.aux));
+                VOLT_TRY64(hipEventRecord(ev_y, ax->aux[0]));
             }
             if (k >= 1 && k + 2 < n) {
-                VOLT_TRY64(hipStreamWaitEvent(ax.aux3, ev_a, 0));
+                VOLT_TRY64(hipStreamWaitEvent(ax->aux[2], ev_a, 0));
                 const int S = slices((n - k - 2) * B, k);
-                hipLaunchKernelGGL(update64_kernel, dim3((n - k - 2) * B * S), dim3(256), spread64((n - k - 2) * B * S), ax.aux3, A, Np,
+                hipLaunchKernelGGL(update64_kernel, dim3((n - k - 2) * B * S), dim3(256), spread64((n - k - 2) * B * S), ax->aux[2], A, Np,
                                    k + 2, k + 2, n - k - 2, 0, k, B, S, 1);          // Z(k): blocks <= k-1 into column k+2
-                VOLT_TRY64(hipEventRecord(ev_z[k & 1], ax.aux3));
+                VOLT_TRY64(hipEventRecord(ev_z[k & 1], ax->aux[2]));
             }
             if (Y && k >= 1) { const int rc_ = tri_step(k); if (rc_) return rc_; }
             if (k >= 1)
@@ -544,15 +543,15 @@ int volt_internal_factor_f64(const StepMats64& m, Region state) {
     for (int k = 0; k < n; ++k) {
         // ---- A(k) on the auxiliary stream (needs column k-1 complete: event a)
         if (k >= 1) {
-            VOLT_TRY64(hipStreamWaitEvent(ax.aux, ev_a, 0));
+            VOLT_TRY64(hipStreamWaitEvent(ax->aux[0], ev_a, 0));
             if (k + 1 < n) {
-                hipLaunchKernelGGL(update64_kernel, dim3((n - k - 1) * B), dim3(256), spread64((n - k - 1) * B), ax.aux, A, Np, k, k + 1,
+                hipLaunchKernelGGL(update64_kernel, dim3((n - k - 1) * B), dim3(256), spread64((n - k - 1) * B), ax->aux[0], A, Np, k, k + 1,
                                    n - k - 1, k - 1, k, B, 1, 0);             // block k-1 into the tiles (i,k), i > k
-                VOLT_TRY64(hipEventRecord(ev_c, ax.aux));
+                VOLT_TRY64(hipEventRecord(ev_c, ax->aux[0]));
                 const int S = slices((n - k - 1) * B, k);
-                hipLaunchKernelGGL(update64_kernel, dim3((n - k - 1) * B * S), dim3(256), spread64((n - k - 1) * B * S), ax.aux, A, Np, k + 1,
+                hipLaunchKernelGGL(update64_kernel, dim3((n - k - 1) * B * S), dim3(256), spread64((n - k - 1) * B * S), ax->aux[0], A, Np, k + 1,
                                    k + 1, n - k - 1, 0, k, B, S, S > 1);     // blocks m < k into every tile of column k+1
-                VOLT_TRY64(hipEventRecord(ev_b[k & 1], ax.aux));
+                VOLT_TRY64(hipEventRecord(ev_b[k & 1], ax->aux[0]));
             }
         }
         // ---- row k-1 of the triangular inverse on the third stream (needs column k-1 and W_{k-1}: event a)
@@ -573,7 +572,7 @@ int volt_internal_factor_f64(const StepMats64& m, Region state) {
     if (Y) {                                                                  // the last row of the inverse, then join
         VOLT_TRY64(hipEventRecord(ev_a, s));
         { const int rc_ = tri_step(n); if (rc_) return rc_; }
-        VOLT_TRY64(hipEventRecord(ev_d, ax.aux2));
+        VOLT_TRY64(hipEventRecord(ev_d, ax->aux[1]));
         VOLT_TRY64(hipStreamWaitEvent(s, ev_d, 0));
     }
     VOLT_LAUNCH_CHECK();

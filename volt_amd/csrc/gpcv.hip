@@ -370,26 +370,22 @@ struct GpcvWs {
 // the "exp" layout is a prefix of the "cv" one.
 static GpcvWs carve_gpcv(void* base, int B, int N, int want_dk, int Kc = 0) {
     const size_t Np = (size_t)volt_padded_n(N), n = Np / TS;
-    size_t off = al256(volt_mll_workspace_bytes(B, N, 1));
-    auto take = [&](size_t floats) {
-        float* p = base ? reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) : nullptr;
-        off += al256(floats * sizeof(float));
-        return p;
-    };
+    Carver c{base};
     GpcvWs w;
     w.mll = base;
-    w.LqT = take((size_t)B * Np * Np);
-    w.W = take((size_t)B * Np * Np);
-    w.Tt = take((size_t)B * Np * Np);
-    w.G = take((size_t)B * Np * Np);
-    w.P = want_dk ? take((size_t)B * Np * Np) : nullptr;
-    w.mllout = take((size_t)B * 8);
-    w.beta = take((size_t)B * N);
-    w.rowstat = take((size_t)B * N * 4);
-    w.frobT = take((size_t)B * n * n);
-    w.frobG = take((size_t)B * n * n);
-    w.cvpart = Kc > 0 ? take((size_t)B * ((N + 3) / 4) * 3 * Kc) : nullptr;
-    w.bytes = off;
+    c.skip(volt_mll_workspace_bytes(B, N, 1));
+    w.LqT = c.take<float>((size_t)B * Np * Np);
+    w.W = c.take<float>((size_t)B * Np * Np);
+    w.Tt = c.take<float>((size_t)B * Np * Np);
+    w.G = c.take<float>((size_t)B * Np * Np);
+    w.P = c.take<float>(want_dk ? (size_t)B * Np * Np : 0);
+    w.mllout = c.take<float>((size_t)B * 8);
+    w.beta = c.take<float>((size_t)B * N);
+    w.rowstat = c.take<float>((size_t)B * N * 4);
+    w.frobT = c.take<float>((size_t)B * n * n);
+    w.frobG = c.take<float>((size_t)B * n * n);
+    w.cvpart = c.take<float>(Kc > 0 ? (size_t)B * ((N + 3) / 4) * 3 * Kc : 0);
+    w.bytes = c.off;
     return w;
 }
 

@@ -253,24 +253,19 @@ struct GpcvBmWs {
 };
 
 static GpcvBmWs carve_gpcv_bm(void* base, int B, int N, int Kc) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        void* p = base ? reinterpret_cast<char*>(base) + off : nullptr;
-        off += al256(bytes);
-        return p;
-    };
+    Carver c{base};
     const size_t b = (size_t)B, n = (size_t)N;
     GpcvBmWs w;
-    w.bm = take(volt_bm_workspace_bytes(B, N, 1));
-    w.z = (double*)take(b * (n * (n + 1) / 2) * sizeof(double));
-    w.colv = (double*)take(3 * b * n * sizeof(double));
-    w.sig = (float*)take(b * sizeof(float));
-    w.mllout = (float*)take(b * 8 * sizeof(float));
-    w.beta = (float*)take(b * n * sizeof(float));
-    w.rowstat = (float*)take(b * n * 4 * sizeof(float));
-    w.frob = (float*)take(2 * b * sizeof(float));
-    w.cvpart = Kc > 0 ? (float*)take(b * ((n + 3) / 4) * 3 * (size_t)Kc * sizeof(float)) : nullptr;
-    w.bytes = off;
+    w.bm = c.region(volt_bm_workspace_bytes(B, N, 1)).p;
+    w.z = c.take<double>(b * (n * (n + 1) / 2));
+    w.colv = c.take<double>(3 * b * n);
+    w.sig = c.take<float>(b);
+    w.mllout = c.take<float>(b * 8);
+    w.beta = c.take<float>(b * n);
+    w.rowstat = c.take<float>(b * n * 4);
+    w.frob = c.take<float>(2 * b);
+    w.cvpart = c.take<float>(Kc > 0 ? b * ((n + 3) / 4) * 3 * (size_t)Kc : 0);
+    w.bytes = c.off;
     return w;
 }
 

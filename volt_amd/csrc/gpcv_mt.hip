@@ -475,41 +475,37 @@ struct MtWs {
 
 static MtWs carve_mt(void* base, int N, int T, int want_dk) {
     const size_t Np = (size_t)volt_padded_n(N), n = Np / TS;
-    size_t off = al256(volt_mll_workspace_bytes(1, N, 1));
-    auto take = [&](size_t floats) {
-        float* p = base ? reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) : nullptr;
-        off += al256(floats * sizeof(float));
-        return p;
-    };
+    Carver c{base};
     MtWs w;
     w.mll = base;
+    c.skip(volt_mll_workspace_bytes(1, N, 1));
     w.ngh = (N + GH_ROWS - 1) / GH_ROWS;
     w.nch = (N + RT_CH * RT_PASSES - 1) / (RT_CH * RT_PASSES);
-    w.LxT = take(Np * Np);
-    w.W = take(Np * Np);
-    w.Tt = take(Np * Np);
-    w.G = take(Np * Np);
-    w.P1 = want_dk ? take(Np * Np) : nullptr;
-    w.P2 = want_dk ? take(Np * Np) : nullptr;
-    w.Bm = want_dk ? take(Np * TS) : nullptr;
-    w.Rt = take(TS * Np);
-    w.V = take(TS * Np);
-    w.At = take(TS * Np);
-    w.mllout = take(8);
-    w.beta = take(N);
-    w.vx = take(N);
-    w.logd = take(N);
-    w.rowred = take(N);
-    w.gm = take((size_t)N * T);
-    w.colpart = take((size_t)w.ngh * T);
-    w.ellpart = take(w.ngh);
-    w.part = take((size_t)w.nch * (2 * (size_t)T * T + T));
-    w.frobT = take(n * n);
-    w.frobG = take(n * n);
-    w.kti = take((size_t)T * T);
-    w.cinv = take((size_t)T * T);
-    w.tsc = take(8);
-    w.bytes = off;
+    w.LxT = c.take<float>(Np * Np);
+    w.W = c.take<float>(Np * Np);
+    w.Tt = c.take<float>(Np * Np);
+    w.G = c.take<float>(Np * Np);
+    w.P1 = c.take<float>(want_dk ? Np * Np : 0);
+    w.P2 = c.take<float>(want_dk ? Np * Np : 0);
+    w.Bm = c.take<float>(want_dk ? Np * TS : 0);
+    w.Rt = c.take<float>(TS * Np);
+    w.V = c.take<float>(TS * Np);
+    w.At = c.take<float>(TS * Np);
+    w.mllout = c.take<float>(8);
+    w.beta = c.take<float>(N);
+    w.vx = c.take<float>(N);
+    w.logd = c.take<float>(N);
+    w.rowred = c.take<float>(N);
+    w.gm = c.take<float>((size_t)N * T);
+    w.colpart = c.take<float>((size_t)w.ngh * T);
+    w.ellpart = c.take<float>(w.ngh);
+    w.part = c.take<float>((size_t)w.nch * (2 * (size_t)T * T + T));
+    w.frobT = c.take<float>(n * n);
+    w.frobG = c.take<float>(n * n);
+    w.kti = c.take<float>((size_t)T * T);
+    w.cinv = c.take<float>((size_t)T * T);
+    w.tsc = c.take<float>(8);
+    w.bytes = c.off;
     return w;
 }
 

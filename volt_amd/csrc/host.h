@@ -9,7 +9,7 @@
 
 // Schedule parameters: compiled-in defaults (measured on MI355X).  A deployment reads NO environment:
 // only a process started with VOLT_TUNE=1 (the experiment scripts) may override them through the VOLT_* variables listed in
-// include/volt_hip_tune.h -- read ONCE, by read_env in chol.hip when tunables() is first called, nowhere else.
+// include/volt_hip_tune.h -- read ONCE, by read_env in runtime.hip when tunables() is first called, nowhere else.
 struct Tunables {
     int groups = 2;                  // stream groups of a large batch (2 >= 4 > 8 with one launch per block column)
     int splitk_target = 512, splitk_minl = 2, splitk_maxs = 8, splitk_groups = 2, splitk_maxb = 22;
@@ -47,7 +47,7 @@ struct Tunables {
     int f64_spread = 512;                      // launches of up to this many workgroups run one workgroup per CU
     int f64_split_target = 512;                // K-sliced launches aim at this many workgroups
 };
-const Tunables& tunables();                    // chol.hip: the table above after the environment (VOLT_TUNE=1 only) and the device's topology, made once per process
+const Tunables& tunables();                    // runtime.hip: the table above after the environment (VOLT_TUNE=1 only) and the device's topology, made once per process
 
 namespace volt {
 
@@ -103,6 +103,17 @@ struct Region {              // a state region of the caller's workspace
     void* p = nullptr;
     size_t bytes = 0;
 };
+struct Carver {              // walks the caller's workspace region by region; base == nullptr: the sizes alone (off, at the end, is the total)
+    void* base;
+    size_t off = 0;
+    template <typename T> T* take(size_t count) {
+        T* p = base && count ? reinterpret_cast<T*>(static_cast<char*>(base) + off) : nullptr;
+        off += al256(count * sizeof(T));
+        return p;
+    }
+    Region region(size_t bytes) { return Region{take<char>(bytes), bytes}; }
+    void skip(size_t bytes) { off += al256(bytes); }     // a workspace embedded at the front (the GPCV layouts begin with the MLL step's)
+};
 struct SplitScratch {        // scratch of the K-sliced / balanced launch-per-column schedules
     float* slab;
     int* count;
@@ -127,16 +138,21 @@ inline int begin_grid(int direct, int strided) {
 
 }  // namespace volt
 
-// ---- chol.hip: the launch-per-column schedules, the stream pool
+// ---- runtime.hip: the process-wide state -- tunables() above and the stream pool of the current device (nullptr: none).
+// chol.hip's stream groups and chol64.hip's look-ahead schedules run on it, under its mutex while they enqueue
+constexpr int MAX_GROUPS = 8;
+struct StreamPool {
+    hipStream_t aux[MAX_GROUPS - 1];
+    hipEvent_t fork, join[MAX_GROUPS - 1], extra[5];     // extra: chol64.hip's look-ahead schedules
+    std::mutex mu;
+    int want_groups = 2;                 // tunables().groups
+    bool ok = false;
+};
+StreamPool* stream_pool();
+// ---- chol.hip: the launch-per-column schedules
 // runs the factorisation group by group on the library's streams and calls `post` on each group's stream when that
 // group's factor (+ inverse) is enqueued, so the O(N^2) tail of one group overlaps the other groups' MFMA work
 typedef void (*volt_group_post_fn)(void* ctx, int b0, int Bg, hipStream_t s);
-struct VoltAux {             // chol64.hip runs its look-ahead on the pool: auxiliary streams, the fork event, twelve more, the enqueue mutex
-    hipStream_t aux, aux2, aux3, aux4;
-    hipEvent_t fork, ev[12];
-    std::mutex* mu;
-};
-bool volt_internal_aux(VoltAux* out);
 size_t volt_internal_sched_bytes(int B, int n);
 int volt_internal_sched_install(volt::Region tab, int B, int n, int has_y, int cap, void* stream);
 int volt_internal_factor(const volt::StepMats& m, const volt::KSource& src, const volt::TriReduce& red, const volt::SplitScratch& sk,

@@ -239,23 +239,18 @@ struct MllWs {
 
 static MllWs carve(void* base, int B, int N, int want_grad) {
     const size_t Np = (size_t)volt_padded_n(N), n = Np / TS;
-    size_t off = 0;
-    auto take = [&](size_t floats) {
-        float* p = base ? reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) : nullptr;
-        off += al256(floats * sizeof(float));
-        return p;
-    };
+    Carver c{base};
     MllWs w;
-    w.A = take((size_t)B * Np * Np);
-    w.Winv = take((size_t)B * n * TS * TS);
-    w.rpad = take((size_t)B * Np);
-    w.z = take((size_t)B * Np);
-    w.scratch = take((size_t)B * Np);
-    w.apad = take((size_t)B * Np);
+    w.A = c.take<float>((size_t)B * Np * Np);
+    w.Winv = c.take<float>((size_t)B * n * TS * TS);
+    w.rpad = c.take<float>((size_t)B * Np);
+    w.z = c.take<float>((size_t)B * Np);
+    w.scratch = c.take<float>((size_t)B * Np);
+    w.apad = c.take<float>((size_t)B * Np);
     if (want_grad) {
-        w.Y = take((size_t)B * Np * Np);
-        w.zpart = take((size_t)B * n * Np);
-        w.frob = take((size_t)B * (n * (n + 1) / 2));
+        w.Y = c.take<float>((size_t)B * Np * Np);
+        w.zpart = c.take<float>((size_t)B * n * Np);
+        w.frob = c.take<float>((size_t)B * (n * (n + 1) / 2));
     } else {
         w.Y = w.zpart = w.frob = nullptr;
     }
@@ -263,17 +258,16 @@ static MllWs carve(void* base, int B, int N, int want_grad) {
     // below 32 matrices; the forward-only step has no trtri rows to fill the late launches with, so it gets 128 rows up to
     // 64 matrices (two slices per tile at 64)
     w.sk.rows = B < 32 ? 64 : (!want_grad && B <= 64 ? 128 : 0);
-    w.sk.slab = w.sk.rows ? take((size_t)w.sk.rows * (n + 1) * TS * TS) : nullptr;
-    w.sk.count = w.sk.rows ? reinterpret_cast<int*>(take((size_t)(n + 1) * (n + 1) * B)) : nullptr;
-    auto region = [&](size_t bytes) { return Region{bytes ? take(bytes / sizeof(float)) : nullptr, bytes}; };
-    w.sk.tab = region(w.sk.rows ? volt_internal_sched_bytes(B, (int)n) : 0);
-    w.small = region(want_grad ? volt_internal_small_bytes(B, (int)n) : 0);
-    w.lng = region(want_grad ? volt_internal_long_bytes(B, (int)n) : 0);
-    w.eslab = w.lng.bytes ? take(volt_internal_long_slab_floats(B, (int)n)) : nullptr;
+    w.sk.slab = c.take<float>(w.sk.rows ? (size_t)w.sk.rows * (n + 1) * TS * TS : 0);
+    w.sk.count = c.take<int>(w.sk.rows ? (size_t)(n + 1) * (n + 1) * B : 0);
+    w.sk.tab = c.region(w.sk.rows ? volt_internal_sched_bytes(B, (int)n) : 0);
+    w.small = c.region(want_grad ? volt_internal_small_bytes(B, (int)n) : 0);
+    w.lng = c.region(want_grad ? volt_internal_long_bytes(B, (int)n) : 0);
+    w.eslab = c.take<float>(w.lng.bytes ? volt_internal_long_slab_floats(B, (int)n) : 0);
     const size_t batch_bytes = volt_internal_batch_bytes(B, (int)n, want_grad);
-    w.apart = (w.small.bytes || w.lng.bytes || (want_grad && batch_bytes)) ? take((size_t)B * n * Np) : nullptr;   // alpha's partial sums, per row of the inverse
-    w.batch = region(batch_bytes);
-    w.bytes = off;
+    w.apart = (w.small.bytes || w.lng.bytes || (want_grad && batch_bytes)) ? c.take<float>((size_t)B * n * Np) : nullptr;   // alpha's partial sums, per row of the inverse
+    w.batch = c.region(batch_bytes);
+    w.bytes = c.off;
     return w;
 }
 

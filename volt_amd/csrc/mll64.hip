@@ -110,24 +110,18 @@ struct Mll64Ws {
 };
 static Mll64Ws carve64(void* base, int B, int N, int want_grad) {
     const size_t Np = (size_t)volt_padded_n(N), n = Np / TS;
-    size_t off = 0;
-    auto take = [&](size_t doubles) {
-        double* p = base ? reinterpret_cast<double*>(reinterpret_cast<char*>(base) + off) : nullptr;
-        off += al256(doubles * sizeof(double));
-        return p;
-    };
+    Carver c{base};
     Mll64Ws w;
-    w.A = take((size_t)B * Np * Np);
-    w.Winv = take((size_t)B * n * TS * TS);
-    w.rpad = take((size_t)B * Np);
-    w.z = take((size_t)B * Np);
-    w.scratch = take((size_t)B * Np + 64);
-    w.apad = take((size_t)B * Np);
-    w.Y = want_grad ? take((size_t)B * Np * Np) : nullptr;
-    w.frob = want_grad ? take((size_t)B * n * (n + 1) / 2) : nullptr;
-    w.prog.bytes = volt_internal_batch64_bytes(B, (int)n, want_grad);
-    w.prog.p = w.prog.bytes ? take(w.prog.bytes / sizeof(double)) : nullptr;
-    w.bytes = off;
+    w.A = c.take<double>((size_t)B * Np * Np);
+    w.Winv = c.take<double>((size_t)B * n * TS * TS);
+    w.rpad = c.take<double>((size_t)B * Np);
+    w.z = c.take<double>((size_t)B * Np);
+    w.scratch = c.take<double>((size_t)B * Np + 64);
+    w.apad = c.take<double>((size_t)B * Np);
+    w.Y = c.take<double>(want_grad ? (size_t)B * Np * Np : 0);
+    w.frob = c.take<double>(want_grad ? (size_t)B * n * (n + 1) / 2 : 0);
+    w.prog = c.region(volt_internal_batch64_bytes(B, (int)n, want_grad));
+    w.bytes = c.off;
     return w;
 }
 

@@ -8,12 +8,10 @@
 #include "tiles.h"
 #include "host.h"
 #include "long_sched.h"
+#include "table_cache.h"
 #include "../../include/volt_hip.h"
 #include "../../include/volt_hip_tune.h"
 #include <algorithm>
-#include <array>
-#include <map>
-#include <mutex>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -1127,8 +1125,8 @@ int volt_internal_small_step(const StepMats& m, const KSource& src, const TriRed
 
 // ---- ONE long series in one launch (long_step_kernel, long_sched.h)
 struct LongPlanDev {
-    int4* items = nullptr;                     // pinned host
-    int nitems = 0, nslabs = 0, ncnt = 0, xcd_from = 0;
+    std::vector<int4> image;                   // the items, then n words of update info
+    int nitems = 0, nslabs = 0, ncnt = 0;
 };
 // blocks in the slice next to the tile (measured with the split spine, 1 x 1500 ... 1 x 4096: 3 wins up to 24 block columns
 // -- 1 x 2048 0.538 -> 0.527 ms --, 4 at 32 -- 1.235 -> 1.175)
@@ -1136,81 +1134,55 @@ static int long_first_for(int n) {
     const int f = tunables().long_first;
     return f > 0 ? f : (n <= 24 ? 3 : 4);
 }
-static const LongPlanDev* get_long_plan(int n, hipStream_t s) {
-    static std::mutex mu;
-    static std::map<std::array<int, 3>, LongPlanDev*> cache;
+// The plan for n block columns (table_cache.h): the workspace layout asks for its sizes on every step (no HIP call), the
+// install and the step for the table.
+using LongCache = TableCache<LongPlanDev, 3>;
+static LongCache& long_cache() {
+    static LongCache cache;
+    return cache;
+}
+static LongCache::Key long_key(int n) { return {n, long_first_for(n), tunables().long_emin}; }
+static void long_plan_build(LongPlanDev& pd, int n) {
     const Tunables& tn = tunables();
-    const int first = long_first_for(n);
-    const std::array<int, 3> key{n, first, tn.long_emin};
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return nullptr;
-    const LongPlan pl = long_build(n, first, tn.long_emin, tn.long_xcd != 0, tn.long_split != 0);
+    const LongPlan pl = long_build(n, long_first_for(n), tn.long_emin, tn.long_xcd != 0, tn.long_split != 0);
     static_assert(sizeof(LongItem) == sizeof(int4), "items are read as int4");
-    LongPlanDev* pd = new LongPlanDev;
-    pd->nitems = (int)pl.items.size();
-    pd->nslabs = pl.nslabs;
-    pd->ncnt = pl.ncnt;
-    pd->xcd_from = pl.xcd_from;
-    if (hipHostMalloc((void**)&pd->items, (pl.items.size() + n) * sizeof(int4), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        delete pd;
-        pd = nullptr;
-    } else {
-        memcpy(pd->items, pl.items.data(), pl.items.size() * sizeof(int4));
-        memcpy(pd->items + pl.items.size(), pl.uinfo.data(), (size_t)n * sizeof(int4));
-    }
-    cache[key] = pd;
-    return pd;
+    pd.nitems = (int)pl.items.size();
+    pd.nslabs = pl.nslabs;
+    pd.ncnt = pl.ncnt;
+    pd.image.resize(pl.items.size() + n);
+    memcpy(pd.image.data(), pl.items.data(), pl.items.size() * sizeof(int4));
+    memcpy(pd.image.data() + pl.items.size(), pl.uinfo.data(), (size_t)n * sizeof(int4));
+}
+static const LongPlanDev& long_plan(int n) {
+    return long_cache().plan(long_key(n), [n](LongPlanDev& pd) { long_plan_build(pd, n); });
+}
+static LongCache::Table get_long_plan(int n, hipStream_t s) {
+    return long_cache().table(long_key(n), s, [n](LongPlanDev& pd) { long_plan_build(pd, n); });
 }
 static bool long_applies(int B, int n) {
     const Tunables& tn = tunables();
     return tn.long_on && B == 1 && n > tn.long_nmin && n <= 32;     // (one series of 4 / 5 / 8 block columns: 0.133 / 0.168 / 0.257 ms here, 0.139 / 0.180 / 0.289 as a short series)
 }
 static size_t long_flag_ints(int n, int ncnt) { return (size_t)SMALL_HDR + (size_t)((4 + 11 * n + 2 * n * n + ncnt + 31) & ~31); }
-// sizes of the plan for n block columns (the workspace layout asks for them on every step: computed once)
-static void long_sizes(int n, size_t& items, int& nslabs, int& ncnt) {
-    static std::mutex mu;
-    static std::map<std::array<int, 3>, std::array<size_t, 3>> cache;
-    const Tunables& tn = tunables();
-    const int first = long_first_for(n);
-    const std::array<int, 3> key{n, first, tn.long_emin};
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(key);
-    if (it == cache.end()) {
-        const LongPlan pl = long_build(n, first, tn.long_emin, tn.long_xcd != 0, tn.long_split != 0);
-        it = cache.emplace(key, std::array<size_t, 3>{pl.items.size(), (size_t)pl.nslabs, (size_t)pl.ncnt}).first;
-    }
-    items = it->second[0];
-    nslabs = (int)it->second[1];
-    ncnt = (int)it->second[2];
-}
 size_t volt_internal_long_bytes(int B, int n) {
     if (!long_applies(B, n)) return 0;
-    size_t items;
-    int nslabs, ncnt;
-    long_sizes(n, items, nslabs, ncnt);
-    return al256(long_flag_ints(n, ncnt) * sizeof(int)) + al256((items + n) * sizeof(int4));
+    const LongPlanDev& pd = long_plan(n);
+    return al256(long_flag_ints(n, pd.ncnt) * sizeof(int)) + al256(pd.image.size() * sizeof(int4));
 }
 size_t volt_internal_long_slab_floats(int B, int n) {
     if (!long_applies(B, n)) return 0;
-    size_t items;
-    int nslabs, ncnt;
-    long_sizes(n, items, nslabs, ncnt);
-    return (size_t)nslabs * TS * TS;
+    return (size_t)long_plan(n).nslabs * TS * TS;
 }
 int volt_internal_long_install(Region state, int B, int n, void* stream) {
     if (!state.p || !long_applies(B, n) || state.bytes < volt_internal_long_bytes(B, n)) return 0;
-    const LongPlanDev* pd = get_long_plan(n, (hipStream_t)stream);
+    const LongCache::Table t = get_long_plan(n, (hipStream_t)stream);
+    const LongPlanDev* pd = t.plan;
     if (!pd) return 0;
     const int count = (int)long_flag_ints(n, pd->ncnt);
     hipLaunchKernelGGL(small_init_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, (int*)state.p, count, 1, n);
     VOLT_LAUNCH_CHECK();
     char* tab = reinterpret_cast<char*>(state.p) + al256((size_t)count * sizeof(int));
-    hipError_t e = hipMemcpyAsync(tab, pd->items, (size_t)(pd->nitems + n) * sizeof(int4), hipMemcpyHostToDevice, (hipStream_t)stream);
-    return e != hipSuccess ? (int)e : 0;
+    return install_table(tab, t.pinned, pd->image.size() * sizeof(int4), (hipStream_t)stream);
 }
 // 1: enqueued (one launch);  0: not applicable (launch-per-column path)
 int volt_internal_long_step(const StepMats& m, const KSource& src, const TriReduce& red, const StepTail& t, float* eslab,
@@ -1218,7 +1190,7 @@ int volt_internal_long_step(const StepMats& m, const KSource& src, const TriRedu
     const int Np = volt_padded_n(m.N), n = Np / TS;
     hipStream_t s = m.stream;
     if (!state.p || !m.Y || !t.apart || !eslab || !long_applies(m.B, n)) return 0;   // (state: only for a workspace declared initialised)
-    const LongPlanDev* pd = get_long_plan(n, s);
+    const LongPlanDev* pd = get_long_plan(n, s).plan;
     if (!pd) return 0;
     int* base = (int*)state.p;
     const size_t flag_bytes = al256(long_flag_ints(n, pd->ncnt) * sizeof(int));
