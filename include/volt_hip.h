@@ -374,6 +374,49 @@ int volt_kron_epilogue_f64(const double* raw_vol, const double* covar_factor, co
                            const double* out, const double* alpha, const double* state, double* res, int N, int T,
                            void* stream);
 
+/* The same step around the LINEAR-TIME chain solver (MultitaskBMGP(solver="linear"); no N x N matrix anywhere):
+ *     volt_kron_prologue_warm_*  ->  volt_bm_step_* (x, vol = 1 [T], sigma2 = 1 / kappa [T], resid = r [T,N]; B = T,
+ *                                    VOLT_WANT_GRAD)  ->  volt_kron_epilogue_ws_*
+ * Stream order is the only synchronisation between and inside the calls: no atomics, no hand-off words, no workgroup waits
+ * for another; every sum has a fixed order that does not depend on the device, results are bitwise repeatable, and the
+ * sequence replays from a hipGraph.  T <= 64, N >= 1, 64-bit indices, fp64 arithmetic, I/O in the step's dtype.
+ *
+ * volt_kron_prologue_warm_*: the prologue's arguments, outputs and `state` layout (volt_kron_state_bytes), in TWO launches:
+ * one workgroup decomposes S, then a grid over chunks of N writes resid.  The eigensolver starts from the Q the previous
+ * call left in `state` (A0 = Q' S Q, same rotation criterion and sweep cap; Q is re-orthonormalised by one Newton-Schulz
+ * step on entry, so it does not drift over a training run) when the stamp in the header's spare doubles says that Q is a
+ * converged, finite decomposition for this T, and cold -- bitwise what volt_kron_prologue_* computes -- otherwise:
+ *     state[1] = stamp (0: the next call starts cold; written by every call, cleared when the solve hit the sweep cap or
+ *                produced a non-finite value);  state[2] = 1 if THIS call started warm, else 0;  state[3..7] unused.
+ * The caller zeroes `state` once (or state[1]) before the first call; volt_kron_prologue_* does not touch state[1..7], so
+ * the two prologues may share a state.  info[0] = sweeps used (>= 0), or -1.  If the decomposition holds a non-finite value
+ * (NaN / inf in a parameter) sigma2 is NaN in every entry, so that the step reports all T directions in its info.
+ * Argument errors (before any launch, in the order of their numbers; those of volt_kron_prologue_*): -1 raw_vol,
+ * -2 covar_factor, -3 raw_var, -4 raw_task_noises, -5 raw_noise, -6 x, -7 Y NULL; -8 ldy < T; -9 resid, -10 sigma2, -11 state,
+ * -12 info NULL; -13 N < 1; -14 T out of range.
+ *
+ * volt_kron_epilogue_ws_*: the epilogue's arguments and result, with the reductions over N spread over workgroups: launch 1,
+ * one workgroup per slice of 256 columns of N (a compile-time constant), writes its partial sums (2 T^2 + T doubles) to
+ * `workspace`; launch 2, one workgroup, adds them in slice order and runs the epilogue's T x T algebra (one device function
+ * with volt_kron_epilogue_*).  workspace: volt_kron_epilogue_workspace_bytes(N, T) bytes (0 if N < 1 or T is out of range),
+ * 256-byte aligned, caller-owned, no initialisation.
+ * Argument errors (before any launch): -1 .. -11 the pointers raw_vol .. res in argument order; -12 workspace NULL or not
+ * 256-byte aligned; -13 N < 1; -14 T out of range. */
+int volt_kron_prologue_warm_f32(const float* raw_vol, const float* covar_factor, const float* raw_var,
+                                const float* raw_task_noises, const float* raw_noise, const float* x, const float* Y, int64_t ldy,
+                                float* resid, float* sigma2, double* state, int* info, int N, int T, void* stream);
+int volt_kron_prologue_warm_f64(const double* raw_vol, const double* covar_factor, const double* raw_var,
+                                const double* raw_task_noises, const double* raw_noise, const double* x, const double* Y,
+                                int64_t ldy, double* resid, double* sigma2, double* state, int* info, int N, int T, void* stream);
+size_t volt_kron_epilogue_workspace_bytes(int N, int T);
+int volt_kron_epilogue_ws_f32(const float* raw_vol, const float* covar_factor, const float* raw_var, const float* raw_task_noises,
+                              const float* raw_noise, const float* x, const float* resid, const float* out, const float* alpha,
+                              const double* state, float* res, void* workspace, int N, int T, void* stream);
+int volt_kron_epilogue_ws_f64(const double* raw_vol, const double* covar_factor, const double* raw_var,
+                              const double* raw_task_noises, const double* raw_noise, const double* x, const double* resid,
+                              const double* out, const double* alpha, const double* state, double* res, void* workspace, int N,
+                              int T, void* stream);
+
 /* ---- Path summaries  (voltron/option_utils.py:26-52 ECDF / Pricer; the weather calibration notebook's per-step ECDF, mean and
  * std) -- what every consumer of a rollout computes on the host after samples.cpu(), here on the device.
  * For every series g and horizon step h the S values samples[g*bs + s*ld + h] (ld >= H: any slice of the horizon is a view)

@@ -70,6 +70,11 @@ _SIGS = {
     "volt_kron_prologue_f64": (C.c_int, [_ptr] * 7 + [_i64] + [_ptr] * 4 + [_i32, _i32, _ptr]),
     "volt_kron_epilogue_f32": (C.c_int, [_ptr] * 11 + [_i32, _i32, _ptr]),
     "volt_kron_epilogue_f64": (C.c_int, [_ptr] * 11 + [_i32, _i32, _ptr]),
+    "volt_kron_prologue_warm_f32": (C.c_int, [_ptr] * 7 + [_i64] + [_ptr] * 4 + [_i32, _i32, _ptr]),
+    "volt_kron_prologue_warm_f64": (C.c_int, [_ptr] * 7 + [_i64] + [_ptr] * 4 + [_i32, _i32, _ptr]),
+    "volt_kron_epilogue_workspace_bytes": (_sz, [_i32, _i32]),
+    "volt_kron_epilogue_ws_f32": (C.c_int, [_ptr] * 12 + [_i32, _i32, _ptr]),
+    "volt_kron_epilogue_ws_f64": (C.c_int, [_ptr] * 12 + [_i32, _i32, _ptr]),
     "volt_path_summary_scratch_bytes": (_sz, [_i32, _i32, _i32]),
     "volt_path_summary_f32": (C.c_int, [_ptr, _i64, _i64, _i32, _i32, _i32, _i32, _ptr, _i32, _ptr, _ptr, _i32] + [_ptr] * 7
                               + [_sz, _ptr]),

@@ -24,7 +24,7 @@ from . import rollout_engine
 from .gp import NanError, NotPSDError, NumericalWarning
 from .distributed import shard_range
 from .rollout_utils import _posterior_draw
-from .train_utils import LearnGPCV, TrainVoltMagpieBatch, TrainVolModelBatch
+from .train_utils import LearnGPCV, TrainVoltMagpieBatch, TrainVolModelBatch, TrainVolModelMultitask
 
 _MODES = {"ewma": 0, "dewma": 1, "tewma": 2}
 _STANDARD = ("constant", "loglinear", "linear")
@@ -61,7 +61,7 @@ def _standard_mean_prediction(model, train_x, log_y, vol, test_x, pred_vol, z):
 
 
 def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator,
-                 graph, vol_solver="dense", gpcv_solver="dense", data_solver="dense", debug=None):
+                 graph, vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False, debug=None):
     """One window for the series in train_y [b, ntrain] (prices): GPCV -> data model -> vol forecasters -> rollouts,
     every stage for all b series at once.  Returns samples [b, S, H] on the device."""
     dev = train_y.device
@@ -74,9 +74,14 @@ def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_ite
     # by series on the rank that saw it): no collective in here
     model, lh, _ = TrainVoltMagpieBatch(train_x, train_y[:, 1:], vol, train_iters=data_iters, k=k, mean_func=mean,
                                         graph=graph, reduce_across_ranks=False, solver=data_solver)
-    vmod, vlh = TrainVolModelBatch(train_x, vol, train_iters=vol_iters, graph=graph, solver=vol_solver)
-    vmod.eval()
-    pred_vol = vmod(test_x).sample(torch.Size((nsample,))).exp().transpose(0, 1).contiguous().detach()   # [b,S,H]
+    if multitask_vol:      # the reference's own vol forecaster of the batched models: ONE Kronecker GP over the b log-vol paths
+        vmod, vlh = TrainVolModelMultitask(train_x, vol, train_iters=vol_iters, graph=graph, solver=vol_solver)
+        vmod.eval()
+        pred_vol = vmod(test_x).sample(torch.Size((nsample,))).exp().permute(2, 0, 1).contiguous().detach()   # [S,H,b] -> [b,S,H]
+    else:
+        vmod, vlh = TrainVolModelBatch(train_x, vol, train_iters=vol_iters, graph=graph, solver=vol_solver)
+        vmod.eval()
+        pred_vol = vmod(test_x).sample(torch.Size((nsample,))).exp().transpose(0, 1).contiguous().detach()   # [b,S,H]
     z = torch.randn(b, nsample, H, device=dev, generator=generator)
     latent = train_y.log().mean(-1) if theta is not None else None                       # rollout_utils.py:60-63
     if mean in _MODES:                                                                   # Rollouts, :110-112
@@ -104,7 +109,7 @@ def _window_summary(samples, series, last_day, spec):
 
 def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample, mean, k, gpcv_iters, vol_iters,
                       data_iters, theta, vol_fn, generator, save, path_fn, debug=None, graph=None, summary=None,
-                      keep_samples=True, vol_solver="dense", gpcv_solver="dense", data_solver="dense"):
+                      keep_samples=True, vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False):
     """One batched pass per window (series [B,T] prices; the window ending at index e trains on series[:, e-ntrain:e]).
     A numerical failure anywhere in the batched pass (NotPSDError / NanError after the jitter ladders) must not take the
     other series down with it: the window is then redone one series at a time, and a series that still fails gets NaN
@@ -121,7 +126,7 @@ def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample,
     summaries = []
     H = test_x.numel()
     args = (nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator, graph, vol_solver, gpcv_solver,
-            data_solver)
+            data_solver, multitask_vol)
     last = None
     for last_day in end_idxs:
         train_y = series[:, last_day - ntrain:last_day].float()                          # [B, ntrain] prices
@@ -158,7 +163,7 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
                                   ntrain=400, mean="ewma", save=False, k=300, ntimes=-1, vol_fn=None,
                                   vol_iters=None, par_dir="./saved-outputs/", generator=None, debug=None, graph=None,
                                   summary=None, keep_samples=True, vol_solver="dense", gpcv_solver="dense",
-                                  data_solver="dense"):
+                                  data_solver="dense", multitask_vol=False):
     """closes [B, T] prices for B tickers on a common calendar (device tensor).  Same window schedule,
     model name and file layout as GenerateStockPredictions (GenerateMultiMeanPreds.py:69-83,128); ``mean`` in
     ewma / dewma / tewma takes the Rollouts branch (:110-112), constant / loglinear / linear the "VOLT + standard
@@ -174,7 +179,10 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
     ``vol_solver``, ignored with a ``vol_fn``, and "dense" changes nothing.
     ``data_solver="linear"``: the data model's fit on the linear-time step over each series' integrated vol path
     (TrainVoltMagpieBatch(solver=...), csrc/bm.hip) -- no N x N matrix per series; independent of the other two, and "dense"
-    changes nothing."""
+    changes nothing.
+    ``multitask_vol=True``: the vol forecaster is ONE MultitaskBMGP over the tickers' log-vol paths (TrainVolModelMultitask;
+    T <= 64 tickers per rank) instead of a BM-GP per ticker, so the vol paths of a draw are correlated across tickers; with
+    ``vol_solver="linear"`` it runs on the linear-time Kronecker step."""
     if mean not in _MODES and mean not in _STANDARD:
         raise ValueError(f"unknown mean {mean!r}: one of {sorted(_MODES) + list(_STANDARD)}")
     dev = closes.device
@@ -196,19 +204,19 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
         return os.path.join(par_dir, tckr, model_name + date + ".pt")                    # :128
     return _forecast_windows(tickers, closes, end_idxs.tolist(), ntrain, train_x, test_x, nsample, mean, k,
                              train_iters, vol_iters, train_iters, None, vol_fn, generator, save, path_fn, debug, graph,
-                             summary, keep_samples, vol_solver, gpcv_solver, data_solver)
+                             summary, keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol)
 
 
 def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=400, n_test_times=10, nsample=1000, k=400,
                                  theta=0.01, gpcv_iters=200, vol_iters=500, data_iters=0, save=False, vol_fn=None,
                                  par_dir="./saved-outputs/", generator=None, graph=None, summary=None, keep_samples=True,
-                                 vol_solver="dense", gpcv_solver="dense", data_solver="dense"):
+                                 vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False):
     """The ``--kernel volt --mean ewma`` branch of experiments/weather/GPGenerator.py:20-112 for B stations at once:
     data [B,T] wind speeds (missing = -99 -> 0, then +1 as at :47,55), dt = 1/365 (:38-41), the schedule of test
     windows of :33-34, GPCV 200 / vol model 500 / data model 0 iterations (:64-67,89-92), EWMA(k=400) mean and
     mean-reverting rollouts with theta = 0.01 (:96-102), files ``stn<idx>/volt_ema<k>_theta<theta>_<last_day>.pt``
     (:103-106).  Stations shard across ranks like tickers.  Returns the last window's samples [B_local,S,H] (CPU).
-    ``summary`` / ``keep_samples`` / ``vol_solver`` / ``gpcv_solver`` / ``data_solver``: as for GenerateStockPredictionsBatch (the truth is the shifted series,
+    ``summary`` / ``keep_samples`` / ``vol_solver`` / ``gpcv_solver`` / ``data_solver`` / ``multitask_vol``: as for GenerateStockPredictionsBatch (the truth is the shifted series,
     data + 1)."""
     dev = data.device
     lo, hi = shard_range(len(stations))
@@ -225,4 +233,4 @@ def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=40
                             str(last_day) + ".pt")
     return _forecast_windows(stations, data, end_idxs, ntrain, train_x, test_x, nsample, "ewma", k, gpcv_iters,
                              vol_iters, data_iters, theta, vol_fn, generator, save, path_fn, None, graph, summary,
-                             keep_samples, vol_solver, gpcv_solver, data_solver)
+                             keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol)

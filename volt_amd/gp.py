@@ -421,10 +421,20 @@ class _KroneckerPrior:
     """Lazy prior covariance of MultitaskBMGP (training mode): K_x (x) K_t with K_x = vol * M, M = min(x_i, x_k) and
     K_t = F F' + diag(var) of ``covar_module`` (a MultitaskKernel over a BMKernel).  Element (n, t) of vec Y sits at n*T + t
     (gpytorch's interleaved order).  ExactMarginalLogLikelihood reads the raw parameters from it (the Kronecker step,
-    _KronMLL); the dense matrix is built only on request."""
+    _KronMLL); the dense matrix is built only on request.  ``M`` None (MultitaskBMGP(solver="linear")): M is never handed to
+    the step -- the MLL runs on the linear-time chain (ops.kron_bm_step) over the grid ``x`` -- and min(x, x') is formed only
+    when ``.evaluate()`` / ``.to_dense()`` (or ``.M`` itself) is asked for."""
 
-    def __init__(self, covar_module, x, M):
-        self.covar_module, self.x, self.M = covar_module, x, M
+    def __init__(self, covar_module, x, M=None):
+        self.covar_module, self.x, self._M = covar_module, x, M
+
+    @property
+    def linear(self):
+        return self._M is None
+
+    @property
+    def M(self):
+        return torch.minimum(self.x.unsqueeze(-1), self.x.unsqueeze(-2)) if self._M is None else self._M
 
     def evaluate(self):
         vol = self.covar_module.data_covar_module.vol.reshape(())
@@ -435,7 +445,7 @@ class _KroneckerPrior:
 
     @property
     def shape(self):
-        n = self.M.shape[-1] * self.covar_module.num_tasks
+        n = self.x.shape[-1] * self.covar_module.num_tasks
         return torch.Size((n, n))
 
 
@@ -814,7 +824,8 @@ class _ChainMLL(torch.autograd.Function):
 class _KronMLL(torch.autograd.Function):
     """mll = log N(vec Y; vec mu, K_x (x) K_t + I (x) D) / (N T) of MultitaskBMGP and its gradient wrt the five raw
     parameters, from ONE prologue -> batched step (B = T over the shared M) -> epilogue sequence (ops.kron_mll_step,
-    include/volt_hip.h).  No host read when the check is deferred, so the iteration captures into a hipGraph.
+    include/volt_hip.h; ``M`` None: ops.kron_bm_step, the same sequence around the linear-time chain step, which has no
+    internal error codes).  No host read when the check is deferred, so the iteration captures into a hipGraph.
     Unlike _ExactMLL there is no jitter ladder: gpytorch would add jitter to the NT x NT matrix, which this path never
     forms; a failed factorisation (each M + sigma_j^2 I has sigma_j^2 = 1 / (vol lambda_j) > 0) raises NotPSDError."""
 
@@ -822,8 +833,12 @@ class _KronMLL(torch.autograd.Function):
     def forward(ctx, raw_vol, covar_factor, raw_var, raw_task_noises, raw_noise, x, target, M, holder):
         params = (raw_vol, covar_factor, raw_var, raw_task_noises, raw_noise)
         n, T = target.shape
-        ws = holder.kron_workspace(n, T, M.device, M.dtype)
-        res, info, eig_info, _ = ops.kron_mll_step(params, x, target, M, ws)
+        if M is None:
+            ws = holder.kron_workspace(n, T, target.device, target.dtype, "linear")
+            res, info, eig_info, _ = ops.kron_bm_step(params, x, target, ws)
+        else:
+            ws = holder.kron_workspace(n, T, M.device, M.dtype)
+            res, info, eig_info, _ = ops.kron_mll_step(params, x, target, M, ws)
         eig_bad = eig_info.clamp(max=0)                       # sweeps used >= 0; -1: the eigensolver hit its sweep cap
         if deferred_checks.settle(info, eig_bad):
             nbad, ebad, internal = torch.stack([(info != 0).sum(), (eig_bad != 0).sum(),
@@ -867,8 +882,8 @@ class ExactMarginalLogLikelihood(Module):
     def bm_workspace(self, B, n, device, dtype=torch.float32):
         return ops.cached_workspace(self, "_bws", ops.BmWorkspace, B, n, device, dtype)
 
-    def kron_workspace(self, n, T, device, dtype=torch.float32):
-        return ops.cached_workspace(self, "_kws", ops.KronWorkspace, n, T, device, dtype)
+    def kron_workspace(self, n, T, device, dtype=torch.float32, solver="dense"):
+        return ops.cached_workspace(self, "_kws", ops.KronWorkspace, n, T, device, dtype, solver)
 
     def _add_log_priors(self, res, num_data):
         """gpytorch: + sum log p(theta) / num_data over the model's registered priors."""
@@ -883,14 +898,14 @@ class ExactMarginalLogLikelihood(Module):
         if tuple(target.shape) != tuple(function_dist.mean.shape):
             raise ValueError(f"ExactMarginalLogLikelihood: target {tuple(target.shape)} does not have the multitask mean's "
                              f"shape {tuple(function_dist.mean.shape)} ([N, T], the layout the model was built with)")
-        if not prior.M.is_cuda or not target.is_cuda:
+        if not prior.x.is_cuda or not target.is_cuda:
             raise ops._lib.VoltHipError("ExactMarginalLogLikelihood: tensors must live on the MI355X; no CPU fallback")
         task, data = prior.covar_module.task_covar_module, prior.covar_module.data_covar_module
         lh = self.likelihood
         params = (data.raw_vol, task.covar_factor, task.raw_var, lh.raw_task_noises, lh.raw_noise)
         f64 = any(t.dtype == torch.float64 for t in (prior.x, target, *params))
         dt = torch.float64 if f64 else torch.float32           # torch's promotion of the reference's own arithmetic
-        res = _KronMLL.apply(*params, prior.x, target.to(dt), prior.M.to(dt), self)
+        res = _KronMLL.apply(*params, prior.x, target.to(dt), None if prior.linear else prior.M.to(dt), self)
         return self._add_log_priors(res, target.numel())       # gpytorch: the MultitaskMultivariateNormal's event size
 
     def forward(self, function_dist, target):

@@ -5,7 +5,8 @@ SURVEY 8(f) row 1: it supplies ``pred_vol`` at voltron/rollout_utils.py:66 throu
 call -> exact-GP posterior at the test points, computed with the same HIP Cholesky / triangular
 inverse as the data model (K_s^-1 = Y Y^T, Y = L^-T), the products on the library's own MFMA GEMM (ops.gemm_nt).
 MultitaskBMGP (:30-56, botorch's KroneckerMultiTaskGP) is below: the vol forecaster of the batched models when they are
-built with ``multitask_vol=True``; its MLL runs on the Kronecker step (gp._KronMLL, csrc/kron.hip).
+built with ``multitask_vol=True``; its MLL runs on the Kronecker step (gp._KronMLL, csrc/kron.hip; ``solver="linear"``: around
+the linear-time chain step, csrc/kron_chain.hip).
 
 Addition: ``train_y`` [T,N] builds T independent vol models over shared inputs in one object (batched kernel
 parameter, noise and posterior) -- what the batched forecast driver trains instead of looping over tickers.
@@ -143,9 +144,23 @@ class MultitaskBMGP(ExactGP):
     Initial values: botorch builds (and the reference discards) modules of its own first, and those draw from the
     generator, so the reference's draws cannot be reproduced.  Here ``covar_factor = randn(T,1)`` then ``raw_var =
     randn(T)`` from torch's default generator, in that order; then, as in the reference (:38-40), ``covar_factor /= 10``
-    while ``task_covar_module.var.data /= 10.`` divides a computed temporary and changes nothing."""
+    while ``task_covar_module.var.data /= 10.`` divides a computed temporary and changes nothing.
 
-    def __init__(self, train_x, train_y, likelihood, base_mean=None, **kwargs):
+    ``solver="dense"`` (default): M = min(x, x') is filled once and every eigen-direction is an N x N dense step.
+    ``solver="linear"``: each direction's M + sigma_j^2 I is the tridiagonal chain of BMGP(solver="linear"), so the MLL step
+    (ops.kron_bm_step) and the posterior run in O(T N + T^2 N) with no N x N matrix anywhere; ``forward`` returns
+    the lazy prior over the training grid, which is validated ONCE here (one host read): 1-D, x_0 >= 0, strictly increasing."""
+    SOLVERS = BMGP.SOLVERS
+    _POST_CHUNK = BMGP._POST_CHUNK
+    _POST_SOLVE_ELEMS = 1 << 19               # directions x N x points per solve of the linear posterior (bounds its three buffers)
+
+    def __init__(self, train_x, train_y, likelihood, base_mean=None, solver="dense", **kwargs):
+        if solver not in self.SOLVERS:
+            raise ValueError(f"MultitaskBMGP: solver must be one of {self.SOLVERS}, got {solver!r}")
+        if solver == "linear":
+            if train_x.ndim != 1:
+                raise ValueError(f"MultitaskBMGP(solver='linear'): the grid must be 1-D [N], got shape {tuple(train_x.shape)}")
+            check_grid(train_x, "MultitaskBMGP(solver='linear')")
         super().__init__(train_x, train_y, likelihood)
         if train_y.ndim != 2:
             raise ValueError("MultitaskBMGP: train_y must be [N, T]")
@@ -153,8 +168,10 @@ class MultitaskBMGP(ExactGP):
         self.covar_module = MultitaskKernel(BMKernel(), num_tasks=train_y.shape[-1], **kwargs).to(train_x.device)
         self.covar_module.task_covar_module.var.data /= 10.              # a computed property: no effect (BMGP.py:39)
         self.covar_module.task_covar_module.covar_factor.data /= 10.
-        x = train_x.reshape(-1)
-        self._base = torch.minimum(x.unsqueeze(-1), x.unsqueeze(-2))      # M = min(x_i, x_k): K_x = vol M, filled once
+        self.solver = solver
+        if solver == "dense":
+            x = train_x.reshape(-1)
+            self._base = torch.minimum(x.unsqueeze(-1), x.unsqueeze(-2))  # M = min(x_i, x_k): K_x = vol M, filled once
         self._post_ws = None
 
     def mean_module(self, x):
@@ -165,18 +182,73 @@ class MultitaskBMGP(ExactGP):
 
     def forward(self, x):
         xs = x[..., 0] if x.ndim > 1 else x
+        if self.solver == "linear":
+            stored = self.train_inputs[0]
+            if not same_values(x, stored) and not (xs.shape == stored.shape[:1] and torch.equal(xs, stored[:, 0])):
+                raise ValueError("MultitaskBMGP(solver='linear'): the prior is over the training grid validated at construction")
+            return MultitaskMultivariateNormal(self.mean_module(xs), _KroneckerPrior(self.covar_module, stored[:, 0]))
         if same_values(x, self.train_inputs[0]):
             M = self._base
         else:
             M = torch.minimum(xs.unsqueeze(-1), xs.unsqueeze(-2))
         return MultitaskMultivariateNormal(self.mean_module(xs), _KroneckerPrior(self.covar_module, xs, M))
 
+    def _posterior_linear(self, x):
+        """`posterior_call` without any N x N matrix: the cold fp64 prologue as there; alpha_j from the linear-time step in
+        fp64; X_j = (M + sigma_j^2 I)^-1 M_x* from the linear-time solve; m~_j = sqrt(kappa_j) M_*x alpha_j and
+        C_j = kappa_j (M_** - M_*x X_j), the two products over N accumulated in fp64 over blocks of rows as
+        BMGP._posterior_linear does.  Returned in fp32, like the dense posterior."""
+        with torch.no_grad():
+            xt = self.train_inputs[0][:, 0]
+            Y = self.train_targets
+            n, T = Y.shape
+            xs = x[..., 0] if x.ndim > 1 else x
+            H = xs.shape[0]
+            dev = xt.device
+            if self._post_ws is None or not self._post_ws.fits(n, T, dev, torch.float64, "linear"):
+                self._post_ws = ops.KronWorkspace(n, T, dev, torch.float64, "linear")
+            ws = self._post_ws
+            task, data = self.covar_module.task_covar_module, self.covar_module.data_covar_module
+            params = (data.raw_vol, task.covar_factor, task.raw_var, self.likelihood.raw_task_noises, self.likelihood.raw_noise)
+            x64, xs64 = xt.double(), xs.double()
+            ops.kron_prologue(params, x64, Y, ws)
+            kap = ws.state[0] * ws.lam()                                                   # [T], fp64
+            _, alpha, info = ops.bm_step(x64, ws.ones, ws.sigma2, ws.resid, ws.bm, want_grad=True)
+            if int((info != 0).sum().item()):
+                if not all(bool(torch.isfinite(p).all()) for p in params) or not bool(torch.isfinite(Y).all()):
+                    raise NanError("MultitaskBMGP posterior: NaN / inf in the targets or the parameters")
+                raise NotPSDError("MultitaskBMGP posterior: M + sigma_j^2 I is not positive definite")
+            mt = torch.zeros(T, H, dtype=torch.float64, device=dev)
+            S = torch.zeros(T, H, H, dtype=torch.float64, device=dev)
+            m_sx = lambda lo, hi, h0=0, h1=H: torch.minimum(xs64[h0:h1].unsqueeze(-1), x64[lo:hi].unsqueeze(-2))   # M_*x block
+            for lo in range(0, n, self._POST_CHUNK):
+                mt += alpha[:, lo:lo + self._POST_CHUNK] @ m_sx(lo, lo + self._POST_CHUNK).t()
+            # the solve in groups of test points (at a large T, of directions too): its right-hand sides, X and workspace are
+            # each [directions, N, points] doubles, and a solve costs the length of the chain however many columns ride on it
+            jb = max(1, min(T, self._POST_SOLVE_ELEMS // n))
+            hb = max(1, min(H, self._POST_SOLVE_ELEMS // (n * jb)))
+            for j in range(0, T, jb):
+                for h in range(0, H, hb):
+                    rhs = m_sx(0, n, h, h + hb).t().unsqueeze(0).expand(min(jb, T - j), n, min(hb, H - h))
+                    X, _ = ops.bm_solve(x64, ws.ones[j:j + jb], ws.sigma2[j:j + jb], rhs)
+                    for lo in range(0, n, self._POST_CHUNK):
+                        S[j:j + jb, :, h:h + hb] += m_sx(lo, lo + self._POST_CHUNK).unsqueeze(0) @ X[:, lo:lo + self._POST_CHUNK]
+                    del X
+            mt = kap.sqrt().reshape(T, 1) * mt                                             # m~_j
+            Mss = torch.minimum(xs64.unsqueeze(-1), xs64.unsqueeze(-2))
+            C = (kap.reshape(T, 1, 1) * (Mss.unsqueeze(0) - S)).to(torch.float32)
+            V64 = ws.d().sqrt().unsqueeze(-1) * ws.Q()                                     # D^1/2 Q
+            mean = (self.mean_module(xs).double() + mt.t() @ V64.t()).to(torch.float32)
+            return MultitaskMultivariateNormal(mean, blocks=(V64.to(torch.float32), C))
+
     def posterior_call(self, x):
         """Exact latent posterior at x [H] (gpytorch's eval-mode ExactGP call): a MultitaskMultivariateNormal with mean [H,T].
         Block by block in the eigenbasis of the task covariance: the prologue (fp64) gives W, Lambda and
         r_j; then per block m~_j = sqrt(kappa_j) M_*x (M + sigma_j^2 I)^-1 r_j and C_j = kappa_j [M_** - M_*x (M +
         sigma_j^2 I)^-1 M_x*] on the HIP potrf / triangular inverse / GEMM, as BMGP.posterior_call does; finally
-        mean = mu_* + m~ V' and cov = (I (x) V) blockdiag(C_j) (I (x) V'), V = D^1/2 Q."""
+        mean = mu_* + m~ V' and cov = (I (x) V) blockdiag(C_j) (I (x) V'), V = D^1/2 Q.  solver="linear": _posterior_linear."""
+        if self.solver == "linear":
+            return self._posterior_linear(x)
         with torch.no_grad():
             xt = self.train_inputs[0][:, 0]
             Y = self.train_targets

@@ -36,18 +36,16 @@ class VolGP(ExactGP):
         # vol forecaster: one BM-GP per series by default.  (The reference's batched models use botorch's Kronecker multitask
         # GP there: MultitaskBMGP, opt-in with multitask_vol=True; the default batched BMGP -- T independent vol models over
         # the shared grid -- leaves out the cross-series correlation.)  ``vol_solver="linear"``: that BM-GP on the linear-time
-        # solver (BMGP(solver="linear"), csrc/bm.hip); MultitaskBMGP keeps its dense path.
+        # solver (BMGP(solver="linear"), csrc/bm.hip), and MultitaskBMGP on the linear-time Kronecker step (csrc/kron_chain.hip).
         if vol_solver not in BMGP.SOLVERS:
             raise ValueError(f"vol_solver must be one of {BMGP.SOLVERS}, got {vol_solver!r}")
         self.vol_solver = vol_solver          # Volt.Train refits the vol forecaster: with the solver the model was built with
-        if multitask_vol and vol_solver != "dense":
-            raise ValueError("vol_solver='linear' is for the per-series BMGP; MultitaskBMGP (multitask_vol=True) has the dense path only")
         if multitask_vol:
             if not len(batch_shape) or self.log_vol_path.shape[:-1] != batch_shape:
                 raise ValueError("multitask_vol=True needs a batched model with a [T,N] vol_path")
             self.vol_lh = MultitaskGaussianLikelihood(num_tasks=batch_shape[0]).to(dev)
             self.vol_lh.noise = 1e-3
-            self.vol_model = MultitaskBMGP(x, self.log_vol_path.t(), self.vol_lh)   # [N] inputs, [N,T] targets
+            self.vol_model = MultitaskBMGP(x, self.log_vol_path.t(), self.vol_lh, solver=vol_solver)   # [N] inputs, [N,T] targets
             return
         self.vol_lh = GaussianLikelihood(batch_shape=batch_shape).to(dev)
         self.vol_model = BMGP(x, self.log_vol_path, self.vol_lh, solver=vol_solver) if self.log_vol_path.shape[:-1] == batch_shape else None

@@ -674,25 +674,38 @@ def syev_small(S: torch.Tensor):
     return (lam[0], Q[0], info[0]) if two_d else (lam, Q, info)
 
 
+KRON_SOLVERS = ("dense", "linear")
+KRON_EPILOGUE_SLICE = 256           # include/volt_hip.h: columns of N per workgroup of volt_kron_epilogue_ws_*'s first launch
+
+
 class KronWorkspace:
     """Caller-owned buffers of one Kronecker MLL iteration of shape (N, T, dtype): the prologue's state (fp64: vol, Lambda,
     d, W, Q), the step's inputs (resid [T,N], sigma2 [T]) and workspace (B = T, with gradient), the eigensolver's info
-    and the epilogue's packed result res [3 + 3T]."""
+    and the epilogue's packed result res [3 + 3T].  ``solver="linear"`` (`kron_bm_step`): the step's workspace is a
+    BmWorkspace(T, N) instead of the MllWorkspace, beside it the step's ``ones`` [T] (its vol) and the scratch of the split
+    epilogue -- O(T N + T^2 N / 256) in all, never an N x N buffer."""
 
-    def __init__(self, N: int, T: int, device, dtype=torch.float32):
+    def __init__(self, N: int, T: int, device, dtype=torch.float32, solver: str = "dense"):
         _check_tasks(T)
-        self.N, self.T, self.dtype = N, T, dtype
+        if solver not in KRON_SOLVERS:
+            raise ValueError(f"KronWorkspace: solver must be one of {KRON_SOLVERS}, got {solver!r}")
+        self.N, self.T, self.dtype, self.solver = N, T, dtype, solver
         L = _lib.lib()
         self.state = torch.zeros(int(L.volt_kron_state_bytes(T)) // 8, dtype=torch.float64, device=device)
         self.resid = torch.empty(T, N, dtype=dtype, device=device)
         self.sigma2 = torch.empty(T, dtype=dtype, device=device)
         self.eig_info = torch.zeros(1, dtype=torch.int32, device=device)
         self.res = torch.empty(3 + 3 * T, dtype=dtype, device=device)
-        self.mll = MllWorkspace(T, N, True, device, dtype)
+        if solver == "linear":
+            self.bm = BmWorkspace(T, N, device, dtype)
+            self.ones = torch.ones(T, dtype=dtype, device=device)
+            self.epi_buf, self.epi_ptr = _scratch(int(L.volt_kron_epilogue_workspace_bytes(N, T)), device)
+        else:
+            self.mll = MllWorkspace(T, N, True, device, dtype)
         self._K = None
 
-    def fits(self, N, T, device, dtype=torch.float32):
-        return (self.N, self.T, self.state.device, self.dtype) == (N, T, device, dtype)
+    def fits(self, N, T, device, dtype=torch.float32, solver="dense"):
+        return (self.N, self.T, self.state.device, self.dtype, self.solver) == (N, T, device, dtype, solver)
 
     def shared_k(self, M: torch.Tensor) -> torch.Tensor:
         """M as the step's [T,N,N] operand: batch stride 0 (KRON_SHARED_K), or T copies made once per M."""
@@ -726,9 +739,10 @@ def _kron_params(params, dt):
     return out
 
 
-def kron_prologue(params, x: torch.Tensor, Y: torch.Tensor, ws: KronWorkspace):
+def kron_prologue(params, x: torch.Tensor, Y: torch.Tensor, ws: KronWorkspace, warm: bool = False):
     """volt_kron_prologue_*: params = (raw_vol [1], covar_factor [T,1], raw_var [T], raw_task_noises [T], raw_noise [1]),
-    x [N], Y [N,T] -> ws.resid, ws.sigma2, ws.state, ws.eig_info."""
+    x [N], Y [N,T] -> ws.resid, ws.sigma2, ws.state, ws.eig_info.  ``warm``: volt_kron_prologue_warm_* -- the same outputs in
+    two launches, the eigensolver started from the Q the previous call left in ws.state (cold on a fresh workspace)."""
     _need_gpu(x, Y, *params)
     dt = ws.dtype
     rv, cf, var, rtn, rn = _kron_params(params, dt)
@@ -739,7 +753,7 @@ def kron_prologue(params, x: torch.Tensor, Y: torch.Tensor, ws: KronWorkspace):
     N, T = ws.N, ws.T
     if tuple(Y.shape) != (N, T) or x.numel() != N or cf.numel() != T:
         raise ValueError(f"kron_prologue: x [N], Y [N,T] and covar_factor [T,1] must agree with the workspace (N={N}, T={T})")
-    fn = _lib.lib().volt_kron_prologue_f32 if dt == torch.float32 else _lib.lib().volt_kron_prologue_f64
+    fn = getattr(_lib.lib(), ("volt_kron_prologue_warm" if warm else "volt_kron_prologue") + ("_f32" if dt == torch.float32 else "_f64"))
     _lib.check(fn(rv.data_ptr(), cf.data_ptr(), var.data_ptr(), rtn.data_ptr(), rn.data_ptr(), x.data_ptr(), Y.data_ptr(),
                   Y.stride(0), ws.resid.data_ptr(), ws.sigma2.data_ptr(), ws.state.data_ptr(), ws.eig_info.data_ptr(), N, T,
                   _lib.stream_ptr()), "volt_kron_prologue")
@@ -768,6 +782,30 @@ def kron_mll_step(params, x: torch.Tensor, Y: torch.Tensor, M: torch.Tensor, ws:
     _lib.check(fn(rv.data_ptr(), cf.data_ptr(), var.data_ptr(), rtn.data_ptr(), rn.data_ptr(), xd.data_ptr(),
                   ws.resid.data_ptr(), out.data_ptr(), alpha.data_ptr(), ws.state.data_ptr(), ws.res.data_ptr(), N, T,
                   _lib.stream_ptr()), "volt_kron_epilogue")
+    return ws.res, info, ws.eig_info, ws
+
+
+def kron_bm_step(params, x: torch.Tensor, Y: torch.Tensor, ws: KronWorkspace | None = None):
+    """`kron_mll_step` without M, in O(T N + T^2 N): warm prologue -> the linear-time chain step (`bm_step` over the grid x
+    with vol = 1, sigma2 = 1 / kappa, B = T) -> the epilogue with its N-reductions spread over workgroups
+    (volt_kron_epilogue_ws_*).  x [N] must be a valid chain grid (x_0 >= 0, strictly increasing: gp.check_grid); the dtype is
+    Y's (fp32 or fp64).  Returns what `kron_mll_step` returns; ``ws`` is a KronWorkspace(solver="linear") and carries the
+    eigenvectors from one call to the next."""
+    _need_gpu(x, Y, *params)
+    dt = torch.float64 if Y.dtype == torch.float64 else torch.float32
+    N, T = Y.shape
+    _check_tasks(T)
+    if ws is None or not ws.fits(N, T, Y.device, dt, "linear"):
+        ws = KronWorkspace(N, T, Y.device, dt, "linear")
+    xd = x.reshape(-1).to(dt).contiguous()
+    with torch.cuda.device(Y.device):
+        kron_prologue(params, xd, Y, ws, warm=True)
+        out, alpha, info = bm_step(xd, ws.ones, ws.sigma2, ws.resid, ws.bm, want_grad=True)
+        rv, cf, var, rtn, rn = _kron_params(params, dt)
+        fn = _lib.lib().volt_kron_epilogue_ws_f32 if dt == torch.float32 else _lib.lib().volt_kron_epilogue_ws_f64
+        _lib.check(fn(rv.data_ptr(), cf.data_ptr(), var.data_ptr(), rtn.data_ptr(), rn.data_ptr(), xd.data_ptr(),
+                      ws.resid.data_ptr(), out.data_ptr(), alpha.data_ptr(), ws.state.data_ptr(), ws.res.data_ptr(), ws.epi_ptr,
+                      N, T, _lib.stream_ptr()), "volt_kron_epilogue_ws")
     return ws.res, info, ws.eig_info, ws
 
 

@@ -410,21 +410,23 @@ def TrainVolModelBatch(train_x, vol_path, train_iters=1000, printing=False, kern
     return vol_model, vol_lh
 
 
-def TrainVolModelMultitask(train_x, vol_path, train_iters=1000, printing=False, graph=None):
+def TrainVolModelMultitask(train_x, vol_path, train_iters=1000, printing=False, graph=None, solver="dense"):
     """The multitask vol forecaster of the batched models (MultitaskBMGP, voltron/models/BMGP.py:30-56) fitted to T vol
     paths: vol_path [T,N] -> (model, likelihood) with the model built as the reference's batched constructors build it
     (VoltMagpie.py:51-55: MultitaskGaussianLikelihood(T), noise = 1e-3, targets log(vol_path).t() [N,T]).  The reference
     has NO trainer for this model (its batched models are only ever built); this one is TrainVolModel's loop -- Adam at
     LR_VOL on every parameter, graph capture where it pays (`_auto_graph`), the deferred ``info`` checks -- over the
-    Kronecker MLL (gp._KronMLL: prologue -> batched step -> epilogue, no host synchronisation)."""
+    Kronecker MLL (gp._KronMLL: prologue -> batched step -> epilogue, no host synchronisation).  ``solver="linear"``: the same
+    sequence around the linear-time chain step (MultitaskBMGP(solver="linear")); the iteration is then launch-bound at every
+    N, so ``graph=None`` captures wherever capturing is possible."""
     from .gp import MultitaskGaussianLikelihood
     from .models import MultitaskBMGP
     T = vol_path.shape[0]
     vol_lh = MultitaskGaussianLikelihood(num_tasks=T).to(train_x.device)
     vol_lh.noise = 1e-3
     target = vol_path.log().t()
-    vol_model = MultitaskBMGP(train_x, target, vol_lh).to(train_x.device)
-    graph = _auto_graph(graph, vol_path)
+    vol_model = MultitaskBMGP(train_x, target, vol_lh, solver=solver).to(train_x.device)
+    graph = _auto_graph(graph, vol_path, launch_bound=solver == "linear")
     _fit_exact(vol_model, vol_lh, train_x, target, list(vol_model.parameters()), LR_VOL, train_iters, printing, graph,
                defer=not graph)
     return vol_model, vol_lh
