@@ -488,6 +488,24 @@ int volt_vk_step_f32(const float* V, int64_t bsv, const float* sigma2, const flo
                      float* alpha /*[B,N]*/, int* info, void* workspace, int B, int N, int flags, void* stream);
 int volt_vk_step_f64(const double* V, int64_t bsv, const double* sigma2, const double* resid, double* out /*[B,8]*/,
                      double* alpha /*[B,N]*/, int* info, void* workspace, int B, int N, int flags, void* stream);
+/* The conditioning of a FORECAST from that data model in O(N) (predict_solver="linear").  The reference factors the train block
+ * of the stacked kernel per sample and solves twice (voltron/rollout_utils.py:35-36, and :44 for the covariance); every
+ * appended point has the same cross-covariance with the train block, u = V (its last column), so all a forecast needs from
+ * the train block are scalars.  Per series, with A_b = V_b[min(i,k)] + jitter_b I:
+ *     out[b,0] = V'A^-1 V (rho),  out[b,1] = V'A^-1 r (tau),  out[b,2] = r'A^-1 r,  out[b,3] = logdet A
+ * -- the forward sweep of volt_vk_step_* with a second z chain over D V next to the one over D r:  rho = sum (z^V_i)^2 / d_i,
+ * tau = sum z^V_i z^r_i / d_i.  No backward sweep, no workspace.  V, bsv: as for volt_vk_step_*.  jitter [B] doubles, >= 0
+ * (a rung of the jitter ladder; 0 is legal: the forms are then V_{N-1}, r_{N-1}, ...) -- doubles for BOTH entries, as is
+ * `out` [B,4]: rho is subtracted from running sums of its own size to leave increments ~dx vol^2.  out[b,2] and out[b,3] are
+ * the r'A^-1 r and logdet volt_vk_step_* returns for sigma2 = jitter.
+ * info[b]: 0, or i + 1 for the first pivot d_i that is not a positive finite number (jitter = 0 and a flat step V_i = V_{i-1},
+ * a NaN in V); out[b,0..3] are then NaN.  One launch, fp64 arithmetic, no atomics, bitwise repeatable, replays from a
+ * hipGraph, 64-bit indices, nothing O(N^2).
+ * Argument errors: -1 V NULL; -2 bsv < 0 or 0 < bsv < N; -3 jitter, -4 resid, -5 out, -6 info NULL; -7 B < 1; -8 N < 1. */
+int volt_vk_forms_f32(const float* V, int64_t bsv, const double* jitter, const float* resid, double* out /*[B,4]*/, int* info,
+                      int B, int N, void* stream);
+int volt_vk_forms_f64(const double* V, int64_t bsv, const double* jitter, const double* resid, double* out /*[B,4]*/, int* info,
+                      int B, int N, void* stream);
 int volt_bm_solve_f32(const float* x, const float* vol, const float* sigma2, const float* R /*[B,N,H]*/,
                       float* X /*[B,N,H]*/, int* info, void* workspace, int B, int N, int H, void* stream);
 int volt_bm_solve_f64(const double* x, const double* vol, const double* sigma2, const double* R /*[B,N,H]*/,

@@ -24,6 +24,9 @@
 //                     V_{b,i-1} and forms delta in fp64.  Both arrays then travel in tiles of BM_VT = 32 steps (two rows per
 //                     load: the half-waves take neighbouring series), so that the two register prefetches together are as
 //                     deep as the one of the shared-grid kernel.  Chain, sums and the backward sweep are the same code.
+//   bm_forms_kernel   (volt_vk_forms_*, the forecast's conditioning: DESIGN 4.15) the VK forward sweep with a second z chain over
+//                     D V = delta next to the one over D r, on the same pivots and the same staged tiles: V'A^-1 V, V'A^-1 r,
+//                     r'A^-1 r and logdet A in doubles.  No workspace, no backward sweep; the "noise" is a jitter rung, 0 allowed.
 //   bm_factor_kernel  the d chain alone, 1/d_i -> workspace (the solve's factorisation, once per series).
 //   bm_solve_kernel   one lane per (series, right-hand side): R [B,N,H] with H contiguous, so the lanes of a series load and
 //                     store whole rows.  Forward z -> workspace, backward X = D'w.  Its chains are one FMA per step.
@@ -253,6 +256,99 @@ __global__ __launch_bounds__(BM_T) void bm_step_kernel(BmStepParams<T> p) {
 }
 
 template <typename T>
+struct BmFormsParams {
+    const T *V, *resid;                    // V: the per-series grids [B,N] with batch stride bsv (0: one grid for all)
+    const double* jitter;                  // [B], >= 0
+    double* out;                           // [B,4]
+    int* info;
+    int64_t B, N, bsv;
+};
+
+// The conditioning scalars of a forecast from the volatility-kernel data model (volt_vk_forms_*): per series, with
+// A = V[min(i,k)] + j I, the forms V'A^-1 V, V'A^-1 r, r'A^-1 r and logdet A.  The forward sweep of the VK step with TWO z
+// chains on the one pivot chain -- z^V over D V = delta, z^r over D r -- and nothing else: no workspace, no backward sweep.
+// j = 0 is legal (c_i = 0, d_i = delta_i: the forms are then V_{N-1}, r_{N-1}, sum (D r)_i^2 / delta_i, sum log delta_i).
+template <typename T>
+__global__ __launch_bounds__(BM_T) void bm_forms_kernel(BmFormsParams<T> p) {
+    constexpr int TS = BM_VT;
+    __shared__ double tile[BM_T * BM_LD];                               // resid [series][step]
+    __shared__ double gl[BM_T * BM_VLD];                                // V [series][step]
+    const int lane = threadIdx.x;
+    const int64_t N = p.N, B = p.B;
+    const int64_t b0 = (int64_t)blockIdx.x * BM_T;
+    const int nb = (int)(B - b0 < BM_T ? B - b0 : BM_T);
+    const bool act = lane < nb;
+    const int64_t b = b0 + lane;
+    const double s = act ? p.jitter[b] : 1.0;
+    const double ss = s * s, s2 = 2.0 * s;
+
+    T pre[TS], pg[TS];
+    auto fetch = [&](int64_t i0) {
+        bm_fetch_rows<T, TS>(p.resid, N, b0, nb, i0, N, pre);
+        bm_fetch_rows<T, TS>(p.V, p.bsv, b0, nb, i0, N, pg);
+    };
+    fetch(0);
+    double inv_prev = 0.0, zr = 0.0, zv = 0.0, rprev = 0.0, gprev = 0.0, rho = 0.0, tau = 0.0, quad = 0.0, P = 1.0;
+    int64_t E = 0;
+    int info = 0;
+    for (int64_t i0 = 0; i0 < N; i0 += TS) {
+        bm_commit_rows<T, TS>(tile, BM_LD, nb, pre);
+        bm_commit_rows<T, TS>(gl, BM_VLD, nb, pg);
+        __syncthreads();
+        if (i0 + TS < N) fetch(i0 + TS);                                       // in flight while this tile's chains run
+        const int cnt = (int)(N - i0 < TS ? N - i0 : TS);
+        int e = 0;
+        for (int j0 = 0; j0 < cnt; j0 += BM_FB) {                              // (as bm_step_kernel: stale steps are discarded by selects)
+            double rr[BM_FB], dd[BM_FB];
+#pragma unroll
+            for (int u = 0; u < BM_FB; ++u) {
+                rr[u] = tile[lane * BM_LD + j0 + u];
+                dd[u] = gl[lane * BM_VLD + j0 + u];
+            }
+#pragma unroll
+            for (int u = 0; u < BM_FB; ++u) {                                  // delta_i = V_i - V_{i-1} (V_{-1} = 0), exact in fp64
+                const double g = dd[u];
+                dd[u] = g - gprev;
+                gprev = j0 + u < cnt ? g : gprev;
+            }
+#pragma unroll
+            for (int u = 0; u < BM_FB; ++u) {
+                const int64_t i = i0 + j0 + u;
+                const bool on = j0 + u < cnt;
+                const double d = __builtin_fma(-ss, inv_prev, dd[u] + (i == 0 ? s : s2));
+                const double c = s * inv_prev;
+                const double inv = bm_rcp(d);
+                const double a = __builtin_fma(c, zv, dd[u]);                  // z^V_i = delta_i + c_i z^V_{i-1}
+                const double z = __builtin_fma(c, zr, rr[u] - rprev);          // z^r_i = (r_i - r_{i-1}) + c_i z^r_{i-1}
+                rho = on ? __builtin_fma(a * a, inv, rho) : rho;
+                tau = on ? __builtin_fma(a * z, inv, tau) : tau;
+                quad = on ? __builtin_fma(z * z, inv, quad) : quad;
+                P = on ? P * __builtin_amdgcn_frexp_mant(d) : P;
+                e += on ? __builtin_amdgcn_frexp_exp(d) : 0;
+                if (on && !bm_pivot_ok(d) && info == 0) info = (int)(i + 1 < 0x7fffffff ? i + 1 : 0x7fffffff);
+                inv_prev = on ? inv : inv_prev;
+                zv = on ? a : zv;
+                zr = on ? z : zr;
+                rprev = on ? rr[u] : rprev;
+            }
+        }
+        e += __builtin_amdgcn_frexp_exp(P);
+        P = __builtin_amdgcn_frexp_mant(P);
+        E += e;
+        __syncthreads();
+    }
+    if (act) {
+        const double nan = __builtin_nan("");
+        double* o = p.out + b * 4;
+        o[0] = info ? nan : rho;
+        o[1] = info ? nan : tau;
+        o[2] = info ? nan : quad;
+        o[3] = info ? nan : log(P) + (double)E * BM_LN2;
+        p.info[b] = info;
+    }
+}
+
+template <typename T>
 struct BmSolveParams {
     const T *x, *vol, *sigma2, *R;
     T* X;
@@ -419,6 +515,23 @@ int vk_step(const T* V, int64_t bsv, const T* sigma2, const T* resid, T* out, T*
     return 0;
 }
 
+// V'A^-1 V, V'A^-1 r, r'A^-1 r and logdet A for A_b = V_b[min(i,k)] + jitter_b I: the forward sweep alone, doubles out
+template <typename T>
+int vk_forms(const T* V, int64_t bsv, const double* jitter, const T* resid, double* out, int* info, int B, int N, void* stream) {
+    if (!V) return -1;
+    if (bsv < 0 || (bsv > 0 && bsv < N)) return -2;
+    if (!jitter) return -3;
+    if (!resid) return -4;
+    if (!out) return -5;
+    if (!info) return -6;
+    if (B < 1) return -7;
+    if (N < 1) return -8;
+    BmFormsParams<T> p{V, resid, jitter, out, info, B, N, bsv};
+    hipLaunchKernelGGL((bm_forms_kernel<T>), dim3((unsigned)((B + BM_T - 1) / BM_T)), dim3(BM_T), 0, (hipStream_t)stream, p);
+    VOLT_LAUNCH_CHECK();
+    return 0;
+}
+
 template <typename T>
 int bm_solve(const T* x, const T* vol, const T* sigma2, const T* R, T* X, int* info, void* workspace, int B, int N, int H,
              void* stream) {
@@ -469,6 +582,14 @@ int volt_vk_step_f32(const float* V, int64_t bsv, const float* sigma2, const flo
 int volt_vk_step_f64(const double* V, int64_t bsv, const double* sigma2, const double* resid, double* out, double* alpha,
                      int* info, void* workspace, int B, int N, int flags, void* stream) {
     return volt::vk_step<double>(V, bsv, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
+}
+int volt_vk_forms_f32(const float* V, int64_t bsv, const double* jitter, const float* resid, double* out, int* info, int B,
+                      int N, void* stream) {
+    return volt::vk_forms<float>(V, bsv, jitter, resid, out, info, B, N, stream);
+}
+int volt_vk_forms_f64(const double* V, int64_t bsv, const double* jitter, const double* resid, double* out, int* info, int B,
+                      int N, void* stream) {
+    return volt::vk_forms<double>(V, bsv, jitter, resid, out, info, B, N, stream);
 }
 int volt_bm_solve_f32(const float* x, const float* vol, const float* sigma2, const float* R, float* X, int* info,
                       void* workspace, int B, int N, int H, void* stream) {

@@ -23,7 +23,7 @@ import torch
 from . import rollout_engine
 from .gp import NanError, NotPSDError, NumericalWarning
 from .distributed import shard_range
-from .rollout_utils import _posterior_draw
+from .rollout_utils import _linear_draw, _posterior_draw, _resolve_solver
 from .train_utils import LearnGPCV, TrainVoltMagpieBatch, TrainVolModelBatch, TrainVolModelMultitask
 
 _MODES = {"ewma": 0, "dewma": 1, "tewma": 2}
@@ -40,17 +40,51 @@ def realised_vol(train_x, prices, span=20, floor=1e-3):
     return v.clamp_min(floor)
 
 
-def _standard_mean_prediction(model, train_x, log_y, vol, test_x, pred_vol, z):
+def _standard_mean_prediction_linear(train_x, resid, m_te, vol, test_x, pred_vol, z, jitter=1e-4, max_blocks=4096):
+    """`_standard_mean_prediction` with solver="linear" (DESIGN 4.15): the train blocks of all B series are conditioned on by
+    ONE volt_vk_forms_* launch (gp._safe_forms) instead of B x S factorisations, and nothing is N x N or N x H.  The stacked
+    integrated path of rollout_utils.py:17-26 splits at the last train point: its train part U [B,N] keeps the full weight
+    on point N-1 (the halved last weight sits on the last test point), and what the H appended points add on top of U[N-1] is
+    the CumTrapz of [vol_{N-1}, pred_vol] less its first entry -- both from ops.cumtrapz in fp64.  The H x H predictive
+    blocks of ``max_blocks`` (series, path) pairs at a time go through `_linear_draw`."""
+    from . import ops
+    from .gp import _safe_forms
+    B, S, H = pred_vol.shape
+    N = train_x.numel()
+    f64 = torch.float64
+    x64 = torch.cat((train_x, test_x)).to(f64)
+    U = ops.cumtrapz(torch.cat((vol, vol[:, -1:]), -1).to(f64), x64[:N + 1], square=True)[:, :N]      # [B,N]
+    forms, _ = _safe_forms(U, resid.to(f64), jitter)                                                   # one launch, B series
+    tail = ops.cumtrapz(torch.cat((vol[:, -1:, None].expand(B, S, 1), pred_vol), -1).to(f64), x64[:H + 1], square=True)
+    V_last = U[:, -1]
+    V_te = V_last[:, None, None] + (tail[..., 1:] - tail[..., :1])                                     # [B,S,H]
+    out = torch.empty(B, S, H, device=train_x.device)
+    step = max(1, max_blocks // S)
+    for b0 in range(0, B, step):
+        sl = slice(b0, min(B, b0 + step))
+        nb = sl.stop - sl.start
+        rep = lambda t: t[sl].repeat_interleave(S)
+        draw = _linear_draw(rep(forms[:, 0]), rep(forms[:, 1]), rep(V_last), V_te[sl].reshape(nb * S, H),
+                            m_te[sl, None, :, None].expand(nb, S, H, 1).reshape(nb * S, H, 1), z[sl].reshape(nb * S, H, 1),
+                            jitter, None, 0.5, torch.float32)
+        out[sl] = draw.reshape(nb, S, H)
+    return out
+
+
+def _standard_mean_prediction(model, train_x, log_y, vol, test_x, pred_vol, z, solver="dense"):
     """"VOLT + standard mean" (GenerateMultiMeanPreds.py:113-119): ONE joint draw over the whole horizon per path,
     GeneratePrediction(train_x, train_y, test_x, predvol, voltron) with predvol [S,H] -- rollout_utils.py:6-53 -- for
     every series of the batched model in turn (each is its own GP; the S systems of a series run batched on the
-    device exactly as in the per-series function).  pred_vol, z [B,S,H] -> samples [B,S,H]."""
+    device exactly as in the per-series function).  pred_vol, z [B,S,H] -> samples [B,S,H].
+    ``solver="linear"``: `_standard_mean_prediction_linear`."""
     B, S, H = pred_vol.shape
     N = train_x.numel()
     full_x = torch.cat((train_x, test_x))
     with torch.no_grad():
         m_tr = model.mean_module(train_x.unsqueeze(-1)).reshape(B, N)
         m_te = model.mean_module(test_x.unsqueeze(-1)).reshape(B, H)
+    if _resolve_solver(solver) == "linear":
+        return _standard_mean_prediction_linear(train_x, log_y - m_tr, m_te, vol, test_x, pred_vol, z)
     out = torch.empty(B, S, H, device=train_x.device)
     for b in range(B):
         full_vol = torch.cat((vol[b].unsqueeze(0).expand(S, N), pred_vol[b]), -1)        # :17-20
@@ -61,11 +95,13 @@ def _standard_mean_prediction(model, train_x, log_y, vol, test_x, pred_vol, z):
 
 
 def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator,
-                 graph, vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False, debug=None):
+                 graph, vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False,
+                 predict_solver="dense", debug=None):
     """One window for the series in train_y [b, ntrain] (prices): GPCV -> data model -> vol forecasters -> rollouts,
     every stage for all b series at once.  Returns samples [b, S, H] on the device."""
     dev = train_y.device
     b, H = train_y.shape[0], test_x.numel()
+    predict_solver = _resolve_solver(predict_solver)
     if vol_fn is None:
         vol = LearnGPCV(train_x, train_y, train_iters=gpcv_iters, graph=graph, solver=gpcv_solver)   # all series at once
     else:
@@ -86,10 +122,11 @@ def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_ite
     latent = train_y.log().mean(-1) if theta is not None else None                       # rollout_utils.py:60-63
     if mean in _MODES:                                                                   # Rollouts, :110-112
         samples, info = rollout_engine.rollout_series(train_x, train_y[:, 1:].log(), vol.log(), test_x, pred_vol, z,
-                                                      _MODES[mean], k, latent_mean=latent, theta=theta)
+                                                      _MODES[mean], k, latent_mean=latent, theta=theta,
+                                                      solve="chain" if predict_solver == "linear" else "factor")
         rollout_engine.report_info(info)                # raises where psd_safe_cholesky(pred_cov) would have (:46), warns on a jittered pivot
     else:                                                                                # VOLT + standard mean, :113-119
-        samples = _standard_mean_prediction(model, train_x, train_y[:, 1:].log(), vol, test_x, pred_vol, z)
+        samples = _standard_mean_prediction(model, train_x, train_y[:, 1:].log(), vol, test_x, pred_vol, z, predict_solver)
     if debug is not None:
         debug.update(vol=vol, pred_vol=pred_vol, z=z, model=model, train_y=train_y)
     return samples.detach()                                                              # .detach(): :118
@@ -109,7 +146,8 @@ def _window_summary(samples, series, last_day, spec):
 
 def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample, mean, k, gpcv_iters, vol_iters,
                       data_iters, theta, vol_fn, generator, save, path_fn, debug=None, graph=None, summary=None,
-                      keep_samples=True, vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False):
+                      keep_samples=True, vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False,
+                      predict_solver="dense"):
     """One batched pass per window (series [B,T] prices; the window ending at index e trains on series[:, e-ntrain:e]).
     A numerical failure anywhere in the batched pass (NotPSDError / NanError after the jitter ladders) must not take the
     other series down with it: the window is then redone one series at a time, and a series that still fails gets NaN
@@ -126,7 +164,7 @@ def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample,
     summaries = []
     H = test_x.numel()
     args = (nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator, graph, vol_solver, gpcv_solver,
-            data_solver, multitask_vol)
+            data_solver, multitask_vol, predict_solver)
     last = None
     for last_day in end_idxs:
         train_y = series[:, last_day - ntrain:last_day].float()                          # [B, ntrain] prices
@@ -163,7 +201,7 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
                                   ntrain=400, mean="ewma", save=False, k=300, ntimes=-1, vol_fn=None,
                                   vol_iters=None, par_dir="./saved-outputs/", generator=None, debug=None, graph=None,
                                   summary=None, keep_samples=True, vol_solver="dense", gpcv_solver="dense",
-                                  data_solver="dense", multitask_vol=False):
+                                  data_solver="dense", multitask_vol=False, predict_solver="dense"):
     """closes [B, T] prices for B tickers on a common calendar (device tensor).  Same window schedule,
     model name and file layout as GenerateStockPredictions (GenerateMultiMeanPreds.py:69-83,128); ``mean`` in
     ewma / dewma / tewma takes the Rollouts branch (:110-112), constant / loglinear / linear the "VOLT + standard
@@ -182,7 +220,11 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
     changes nothing.
     ``multitask_vol=True``: the vol forecaster is ONE MultitaskBMGP over the tickers' log-vol paths (TrainVolModelMultitask;
     T <= 64 tickers per rank) instead of a BM-GP per ticker, so the vol paths of a draw are correlated across tickers; with
-    ``vol_solver="linear"`` it runs on the linear-time Kronecker step."""
+    ``vol_solver="linear"`` it runs on the linear-time Kronecker step.
+    ``predict_solver="linear"``: the forecast conditions on each series' train block through the O(N) chain (volt_vk_forms_*,
+    DESIGN 4.15) -- solve="chain" on the Rollouts branch, one launch for all tickers on the standard-mean branch -- instead
+    of filling and factoring an N x N block per series (per path, on the standard-mean branch); independent of the other
+    three, and "dense" changes nothing."""
     if mean not in _MODES and mean not in _STANDARD:
         raise ValueError(f"unknown mean {mean!r}: one of {sorted(_MODES) + list(_STANDARD)}")
     dev = closes.device
@@ -204,19 +246,20 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
         return os.path.join(par_dir, tckr, model_name + date + ".pt")                    # :128
     return _forecast_windows(tickers, closes, end_idxs.tolist(), ntrain, train_x, test_x, nsample, mean, k,
                              train_iters, vol_iters, train_iters, None, vol_fn, generator, save, path_fn, debug, graph,
-                             summary, keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol)
+                             summary, keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol, predict_solver)
 
 
 def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=400, n_test_times=10, nsample=1000, k=400,
                                  theta=0.01, gpcv_iters=200, vol_iters=500, data_iters=0, save=False, vol_fn=None,
                                  par_dir="./saved-outputs/", generator=None, graph=None, summary=None, keep_samples=True,
-                                 vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False):
+                                 vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False,
+                                 predict_solver="dense"):
     """The ``--kernel volt --mean ewma`` branch of experiments/weather/GPGenerator.py:20-112 for B stations at once:
     data [B,T] wind speeds (missing = -99 -> 0, then +1 as at :47,55), dt = 1/365 (:38-41), the schedule of test
     windows of :33-34, GPCV 200 / vol model 500 / data model 0 iterations (:64-67,89-92), EWMA(k=400) mean and
     mean-reverting rollouts with theta = 0.01 (:96-102), files ``stn<idx>/volt_ema<k>_theta<theta>_<last_day>.pt``
     (:103-106).  Stations shard across ranks like tickers.  Returns the last window's samples [B_local,S,H] (CPU).
-    ``summary`` / ``keep_samples`` / ``vol_solver`` / ``gpcv_solver`` / ``data_solver`` / ``multitask_vol``: as for GenerateStockPredictionsBatch (the truth is the shifted series,
+    ``summary`` / ``keep_samples`` / ``vol_solver`` / ``gpcv_solver`` / ``data_solver`` / ``multitask_vol`` / ``predict_solver``: as for GenerateStockPredictionsBatch (the truth is the shifted series,
     data + 1)."""
     dev = data.device
     lo, hi = shard_range(len(stations))
@@ -233,4 +276,4 @@ def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=40
                             str(last_day) + ".pt")
     return _forecast_windows(stations, data, end_idxs, ntrain, train_x, test_x, nsample, "ewma", k, gpcv_iters,
                              vol_iters, data_iters, theta, vol_fn, generator, save, path_fn, None, graph, summary,
-                             keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol)
+                             keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol, predict_solver)

@@ -999,4 +999,25 @@ def _safe_factor(A, jitter=None, max_tries=3):
     raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitter_new:.1e}.")
 
 
+def _safe_forms(V, resid, jitter=None, max_tries=3):
+    """`_safe_factor`'s retry policy around ops.vk_forms: the conditioning scalars of the train block A = V[min(i,j)] + j I that
+    the dense route gets from a factorisation, in O(N).  Plain first (j = 0), then jitter * 10^i for the whole batch; the
+    default rung is 1e-6 for fp32 input and 1e-8 for fp64 input.  V [N] or [G,N], resid [G,N].  Returns
+    (out [G,4] fp64 = V'A^-1 V, V'A^-1 r, r'A^-1 r, logdet A; the jitter used)."""
+    out, info = ops.vk_forms(V, 0.0, resid)
+    if not bool((info != 0).any().item()):
+        return out, 0.0
+    if torch.isnan(V).any():
+        raise NanError(f"cholesky_cpu: {int(torch.isnan(V).sum())} of {V.numel()} elements of the {tuple(V.shape)} tensor are NaN.")
+    if jitter is None:
+        jitter = 1e-6 if resid.dtype != torch.float64 else 1e-8
+    for i in range(max_tries):
+        jitter_new = jitter * (10 ** i)
+        out, info = ops.vk_forms(V, jitter_new, resid)
+        if not bool((info != 0).any().item()):
+            warnings.warn(f"A not p.d., added jitter of {jitter_new:.1e} to the diagonal", NumericalWarning)
+            return out, jitter_new
+    raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitter_new:.1e}.")
+
+
 LOG_2PI = math.log(2 * math.pi)

@@ -12,14 +12,22 @@ from .BMGP import BMGP, MultitaskBMGP
 
 
 class VolGP(ExactGP):
-    def _init_vol_state(self, x, y, vol_path, multitask_vol=False, vol_solver="dense", data_solver="dense"):
+    def _init_vol_state(self, x, y, vol_path, multitask_vol=False, vol_solver="dense", data_solver="dense",
+                        predict_solver="dense"):
         """x [N], y [N] or [T,N] (batched layout: one shared input grid, T target / vol rows), vol_path like y or None.
         Call after ``mean_module`` is set so that the modules register in the reference's order.  ``multitask_vol`` (batched
         models only): the reference's own vol forecaster, a MultitaskBMGP over the [N,T] log-vol paths with a
         MultitaskGaussianLikelihood(T) at noise 1e-3 (VoltMagpie.py:51-55) -- the T forecasts are then jointly drawn and
         correlated; without it T independent BM-GPs (the batched BMGP).  ``data_solver="linear"``: ``train_cov`` is the lazy
         _VolPrior over V = CumTrapz(vol^2, x) instead of the N x N fill, and the MLL of the training inputs runs on the linear-time
-        step (gp._ChainMLL, csrc/bm.hip); the default "dense" is the filled matrix and the dense step."""
+        step (gp._ChainMLL, csrc/bm.hip); the default "dense" is the filled matrix and the dense step.
+        ``predict_solver="linear"``: GeneratePrediction / SamplePrediction / MeanPrediction, rollout_utils.GeneratePrediction
+        and Rollouts condition on the train block through the O(N) chain (volt_vk_forms_*) instead of filling
+        and factoring it; independent of ``data_solver`` (a dense-trained model may predict linearly), and "dense" changes
+        nothing."""
+        if predict_solver not in BMGP.SOLVERS:
+            raise ValueError(f"predict_solver must be one of {BMGP.SOLVERS}, got {predict_solver!r}")
+        self.predict_solver = predict_solver
         if data_solver not in BMGP.SOLVERS:
             raise ValueError(f"data_solver must be one of {BMGP.SOLVERS}, got {data_solver!r}")
         self.data_solver = data_solver        # Volt.Train fits the data model with the solver the model was built with

@@ -351,6 +351,13 @@ def vk_step(V: torch.Tensor, sigma2: torch.Tensor, resid: torch.Tensor, ws: BmWo
     if resid.ndim != 2:
         raise ValueError("resid must be [B,N]")
     B, n = resid.shape
+    V, bsv = _vk_grid(V, B, n, dt)
+    sigma2 = sigma2.to(dt).reshape(-1).expand(B).contiguous()
+    return _chain_step("volt_vk_step", (V.data_ptr(), bsv), sigma2, resid, dt, ws, want_grad)
+
+
+def _vk_grid(V, B, n, dt):
+    """V [N] or [B,N] as volt_vk_* take it: (V in ``dt`` with unit inner stride and rows that do not overlap, bsv)."""
     if V.ndim not in (1, 2) or V.shape[-1] != n:
         raise ValueError("V must be [N] or [B,N] with resid's N")
     if V.ndim == 2 and V.shape[0] != B:
@@ -358,9 +365,29 @@ def vk_step(V: torch.Tensor, sigma2: torch.Tensor, resid: torch.Tensor, ws: BmWo
     V = V.to(dt)
     if V.stride(-1) != 1 or (V.ndim == 2 and B > 1 and V.stride(0) < n):
         V = V.contiguous()
-    bsv = 0 if V.ndim == 1 or B == 1 else V.stride(0)
-    sigma2 = sigma2.to(dt).reshape(-1).expand(B).contiguous()
-    return _chain_step("volt_vk_step", (V.data_ptr(), bsv), sigma2, resid, dt, ws, want_grad)
+    return V, (0 if V.ndim == 1 or B == 1 else V.stride(0))
+
+
+def vk_forms(V: torch.Tensor, jitter, resid: torch.Tensor):
+    """The conditioning scalars of a forecast from the volatility-kernel data model in O(N) (volt_vk_forms_f32 / _f64 by
+    resid's dtype; the arithmetic and the outputs are fp64 either way): per series, with A_b = V_b[min(i, j)] + jitter_b I,
+    out[b] = (V'A^-1 V, V'A^-1 r, r'A^-1 r, logdet A).  V [N] or [B,N] (strided rows allowed) as for `vk_step`; jitter a
+    number or [B], >= 0 (0 is legal); resid [B,N].  Returns (out [B,4] fp64, info [B] int32), freshly allocated."""
+    _need_gpu(V, resid, jitter if torch.is_tensor(jitter) else None)
+    dt = torch.float64 if resid.dtype == torch.float64 else torch.float32
+    if resid.ndim != 2:
+        raise ValueError("resid must be [B,N]")
+    B, n = resid.shape
+    V, bsv = _vk_grid(V, B, n, dt)
+    resid = resid.to(dt).contiguous()
+    jit = torch.as_tensor(jitter, dtype=torch.float64, device=resid.device).reshape(-1).expand(B).contiguous()
+    out = torch.empty(B, 4, dtype=torch.float64, device=resid.device)
+    info = torch.empty(B, dtype=torch.int32, device=resid.device)
+    fn = _lib.lib().volt_vk_forms_f32 if dt == torch.float32 else _lib.lib().volt_vk_forms_f64
+    with torch.cuda.device(resid.device):
+        _lib.check(fn(V.data_ptr(), bsv, jit.data_ptr(), resid.data_ptr(), out.data_ptr(), info.data_ptr(), B, n,
+                      _lib.stream_ptr()), "volt_vk_forms")
+    return out, info
 
 
 def _chain_step(entry, grid_args, sigma2, resid, dt, ws, want_grad):

@@ -13,7 +13,7 @@ import warnings
 import torch
 
 from . import _lib, ops
-from .gp import NotPSDError, NumericalWarning, _safe_factor, _dense as _dense_cov
+from .gp import NotPSDError, NumericalWarning, _safe_factor, _safe_forms, _dense as _dense_cov
 from .means import DEWMAMean, EWMAMean, MeanRevertingEMAMean, TEWMAMean
 
 _MODES = {EWMAMean: 0, DEWMAMean: 1, TEWMAMean: 2, MeanRevertingEMAMean: 3}
@@ -71,10 +71,16 @@ def train_block_terms(U, r_tr, solve="factor", jitter=1e-4):
     factor the train block, two solves) -- in fp64 on volt_potrf_f64 / volt_trsv_*_f64, because the noise-free block has
     condition number 1e6 (N = 400) .. 1e8 (N = 4096) and an fp32 factor cannot carry it.  The closed form is one of the
     min-structure identities SURVEY 4 reserves for testing: it stays available (and the tests hold the two against each
-    other), but the product path no longer leans on it."""
+    other), but the product path no longer leans on it.
+    solve="chain" takes the same general jittered route in O(N) per series, with no N x N block: gp._safe_forms, the ladder
+    of `_safe_factor` around volt_vk_forms_* (csrc/bm.hip; fp64 arithmetic on U as stored, one launch for all G series).  It
+    is what a model with predict_solver="linear" runs."""
     U64 = U.double()
     if solve == "closed":
         return U64[:, -1].contiguous(), r_tr[:, -1].double().contiguous()
+    if solve == "chain":
+        out, _ = _safe_forms(U, r_tr, jitter)
+        return out[:, 0].contiguous(), out[:, 1].contiguous()
     if solve != "factor":
         raise ValueError(f"unknown train-block solve {solve!r}")
     fct, _ = _safe_factor(ops.fill(U64), jitter)                 # psd_safe_cholesky(K_tr, 1e-4), :35, in fp64
@@ -177,10 +183,11 @@ def _depends_on_x_alone(mm):
     return isinstance(mm, (ConstantMean, LinearMean))
 
 
-def rollouts_bordered(train_x, train_y, test_x, model, pred_vol, z, latent_mean, theta):
+def rollouts_bordered(train_x, train_y, test_x, model, pred_vol, z, latent_mean, theta, solve="factor"):
     """Rollouts(..., engine="bordered"): same inputs / outputs / model mutation as rollout_utils.Rollouts.  Returns None
     for a mean module this engine has no mode for (neither the EWMA family nor a function of x alone): the caller then
-    runs the dense engine, which takes any mean module -- as it does for horizons beyond MAX_H."""
+    runs the dense engine, which takes any mean module -- as it does for horizons beyond MAX_H.  ``solve``: how the train
+    block is conditioned on (train_block_terms; "chain" when the solver resolves to "linear")."""
     mm = model.mean_module
     given = None
     if type(mm) not in _MODES:
@@ -201,7 +208,7 @@ def rollouts_bordered(train_x, train_y, test_x, model, pred_vol, z, latent_mean,
         kw = dict(given_mean=given)
     samples, info = rollout_series(train_x, log_y.unsqueeze(0), model.log_vol_path.unsqueeze(0), test_x,
                                    pred_vol.unsqueeze(0), z.unsqueeze(0), MODE_GIVEN if given is not None else _MODES[type(mm)],
-                                   1 if given is not None else mm.k, latent_mean, theta, **kw)
+                                   1 if given is not None else mm.k, latent_mean, theta, solve=solve, **kw)
     report_info(info[0])
     samples = samples[0]
     # leave the model in the state the reference leaves it in (rollout_utils.py:80-86, last idx = H-1)

@@ -15,6 +15,8 @@ Two engines compute the same conditional:
 
 Extra keyword-only arguments (``pred_vol``, ``z``, ``engine``) let tests inject the vol-path
 sample and the N(0,1) draws the reference takes from ``model.vol_model`` and ``torch.randn``.
+``solver="linear"`` (or a model built with ``predict_solver="linear"``) conditions on the train block in
+O(N) instead: `_posterior_draw_linear`, ``train_block_terms(solve="chain")`` -- DESIGN 4.15.
 """
 from __future__ import annotations
 
@@ -77,9 +79,85 @@ def _posterior_draw(covar_module, full_x, full_vol, idx_cut, train_diffs, test_m
     return ops.gemm_nt(fc.L, z.mT.contiguous(), uplo_a=1).to(dt) + pred_mean               # :48,:53
 
 
-def GeneratePrediction(train_x, train_y, test_x, pred_vol, model, latent_mean=None, theta=0.5, *, z=None):
+SOLVERS = ("dense", "linear")
+
+
+def _resolve_solver(solver, model=None):
+    """``solver=None`` reads the model's ``predict_solver`` ("dense" for a model without one)."""
+    if solver is None:
+        solver = getattr(model, "predict_solver", "dense")
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    return solver
+
+
+def _rows_shared(t):
+    """Whether the rows of t [S,n] are one row (an expanded view, or equal values: one device read)."""
+    return t.shape[0] == 1 or t.stride(0) == 0 or bool((t == t[:1]).all())
+
+
+def _linear_draw(rho, tau, V_last, V_te, test_mean_term, z, jitter, latent_mean, theta, dt):
+    """The draw from the conditional whose train block enters through rho = u'A^-1 u and tau = u'A^-1 r (fp64, [G] each with
+    G = S or 1) -- every appended point has the same cross-covariance u = V with the train block, so
+        mean_t = tau + m(x_t),     cov_st = V_te[min(s,t)] - rho = (V_te[min(s,t)] - V_last) + (V_last - rho),
+    the sum of the test increments plus what the jitter rung leaves of the last train entry, in fp64 (the two terms of the
+    second bracket agree to rounding at rung 0).  V_te [S,T] fp64, z [S,T,n].  Returns samples + pred_mean [S,T,n] in ``dt``."""
+    f64 = torch.float64
+    S, T = V_te.shape
+    pred_mean = tau.reshape(-1, 1, 1) + test_mean_term.to(f64)                            # [S,T,1] (or broadcastable)
+    if latent_mean is not None:
+        pred_mean = pred_mean - theta * (pred_mean - torch.as_tensor(latent_mean, device=V_te.device).to(f64))
+    W = (V_te - V_last.reshape(-1, 1)) + (V_last - rho).reshape(-1, 1)                  # [S,T]: the diagonal of the T x T block
+    if T == 1:
+        pred_cov_L = _chol_1x1(W.reshape(S, 1, 1), jitter)
+        return (pred_cov_L * z.to(f64) + pred_mean).to(dt)
+    idx = torch.arange(T, device=V_te.device)
+    pred_cov = W[:, torch.minimum(idx[:, None], idx[None, :])]                           # [S,T,T]
+    fc, _ = _safe_factor(pred_cov.to(dt), jitter)
+    noise = ops.gemm_nt(fc.L.to(torch.float32), z.to(torch.float32).mT.contiguous(), uplo_a=1)
+    return (noise.to(f64) + pred_mean).to(dt)
+
+
+def _posterior_draw_linear(covar_module, full_x, full_vol, idx_cut, train_diffs, test_mean_term, z, jitter,
+                           latent_mean=None, theta=0.5):
+    """`_posterior_draw` without any N x N or N x T array (solver="linear"): same arguments, same result to
+    rounding.  The stacked integrated path V comes from ops.cumtrapz in fp64; its first N entries are the train block
+    K = V[min(i,j)] (they do not depend on the test vols: CumTrapz's halved last weight sits on the last test point), and the
+    train block enters only through the two scalars of gp._safe_forms (volt_vk_forms_*, one O(N) sweep per grid, the
+    project's jitter ladder around it).  One grid serves all S samples when their train rows are shared; per-sample histories
+    (the dense Rollouts engine after its first step) run as S grids in one launch."""
+    from .gp import _safe_forms
+    from .kernels import VolatilityKernel
+    if not isinstance(covar_module, VolatilityKernel):
+        raise TypeError("solver='linear' conditions on the volatility kernel's min structure; "
+                        f"got {type(covar_module).__name__} (use solver='dense')")
+    f64 = torch.float64
+    dt = torch.float64 if full_vol.dtype == torch.float64 else torch.float32
+    N = idx_cut
+    vol = full_vol.reshape(-1, full_vol.shape[-1])
+    x = full_x.reshape(-1, full_x.shape[-1])
+    S, T = vol.shape[0], vol.shape[-1] - N
+    td = train_diffs.reshape(-1, N) if train_diffs.ndim > 1 else train_diffs.reshape(1, N)
+    one_x = _rows_shared(x)
+    V = ops.cumtrapz(vol.to(f64), (x[0] if one_x else x).to(f64), square=True)             # [S,N+T]
+    G = 1 if one_x and _rows_shared(vol[:, :N]) and _rows_shared(td) else S              # grids: one for all samples, or one each
+    out, _ = _safe_forms(V[:G, :N], td.to(f64).expand(S, N)[:G], _ladder_start(jitter, dt))
+    return _linear_draw(out[:, 0], out[:, 1], V[:, N - 1], V[:, N:], test_mean_term, z, jitter, latent_mean, theta, dt)
+
+
+def _ladder_start(jitter, dt):
+    """The first rung of the train block's jitter ladder: the caller's, or `_safe_factor`'s default for the input dtype (the
+    linear route computes in fp64 whatever the input, so the default goes by what came in)."""
+    if jitter is not None:
+        return jitter
+    return 1e-8 if dt == torch.float64 else 1e-6
+
+
+def GeneratePrediction(train_x, train_y, test_x, pred_vol, model, latent_mean=None, theta=0.5, *, z=None, solver=None):
     """voltron/rollout_utils.py:6-53.  Reads model.{log_vol_path, train_x, train_y, mean_module,
-    covar_module}; returns [S, T] (T = test_x.shape[0])."""
+    covar_module}; returns [S, T] (T = test_x.shape[0]).  ``solver``: "dense" (the reference's route) or "linear"
+    (`_posterior_draw_linear`, no N x N array); None reads ``model.predict_solver``."""
+    draw = _posterior_draw_linear if _resolve_solver(solver, model) == "linear" else _posterior_draw
     vol = model.log_vol_path.exp()
     if model.train_x.ndim != test_x.ndim:
         test_x_for_stack = test_x.unsqueeze(0).repeat(model.train_x.shape[0], 1)
@@ -99,14 +177,15 @@ def GeneratePrediction(train_x, train_y, test_x, pred_vol, model, latent_mean=No
     S, T = full_vol.shape[0], test_x.shape[0]
     if z is None:
         z = torch.randn(S, T, 1).to(test_x.device)                                         # :47
-    out = _posterior_draw(model.covar_module, full_x, full_vol, idx_cut, train_diffs, test_mean_term,
-                          z.reshape(S, T, 1), 1e-4, latent_mean, theta)
+    out = draw(model.covar_module, full_x, full_vol, idx_cut, train_diffs, test_mean_term,
+               z.reshape(S, T, 1), 1e-4, latent_mean, theta)
     return out.squeeze(-1)
 
 
 def _model_generate_prediction(model, test_x, pred_vol, n_sample=1):
     """The model-method twins, VoltronGP.py:62-95 / VoltMagpie.py:67-99 (default jitter, n_sample
-    draws per test point, mean from model.train_inputs)."""
+    draws per test point, mean from model.train_inputs).  A model built with ``predict_solver="linear"`` conditions through
+    `_posterior_draw_linear`."""
     if model.train_x.ndim != test_x.ndim:
         test_x_for_stack = test_x.unsqueeze(0).repeat(model.train_x.shape[0], 1)
     else:
@@ -121,8 +200,8 @@ def _model_generate_prediction(model, test_x, pred_vol, n_sample=1):
     T = test_x.shape[0]
     z = torch.randn(*batch, T, n_sample).to(test_x.device)
     S = 1 if len(batch) == 0 else batch[0]
-    out = _posterior_draw(model.covar_module, full_x, full_vol, idx_cut, train_diffs, test_mean_term,
-                          z.reshape(S, T, n_sample), None)
+    draw = _posterior_draw_linear if _resolve_solver(None, model) == "linear" else _posterior_draw
+    out = draw(model.covar_module, full_x, full_vol, idx_cut, train_diffs, test_mean_term, z.reshape(S, T, n_sample), None)
     out = out.reshape(*batch, T, n_sample)
     return out.squeeze(-1)                                  # (samples + pred_mean).squeeze(-1), VoltMagpie.py:96-99: [T] for n_sample = 1
 
@@ -133,11 +212,15 @@ def rollout_engine_max_h():
 
 
 def Rollouts(train_x, train_y, test_x, model, nsample=50, method="volt", theta=None, *, pred_vol=None, z=None,
-             engine=None):
+             engine=None, solver=None):
     """voltron/rollout_utils.py:57-93.  train_x [N], train_y [N+1] raw prices, test_x [H] ->
-    samples [nsample, H] on the CPU (log-price units).  Mutates ``model`` like the reference."""
+    samples [nsample, H] on the CPU (log-price units).  Mutates ``model`` like the reference.
+    ``solver``: "dense" or "linear" (None: ``model.predict_solver``) -- with "linear" the bordered engine conditions on the
+    train block through the O(N) chain (train_block_terms(solve="chain")) and the dense engine draws every step with
+    `_posterior_draw_linear`; no N x N array either way."""
     if method != "volt":
         return nonvol_rollouts(train_x, train_y, test_x, model, nsample=nsample)
+    solver = _resolve_solver(solver, model)
     engine = engine or os.environ.get("VOLT_ROLLOUT_ENGINE", "bordered")
     if theta is None:
         latent_mean = None
@@ -153,7 +236,8 @@ def Rollouts(train_x, train_y, test_x, model, nsample=50, method="volt", theta=N
         engine = "dense"                         # the bordered kernel holds <= 1024 appended points per sample
     if engine == "bordered":
         from .rollout_engine import rollouts_bordered
-        out = rollouts_bordered(train_x, train_y, test_x, model, pred_vol, z, latent_mean, theta)
+        out = rollouts_bordered(train_x, train_y, test_x, model, pred_vol, z, latent_mean, theta,
+                                solve="chain" if solver == "linear" else "factor")
         if out is not None:
             return out
         engine = "dense"                         # a mean module the bordered kernel has no mode for: the general route
@@ -163,7 +247,8 @@ def Rollouts(train_x, train_y, test_x, model, nsample=50, method="volt", theta=N
     samples = torch.zeros(nsample, ntest)                                                  # on the CPU, :65
     th = 0.5 if theta is None else theta
     samples[:, 0] = GeneratePrediction(train_x, train_y, test_x[0].unsqueeze(0), pred_vol[:, 0].unsqueeze(1),
-                                       model, latent_mean, th, z=None if z is None else z[:, 0:1]).squeeze().cpu()
+                                       model, latent_mean, th, z=None if z is None else z[:, 0:1],
+                                       solver=solver).squeeze().cpu()
     train_stack_y = train_y[1:].log().repeat(nsample, 1)
     train_stack_vol = model.log_vol_path.repeat(nsample, 1)
 
@@ -178,7 +263,7 @@ def Rollouts(train_x, train_y, test_x, model, nsample=50, method="volt", theta=N
         model.log_vol_path = stack_vol
         samples[:, idx] = GeneratePrediction(train_x, train_y, test_x[idx].unsqueeze(0),
                                              pred_vol[:, idx].unsqueeze(-1), model, latent_mean, th,
-                                             z=None if z is None else z[:, idx:idx + 1]).squeeze().cpu()
+                                             z=None if z is None else z[:, idx:idx + 1], solver=solver).squeeze().cpu()
     return samples
 
 
