@@ -506,6 +506,24 @@ int volt_vk_forms_f32(const float* V, int64_t bsv, const double* jitter, const f
                       int B, int N, void* stream);
 int volt_vk_forms_f64(const double* V, int64_t bsv, const double* jitter, const double* resid, double* out /*[B,4]*/, int* info,
                       int B, int N, void* stream);
+/* The POSTERIOR of the Brownian-motion vol forecaster at H test points in O(N H) time and O(H) memory (BMGP / MultitaskBMGP
+ * with posterior="sweep").  For a test point xi >= 0 the cross-covariance column k = v min(x, xi) has the first difference
+ * (D k)_i = v clamp(xi - x_{i-1}, 0, delta_i), so its chain z(xi) is formed on the fly; over xs [H] sorted ascending (shared by
+ * the batch), per series
+ *     out[b,0,h] = m_h = k_h'A^-1 r,   out[b,1,h] = p_h = k_h'A^-1 k_h,   out[b,2,h] = q_h = k_h'A^-1 k_{h+1}  (q_{H-1} = p_{H-1})
+ * -- doubles for BOTH entries.  The posterior mean at xi_h is m(xi_h) + m_h, its variance v xi_h - p_h, the covariance of
+ * neighbours v xi_h - q_h; the posterior is Markov, so these fix the whole H x H covariance.  Test points beyond the grid give
+ * p = q bitwise.  x [N] (bsx = 0: one grid for the batch) or [B,N] with batch stride bsx >= N in elements; vol, sigma2 [B];
+ * resid [B,N].  One wave per (series, 64 test points), the forward sweep alone: ONE launch, no workspace, fp64 arithmetic, no
+ * atomics, bitwise repeatable, replays from a hipGraph, 64-bit indices.
+ * info[b]: 0; i + 1 for the first pivot d_i that is not a positive finite number; or -(h + 1) for the first test point that
+ * is NaN / inf, negative or smaller than its predecessor (no sweep runs then).  The series' rows of out are NaN in both cases.
+ * Argument errors: -1 x NULL; -2 bsx < 0 or 0 < bsx < N; -3 xs, -4 vol, -5 sigma2, -6 resid, -7 out, -8 info NULL; -9 B < 1;
+ * -10 N < 1; -11 H < 1 (or beyond 65535 blocks of 64). */
+int volt_bm_post_f32(const float* x, int64_t bsx, const float* xs, const float* vol, const float* sigma2, const float* resid,
+                     double* out /*[B,3,H]*/, int* info, int B, int N, int H, void* stream);
+int volt_bm_post_f64(const double* x, int64_t bsx, const double* xs, const double* vol, const double* sigma2, const double* resid,
+                     double* out /*[B,3,H]*/, int* info, int B, int N, int H, void* stream);
 int volt_bm_solve_f32(const float* x, const float* vol, const float* sigma2, const float* R /*[B,N,H]*/,
                       float* X /*[B,N,H]*/, int* info, void* workspace, int B, int N, int H, void* stream);
 int volt_bm_solve_f64(const double* x, const double* vol, const double* sigma2, const double* R /*[B,N,H]*/,

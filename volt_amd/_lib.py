@@ -85,6 +85,8 @@ _SIGS = {
     "volt_vk_step_f64": (C.c_int, [_ptr, _i64] + [_ptr] * 6 + [_i32, _i32, _i32, _ptr]),
     "volt_vk_forms_f32": (C.c_int, [_ptr, _i64] + [_ptr] * 4 + [_i32, _i32, _ptr]),
     "volt_vk_forms_f64": (C.c_int, [_ptr, _i64] + [_ptr] * 4 + [_i32, _i32, _ptr]),
+    "volt_bm_post_f32": (C.c_int, [_ptr, _i64] + [_ptr] * 6 + [_i32, _i32, _i32, _ptr]),
+    "volt_bm_post_f64": (C.c_int, [_ptr, _i64] + [_ptr] * 6 + [_i32, _i32, _i32, _ptr]),
     "volt_bm_solve_f32": (C.c_int, [_ptr] * 7 + [_i32, _i32, _i32, _ptr]),
     "volt_bm_solve_f64": (C.c_int, [_ptr] * 7 + [_i32, _i32, _i32, _ptr]),
     "volt_gpcv_bm_workspace_bytes": (_sz, [_i32, _i32, _i32]),

@@ -27,6 +27,9 @@
 //   bm_forms_kernel   (volt_vk_forms_*, the forecast's conditioning: DESIGN 4.15) the VK forward sweep with a second z chain over
 //                     D V = delta next to the one over D r, on the same pivots and the same staged tiles: V'A^-1 V, V'A^-1 r,
 //                     r'A^-1 r and logdet A in doubles.  No workspace, no backward sweep; the "noise" is a jitter rung, 0 allowed.
+//   bm_post_kernel    (volt_bm_post_*, the vol forecaster's posterior: DESIGN 4.16) one wave per (series, 64 sorted test points):
+//                     the pivot chain and z^r wave-uniform off broadcast LDS reads, per lane the z chains of its test point and
+//                     of the next one over clipped grid increments, and the sums m, p, q.  Forward sweep only, no workspace.
 //   bm_factor_kernel  the d chain alone, 1/d_i -> workspace (the solve's factorisation, once per series).
 //   bm_solve_kernel   one lane per (series, right-hand side): R [B,N,H] with H contiguous, so the lanes of a series load and
 //                     store whole rows.  Forward z -> workspace, backward X = D'w.  Its chains are one FMA per step.
@@ -349,6 +352,99 @@ __global__ __launch_bounds__(BM_T) void bm_forms_kernel(BmFormsParams<T> p) {
 }
 
 template <typename T>
+struct BmPostParams {
+    const T *x, *xs, *vol, *sigma2, *resid; // x: the grid [N] (bsx = 0) or per-series grids [B,N] with batch stride bsx; xs [H] ascending
+    double* out;                           // [B,3,H]: rows m, p, q
+    int* info;
+    int64_t B, N, H, bsx;
+};
+
+// The posterior of the Brownian-motion vol forecaster at H sorted test points xi_0 <= .. <= xi_{H-1} (volt_bm_post_*; DESIGN
+// 4.16): per series the forms m_h = k_h'A^-1 r, p_h = k_h'A^-1 k_h, q_h = k_h'A^-1 k_{h+1} (q_{H-1} = p_{H-1}) of the columns
+// k_h = v min(x, xi_h), from the forward sweep alone.  (D k_h)_i = v clamp(xi_h - x_{i-1}, 0, delta_i) is formed on the fly, so
+// nothing is N x H.  One wave per (series, block of 64 test points): the pivot chain, z^r and the staged tile (delta_i, x_{i-1},
+// (D r)_i, one step per lane into LDS, read back as broadcasts) are the same in every lane; a lane carries the z chain of its
+// own point and of its right neighbour (the last point's neighbour is the point itself) and the three running sums.  No
+// workspace, no atomics, no traffic between lanes or waves: every sum has a fixed order.
+template <typename T>
+__global__ __launch_bounds__(BM_T) void bm_post_kernel(BmPostParams<T> p) {
+    __shared__ double sd[BM_T], sx[BM_T], sr[BM_T];
+    const int lane = threadIdx.x;
+    const int64_t N = p.N, H = p.H;
+    const int64_t b = blockIdx.x, h = (int64_t)blockIdx.y * BM_T + lane;
+    const bool act = h < H;
+    const double nan = __builtin_nan("");
+    double* o = p.out + b * 3 * H + h;
+
+    // the test points, checked by every wave (H / 64 loads): the first that is NaN / inf, negative or below its predecessor
+    for (int64_t h0 = 0; h0 < H; h0 += BM_T) {
+        const int64_t k = h0 + lane;
+        double a = 0.0, pr = 0.0;
+        if (k < H) a = (double)p.xs[k];
+        if (k < H && k > 0) pr = (double)p.xs[k - 1];
+        const unsigned long long bad = __ballot(!(a >= pr && a < __builtin_inf()));     // (a lane past H holds 0 >= 0)
+        if (bad) {
+            if (act) o[0] = nan, o[H] = nan, o[2 * H] = nan;
+            if (blockIdx.y == 0 && lane == 0) p.info[b] = -(int)(h0 + __builtin_ctzll(bad) + 1);
+            return;
+        }
+    }
+
+    const double xa = act ? (double)p.xs[h] : 0.0, xb = act ? (double)p.xs[h + 1 < H ? h + 1 : h] : 0.0;
+    const double v = (double)p.vol[b], s = (double)p.sigma2[b];
+    const double ss = s * s, s2 = 2.0 * s;
+    const T* xg = p.x + b * p.bsx;
+    const T* rg = p.resid + b * N;
+
+    T px, pxm, pr, prm;                                                // x_i, x_{i-1}, r_i, r_{i-1} of this lane's step of the next tile
+    auto fetch = [&](int64_t i0) {
+        const int64_t i = i0 + lane;
+        px = pxm = pr = prm = (T)0;
+        if (i < N) px = xg[i], pr = rg[i];
+        if (i < N && i > 0) pxm = xg[i - 1], prm = rg[i - 1];
+    };
+    fetch(0);
+    double inv_prev = 0.0, zr = 0.0, za = 0.0, zb = 0.0, m = 0.0, pp = 0.0, q = 0.0;
+    int info = 0;
+    auto step = [&](int64_t i, double dl, double xp, double dr) {
+        const double base = __builtin_fma(v, dl, i == 0 ? s : s2);
+        const double d = __builtin_fma(-ss, inv_prev, base);
+        const double c = s * inv_prev;
+        const double inv = bm_rcp(d);
+        zr = __builtin_fma(c, zr, dr);
+        // (D k)_i by selects: v delta_i up to the bracket, the partial increment at it, 0 after; xi >= x_i gives delta_i exactly
+        za = __builtin_fma(c, za, v * __builtin_fmin(__builtin_fmax(xa - xp, 0.0), dl));
+        zb = __builtin_fma(c, zb, v * __builtin_fmin(__builtin_fmax(xb - xp, 0.0), dl));
+        const double w = za * inv;
+        m = __builtin_fma(w, zr, m);
+        pp = __builtin_fma(w, za, pp);
+        q = __builtin_fma(w, zb, q);
+        if (!bm_pivot_ok(d) && info == 0) info = (int)(i + 1 < 0x7fffffff ? i + 1 : 0x7fffffff);
+        inv_prev = inv;
+    };
+    for (int64_t i0 = 0; i0 < N; i0 += BM_T) {
+        sd[lane] = (double)px - (double)pxm;
+        sx[lane] = (double)pxm;
+        sr[lane] = (double)pr - (double)prm;
+        __syncthreads();
+        if (i0 + BM_T < N) fetch(i0 + BM_T);                                   // in flight while this tile's chains run
+        const int cnt = (int)(N - i0 < BM_T ? N - i0 : BM_T);                  // (wave-uniform: the loops below do not diverge)
+        int j0 = 0;
+        for (; j0 + BM_FB <= cnt; j0 += BM_FB) {
+            double dd[BM_FB], xp[BM_FB], rr[BM_FB];
+#pragma unroll
+            for (int u = 0; u < BM_FB; ++u) dd[u] = sd[j0 + u], xp[u] = sx[j0 + u], rr[u] = sr[j0 + u];
+#pragma unroll
+            for (int u = 0; u < BM_FB; ++u) step(i0 + j0 + u, dd[u], xp[u], rr[u]);
+        }
+        for (; j0 < cnt; ++j0) step(i0 + j0, sd[j0], sx[j0], sr[j0]);          // the last tile's remainder
+        __syncthreads();
+    }
+    if (act) o[0] = info ? nan : m, o[H] = info ? nan : pp, o[2 * H] = info ? nan : q;
+    if (blockIdx.y == 0 && lane == 0) p.info[b] = info;
+}
+
+template <typename T>
 struct BmSolveParams {
     const T *x, *vol, *sigma2, *R;
     T* X;
@@ -532,6 +628,28 @@ int vk_forms(const T* V, int64_t bsv, const double* jitter, const T* resid, doub
     return 0;
 }
 
+// m_h, p_h, q_h of the Brownian-motion posterior at H sorted test points: the forward sweep alone, doubles out
+template <typename T>
+int bm_post(const T* x, int64_t bsx, const T* xs, const T* vol, const T* sigma2, const T* resid, double* out, int* info, int B,
+            int N, int H, void* stream) {
+    if (!x) return -1;
+    if (bsx < 0 || (bsx > 0 && bsx < N)) return -2;
+    if (!xs) return -3;
+    if (!vol) return -4;
+    if (!sigma2) return -5;
+    if (!resid) return -6;
+    if (!out) return -7;
+    if (!info) return -8;
+    if (B < 1) return -9;
+    if (N < 1) return -10;
+    const int64_t blocks = ((int64_t)H + BM_T - 1) / BM_T;
+    if (H < 1 || blocks > 65535) return -11;
+    BmPostParams<T> p{x, xs, vol, sigma2, resid, out, info, B, N, H, bsx};
+    hipLaunchKernelGGL((bm_post_kernel<T>), dim3((unsigned)B, (unsigned)blocks), dim3(BM_T), 0, (hipStream_t)stream, p);
+    VOLT_LAUNCH_CHECK();
+    return 0;
+}
+
 template <typename T>
 int bm_solve(const T* x, const T* vol, const T* sigma2, const T* R, T* X, int* info, void* workspace, int B, int N, int H,
              void* stream) {
@@ -590,6 +708,14 @@ int volt_vk_forms_f32(const float* V, int64_t bsv, const double* jitter, const f
 int volt_vk_forms_f64(const double* V, int64_t bsv, const double* jitter, const double* resid, double* out, int* info, int B,
                       int N, void* stream) {
     return volt::vk_forms<double>(V, bsv, jitter, resid, out, info, B, N, stream);
+}
+int volt_bm_post_f32(const float* x, int64_t bsx, const float* xs, const float* vol, const float* sigma2, const float* resid,
+                     double* out, int* info, int B, int N, int H, void* stream) {
+    return volt::bm_post<float>(x, bsx, xs, vol, sigma2, resid, out, info, B, N, H, stream);
+}
+int volt_bm_post_f64(const double* x, int64_t bsx, const double* xs, const double* vol, const double* sigma2, const double* resid,
+                     double* out, int* info, int B, int N, int H, void* stream) {
+    return volt::bm_post<double>(x, bsx, xs, vol, sigma2, resid, out, info, B, N, H, stream);
 }
 int volt_bm_solve_f32(const float* x, const float* vol, const float* sigma2, const float* R, float* X, int* info,
                       void* workspace, int B, int N, int H, void* stream) {

@@ -94,9 +94,15 @@ def _standard_mean_prediction(model, train_x, log_y, vol, test_x, pred_vol, z, s
     return out
 
 
+def _check_vol_posterior(vol_posterior, vol_solver):
+    """Before any window trains: the vol forecaster's constructor would raise the same, one GPCV fit later."""
+    from .models.BMGP import _check_posterior
+    _check_posterior("vol_posterior", vol_posterior, vol_solver)
+
+
 def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator,
                  graph, vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False,
-                 predict_solver="dense", debug=None):
+                 predict_solver="dense", vol_posterior="solve", debug=None):
     """One window for the series in train_y [b, ntrain] (prices): GPCV -> data model -> vol forecasters -> rollouts,
     every stage for all b series at once.  Returns samples [b, S, H] on the device."""
     dev = train_y.device
@@ -111,11 +117,13 @@ def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_ite
     model, lh, _ = TrainVoltMagpieBatch(train_x, train_y[:, 1:], vol, train_iters=data_iters, k=k, mean_func=mean,
                                         graph=graph, reduce_across_ranks=False, solver=data_solver)
     if multitask_vol:      # the reference's own vol forecaster of the batched models: ONE Kronecker GP over the b log-vol paths
-        vmod, vlh = TrainVolModelMultitask(train_x, vol, train_iters=vol_iters, graph=graph, solver=vol_solver)
+        vmod, vlh = TrainVolModelMultitask(train_x, vol, train_iters=vol_iters, graph=graph, solver=vol_solver,
+                                           vol_posterior=vol_posterior)
         vmod.eval()
         pred_vol = vmod(test_x).sample(torch.Size((nsample,))).exp().permute(2, 0, 1).contiguous().detach()   # [S,H,b] -> [b,S,H]
     else:
-        vmod, vlh = TrainVolModelBatch(train_x, vol, train_iters=vol_iters, graph=graph, solver=vol_solver)
+        vmod, vlh = TrainVolModelBatch(train_x, vol, train_iters=vol_iters, graph=graph, solver=vol_solver,
+                                       vol_posterior=vol_posterior)
         vmod.eval()
         pred_vol = vmod(test_x).sample(torch.Size((nsample,))).exp().transpose(0, 1).contiguous().detach()   # [b,S,H]
     z = torch.randn(b, nsample, H, device=dev, generator=generator)
@@ -147,7 +155,7 @@ def _window_summary(samples, series, last_day, spec):
 def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample, mean, k, gpcv_iters, vol_iters,
                       data_iters, theta, vol_fn, generator, save, path_fn, debug=None, graph=None, summary=None,
                       keep_samples=True, vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False,
-                      predict_solver="dense"):
+                      predict_solver="dense", vol_posterior="solve"):
     """One batched pass per window (series [B,T] prices; the window ending at index e trains on series[:, e-ntrain:e]).
     A numerical failure anywhere in the batched pass (NotPSDError / NanError after the jitter ladders) must not take the
     other series down with it: the window is then redone one series at a time, and a series that still fails gets NaN
@@ -164,7 +172,7 @@ def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample,
     summaries = []
     H = test_x.numel()
     args = (nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator, graph, vol_solver, gpcv_solver,
-            data_solver, multitask_vol, predict_solver)
+            data_solver, multitask_vol, predict_solver, vol_posterior)
     last = None
     for last_day in end_idxs:
         train_y = series[:, last_day - ntrain:last_day].float()                          # [B, ntrain] prices
@@ -201,7 +209,8 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
                                   ntrain=400, mean="ewma", save=False, k=300, ntimes=-1, vol_fn=None,
                                   vol_iters=None, par_dir="./saved-outputs/", generator=None, debug=None, graph=None,
                                   summary=None, keep_samples=True, vol_solver="dense", gpcv_solver="dense",
-                                  data_solver="dense", multitask_vol=False, predict_solver="dense"):
+                                  data_solver="dense", multitask_vol=False, predict_solver="dense",
+                                  vol_posterior="solve"):
     """closes [B, T] prices for B tickers on a common calendar (device tensor).  Same window schedule,
     model name and file layout as GenerateStockPredictions (GenerateMultiMeanPreds.py:69-83,128); ``mean`` in
     ewma / dewma / tewma takes the Rollouts branch (:110-112), constant / loglinear / linear the "VOLT + standard
@@ -224,7 +233,11 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
     ``predict_solver="linear"``: the forecast conditions on each series' train block through the O(N) chain (volt_vk_forms_*,
     DESIGN 4.15) -- solve="chain" on the Rollouts branch, one launch for all tickers on the standard-mean branch -- instead
     of filling and factoring an N x N block per series (per path, on the standard-mean branch); independent of the other
-    three, and "dense" changes nothing."""
+    three, and "dense" changes nothing.
+    ``vol_posterior="sweep"`` (with ``vol_solver="linear"``): the vol forecaster's posterior from ONE forward sweep per window
+    (BMGP / MultitaskBMGP(posterior="sweep"), volt_bm_post_*) instead of a chain solve on K_t* [T,N,H]; the
+    default "solve" changes nothing."""
+    _check_vol_posterior(vol_posterior, vol_solver)
     if mean not in _MODES and mean not in _STANDARD:
         raise ValueError(f"unknown mean {mean!r}: one of {sorted(_MODES) + list(_STANDARD)}")
     dev = closes.device
@@ -246,21 +259,23 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
         return os.path.join(par_dir, tckr, model_name + date + ".pt")                    # :128
     return _forecast_windows(tickers, closes, end_idxs.tolist(), ntrain, train_x, test_x, nsample, mean, k,
                              train_iters, vol_iters, train_iters, None, vol_fn, generator, save, path_fn, debug, graph,
-                             summary, keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol, predict_solver)
+                             summary, keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol, predict_solver,
+                             vol_posterior)
 
 
 def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=400, n_test_times=10, nsample=1000, k=400,
                                  theta=0.01, gpcv_iters=200, vol_iters=500, data_iters=0, save=False, vol_fn=None,
                                  par_dir="./saved-outputs/", generator=None, graph=None, summary=None, keep_samples=True,
                                  vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False,
-                                 predict_solver="dense"):
+                                 predict_solver="dense", vol_posterior="solve"):
     """The ``--kernel volt --mean ewma`` branch of experiments/weather/GPGenerator.py:20-112 for B stations at once:
     data [B,T] wind speeds (missing = -99 -> 0, then +1 as at :47,55), dt = 1/365 (:38-41), the schedule of test
     windows of :33-34, GPCV 200 / vol model 500 / data model 0 iterations (:64-67,89-92), EWMA(k=400) mean and
     mean-reverting rollouts with theta = 0.01 (:96-102), files ``stn<idx>/volt_ema<k>_theta<theta>_<last_day>.pt``
     (:103-106).  Stations shard across ranks like tickers.  Returns the last window's samples [B_local,S,H] (CPU).
-    ``summary`` / ``keep_samples`` / ``vol_solver`` / ``gpcv_solver`` / ``data_solver`` / ``multitask_vol`` / ``predict_solver``: as for GenerateStockPredictionsBatch (the truth is the shifted series,
+    ``summary`` / ``keep_samples`` / ``vol_solver`` / ``gpcv_solver`` / ``data_solver`` / ``multitask_vol`` / ``predict_solver`` / ``vol_posterior``: as for GenerateStockPredictionsBatch (the truth is the shifted series,
     data + 1)."""
+    _check_vol_posterior(vol_posterior, vol_solver)
     dev = data.device
     lo, hi = shard_range(len(stations))
     stations, data = list(stations)[lo:hi], data[lo:hi].float()
@@ -276,4 +291,4 @@ def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=40
                             str(last_day) + ".pt")
     return _forecast_windows(stations, data, end_idxs, ntrain, train_x, test_x, nsample, "ewma", k, gpcv_iters,
                              vol_iters, data_iters, theta, vol_fn, generator, save, path_fn, None, graph, summary,
-                             keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol, predict_solver)
+                             keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol, predict_solver, vol_posterior)

@@ -267,6 +267,27 @@ class _BrownianPrior(_ScaledDense):
         return torch.Size((n, n))
 
 
+def _markov_cov(diag, off):
+    """The covariance [..,H,H] of a Markov process over H ordered points from its diagonal ``diag`` [..,H] and its first
+    off-diagonal ``off`` [..,H] (off[.., j] = cov(j, j+1); the last entry is not read): cov(a, c) = diag_a prod_{a <= j < c} g_j
+    with g_j = off_j / diag_j -- what the posterior of a Markov prior under independent noise is (BMGP(posterior="sweep")).
+    fp64; the product is exp(L_c - L_a) over L = cumsum log g, never a ratio of cumulative products (which underflow).
+    Where diag_j <= 0 (a point of zero variance: f(0) = 0) g_j := 0: that row and column are zero and nothing couples
+    across it -- the zeros are counted beside L, not sent through the logarithm.  Symmetric by construction."""
+    diag, off = diag.double(), off.double()
+    H = diag.shape[-1]
+    g = torch.where(diag > 0, off / torch.where(diag > 0, diag, torch.ones_like(diag)), torch.zeros_like(diag))
+    g = g.clamp_min(0.0)[..., :H - 1]
+    zero = g <= 0
+    pad = torch.zeros_like(diag[..., :1])
+    L = torch.cat([pad, torch.where(zero, torch.ones_like(g), g).log().cumsum(-1)], -1)           # L_0 = 0
+    Z = torch.cat([pad, zero.to(torch.float64).cumsum(-1)], -1)                                   # zeros of g before each point
+    dL = L.unsqueeze(-2) - L.unsqueeze(-1)                                                        # [a, c] = L_c - L_a
+    upper = diag.clamp_min(0.0).unsqueeze(-1) * torch.exp(dL) * (Z.unsqueeze(-2) == Z.unsqueeze(-1))
+    upper = torch.triu(upper)
+    return upper + torch.triu(upper, 1).mT
+
+
 def check_grid(x, who):
     """What the linear-time solvers (csrc/bm.hip, csrc/gpcv_bm.hip) need of their 1-D grid ``x``, checked once with ONE host
     read: x[0] >= 0 and strictly increasing.  ``who`` names the caller in the message."""

@@ -15,23 +15,51 @@ import torch
 
 from .. import ops
 from ..gp import (ExactGP, MultitaskMultivariateNormal, MultivariateNormal, NanError, NotPSDError, _BrownianPrior, _KroneckerPrior,
-                  _safe_factor, check_grid, same_values)
+                  _markov_cov, _safe_factor, check_grid, same_values)
 from ..kernels.BMKernel import BMKernel
 from ..kernels.FBMKernel import FBMKernel
 from ..kernels.MultitaskKernel import MultitaskKernel
+
+
+def _check_posterior(who, posterior, solver):
+    if posterior not in BMGP.POSTERIORS:
+        raise ValueError(f"{who}: posterior must be one of {BMGP.POSTERIORS}, got {posterior!r}")
+    if posterior != "solve" and solver != "linear":
+        raise ValueError(f"{who}: posterior={posterior!r} needs solver='linear' (the dense solver has one posterior)")
+
+
+def _check_post_info(info, order, who, params, not_psd):
+    """ONE host read of ops.bm_post's info.  NaN / inf parameters (``params``: tensors looked at only on failure) are a
+    NanError before a failed pivot is a NotPSDError; a negative code names the offending test point by its index in the
+    caller's order (``order``: the sort's permutation)."""
+    info = info.tolist()
+    if not any(info):
+        return
+    if not all(bool(torch.isfinite(p).all()) for p in params):
+        raise NanError(f"{who} posterior: NaN / inf in the targets or the parameters")
+    code = next(i for i in info if i)
+    if code < 0:
+        raise ValueError(f"{who} posterior: test point {int(order[-code - 1])} is NaN / inf or negative "
+                         "(Brownian motion starts at x = 0)")
+    raise NotPSDError(f"{who} posterior: {not_psd}")
 
 
 class BMGP(ExactGP):
     """``solver="dense"`` (default): the N x N machinery of the data model.  ``solver="linear"`` (kernel "bm" only): Brownian
     motion is Markov, so the MLL step and the posterior solve run in O(N) on csrc/bm.hip (fp64 arithmetic, no N x N matrix
     anywhere) -- ``forward`` returns a lazy prior, ``posterior_call`` goes through ops.bm_step / ops.bm_solve.
-    The training grid is validated ONCE here (one host read): 1-D, x_0 >= 0, strictly increasing."""
+    The training grid is validated ONCE here (one host read): 1-D, x_0 >= 0, strictly increasing.
+    ``posterior`` (solver="linear" only): "solve" (default) conditions through ops.bm_step / ops.bm_solve on K_t* [T,N,H];
+    "sweep" through ONE forward sweep (ops.bm_post) that forms the clipped increments of K_t* on the fly and
+    rebuilds the H x H covariance from its diagonal and first off-diagonal (the posterior is Markov): nothing is N x H."""
     SOLVERS = ("dense", "linear")
+    POSTERIORS = ("solve", "sweep")
     _POST_CHUNK = 4096                        # rows of K_t* per fp64 product of the linear posterior (bounds its temporaries)
 
-    def __init__(self, train_x, train_y, likelihood, kernel="bm", solver="dense"):
+    def __init__(self, train_x, train_y, likelihood, kernel="bm", solver="dense", posterior="solve"):
         if solver not in self.SOLVERS:
             raise ValueError(f"BMGP: solver must be one of {self.SOLVERS}, got {solver!r}")
+        _check_posterior("BMGP", posterior, solver)
         if solver == "linear" and kernel != "bm":
             raise ValueError(f"BMGP: solver='linear' needs kernel='bm' (Brownian motion is Markov; kernel {kernel!r} is not)")
         if solver == "linear":
@@ -45,6 +73,7 @@ class BMGP(ExactGP):
         elif kernel == "fbm":
             self.covar_module = FBMKernel(**kw).to(train_x.device)      # BMGP.py:15-16; dense d mll / d K path
         self.solver = solver
+        self.posterior = posterior
         self.scaling = (train_x[1] - train_x[0])
 
     def mean_module(self, x):
@@ -99,12 +128,46 @@ class BMGP(ExactGP):
                 mean, cov = mean[0], cov[0]
             return MultivariateNormal(mean, cov)
 
+    def _posterior_sweep(self, x):
+        """The same posterior from ONE ops.bm_post launch over the sorted test points (any order and duplicates accepted:
+        sorted on the device, the order restored on the way out) and one host read of its info: mean* = m(x*) + m_h,
+        var = v xi_h - p_h, cov of neighbours = v xi_h - q_h, the rest by gp._markov_cov; fp64 throughout (the upcasts of
+        `_posterior_linear`), rounded once to the model's dtype."""
+        with torch.no_grad():
+            xt = self.train_inputs[0][:, 0]
+            y = self.train_targets
+            batched = y.ndim > 1
+            T = y.shape[0] if batched else 1
+            n = xt.shape[0]
+            xs = x[:, 0] if x.ndim > 1 else x
+            H = xs.shape[0]
+            dt = torch.float64 if y.dtype == torch.float64 else torch.float32
+            vol = self.covar_module.vol.reshape(-1).expand(T)
+            noise = self.likelihood.noise.reshape(-1).expand(T)
+            resid = (y - self.mean_module(xt)).reshape(T, n)
+            xs64, order = torch.sort(xs.double())
+            out, info = ops.bm_post(xt.double(), xs64, vol, noise, resid.double())
+            _check_post_info(info, order, "BMGP", (vol, noise, y),
+                             "vol min(x, x') + sigma^2 I is not positive definite (the noise must be positive)")
+            prior = vol.double().reshape(T, 1) * xs64
+            mean_s = self.mean_module(xs64).reshape(T, H) + out[:, 0]
+            cov_s = _markov_cov(prior - out[:, 1], prior - out[:, 2])
+            mean = torch.empty_like(mean_s)
+            mean[:, order] = mean_s
+            cov = torch.empty_like(cov_s)
+            cov[:, order.unsqueeze(-1), order.unsqueeze(0)] = cov_s
+            mean, cov = mean.to(dt), cov.to(dt)
+            if not batched:
+                mean, cov = mean[0], cov[0]
+            return MultivariateNormal(mean, cov)
+
     def posterior_call(self, x):
         """Exact-GP posterior at the test points: K_s = L L' on the HIP potrf, K_s^-1 = Y Y' with Y = L^-T from the HIP
         triangular inverse, every product on the library GEMM.  One series -> MultivariateNormal(mean [H], cov [H,H]);
-        T series over the shared grid -> (mean [T,H], cov [T,H,H]).  solver="linear": _posterior_linear."""
+        T series over the shared grid -> (mean [T,H], cov [T,H,H]).  solver="linear": _posterior_linear, or _posterior_sweep
+        with posterior="sweep"."""
         if self.solver == "linear":
-            return self._posterior_linear(x)
+            return self._posterior_sweep(x) if self.posterior == "sweep" else self._posterior_linear(x)
         with torch.no_grad():
             from ..gp import _dense
             xt = self.train_inputs[0]
@@ -149,14 +212,18 @@ class MultitaskBMGP(ExactGP):
     ``solver="dense"`` (default): M = min(x, x') is filled once and every eigen-direction is an N x N dense step.
     ``solver="linear"``: each direction's M + sigma_j^2 I is the tridiagonal chain of BMGP(solver="linear"), so the MLL step
     (ops.kron_bm_step) and the posterior run in O(T N + T^2 N) with no N x N matrix anywhere; ``forward`` returns
-    the lazy prior over the training grid, which is validated ONCE here (one host read): 1-D, x_0 >= 0, strictly increasing."""
+    the lazy prior over the training grid, which is validated ONCE here (one host read): 1-D, x_0 >= 0, strictly increasing.
+    ``posterior`` (solver="linear" only): "solve" (default) or "sweep", as for BMGP -- one ops.bm_post launch for all
+    eigen-directions instead of a chain solve per group of test points."""
     SOLVERS = BMGP.SOLVERS
+    POSTERIORS = BMGP.POSTERIORS
     _POST_CHUNK = BMGP._POST_CHUNK
     _POST_SOLVE_ELEMS = 1 << 19               # directions x N x points per solve of the linear posterior (bounds its three buffers)
 
-    def __init__(self, train_x, train_y, likelihood, base_mean=None, solver="dense", **kwargs):
+    def __init__(self, train_x, train_y, likelihood, base_mean=None, solver="dense", posterior="solve", **kwargs):
         if solver not in self.SOLVERS:
             raise ValueError(f"MultitaskBMGP: solver must be one of {self.SOLVERS}, got {solver!r}")
+        _check_posterior("MultitaskBMGP", posterior, solver)
         if solver == "linear":
             if train_x.ndim != 1:
                 raise ValueError(f"MultitaskBMGP(solver='linear'): the grid must be 1-D [N], got shape {tuple(train_x.shape)}")
@@ -169,6 +236,7 @@ class MultitaskBMGP(ExactGP):
         self.covar_module.task_covar_module.var.data /= 10.              # a computed property: no effect (BMGP.py:39)
         self.covar_module.task_covar_module.covar_factor.data /= 10.
         self.solver = solver
+        self.posterior = posterior
         if solver == "dense":
             x = train_x.reshape(-1)
             self._base = torch.minimum(x.unsqueeze(-1), x.unsqueeze(-2))  # M = min(x_i, x_k): K_x = vol M, filled once
@@ -241,14 +309,46 @@ class MultitaskBMGP(ExactGP):
             mean = (self.mean_module(xs).double() + mt.t() @ V64.t()).to(torch.float32)
             return MultitaskMultivariateNormal(mean, blocks=(V64.to(torch.float32), C))
 
+    def _posterior_sweep(self, x):
+        """`_posterior_linear` with the T chain solves and the products over N replaced by ONE ops.bm_post launch over the
+        sorted test points (unit vol, the directions' sigma_j^2 and residuals of the cold fp64 prologue) and one host read of
+        its info: m~_j = sqrt(kappa_j) m_j and C_j = kappa_j markov_cov(xi - p_j, xi - q_j); the assembly is unchanged."""
+        with torch.no_grad():
+            xt = self.train_inputs[0][:, 0]
+            Y = self.train_targets
+            n, T = Y.shape
+            xs = x[..., 0] if x.ndim > 1 else x
+            dev = xt.device
+            if self._post_ws is None or not self._post_ws.fits(n, T, dev, torch.float64, "linear"):
+                self._post_ws = ops.KronWorkspace(n, T, dev, torch.float64, "linear")
+            ws = self._post_ws
+            task, data = self.covar_module.task_covar_module, self.covar_module.data_covar_module
+            params = (data.raw_vol, task.covar_factor, task.raw_var, self.likelihood.raw_task_noises, self.likelihood.raw_noise)
+            x64 = xt.double()
+            ops.kron_prologue(params, x64, Y, ws)
+            kap = ws.state[0] * ws.lam()                                                   # [T], fp64
+            xs64, order = torch.sort(xs.double())
+            out, info = ops.bm_post(x64, xs64, ws.ones, ws.sigma2, ws.resid)
+            _check_post_info(info, order, "MultitaskBMGP", params + (Y,), "M + sigma_j^2 I is not positive definite")
+            mt_s = kap.sqrt().reshape(T, 1) * out[:, 0]                                    # m~_j over the sorted points
+            C_s = kap.reshape(T, 1, 1) * _markov_cov(xs64 - out[:, 1], xs64 - out[:, 2])
+            mt = torch.empty_like(mt_s)
+            mt[:, order] = mt_s
+            C = torch.empty_like(C_s)
+            C[:, order.unsqueeze(-1), order.unsqueeze(0)] = C_s
+            V64 = ws.d().sqrt().unsqueeze(-1) * ws.Q()                                     # D^1/2 Q
+            mean = (self.mean_module(xs).double() + mt.t() @ V64.t()).to(torch.float32)
+            return MultitaskMultivariateNormal(mean, blocks=(V64.to(torch.float32), C.to(torch.float32)))
+
     def posterior_call(self, x):
         """Exact latent posterior at x [H] (gpytorch's eval-mode ExactGP call): a MultitaskMultivariateNormal with mean [H,T].
         Block by block in the eigenbasis of the task covariance: the prologue (fp64) gives W, Lambda and
         r_j; then per block m~_j = sqrt(kappa_j) M_*x (M + sigma_j^2 I)^-1 r_j and C_j = kappa_j [M_** - M_*x (M +
         sigma_j^2 I)^-1 M_x*] on the HIP potrf / triangular inverse / GEMM, as BMGP.posterior_call does; finally
-        mean = mu_* + m~ V' and cov = (I (x) V) blockdiag(C_j) (I (x) V'), V = D^1/2 Q.  solver="linear": _posterior_linear."""
+        mean = mu_* + m~ V' and cov = (I (x) V) blockdiag(C_j) (I (x) V'), V = D^1/2 Q.  solver="linear": _posterior_linear, or
+        _posterior_sweep with posterior="sweep"."""
         if self.solver == "linear":
-            return self._posterior_linear(x)
+            return self._posterior_sweep(x) if self.posterior == "sweep" else self._posterior_linear(x)
         with torch.no_grad():
             xt = self.train_inputs[0][:, 0]
             Y = self.train_targets

@@ -22,7 +22,7 @@ _MEAN_CLASSES = {"ewma": EWMAMean, "dewma": DEWMAMean, "tewma": TEWMAMean}
 
 class Volt(VolGP):
     def __init__(self, train_x, log_data, mean='constant', vol_path=None, k=25, *, multitask_vol=False, vol_solver="dense",
-                 data_solver="dense", predict_solver="dense"):
+                 data_solver="dense", predict_solver="dense", vol_posterior="solve"):
         # The reference builds the ExactGP on [1:] but keeps the FULL train_x / log_data as attributes (Volt.py:52-62);
         # with a vol_path of length N-1 its own train_cov line is then shape-inconsistent.  The [1:] view is kept
         # everywhere here, so that train_cov matches train_inputs.
@@ -35,14 +35,15 @@ class Volt(VolGP):
             self.mean_module = _MEAN_CLASSES[name](x, y, k).to(train_x.device)
         else:
             raise ValueError("ERROR: Mean not implemented")      # the reference prints this and fails on the next line
-        self._init_vol_state(x, y, vol_path, multitask_vol, vol_solver, data_solver, predict_solver)
+        self._init_vol_state(x, y, vol_path, multitask_vol, vol_solver, data_solver, predict_solver,
+                             vol_posterior)
         self._full_x, self._full_log_data = train_x, log_data    # Train's GPCV stage starts from the prices
 
     def Train(self, gpcv_iters=400, vol_mod_iters=1000, data_mod_iters=400, display=False, vol=None,
               vol_model=None, vol_lh=None, *, gpcv_solver="dense"):
         """Volt.py:95-146: GPCV + vol model (:103-104), then the data model (:108-146).  ``vol`` (and optionally a
         trained ``vol_model`` / ``vol_lh``) skips the first stage.  ``gpcv_solver="linear"``: the GPCV stage on the O(N^2)
-        ELBO step (LearnGPCV(solver=...)); the vol forecaster keeps the solver the model was built with (``vol_solver``), and so does the data
+        ELBO step (LearnGPCV(solver=...)); the vol forecaster keeps the solver and posterior the model was built with (``vol_solver``, ``vol_posterior``), and so does the data
         model (``data_solver``: UpdateVolPath rebuilds the lazy prior, the fit below steps on it)."""
         from ..train_utils import LR_DATA, LearnGPCV, TrainVolModel, _attach_vol, _fit_exact, _train_noise_and_mean
         x = self.train_x.squeeze()
@@ -52,7 +53,8 @@ class Volt(VolGP):
                                           "and pass it as vol= (the reference's GPCV + MultitaskBMGP stage is not wired into "
                                           "batched Train; TrainVolModelMultitask fits the multitask vol model)")
             vol = LearnGPCV(self._full_x[1:], self._full_log_data.exp(), gpcv_iters, printing=display, solver=gpcv_solver)
-            vol_model, vol_lh = TrainVolModel(self._full_x[1:], vol, vol_mod_iters, printing=display, solver=self.vol_solver)
+            vol_model, vol_lh = TrainVolModel(self._full_x[1:], vol, vol_mod_iters, printing=display, solver=self.vol_solver,
+                                              vol_posterior=self.vol_posterior)
         self.UpdateVolPath(vol)
         _attach_vol(self, vol_model, vol_lh, x.device)
         params = _train_noise_and_mean(self, self.likelihood)    # noise (+ the constant mean), Volt.py:110-127

@@ -8,12 +8,12 @@ from .. import ops
 from ..gp import (ExactGP, ExactMarginalLogLikelihood, GaussianLikelihood, MultitaskGaussianLikelihood, MultivariateNormal,
                   _VolPrior, same_values)
 from ..kernels import VolatilityKernel
-from .BMGP import BMGP, MultitaskBMGP
+from .BMGP import BMGP, MultitaskBMGP, _check_posterior
 
 
 class VolGP(ExactGP):
     def _init_vol_state(self, x, y, vol_path, multitask_vol=False, vol_solver="dense", data_solver="dense",
-                        predict_solver="dense"):
+                        predict_solver="dense", vol_posterior="solve"):
         """x [N], y [N] or [T,N] (batched layout: one shared input grid, T target / vol rows), vol_path like y or None.
         Call after ``mean_module`` is set so that the modules register in the reference's order.  ``multitask_vol`` (batched
         models only): the reference's own vol forecaster, a MultitaskBMGP over the [N,T] log-vol paths with a
@@ -24,7 +24,8 @@ class VolGP(ExactGP):
         ``predict_solver="linear"``: GeneratePrediction / SamplePrediction / MeanPrediction, rollout_utils.GeneratePrediction
         and Rollouts condition on the train block through the O(N) chain (volt_vk_forms_*) instead of filling
         and factoring it; independent of ``data_solver`` (a dense-trained model may predict linearly), and "dense" changes
-        nothing."""
+        nothing.  ``vol_posterior`` (with ``vol_solver="linear"``): the vol forecaster's ``posterior``, "solve" or "sweep"
+        (BMGP / MultitaskBMGP)."""
         if predict_solver not in BMGP.SOLVERS:
             raise ValueError(f"predict_solver must be one of {BMGP.SOLVERS}, got {predict_solver!r}")
         self.predict_solver = predict_solver
@@ -47,16 +48,19 @@ class VolGP(ExactGP):
         # solver (BMGP(solver="linear"), csrc/bm.hip), and MultitaskBMGP on the linear-time Kronecker step (csrc/kron_chain.hip).
         if vol_solver not in BMGP.SOLVERS:
             raise ValueError(f"vol_solver must be one of {BMGP.SOLVERS}, got {vol_solver!r}")
+        _check_posterior("vol_posterior", vol_posterior, vol_solver)
         self.vol_solver = vol_solver          # Volt.Train refits the vol forecaster: with the solver the model was built with
+        self.vol_posterior = vol_posterior    # ... and with the same posterior
         if multitask_vol:
             if not len(batch_shape) or self.log_vol_path.shape[:-1] != batch_shape:
                 raise ValueError("multitask_vol=True needs a batched model with a [T,N] vol_path")
             self.vol_lh = MultitaskGaussianLikelihood(num_tasks=batch_shape[0]).to(dev)
             self.vol_lh.noise = 1e-3
-            self.vol_model = MultitaskBMGP(x, self.log_vol_path.t(), self.vol_lh, solver=vol_solver)   # [N] inputs, [N,T] targets
+            self.vol_model = MultitaskBMGP(x, self.log_vol_path.t(), self.vol_lh, solver=vol_solver, posterior=vol_posterior)   # [N] inputs, [N,T] targets
             return
         self.vol_lh = GaussianLikelihood(batch_shape=batch_shape).to(dev)
-        self.vol_model = BMGP(x, self.log_vol_path, self.vol_lh, solver=vol_solver) if self.log_vol_path.shape[:-1] == batch_shape else None
+        self.vol_model = (BMGP(x, self.log_vol_path, self.vol_lh, solver=vol_solver, posterior=vol_posterior)
+                          if self.log_vol_path.shape[:-1] == batch_shape else None)
 
     @staticmethod
     def _vol_prior(x, vol):

@@ -404,6 +404,39 @@ def _chain_step(entry, grid_args, sigma2, resid, dt, ws, want_grad):
     return ws.out, ws.alpha, ws.info
 
 
+def bm_post(x: torch.Tensor, xs_sorted: torch.Tensor, vol: torch.Tensor, sigma2: torch.Tensor, resid: torch.Tensor):
+    """The forms of the Brownian-motion posterior at H test points in ONE O(N H) sweep with no workspace (volt_bm_post_f32 /
+    _f64 by resid's dtype; the arithmetic and the outputs are fp64 either way): per series, with A_b = vol_b min(x, x') +
+    sigma2_b I and k_h = vol_b min(x, xi_h), out[b] = rows (k_h'A^-1 r, k_h'A^-1 k_h, k_h'A^-1 k_{h+1}).  x [N] (one grid for
+    all series) or [B,N] (strided rows allowed); xs_sorted [H] ascending, >= 0, shared; vol, sigma2 [B] (or one value);
+    resid [B,N].  Returns (out [B,3,H] fp64, info [B] int32), freshly allocated; info[b] = i + 1 at the first bad pivot,
+    -(h + 1) at the first test point that is NaN / inf, negative or out of order, and the series' rows are then NaN."""
+    _need_gpu(x, xs_sorted, vol, sigma2, resid)
+    dt = torch.float64 if resid.dtype == torch.float64 else torch.float32
+    if resid.ndim != 2:
+        raise ValueError("resid must be [B,N]")
+    if xs_sorted.ndim != 1 or xs_sorted.shape[0] < 1:
+        raise ValueError("xs_sorted must be [H], H >= 1")
+    B, n = resid.shape
+    if x.ndim not in (1, 2) or x.shape[-1] != n:
+        raise ValueError("x must be [N] or [B,N] with resid's N")
+    if x.ndim == 2 and x.shape[0] != B:
+        raise ValueError("x [B,N] and resid disagree on B")
+    x, bsx = _vk_grid(x, B, n, dt)
+    H = xs_sorted.shape[0]
+    xs = xs_sorted.to(dt).contiguous()
+    vol = vol.to(dt).reshape(-1).expand(B).contiguous()
+    sigma2 = sigma2.to(dt).reshape(-1).expand(B).contiguous()
+    resid = resid.to(dt).contiguous()
+    out = torch.empty(B, 3, H, dtype=torch.float64, device=resid.device)
+    info = torch.empty(B, dtype=torch.int32, device=resid.device)
+    fn = _lib.lib().volt_bm_post_f32 if dt == torch.float32 else _lib.lib().volt_bm_post_f64
+    with torch.cuda.device(resid.device):
+        _lib.check(fn(x.data_ptr(), bsx, xs.data_ptr(), vol.data_ptr(), sigma2.data_ptr(), resid.data_ptr(), out.data_ptr(),
+                      info.data_ptr(), B, n, H, _lib.stream_ptr()), "volt_bm_post")
+    return out, info
+
+
 def bm_solve(x: torch.Tensor, vol: torch.Tensor, sigma2: torch.Tensor, R: torch.Tensor, ws: BmWorkspace | None = None):
     """X = (vol_b min(x, x') + sigma2_b I)^-1 R_b in O(N H) per series (volt_bm_solve_f32 / _f64 by R's dtype).
     R [B,N,H].  Returns (X [B,N,H], info [B]); they live in ``ws``."""

@@ -382,35 +382,39 @@ def LearnGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kerne
 
 
 # ------------------------------------------------------------------------------------------------ (f)1: vol forecaster
-def _vol_model(train_x, vol_path, kernel, batch_shape, solver="dense"):
+def _vol_model(train_x, vol_path, kernel, batch_shape, solver="dense", posterior="solve"):
     from .models import BMGP
     vol_lh = GaussianLikelihood(batch_shape=batch_shape).to(train_x.device)
     # (the reference's `vol_lh.noise.data = 1e-2` at :71 writes to a temporary: the noise starts at softplus(0) + 1e-4)
-    return BMGP(train_x, vol_path.log(), vol_lh, kernel=kernel, solver=solver).to(train_x.device), vol_lh
+    return BMGP(train_x, vol_path.log(), vol_lh, kernel=kernel, solver=solver, posterior=posterior).to(train_x.device), vol_lh
 
 
-def TrainVolModel(train_x, vol_path, train_iters=1000, printing=False, kernel="bm", graph=None, solver="dense"):
+def TrainVolModel(train_x, vol_path, train_iters=1000, printing=False, kernel="bm", graph=None, solver="dense",
+                  vol_posterior="solve"):
     """voltron/train_utils.py:69-95: the Brownian-motion GP over log-vol that supplies pred_vol to Rollouts.  The MLL
     and its gradient wrt the kernel's `vol` and the noise run on the HIP step (K = vol * min(x,x') keeps d mll / d vol
     in closed form, gp._ExactMLL).  ``solver="linear"``: the O(N) step of csrc/bm.hip (gp._ChainMLL) instead of the dense
-    one; launch-bound at every N, so ``graph=None`` captures wherever capturing is possible."""
-    vol_model, vol_lh = _vol_model(train_x, vol_path, kernel, torch.Size(), solver)
+    one; launch-bound at every N, so ``graph=None`` captures wherever capturing is possible.  ``vol_posterior`` (with
+    ``solver="linear"``): the fitted model's ``posterior``, "solve" or "sweep" (BMGP) -- the fit is the same."""
+    vol_model, vol_lh = _vol_model(train_x, vol_path, kernel, torch.Size(), solver, vol_posterior)
     _fit_exact(vol_model, vol_lh, train_x, vol_path.log(), list(vol_model.parameters()), LR_VOL, train_iters, printing,
                _auto_graph(graph, vol_path, launch_bound=solver == "linear"))
     return vol_model, vol_lh
 
 
-def TrainVolModelBatch(train_x, vol_path, train_iters=1000, printing=False, kernel="bm", graph=None, solver="dense"):
+def TrainVolModelBatch(train_x, vol_path, train_iters=1000, printing=False, kernel="bm", graph=None, solver="dense",
+                       vol_posterior="solve"):
     """TrainVolModel for T series at once: vol_path [T,N] -> one batched BMGP (per-series kernel parameter and noise)."""
     T = vol_path.shape[0]
-    vol_model, vol_lh = _vol_model(train_x, vol_path, kernel, torch.Size([T]), solver)
+    vol_model, vol_lh = _vol_model(train_x, vol_path, kernel, torch.Size([T]), solver, vol_posterior)
     graph = _auto_graph(graph, vol_path, launch_bound=solver == "linear")
     _fit_exact(vol_model, vol_lh, train_x, vol_path.log(), list(vol_model.parameters()), LR_VOL, train_iters, printing, graph,
                defer=not graph, batched=True, scale=1.0 / T)
     return vol_model, vol_lh
 
 
-def TrainVolModelMultitask(train_x, vol_path, train_iters=1000, printing=False, graph=None, solver="dense"):
+def TrainVolModelMultitask(train_x, vol_path, train_iters=1000, printing=False, graph=None, solver="dense",
+                           vol_posterior="solve"):
     """The multitask vol forecaster of the batched models (MultitaskBMGP, voltron/models/BMGP.py:30-56) fitted to T vol
     paths: vol_path [T,N] -> (model, likelihood) with the model built as the reference's batched constructors build it
     (VoltMagpie.py:51-55: MultitaskGaussianLikelihood(T), noise = 1e-3, targets log(vol_path).t() [N,T]).  The reference
@@ -418,14 +422,14 @@ def TrainVolModelMultitask(train_x, vol_path, train_iters=1000, printing=False, 
     LR_VOL on every parameter, graph capture where it pays (`_auto_graph`), the deferred ``info`` checks -- over the
     Kronecker MLL (gp._KronMLL: prologue -> batched step -> epilogue, no host synchronisation).  ``solver="linear"``: the same
     sequence around the linear-time chain step (MultitaskBMGP(solver="linear")); the iteration is then launch-bound at every
-    N, so ``graph=None`` captures wherever capturing is possible."""
+    N, so ``graph=None`` captures wherever capturing is possible.  ``vol_posterior``: as in TrainVolModel."""
     from .gp import MultitaskGaussianLikelihood
     from .models import MultitaskBMGP
     T = vol_path.shape[0]
     vol_lh = MultitaskGaussianLikelihood(num_tasks=T).to(train_x.device)
     vol_lh.noise = 1e-3
     target = vol_path.log().t()
-    vol_model = MultitaskBMGP(train_x, target, vol_lh, solver=solver).to(train_x.device)
+    vol_model = MultitaskBMGP(train_x, target, vol_lh, solver=solver, posterior=vol_posterior).to(train_x.device)
     graph = _auto_graph(graph, vol_path, launch_bound=solver == "linear")
     _fit_exact(vol_model, vol_lh, train_x, target, list(vol_model.parameters()), LR_VOL, train_iters, printing, graph,
                defer=not graph)
