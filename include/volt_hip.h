@@ -529,6 +529,44 @@ int volt_bm_solve_f32(const float* x, const float* vol, const float* sigma2, con
 int volt_bm_solve_f64(const double* x, const double* vol, const double* sigma2, const double* R /*[B,N,H]*/,
                       double* X /*[B,N,H]*/, int* info, void* workspace, int B, int N, int H, void* stream);
 
+/* ---- Joint draws in O(S H) from the two covariances of the forecast that are semiseparable plus a diagonal (DESIGN 4.17;
+ * csrc/chain_draw.hip has the recursion).  For cov(i,i) = c_i, cov(i+1,j) = g_i cov(i,j) (j <= i) and a jitter j on the
+ * diagonal, out = mean + chol(C + j I) z without C: two running scalars per path.  One lane per path, H unbounded and streamed
+ * through LDS in chunks, fp64 arithmetic (z and out carry the entry's type), ONE launch, no workspace, no atomics, bitwise
+ * repeatable, replays from a hipGraph, 64-bit indices.  jitter [G] doubles, >= 0 (a rung of the ladder; 0 is legal).
+ *
+ * volt_markov_draw_*: the Markov posterior of the vol forecaster (BMGP / MultitaskBMGP(posterior="chain")): c = max(diag, 0),
+ * g_i = max(off_i / diag_i, 0), 0 where diag_i <= 0 (off[., H-1] is not read) -- the matrix gp._markov_cov builds.  mean, diag,
+ * off [G,H] doubles; z, out [G,S,H].  flags: VOLT_DRAW_EXP writes exp(out), computed in double and rounded once.
+ * info[g]: 0, or i + 1 for the first step whose e_i + j is not a positive finite number; ALL S x H outputs of the series are
+ * then NaN.
+ * Argument errors: -1 mean, -2 diag, -3 off, -4 z, -5 jitter, -6 out, -7 info NULL; -8 G < 1; -9 S < 1 (or beyond 65535 blocks
+ * of 1024 paths); -10 H < 1; -11 an unknown flag.
+ *
+ * volt_vk_draw_*: the predictive block of the volatility-kernel data model, C = W[min(s,t)] (g = 1), with
+ * W_h = (V_last - rho) + sum_{k <= h} w_k pred_vol_k^2 formed on the fly in fp64: CumTrapz's weights over the H + 1 points
+ * [vol_last, pred_vol] on one uniform step dx (dx / 2 on the first and the last point, dx between) less its first entry.
+ * pred_vol [G,S,H]; vol_last, vlr = V_last - rho, dx [G] doubles; mean [G,H] doubles (tau, m(x_t) and the theta pull folded in
+ * by the caller); z, out [G,S*reps,H]: `reps` >= 1 consecutive paths share a row of pred_vol.
+ * info [G,S]: 0, or i + 1 as above, per pred_vol row; all H outputs of its `reps` paths are then NaN, other paths unchanged.
+ * Argument errors: -1 pred_vol, -2 vol_last, -3 vlr, -4 dx, -5 mean, -6 z, -7 jitter, -8 out, -9 info NULL; -10 G < 1;
+ * -11 S < 1; -12 H < 1; -13 reps < 1 (or more than 2^31 - 1 blocks of 64 paths). */
+#define VOLT_DRAW_EXP 1           /* flag bit of volt_markov_draw_* */
+/* volt_markov_mix_f32: the draws of T eigen-directions carried to the T tasks of MultitaskBMGP(posterior="chain"):
+ * out[s,h,t] = mean[h,t] + sum_j V[t,j] lz[j,s,h], lz [T,S,n] doubles (volt_markov_draw_f64 with G = T), V [T,T] doubles
+ * (row t: task t), mean [n,T], out [S,n,T].  The sum is fp64 in the fixed order j = 0 .. T-1, rounded once.  One launch.
+ * Argument errors: -1 lz, -2 V, -3 mean, -4 out NULL; -5 T < 1 or T > 64; -6 S < 1 (or more than 2^31 - 1 blocks of 64 points); -7 n < 1. */
+int volt_markov_mix_f32(const double* lz /*[T,S,n]*/, const double* V /*[T,T]*/, const float* mean /*[n,T]*/, float* out /*[S,n,T]*/,
+                        int T, int S, int n, void* stream);
+int volt_markov_draw_f32(const double* mean, const double* diag, const double* off, const float* z, const double* jitter,
+                         float* out, int* info, int G, int S, int H, int flags, void* stream);
+int volt_markov_draw_f64(const double* mean, const double* diag, const double* off, const double* z, const double* jitter,
+                         double* out, int* info, int G, int S, int H, int flags, void* stream);
+int volt_vk_draw_f32(const float* pred_vol, const double* vol_last, const double* vlr, const double* dx, const double* mean,
+                     const float* z, const double* jitter, float* out, int* info, int G, int S, int H, int reps, void* stream);
+int volt_vk_draw_f64(const double* pred_vol, const double* vol_last, const double* vlr, const double* dx, const double* mean,
+                     const double* z, const double* jitter, double* out, int* info, int G, int S, int H, int reps, void* stream);
+
 /* ---- GPCV ELBO step for the Brownian-motion prior in O(N^2)  (SingleTaskVariationalGP(prior_solver="linear"): LearnGPCV's
  * default prior, K = vol min(x, x'), without the N x N factorisation).  The step of volt_gpcv_step_f32 / volt_gpcv_cv_step_f32
  * with K given as (x [N], vol [B]) over a grid 0 <= x_0 < x_1 < .. shared by the batch:  A = K + jitter I = D^-1 T D^-T with T

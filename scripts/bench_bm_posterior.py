@@ -39,7 +39,7 @@ def bmgp_arms(T, N, H, warmup):
     y = vp.log() if T > 1 else vp[0].log()
     xs = test_points(tx, H)
     arms = {}
-    for posterior in BMGP.POSTERIORS:
+    for posterior in ("solve", "sweep"):
         lh = gp.GaussianLikelihood(batch_shape=torch.Size([T]) if T > 1 else torch.Size()).cuda()
         m = BMGP(tx, y, lh, solver="linear", posterior=posterior).cuda().eval()
         arms[posterior] = prepare(lambda m=m: m(xs), warmup, False)
@@ -50,7 +50,7 @@ def multitask_arms(N, T, H, warmup):
     tx, vp = data(T, N)
     xs = test_points(tx, H)
     arms = {}
-    for posterior in MultitaskBMGP.POSTERIORS:
+    for posterior in ("solve", "sweep"):
         lh = gp.MultitaskGaussianLikelihood(num_tasks=T).cuda()
         lh.noise = 1e-3
         m = MultitaskBMGP(tx, vp.log().t().contiguous(), lh, solver="linear", posterior=posterior).cuda().eval()

@@ -89,10 +89,16 @@ _SIGS = {
     "volt_bm_post_f64": (C.c_int, [_ptr, _i64] + [_ptr] * 6 + [_i32, _i32, _i32, _ptr]),
     "volt_bm_solve_f32": (C.c_int, [_ptr] * 7 + [_i32, _i32, _i32, _ptr]),
     "volt_bm_solve_f64": (C.c_int, [_ptr] * 7 + [_i32, _i32, _i32, _ptr]),
+    "volt_markov_draw_f32": (C.c_int, [_ptr] * 7 + [_i32] * 4 + [_ptr]),
+    "volt_markov_draw_f64": (C.c_int, [_ptr] * 7 + [_i32] * 4 + [_ptr]),
+    "volt_markov_mix_f32": (C.c_int, [_ptr] * 4 + [_i32] * 3 + [_ptr]),
+    "volt_vk_draw_f32": (C.c_int, [_ptr] * 9 + [_i32] * 4 + [_ptr]),
+    "volt_vk_draw_f64": (C.c_int, [_ptr] * 9 + [_i32] * 4 + [_ptr]),
     "volt_gpcv_bm_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "volt_gpcv_bm_step_f32": (C.c_int, [_ptr, _ptr, _f32] + [_ptr] * 5 + [_i32, _ptr, _ptr, _i32, _f32, _f32, _f32, _f32]
                               + [_ptr] * 7 + [_i32, _i32, _ptr]),
 }
+DRAW_EXP = 1                                            # include/volt_hip.h: VOLT_DRAW_EXP
 SUMMARY_MAX_S, SUMMARY_EXP = 32768, 1                   # include/volt_hip.h: VOLT_SUMMARY_MAX_S, VOLT_SUMMARY_EXP
 
 # measurement / tuning hooks: include/volt_hip_tune.h, not part of the drop-in boundary

@@ -23,7 +23,7 @@ import torch
 from . import rollout_engine
 from .gp import NanError, NotPSDError, NumericalWarning
 from .distributed import shard_range
-from .rollout_utils import _linear_draw, _posterior_draw, _resolve_solver
+from .rollout_utils import _linear_draw, _posterior_draw, _resolve_draw, _resolve_solver
 from .train_utils import LearnGPCV, TrainVoltMagpieBatch, TrainVolModelBatch, TrainVolModelMultitask
 
 _MODES = {"ewma": 0, "dewma": 1, "tewma": 2}
@@ -40,21 +40,31 @@ def realised_vol(train_x, prices, span=20, floor=1e-3):
     return v.clamp_min(floor)
 
 
-def _standard_mean_prediction_linear(train_x, resid, m_te, vol, test_x, pred_vol, z, jitter=1e-4, max_blocks=4096):
+def _standard_mean_prediction_linear(train_x, resid, m_te, vol, test_x, pred_vol, z, jitter=1e-4, max_blocks=4096,
+                                     draw="factor"):
     """`_standard_mean_prediction` with solver="linear" (DESIGN 4.15): the train blocks of all B series are conditioned on by
     ONE volt_vk_forms_* launch (gp._safe_forms) instead of B x S factorisations, and nothing is N x N or N x H.  The stacked
     integrated path of rollout_utils.py:17-26 splits at the last train point: its train part U [B,N] keeps the full weight
     on point N-1 (the halved last weight sits on the last test point), and what the H appended points add on top of U[N-1] is
     the CumTrapz of [vol_{N-1}, pred_vol] less its first entry -- both from ops.cumtrapz in fp64.  The H x H predictive
-    blocks of ``max_blocks`` (series, path) pairs at a time go through `_linear_draw`."""
+    blocks of ``max_blocks`` (series, path) pairs at a time go through `_linear_draw`.
+    ``draw="chain"``: ONE ops.vk_draw launch for all B series instead -- the test part of the integrated path
+    is formed inside the kernel, so there is no ``tail`` / ``V_te`` tensor, no H x H block and no ``max_blocks`` loop: nothing
+    beyond the inputs and the [B,S,H] result."""
     from . import ops
-    from .gp import _safe_forms
+    from .gp import _safe_draw, _safe_forms
     B, S, H = pred_vol.shape
     N = train_x.numel()
     f64 = torch.float64
     x64 = torch.cat((train_x, test_x)).to(f64)
     U = ops.cumtrapz(torch.cat((vol, vol[:, -1:]), -1).to(f64), x64[:N + 1], square=True)[:, :N]      # [B,N]
     forms, _ = _safe_forms(U, resid.to(f64), jitter)                                                   # one launch, B series
+    if draw == "chain":
+        mean = forms[:, 1:2] + m_te.to(f64)                                                            # tau + m(x_t), [B,H]
+        vlr = U[:, -1] - forms[:, 0]
+        pv, zz = pred_vol.to(torch.float32), z.to(torch.float32)
+        out, _ = _safe_draw(lambda j: ops.vk_draw(pv, vol[:, -1], vlr, x64[1] - x64[0], mean, zz, j), (pv, vlr, mean, zz), jitter)
+        return out
     tail = ops.cumtrapz(torch.cat((vol[:, -1:, None].expand(B, S, 1), pred_vol), -1).to(f64), x64[:H + 1], square=True)
     V_last = U[:, -1]
     V_te = V_last[:, None, None] + (tail[..., 1:] - tail[..., :1])                                     # [B,S,H]
@@ -71,20 +81,22 @@ def _standard_mean_prediction_linear(train_x, resid, m_te, vol, test_x, pred_vol
     return out
 
 
-def _standard_mean_prediction(model, train_x, log_y, vol, test_x, pred_vol, z, solver="dense"):
+def _standard_mean_prediction(model, train_x, log_y, vol, test_x, pred_vol, z, solver="dense", draw="factor"):
     """"VOLT + standard mean" (GenerateMultiMeanPreds.py:113-119): ONE joint draw over the whole horizon per path,
     GeneratePrediction(train_x, train_y, test_x, predvol, voltron) with predvol [S,H] -- rollout_utils.py:6-53 -- for
     every series of the batched model in turn (each is its own GP; the S systems of a series run batched on the
     device exactly as in the per-series function).  pred_vol, z [B,S,H] -> samples [B,S,H].
-    ``solver="linear"``: `_standard_mean_prediction_linear`."""
+    ``solver="linear"``: `_standard_mean_prediction_linear`, which takes ``draw``."""
     B, S, H = pred_vol.shape
     N = train_x.numel()
     full_x = torch.cat((train_x, test_x))
     with torch.no_grad():
         m_tr = model.mean_module(train_x.unsqueeze(-1)).reshape(B, N)
         m_te = model.mean_module(test_x.unsqueeze(-1)).reshape(B, H)
-    if _resolve_solver(solver) == "linear":
-        return _standard_mean_prediction_linear(train_x, log_y - m_tr, m_te, vol, test_x, pred_vol, z)
+    solver = _resolve_solver(solver)
+    draw = _resolve_draw(draw, solver)
+    if solver == "linear":
+        return _standard_mean_prediction_linear(train_x, log_y - m_tr, m_te, vol, test_x, pred_vol, z, draw=draw)
     out = torch.empty(B, S, H, device=train_x.device)
     for b in range(B):
         full_vol = torch.cat((vol[b].unsqueeze(0).expand(S, N), pred_vol[b]), -1)        # :17-20
@@ -102,7 +114,7 @@ def _check_vol_posterior(vol_posterior, vol_solver):
 
 def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator,
                  graph, vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False,
-                 predict_solver="dense", vol_posterior="solve", debug=None):
+                 predict_solver="dense", vol_posterior="solve", predict_draw="factor", debug=None):
     """One window for the series in train_y [b, ntrain] (prices): GPCV -> data model -> vol forecasters -> rollouts,
     every stage for all b series at once.  Returns samples [b, S, H] on the device."""
     dev = train_y.device
@@ -134,7 +146,8 @@ def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_ite
                                                       solve="chain" if predict_solver == "linear" else "factor")
         rollout_engine.report_info(info)                # raises where psd_safe_cholesky(pred_cov) would have (:46), warns on a jittered pivot
     else:                                                                                # VOLT + standard mean, :113-119
-        samples = _standard_mean_prediction(model, train_x, train_y[:, 1:].log(), vol, test_x, pred_vol, z, predict_solver)
+        samples = _standard_mean_prediction(model, train_x, train_y[:, 1:].log(), vol, test_x, pred_vol, z, predict_solver,
+                                            predict_draw)
     if debug is not None:
         debug.update(vol=vol, pred_vol=pred_vol, z=z, model=model, train_y=train_y)
     return samples.detach()                                                              # .detach(): :118
@@ -155,7 +168,7 @@ def _window_summary(samples, series, last_day, spec):
 def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample, mean, k, gpcv_iters, vol_iters,
                       data_iters, theta, vol_fn, generator, save, path_fn, debug=None, graph=None, summary=None,
                       keep_samples=True, vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False,
-                      predict_solver="dense", vol_posterior="solve"):
+                      predict_solver="dense", vol_posterior="solve", predict_draw="factor"):
     """One batched pass per window (series [B,T] prices; the window ending at index e trains on series[:, e-ntrain:e]).
     A numerical failure anywhere in the batched pass (NotPSDError / NanError after the jitter ladders) must not take the
     other series down with it: the window is then redone one series at a time, and a series that still fails gets NaN
@@ -172,7 +185,7 @@ def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample,
     summaries = []
     H = test_x.numel()
     args = (nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator, graph, vol_solver, gpcv_solver,
-            data_solver, multitask_vol, predict_solver, vol_posterior)
+            data_solver, multitask_vol, predict_solver, vol_posterior, predict_draw)
     last = None
     for last_day in end_idxs:
         train_y = series[:, last_day - ntrain:last_day].float()                          # [B, ntrain] prices
@@ -210,7 +223,7 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
                                   vol_iters=None, par_dir="./saved-outputs/", generator=None, debug=None, graph=None,
                                   summary=None, keep_samples=True, vol_solver="dense", gpcv_solver="dense",
                                   data_solver="dense", multitask_vol=False, predict_solver="dense",
-                                  vol_posterior="solve"):
+                                  vol_posterior="solve", predict_draw="factor"):
     """closes [B, T] prices for B tickers on a common calendar (device tensor).  Same window schedule,
     model name and file layout as GenerateStockPredictions (GenerateMultiMeanPreds.py:69-83,128); ``mean`` in
     ewma / dewma / tewma takes the Rollouts branch (:110-112), constant / loglinear / linear the "VOLT + standard
@@ -236,8 +249,13 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
     three, and "dense" changes nothing.
     ``vol_posterior="sweep"`` (with ``vol_solver="linear"``): the vol forecaster's posterior from ONE forward sweep per window
     (BMGP / MultitaskBMGP(posterior="sweep"), volt_bm_post_*) instead of a chain solve on K_t* [T,N,H]; the
-    default "solve" changes nothing."""
+    default "solve" changes nothing.  ``vol_posterior="chain"``: the same sweep, and the vol paths are drawn in O(S H) without the
+    H x H covariance (ops.markov_draw).
+    ``predict_draw="chain"`` (with ``predict_solver="linear"``): the joint draw of the standard-mean branch from ONE ops.vk_draw
+    launch for all tickers, with no H x H block per path; the Rollouts branch has its own recursion and is not
+    changed by it; the default "factor" changes nothing."""
     _check_vol_posterior(vol_posterior, vol_solver)
+    _resolve_draw(predict_draw, predict_solver)
     if mean not in _MODES and mean not in _STANDARD:
         raise ValueError(f"unknown mean {mean!r}: one of {sorted(_MODES) + list(_STANDARD)}")
     dev = closes.device
@@ -260,22 +278,23 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
     return _forecast_windows(tickers, closes, end_idxs.tolist(), ntrain, train_x, test_x, nsample, mean, k,
                              train_iters, vol_iters, train_iters, None, vol_fn, generator, save, path_fn, debug, graph,
                              summary, keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol, predict_solver,
-                             vol_posterior)
+                             vol_posterior, predict_draw)
 
 
 def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=400, n_test_times=10, nsample=1000, k=400,
                                  theta=0.01, gpcv_iters=200, vol_iters=500, data_iters=0, save=False, vol_fn=None,
                                  par_dir="./saved-outputs/", generator=None, graph=None, summary=None, keep_samples=True,
                                  vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False,
-                                 predict_solver="dense", vol_posterior="solve"):
+                                 predict_solver="dense", vol_posterior="solve", predict_draw="factor"):
     """The ``--kernel volt --mean ewma`` branch of experiments/weather/GPGenerator.py:20-112 for B stations at once:
     data [B,T] wind speeds (missing = -99 -> 0, then +1 as at :47,55), dt = 1/365 (:38-41), the schedule of test
     windows of :33-34, GPCV 200 / vol model 500 / data model 0 iterations (:64-67,89-92), EWMA(k=400) mean and
     mean-reverting rollouts with theta = 0.01 (:96-102), files ``stn<idx>/volt_ema<k>_theta<theta>_<last_day>.pt``
     (:103-106).  Stations shard across ranks like tickers.  Returns the last window's samples [B_local,S,H] (CPU).
-    ``summary`` / ``keep_samples`` / ``vol_solver`` / ``gpcv_solver`` / ``data_solver`` / ``multitask_vol`` / ``predict_solver`` / ``vol_posterior``: as for GenerateStockPredictionsBatch (the truth is the shifted series,
+    ``summary`` / ``keep_samples`` / ``vol_solver`` / ``gpcv_solver`` / ``data_solver`` / ``multitask_vol`` / ``predict_solver`` / ``vol_posterior`` / ``predict_draw``: as for GenerateStockPredictionsBatch (the truth is the shifted series,
     data + 1)."""
     _check_vol_posterior(vol_posterior, vol_solver)
+    _resolve_draw(predict_draw, predict_solver)
     dev = data.device
     lo, hi = shard_range(len(stations))
     stations, data = list(stations)[lo:hi], data[lo:hi].float()
@@ -291,4 +310,5 @@ def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=40
                             str(last_day) + ".pt")
     return _forecast_windows(stations, data, end_idxs, ntrain, train_x, test_x, nsample, "ewma", k, gpcv_iters,
                              vol_iters, data_iters, theta, vol_fn, generator, save, path_fn, None, graph, summary,
-                             keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol, predict_solver, vol_posterior)
+                             keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol, predict_solver, vol_posterior,
+                             predict_draw)

@@ -288,6 +288,70 @@ def _markov_cov(diag, off):
     return upper + torch.triu(upper, 1).mT
 
 
+class _MarkovCov(_Evaluated):
+    """Lazy covariance of a Markov posterior over H points (BMGP / MultitaskBMGP(posterior="chain")):
+    ``scale`` * _markov_cov(diag, off) over the points in ASCENDING order, with ``order`` the permutation that sorted the
+    caller's points (None: they were ascending) -- what `_posterior_sweep` builds at once.  diag, off [..,H] fp64; scale None
+    or [T] (the eigen-directions' kappa_j).  The [..,H,H] matrix is formed, through `_markov_cov`, only when ``.evaluate()`` /
+    ``.to_dense()`` / ``.tensor`` is asked for, and rounded to ``dtype``; draws go through `draw`, which never forms it.
+
+    Unsorted points: the chain runs over the sorted points, the N(0,1) number at the caller's position i drives the point at
+    position i, and the result comes back in the caller's order: mean + P L_sorted P' z with P the sort's permutation.  For
+    ascending points (what every driver passes) that is the dense route's mean + chol(C) z path by path; for other orders
+    it has the same distribution but is a different root of C than chol(C) of the unsorted matrix."""
+
+    def __init__(self, diag, off, order=None, scale=None, dtype=torch.float32, mean=None):
+        self.diag, self.off, self.order, self.scale, self.dtype = diag, off, order, scale, dtype
+        self.mean = mean                  # the posterior mean before its rounding to ``dtype`` (fp64, the caller's order), or None
+
+    @property
+    def tensor(self):
+        cov = _markov_cov(self.diag, self.off)
+        if self.scale is not None:
+            cov = self.scale.reshape(-1, 1, 1) * cov
+        if self.order is not None:
+            full = torch.empty_like(cov)
+            full[..., self.order.unsqueeze(-1), self.order.unsqueeze(0)] = cov
+            cov = full
+        return cov.to(self.dtype)
+
+    @tensor.setter
+    def tensor(self, v):
+        raise AttributeError("read-only")
+
+    def evaluate(self):
+        return self.tensor
+
+    def to_dense(self):
+        return self.tensor
+
+    def detach(self):
+        return self.tensor
+
+    @property
+    def shape(self):
+        H = self.diag.shape[-1]
+        return torch.Size((*self.diag.shape[:-1], H, H))
+
+    def draw(self, mean, z, exp=False):
+        """mean + L z for z [G,S,H] (G = the number of chains, 1 for an unbatched posterior) and mean [G,H] or None, both in
+        the CALLER's order of the points, on ops.markov_draw under `_safe_draw`'s jitter ladder; [G,S,H] in z's dtype."""
+        H = self.diag.shape[-1]
+        diag, off = self.diag.reshape(-1, H), self.off.reshape(-1, H)
+        if self.scale is not None:
+            diag, off = self.scale.reshape(-1, 1) * diag, self.scale.reshape(-1, 1) * off
+        mean = torch.zeros_like(diag) if mean is None else mean.reshape(-1, H).to(torch.float64)
+        if self.order is not None:
+            mean, z = mean[:, self.order], z[..., self.order]
+        out, _ = _safe_draw(lambda j: ops.markov_draw(mean, diag, off, z, j, exp=exp), (diag, off, mean, z),
+                            f64=self.dtype == torch.float64)
+        if self.order is not None:
+            back = torch.empty_like(out)
+            back[..., self.order] = out
+            out = back
+        return out
+
+
 def check_grid(x, who):
     """What the linear-time solvers (csrc/bm.hip, csrc/gpcv_bm.hip) need of their 1-D grid ``x``, checked once with ONE host
     read: x[0] >= 0 and strictly increasing.  ``who`` names the caller in the message."""
@@ -418,11 +482,17 @@ class MultivariateNormal:
         return torch.diagonal(self.covariance_matrix, dim1=-2, dim2=-1)
 
     def rsample(self, sample_shape=torch.Size(), base_samples=None):
-        cov = self.covariance_matrix
-        L = psd_safe_cholesky(cov)
         shape = torch.Size(sample_shape) + self.loc.shape
         if base_samples is None:
             base_samples = torch.randn(shape, dtype=self.loc.dtype, device=self.loc.device)
+        if isinstance(self._covar, _MarkovCov):              # posterior="chain": O(S H), no H x H matrix (ops.markov_draw)
+            H = self.loc.shape[-1]
+            G = self.loc.numel() // H
+            zb = base_samples.reshape(-1, G, H).transpose(0, 1).to(self.loc.dtype)         # [G,S,H] (a view when G = 1)
+            out = self._covar.draw(self.loc if self._covar.mean is None else self._covar.mean, zb)   # (fp64 mean: ONE rounding, the output's)
+            return out.transpose(0, 1).reshape(base_samples.shape)
+        cov = self.covariance_matrix
+        L = psd_safe_cholesky(cov)
         # loc + L z on the library GEMM: rows of z times L' (batched covariances: the batch leads the GEMM)
         H = L.shape[-1]
         if L.ndim == 2:
@@ -506,7 +576,7 @@ class MultitaskMultivariateNormal:
     @property
     def covariance_matrix(self):
         if self._blocks is not None:
-            V, C = self._blocks
+            V, C = self._dense_blocks()
             n, T = self.loc.shape
             return torch.einsum("tj,sj,jhk->htks", V, V, C).reshape(n * T, n * T)
         return _dense(self._covar)
@@ -514,16 +584,21 @@ class MultitaskMultivariateNormal:
     @property
     def variance(self):
         if self._blocks is not None:
-            V, C = self._blocks
+            V, C = self._dense_blocks()
             return torch.einsum("jh,tj->ht", torch.diagonal(C, dim1=-2, dim2=-1), V * V)
         return torch.diagonal(self.covariance_matrix).reshape(self.loc.shape)
+
+    def _dense_blocks(self):
+        """(V, C [T,n,n]): a lazy C (gp._MarkovCov, posterior="chain") is densified here, on request only."""
+        V, C = self._blocks
+        return V, _dense(C)
 
     def root_blocks(self):
         """(V [T,T], L [T,n,n]) of the posterior form: L_j L_j' = C_j from the HIP potrf (psd_safe_cholesky's jitter policy)."""
         if self._blocks is None:
             raise ValueError("root_blocks: not a Kronecker posterior")
         if self._root is None:
-            V, C = self._blocks
+            V, C = self._dense_blocks()
             self._root = (V, psd_safe_cholesky(C))
         return self._root
 
@@ -537,9 +612,13 @@ class MultitaskMultivariateNormal:
         if self._blocks is None:                                  # prior form: the dense root, on the HIP factorisation
             flat = MultivariateNormal(self.loc.reshape(-1), self.covariance_matrix)
             return flat.rsample(base_samples=base_samples.reshape(*base_samples.shape[:-2], n * T)).reshape(base_samples.shape)
-        V, L = self.root_blocks()
         z = base_samples.reshape(-1, n, T).to(torch.float32)
         S = z.shape[0]
+        if isinstance(self._blocks[1], _MarkovCov):          # posterior="chain": every L_j z_j from ONE ops.markov_draw launch, G = T
+            lz = self._blocks[1].draw(None, z.permute(2, 0, 1).to(torch.float64))             # [T,S,n], kept in fp64 ...
+            out = ops.markov_mix(lz, self._blocks[0], self.loc)                               # ... through V': ONE rounding, the output's
+            return out.to(self.loc.dtype).reshape(base_samples.shape)
+        V, L = self.root_blocks()
         lz = ops.gemm_nt(z.permute(2, 0, 1).contiguous(), L.to(torch.float32), uplo_b=1)      # [T,S,n]: (L_j z_j)'
         lz = lz.permute(1, 2, 0).reshape(S * n, T)
         out = self.loc + ops.gemm_nt(lz, V.to(torch.float32)).reshape(S, n, T).to(self.loc.dtype)
@@ -1035,6 +1114,27 @@ def _safe_forms(V, resid, jitter=None, max_tries=3):
     for i in range(max_tries):
         jitter_new = jitter * (10 ** i)
         out, info = ops.vk_forms(V, jitter_new, resid)
+        if not bool((info != 0).any().item()):
+            warnings.warn(f"A not p.d., added jitter of {jitter_new:.1e} to the diagonal", NumericalWarning)
+            return out, jitter_new
+    raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitter_new:.1e}.")
+
+
+def _safe_draw(draw, inputs=(), jitter=None, max_tries=3, f64=False):
+    """`_safe_forms`'s retry policy around a chain draw (ops.markov_draw / ops.vk_draw): ``draw(j) -> (out, info)`` is tried
+    plain first (j = 0), then with jitter * 10^i for the whole batch; the default rung is 1e-6, or 1e-8 for an fp64 model
+    (``f64``), as in `_safe_factor`.  ``inputs``: the tensors looked at for NaN on a failure.  Returns (out, the jitter used)."""
+    out, info = draw(0.0)
+    if not bool((info != 0).any().item()):
+        return out, 0.0
+    for t in inputs:
+        if torch.is_tensor(t) and torch.isnan(t).any():
+            raise NanError(f"cholesky_cpu: {int(torch.isnan(t).sum())} of {t.numel()} elements of the {tuple(t.shape)} tensor are NaN.")
+    if jitter is None:
+        jitter = 1e-8 if f64 else 1e-6
+    for i in range(max_tries):
+        jitter_new = jitter * (10 ** i)
+        out, info = draw(jitter_new)
         if not bool((info != 0).any().item()):
             warnings.warn(f"A not p.d., added jitter of {jitter_new:.1e} to the diagonal", NumericalWarning)
             return out, jitter_new

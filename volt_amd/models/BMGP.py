@@ -15,7 +15,7 @@ import torch
 
 from .. import ops
 from ..gp import (ExactGP, MultitaskMultivariateNormal, MultivariateNormal, NanError, NotPSDError, _BrownianPrior, _KroneckerPrior,
-                  _markov_cov, _safe_factor, check_grid, same_values)
+                  _MarkovCov, _markov_cov, _safe_factor, check_grid, same_values)
 from ..kernels.BMKernel import BMKernel
 from ..kernels.FBMKernel import FBMKernel
 from ..kernels.MultitaskKernel import MultitaskKernel
@@ -26,6 +26,14 @@ def _check_posterior(who, posterior, solver):
         raise ValueError(f"{who}: posterior must be one of {BMGP.POSTERIORS}, got {posterior!r}")
     if posterior != "solve" and solver != "linear":
         raise ValueError(f"{who}: posterior={posterior!r} needs solver='linear' (the dense solver has one posterior)")
+
+
+def _sort_order(xs, order):
+    """``order`` (the permutation that sorted xs), or None where xs was ascending already (ONE host read): the chain draw then
+    skips the gather of z and the scatter of the result."""
+    if xs.shape[0] < 2 or bool((xs[1:] >= xs[:-1]).all()):
+        return None
+    return order
 
 
 def _check_post_info(info, order, who, params, not_psd):
@@ -51,9 +59,11 @@ class BMGP(ExactGP):
     The training grid is validated ONCE here (one host read): 1-D, x_0 >= 0, strictly increasing.
     ``posterior`` (solver="linear" only): "solve" (default) conditions through ops.bm_step / ops.bm_solve on K_t* [T,N,H];
     "sweep" through ONE forward sweep (ops.bm_post) that forms the clipped increments of K_t* on the fly and
-    rebuilds the H x H covariance from its diagonal and first off-diagonal (the posterior is Markov): nothing is N x H."""
+    rebuilds the H x H covariance from its diagonal and first off-diagonal (the posterior is Markov): nothing is N x H;
+    "chain" is the same sweep with the covariance left lazy (gp._MarkovCov): samples come from ops.markov_draw in O(S H) and
+    the H x H matrix is built only when ``.covariance_matrix`` / ``.variance`` is asked for."""
     SOLVERS = ("dense", "linear")
-    POSTERIORS = ("solve", "sweep")
+    POSTERIORS = ("solve", "sweep", "chain")
     _POST_CHUNK = 4096                        # rows of K_t* per fp64 product of the linear posterior (bounds its temporaries)
 
     def __init__(self, train_x, train_y, likelihood, kernel="bm", solver="dense", posterior="solve"):
@@ -151,6 +161,13 @@ class BMGP(ExactGP):
                              "vol min(x, x') + sigma^2 I is not positive definite (the noise must be positive)")
             prior = vol.double().reshape(T, 1) * xs64
             mean_s = self.mean_module(xs64).reshape(T, H) + out[:, 0]
+            if self.posterior == "chain":                      # the same forms, the covariance left lazy
+                mean = torch.empty_like(mean_s)
+                mean[:, order] = mean_s
+                diag, off = prior - out[:, 1], prior - out[:, 2]
+                if not batched:
+                    mean, diag, off = mean[0], diag[0], off[0]
+                return MultivariateNormal(mean.to(dt), _MarkovCov(diag, off, _sort_order(xs, order), dtype=dt, mean=mean))
             cov_s = _markov_cov(prior - out[:, 1], prior - out[:, 2])
             mean = torch.empty_like(mean_s)
             mean[:, order] = mean_s
@@ -165,9 +182,9 @@ class BMGP(ExactGP):
         """Exact-GP posterior at the test points: K_s = L L' on the HIP potrf, K_s^-1 = Y Y' with Y = L^-T from the HIP
         triangular inverse, every product on the library GEMM.  One series -> MultivariateNormal(mean [H], cov [H,H]);
         T series over the shared grid -> (mean [T,H], cov [T,H,H]).  solver="linear": _posterior_linear, or _posterior_sweep
-        with posterior="sweep"."""
+        with posterior="sweep" / "chain"."""
         if self.solver == "linear":
-            return self._posterior_sweep(x) if self.posterior == "sweep" else self._posterior_linear(x)
+            return self._posterior_linear(x) if self.posterior == "solve" else self._posterior_sweep(x)
         with torch.no_grad():
             from ..gp import _dense
             xt = self.train_inputs[0]
@@ -214,7 +231,8 @@ class MultitaskBMGP(ExactGP):
     (ops.kron_bm_step) and the posterior run in O(T N + T^2 N) with no N x N matrix anywhere; ``forward`` returns
     the lazy prior over the training grid, which is validated ONCE here (one host read): 1-D, x_0 >= 0, strictly increasing.
     ``posterior`` (solver="linear" only): "solve" (default) or "sweep", as for BMGP -- one ops.bm_post launch for all
-    eigen-directions instead of a chain solve per group of test points."""
+    eigen-directions instead of a chain solve per group of test points -- or "chain": the sweep with the blocks
+    C_j left lazy, every L_j z_j of a draw from one ops.markov_draw launch."""
     SOLVERS = BMGP.SOLVERS
     POSTERIORS = BMGP.POSTERIORS
     _POST_CHUNK = BMGP._POST_CHUNK
@@ -331,12 +349,18 @@ class MultitaskBMGP(ExactGP):
             out, info = ops.bm_post(x64, xs64, ws.ones, ws.sigma2, ws.resid)
             _check_post_info(info, order, "MultitaskBMGP", params + (Y,), "M + sigma_j^2 I is not positive definite")
             mt_s = kap.sqrt().reshape(T, 1) * out[:, 0]                                    # m~_j over the sorted points
+            V64 = ws.d().sqrt().unsqueeze(-1) * ws.Q()                                     # D^1/2 Q
+            if self.posterior == "chain":                      # the same forms, the blocks C_j left lazy
+                mt = torch.empty_like(mt_s)
+                mt[:, order] = mt_s
+                mean = (self.mean_module(xs).double() + mt.t() @ V64.t()).to(torch.float32)
+                C = _MarkovCov(xs64 - out[:, 1], xs64 - out[:, 2], _sort_order(xs, order), scale=kap, dtype=torch.float32)
+                return MultitaskMultivariateNormal(mean, blocks=(V64.to(torch.float32), C))
             C_s = kap.reshape(T, 1, 1) * _markov_cov(xs64 - out[:, 1], xs64 - out[:, 2])
             mt = torch.empty_like(mt_s)
             mt[:, order] = mt_s
             C = torch.empty_like(C_s)
             C[:, order.unsqueeze(-1), order.unsqueeze(0)] = C_s
-            V64 = ws.d().sqrt().unsqueeze(-1) * ws.Q()                                     # D^1/2 Q
             mean = (self.mean_module(xs).double() + mt.t() @ V64.t()).to(torch.float32)
             return MultitaskMultivariateNormal(mean, blocks=(V64.to(torch.float32), C.to(torch.float32)))
 
@@ -346,9 +370,9 @@ class MultitaskBMGP(ExactGP):
         r_j; then per block m~_j = sqrt(kappa_j) M_*x (M + sigma_j^2 I)^-1 r_j and C_j = kappa_j [M_** - M_*x (M +
         sigma_j^2 I)^-1 M_x*] on the HIP potrf / triangular inverse / GEMM, as BMGP.posterior_call does; finally
         mean = mu_* + m~ V' and cov = (I (x) V) blockdiag(C_j) (I (x) V'), V = D^1/2 Q.  solver="linear": _posterior_linear, or
-        _posterior_sweep with posterior="sweep"."""
+        _posterior_sweep with posterior="sweep" / "chain"."""
         if self.solver == "linear":
-            return self._posterior_sweep(x) if self.posterior == "sweep" else self._posterior_linear(x)
+            return self._posterior_linear(x) if self.posterior == "solve" else self._posterior_sweep(x)
         with torch.no_grad():
             xt = self.train_inputs[0][:, 0]
             Y = self.train_targets

@@ -22,7 +22,7 @@ _MEAN_CLASSES = {"ewma": EWMAMean, "dewma": DEWMAMean, "tewma": TEWMAMean}
 
 class Volt(VolGP):
     def __init__(self, train_x, log_data, mean='constant', vol_path=None, k=25, *, multitask_vol=False, vol_solver="dense",
-                 data_solver="dense", predict_solver="dense", vol_posterior="solve"):
+                 data_solver="dense", predict_solver="dense", vol_posterior="solve", predict_draw="factor"):
         # The reference builds the ExactGP on [1:] but keeps the FULL train_x / log_data as attributes (Volt.py:52-62);
         # with a vol_path of length N-1 its own train_cov line is then shape-inconsistent.  The [1:] view is kept
         # everywhere here, so that train_cov matches train_inputs.
@@ -36,7 +36,7 @@ class Volt(VolGP):
         else:
             raise ValueError("ERROR: Mean not implemented")      # the reference prints this and fails on the next line
         self._init_vol_state(x, y, vol_path, multitask_vol, vol_solver, data_solver, predict_solver,
-                             vol_posterior)
+                             vol_posterior, predict_draw)
         self._full_x, self._full_log_data = train_x, log_data    # Train's GPCV stage starts from the prices
 
     def Train(self, gpcv_iters=400, vol_mod_iters=1000, data_mod_iters=400, display=False, vol=None,

@@ -13,7 +13,7 @@ from .BMGP import BMGP, MultitaskBMGP, _check_posterior
 
 class VolGP(ExactGP):
     def _init_vol_state(self, x, y, vol_path, multitask_vol=False, vol_solver="dense", data_solver="dense",
-                        predict_solver="dense", vol_posterior="solve"):
+                        predict_solver="dense", vol_posterior="solve", predict_draw="factor"):
         """x [N], y [N] or [T,N] (batched layout: one shared input grid, T target / vol rows), vol_path like y or None.
         Call after ``mean_module`` is set so that the modules register in the reference's order.  ``multitask_vol`` (batched
         models only): the reference's own vol forecaster, a MultitaskBMGP over the [N,T] log-vol paths with a
@@ -24,11 +24,14 @@ class VolGP(ExactGP):
         ``predict_solver="linear"``: GeneratePrediction / SamplePrediction / MeanPrediction, rollout_utils.GeneratePrediction
         and Rollouts condition on the train block through the O(N) chain (volt_vk_forms_*) instead of filling
         and factoring it; independent of ``data_solver`` (a dense-trained model may predict linearly), and "dense" changes
-        nothing.  ``vol_posterior`` (with ``vol_solver="linear"``): the vol forecaster's ``posterior``, "solve" or "sweep"
-        (BMGP / MultitaskBMGP)."""
+        nothing.  ``vol_posterior`` (with ``vol_solver="linear"``): the vol forecaster's ``posterior``, "solve", "sweep" or "chain"
+        (BMGP / MultitaskBMGP).  ``predict_draw`` (with ``predict_solver="linear"``): "factor" (default) fills
+        and factors the T x T predictive block of a joint draw, "chain" draws it in O(T) per path (ops.vk_draw)."""
         if predict_solver not in BMGP.SOLVERS:
             raise ValueError(f"predict_solver must be one of {BMGP.SOLVERS}, got {predict_solver!r}")
         self.predict_solver = predict_solver
+        from ..rollout_utils import _resolve_draw
+        self.predict_draw = _resolve_draw(predict_draw, predict_solver)
         if data_solver not in BMGP.SOLVERS:
             raise ValueError(f"data_solver must be one of {BMGP.SOLVERS}, got {data_solver!r}")
         self.data_solver = data_solver        # Volt.Train fits the data model with the solver the model was built with

@@ -437,6 +437,100 @@ def bm_post(x: torch.Tensor, xs_sorted: torch.Tensor, vol: torch.Tensor, sigma2:
     return out, info
 
 
+def _draw_buffers(z, out, info, info_shape):
+    """The output pair of the chain draws: the caller's ``out`` / ``info`` (contiguous, z's shape and dtype / int32) or fresh ones."""
+    if out is None:
+        out = torch.empty_like(z)
+    elif out.shape != z.shape or out.dtype != z.dtype or not out.is_contiguous() or out.device != z.device:
+        raise ValueError("out must be contiguous with z's shape, dtype and device")
+    if info is None:
+        info = torch.empty(info_shape, dtype=torch.int32, device=z.device)
+    elif tuple(info.shape) != tuple(info_shape) or info.dtype != torch.int32 or not info.is_contiguous() or info.device != z.device:
+        raise ValueError(f"info must be a contiguous int32 tensor of shape {tuple(info_shape)} on z's device")
+    return out, info
+
+
+def _per_series(v, G, device):
+    return torch.as_tensor(v, dtype=torch.float64, device=device).reshape(-1).expand(G).contiguous()
+
+
+def markov_draw(mean: torch.Tensor, diag: torch.Tensor, off: torch.Tensor, z: torch.Tensor, jitter=0.0, exp: bool = False,
+                out: torch.Tensor | None = None, info: torch.Tensor | None = None):
+    """mean + chol(C + jitter I) z in O(S H) for the Markov covariance C = gp._markov_cov(diag, off), never formed
+    (volt_markov_draw_f32 / _f64 by z's dtype; fp64 arithmetic either way).  mean, diag, off [G,H] (the last entry of
+    off is not read); z [G,S,H]; jitter a number or [G], >= 0; ``exp``: the exponential of the draw, computed in double and
+    rounded once.  Strided inputs are accepted (copied where the kernel needs them dense).  Returns (out [G,S,H] in z's dtype,
+    info [G] int32) -- ``out`` / ``info`` given: written in place.  info[g] = i + 1 at the first step whose pivot is not a
+    positive finite number; the series' outputs are then all NaN."""
+    _need_gpu(mean, diag, off, z, jitter if torch.is_tensor(jitter) else None)
+    if z.ndim != 3:
+        raise ValueError("z must be [G,S,H]")
+    G, S, H = z.shape
+    if G < 1 or S < 1 or H < 1:
+        raise ValueError("z [G,S,H] must not be empty")
+    for name, t in (("mean", mean), ("diag", diag), ("off", off)):
+        if tuple(t.shape) != (G, H):
+            raise ValueError(f"{name} must be [G,H] = {(G, H)}, got {tuple(t.shape)}")
+    dt = torch.float64 if z.dtype == torch.float64 else torch.float32
+    z = z.to(dt).contiguous()
+    mean, diag, off = (t.to(torch.float64).contiguous() for t in (mean, diag, off))
+    jit = _per_series(jitter, G, z.device)
+    out, info = _draw_buffers(z, out, info, (G,))
+    fn = _lib.lib().volt_markov_draw_f32 if dt == torch.float32 else _lib.lib().volt_markov_draw_f64
+    with torch.cuda.device(z.device):
+        _lib.check(fn(mean.data_ptr(), diag.data_ptr(), off.data_ptr(), z.data_ptr(), jit.data_ptr(), out.data_ptr(),
+                      info.data_ptr(), G, S, H, _lib.DRAW_EXP if exp else 0, _lib.stream_ptr()), "volt_markov_draw")
+    return out, info
+
+
+def markov_mix(lz: torch.Tensor, V: torch.Tensor, mean: torch.Tensor) -> torch.Tensor:
+    """mean + (L_j z_j)_j V' of a MultitaskBMGP(posterior="chain") draw (volt_markov_mix_f32): lz [T,S,n] fp64 (ops.markov_draw
+    with G = T), V [T,T], mean [n,T].  The sum over the T directions is fp64 in a fixed order, rounded once.  Returns [S,n,T] fp32."""
+    _need_gpu(lz, V, mean)
+    if lz.ndim != 3 or lz.dtype != torch.float64:
+        raise ValueError("lz must be [T,S,n] float64")
+    T, S, n = lz.shape
+    if tuple(V.shape) != (T, T) or tuple(mean.shape) != (n, T):
+        raise ValueError(f"V must be [T,T] = {(T, T)} and mean [n,T] = {(n, T)}, got {tuple(V.shape)} and {tuple(mean.shape)}")
+    lz, V, mean = lz.contiguous(), V.to(torch.float64).contiguous(), mean.to(torch.float32).contiguous()
+    out = torch.empty(S, n, T, dtype=torch.float32, device=lz.device)
+    with torch.cuda.device(lz.device):
+        _lib.check(_lib.lib().volt_markov_mix_f32(lz.data_ptr(), V.data_ptr(), mean.data_ptr(), out.data_ptr(), T, S, n,
+                                                  _lib.stream_ptr()), "volt_markov_mix")
+    return out
+
+
+def vk_draw(pred_vol: torch.Tensor, vol_last, vlr, dx, mean: torch.Tensor, z: torch.Tensor, jitter=0.0, reps: int = 1,
+            out: torch.Tensor | None = None, info: torch.Tensor | None = None):
+    """The joint draw over H appended points from the volatility-kernel data model in O(S H) (volt_vk_draw_f32 / _f64 by z's
+    dtype; fp64 arithmetic either way): mean + chol(W[min(s,t)] + jitter I) z with W_h = vlr + the CumTrapz of
+    [vol_last, pred_vol]^2 over a uniform step dx less its first entry, formed on the fly.  pred_vol [G,S,H]; vol_last, vlr
+    (= V_last - rho), dx, jitter numbers or [G]; mean [G,H]; z [G,S*reps,H]: ``reps`` consecutive paths share a row of
+    pred_vol.  Returns (out like z, info [G,S] int32; ``out`` / ``info`` given: written in place); info = i + 1 at the first
+    failed pivot of a pred_vol row, whose paths are then all NaN."""
+    _need_gpu(pred_vol, mean, z, *(t for t in (vol_last, vlr, dx, jitter) if torch.is_tensor(t)))
+    if pred_vol.ndim != 3 or z.ndim != 3:
+        raise ValueError("pred_vol must be [G,S,H] and z [G,S*reps,H]")
+    G, S, H = pred_vol.shape
+    if G < 1 or S < 1 or H < 1 or reps < 1:
+        raise ValueError("pred_vol [G,S,H] must not be empty and reps >= 1")
+    if tuple(z.shape) != (G, S * reps, H):
+        raise ValueError(f"z must be [G,S*reps,H] = {(G, S * reps, H)}, got {tuple(z.shape)}")
+    if tuple(mean.shape) != (G, H):
+        raise ValueError(f"mean must be [G,H] = {(G, H)}, got {tuple(mean.shape)}")
+    dt = torch.float64 if z.dtype == torch.float64 else torch.float32
+    z = z.to(dt).contiguous()
+    pred_vol = pred_vol.to(dt).contiguous()
+    mean = mean.to(torch.float64).contiguous()
+    vol_last, vlr, dx, jit = (_per_series(t, G, z.device) for t in (vol_last, vlr, dx, jitter))
+    out, info = _draw_buffers(z, out, info, (G, S))
+    fn = _lib.lib().volt_vk_draw_f32 if dt == torch.float32 else _lib.lib().volt_vk_draw_f64
+    with torch.cuda.device(z.device):
+        _lib.check(fn(pred_vol.data_ptr(), vol_last.data_ptr(), vlr.data_ptr(), dx.data_ptr(), mean.data_ptr(), z.data_ptr(),
+                      jit.data_ptr(), out.data_ptr(), info.data_ptr(), G, S, H, reps, _lib.stream_ptr()), "volt_vk_draw")
+    return out, info
+
+
 def bm_solve(x: torch.Tensor, vol: torch.Tensor, sigma2: torch.Tensor, R: torch.Tensor, ws: BmWorkspace | None = None):
     """X = (vol_b min(x, x') + sigma2_b I)^-1 R_b in O(N H) per series (volt_bm_solve_f32 / _f64 by R's dtype).
     R [B,N,H].  Returns (X [B,N,H], info [B]); they live in ``ws``."""

@@ -26,7 +26,7 @@ import warnings
 import torch
 
 from . import ops
-from .gp import NanError, NotPSDError, NumericalWarning, _safe_factor
+from .gp import NanError, NotPSDError, NumericalWarning, _safe_draw, _safe_factor
 
 
 def _chol_1x1(pc: torch.Tensor, jitter):
@@ -91,18 +91,54 @@ def _resolve_solver(solver, model=None):
     return solver
 
 
+DRAWS = ("factor", "chain")
+
+
+def _resolve_draw(draw, solver, model=None):
+    """``draw=None`` reads the model's ``predict_draw`` ("factor" for a model without one).  "chain" (ops.vk_draw, DESIGN
+    4.17) exists on the linear route only."""
+    if draw is None:
+        draw = getattr(model, "predict_draw", "factor")
+    if draw not in DRAWS:
+        raise ValueError(f"draw must be one of {DRAWS}, got {draw!r}")
+    if draw == "chain" and solver != "linear":
+        raise ValueError("draw='chain' needs solver='linear' (predict_solver='linear'): the dense route factors its own blocks")
+    return draw
+
+
 def _rows_shared(t):
     """Whether the rows of t [S,n] are one row (an expanded view, or equal values: one device read)."""
     return t.shape[0] == 1 or t.stride(0) == 0 or bool((t == t[:1]).all())
 
 
-def _linear_draw(rho, tau, V_last, V_te, test_mean_term, z, jitter, latent_mean, theta, dt):
+def _linear_draw(rho, tau, V_last, V_te, test_mean_term, z, jitter, latent_mean, theta, dt, draw="factor", test_vol=None):
     """The draw from the conditional whose train block enters through rho = u'A^-1 u and tau = u'A^-1 r (fp64, [G] each with
     G = S or 1) -- every appended point has the same cross-covariance u = V with the train block, so
         mean_t = tau + m(x_t),     cov_st = V_te[min(s,t)] - rho = (V_te[min(s,t)] - V_last) + (V_last - rho),
     the sum of the test increments plus what the jitter rung leaves of the last train entry, in fp64 (the two terms of the
-    second bracket agree to rounding at rung 0).  V_te [S,T] fp64, z [S,T,n].  Returns samples + pred_mean [S,T,n] in ``dt``."""
+    second bracket agree to rounding at rung 0).  V_te [S,T] fp64, z [S,T,n].  Returns samples + pred_mean [S,T,n] in ``dt``.
+    ``draw="chain"``: the same draw from ONE ops.vk_draw launch in O(T) per path -- no [S,T,T] array, no
+    factorisation; T = 1 is the chain's first step.  It forms W itself from ``test_vol`` = (vol_last [G], pred_vol [S,T], dx
+    [G] or a number): the last train vol, the test vols and the uniform grid step; ``V_te`` is not read (pass None)."""
     f64 = torch.float64
+    if draw == "chain":
+        vol_last, pred_vol, dx = test_vol
+        S, T = pred_vol.shape
+        n = z.shape[-1]
+        pred_mean = tau.reshape(-1, 1, 1) + test_mean_term.to(f64)
+        if latent_mean is not None:
+            pred_mean = pred_mean - theta * (pred_mean - torch.as_tensor(latent_mean, device=pred_vol.device).to(f64))
+        vlr = (V_last - rho).reshape(-1)
+        shared = pred_mean.shape[0] == 1 and all(not torch.is_tensor(t) or t.numel() == 1 for t in (vlr, vol_last, dx))
+        G, Sg = (1, S) if shared else (S, 1)                                             # one series of S paths, or S series of one
+        mean = pred_mean.expand(G, T, 1).reshape(G, T)
+        zc = z.to(dt).mT.reshape(G, Sg * n, T)                                             # [S,n,T]: the n columns are `reps`
+        pv = pred_vol.to(dt).reshape(G, Sg, T)
+        if T == 1 and jitter is None:
+            jitter = 1e-6                                                                  # `_chol_1x1`'s first rung, whatever the dtype
+        out, _ = _safe_draw(lambda j: ops.vk_draw(pv, vol_last, vlr, dx, mean, zc, j, reps=n), (pv, vlr, mean, zc), jitter,
+                            f64=dt == f64)
+        return out.reshape(S, n, T).mT
     S, T = V_te.shape
     pred_mean = tau.reshape(-1, 1, 1) + test_mean_term.to(f64)                            # [S,T,1] (or broadcastable)
     if latent_mean is not None:
@@ -119,13 +155,15 @@ def _linear_draw(rho, tau, V_last, V_te, test_mean_term, z, jitter, latent_mean,
 
 
 def _posterior_draw_linear(covar_module, full_x, full_vol, idx_cut, train_diffs, test_mean_term, z, jitter,
-                           latent_mean=None, theta=0.5):
+                           latent_mean=None, theta=0.5, draw="factor"):
     """`_posterior_draw` without any N x N or N x T array (solver="linear"): same arguments, same result to
     rounding.  The stacked integrated path V comes from ops.cumtrapz in fp64; its first N entries are the train block
     K = V[min(i,j)] (they do not depend on the test vols: CumTrapz's halved last weight sits on the last test point), and the
     train block enters only through the two scalars of gp._safe_forms (volt_vk_forms_*, one O(N) sweep per grid, the
     project's jitter ladder around it).  One grid serves all S samples when their train rows are shared; per-sample histories
-    (the dense Rollouts engine after its first step) run as S grids in one launch."""
+    (the dense Rollouts engine after its first step) run as S grids in one launch.
+    ``draw="chain"``: the integrated path is formed over the train part alone (the same products in the same order: its N
+    entries are bit for bit those of the stacked path) and the test part inside ops.vk_draw -- `_linear_draw`."""
     from .gp import _safe_forms
     from .kernels import VolatilityKernel
     if not isinstance(covar_module, VolatilityKernel):
@@ -139,8 +177,14 @@ def _posterior_draw_linear(covar_module, full_x, full_vol, idx_cut, train_diffs,
     S, T = vol.shape[0], vol.shape[-1] - N
     td = train_diffs.reshape(-1, N) if train_diffs.ndim > 1 else train_diffs.reshape(1, N)
     one_x = _rows_shared(x)
-    V = ops.cumtrapz(vol.to(f64), (x[0] if one_x else x).to(f64), square=True)             # [S,N+T]
     G = 1 if one_x and _rows_shared(vol[:, :N]) and _rows_shared(td) else S              # grids: one for all samples, or one each
+    if draw == "chain":
+        xg = (x[0] if one_x else x[:G]).to(f64)
+        U = ops.cumtrapz(torch.cat((vol[:G, :N], vol[:G, N - 1:N]), -1).to(f64), xg[..., :N + 1], square=True)[:, :N]   # [G,N]
+        out, _ = _safe_forms(U, td.to(f64).expand(S, N)[:G], _ladder_start(jitter, dt))
+        return _linear_draw(out[:, 0], out[:, 1], U[:, N - 1], None, test_mean_term, z, jitter, latent_mean, theta, dt, "chain",
+                            (vol[:G, N - 1], vol[:, N:], xg[..., 1] - xg[..., 0]))
+    V = ops.cumtrapz(vol.to(f64), (x[0] if one_x else x).to(f64), square=True)             # [S,N+T]
     out, _ = _safe_forms(V[:G, :N], td.to(f64).expand(S, N)[:G], _ladder_start(jitter, dt))
     return _linear_draw(out[:, 0], out[:, 1], V[:, N - 1], V[:, N:], test_mean_term, z, jitter, latent_mean, theta, dt)
 
@@ -153,11 +197,16 @@ def _ladder_start(jitter, dt):
     return 1e-8 if dt == torch.float64 else 1e-6
 
 
-def GeneratePrediction(train_x, train_y, test_x, pred_vol, model, latent_mean=None, theta=0.5, *, z=None, solver=None):
+def GeneratePrediction(train_x, train_y, test_x, pred_vol, model, latent_mean=None, theta=0.5, *, z=None, solver=None,
+                       draw=None):
     """voltron/rollout_utils.py:6-53.  Reads model.{log_vol_path, train_x, train_y, mean_module,
     covar_module}; returns [S, T] (T = test_x.shape[0]).  ``solver``: "dense" (the reference's route) or "linear"
-    (`_posterior_draw_linear`, no N x N array); None reads ``model.predict_solver``."""
-    draw = _posterior_draw_linear if _resolve_solver(solver, model) == "linear" else _posterior_draw
+    (`_posterior_draw_linear`, no N x N array); None reads ``model.predict_solver``.  ``draw`` (solver="linear" only):
+    "factor" or "chain" (ops.vk_draw: no T x T array either); None reads ``model.predict_draw``."""
+    solver = _resolve_solver(solver, model)
+    how = _resolve_draw(draw, solver, model)
+    draw = _posterior_draw_linear if solver == "linear" else _posterior_draw
+    kw = {"draw": how} if solver == "linear" else {}
     vol = model.log_vol_path.exp()
     if model.train_x.ndim != test_x.ndim:
         test_x_for_stack = test_x.unsqueeze(0).repeat(model.train_x.shape[0], 1)
@@ -178,7 +227,7 @@ def GeneratePrediction(train_x, train_y, test_x, pred_vol, model, latent_mean=No
     if z is None:
         z = torch.randn(S, T, 1).to(test_x.device)                                         # :47
     out = draw(model.covar_module, full_x, full_vol, idx_cut, train_diffs, test_mean_term,
-               z.reshape(S, T, 1), 1e-4, latent_mean, theta)
+               z.reshape(S, T, 1), 1e-4, latent_mean, theta, **kw)
     return out.squeeze(-1)
 
 
@@ -200,8 +249,10 @@ def _model_generate_prediction(model, test_x, pred_vol, n_sample=1):
     T = test_x.shape[0]
     z = torch.randn(*batch, T, n_sample).to(test_x.device)
     S = 1 if len(batch) == 0 else batch[0]
-    draw = _posterior_draw_linear if _resolve_solver(None, model) == "linear" else _posterior_draw
-    out = draw(model.covar_module, full_x, full_vol, idx_cut, train_diffs, test_mean_term, z.reshape(S, T, n_sample), None)
+    solver = _resolve_solver(None, model)
+    draw = _posterior_draw_linear if solver == "linear" else _posterior_draw
+    kw = {"draw": _resolve_draw(None, solver, model)} if solver == "linear" else {}
+    out = draw(model.covar_module, full_x, full_vol, idx_cut, train_diffs, test_mean_term, z.reshape(S, T, n_sample), None, **kw)
     out = out.reshape(*batch, T, n_sample)
     return out.squeeze(-1)                                  # (samples + pred_mean).squeeze(-1), VoltMagpie.py:96-99: [T] for n_sample = 1
 
@@ -212,15 +263,18 @@ def rollout_engine_max_h():
 
 
 def Rollouts(train_x, train_y, test_x, model, nsample=50, method="volt", theta=None, *, pred_vol=None, z=None,
-             engine=None, solver=None):
+             engine=None, solver=None, draw=None):
     """voltron/rollout_utils.py:57-93.  train_x [N], train_y [N+1] raw prices, test_x [H] ->
     samples [nsample, H] on the CPU (log-price units).  Mutates ``model`` like the reference.
     ``solver``: "dense" or "linear" (None: ``model.predict_solver``) -- with "linear" the bordered engine conditions on the
     train block through the O(N) chain (train_block_terms(solve="chain")) and the dense engine draws every step with
-    `_posterior_draw_linear`; no N x N array either way."""
+    `_posterior_draw_linear`; no N x N array either way.  ``draw`` (solver="linear" only; None: ``model.predict_draw``):
+    "chain" draws every step of the dense engine through ops.vk_draw; the bordered engine has one recursion of
+    its own and is not changed by it."""
     if method != "volt":
         return nonvol_rollouts(train_x, train_y, test_x, model, nsample=nsample)
     solver = _resolve_solver(solver, model)
+    draw = _resolve_draw(draw, solver, model)
     engine = engine or os.environ.get("VOLT_ROLLOUT_ENGINE", "bordered")
     if theta is None:
         latent_mean = None
@@ -248,7 +302,7 @@ def Rollouts(train_x, train_y, test_x, model, nsample=50, method="volt", theta=N
     th = 0.5 if theta is None else theta
     samples[:, 0] = GeneratePrediction(train_x, train_y, test_x[0].unsqueeze(0), pred_vol[:, 0].unsqueeze(1),
                                        model, latent_mean, th, z=None if z is None else z[:, 0:1],
-                                       solver=solver).squeeze().cpu()
+                                       solver=solver, draw=draw).squeeze().cpu()
     train_stack_y = train_y[1:].log().repeat(nsample, 1)
     train_stack_vol = model.log_vol_path.repeat(nsample, 1)
 
@@ -263,7 +317,8 @@ def Rollouts(train_x, train_y, test_x, model, nsample=50, method="volt", theta=N
         model.log_vol_path = stack_vol
         samples[:, idx] = GeneratePrediction(train_x, train_y, test_x[idx].unsqueeze(0),
                                              pred_vol[:, idx].unsqueeze(-1), model, latent_mean, th,
-                                             z=None if z is None else z[:, idx:idx + 1], solver=solver).squeeze().cpu()
+                                             z=None if z is None else z[:, idx:idx + 1], solver=solver,
+                                             draw=draw).squeeze().cpu()
     return samples
 
 
