@@ -52,7 +52,8 @@ def test_step_matches_oracle(N, T, kernel, x0):
     p, x, y = R.case(N, T, seed=100 + N + T, x0=x0)
     fbm = kernel == "fbm"
     terms, grads = R.value_and_grads(R.struct, p, x, y, kernel=kernel)
-    ws = _step(p, x, y, kernel, want_dk=fbm)
+    dk = fbm or (N, T, x0) in ((399, 8, 1), (1024, 8, 1))       # grad_K on the model's own prior too, at two of its shapes
+    ws = _step(p, x, y, kernel, want_dk=dk)
     assert ws.info.tolist() == [0, 0, 0]
     out = ws.out.double().cpu()
     for col, key in SCALARS:
@@ -65,9 +66,10 @@ def test_step_matches_oracle(N, T, kernel, x0):
             "F": _rel(ws.grad_covar_factor, grads["F"]), "raw_var": _rel(ws.grad_raw_var, grads["raw_var"]),
             "c": _rel(ws.grad_c, grads["c"])}
     vol = torch.sigmoid(p["raw_vol"]).reshape(())
-    if fbm:
+    if dk:
         _, gk = R.value_and_grads(R.struct, p, x, y, kernel=kernel, with_K=True)
         errs["K"] = _rel(ws.grad_K, gk["K"])
+    if fbm:
         # d/d raw_vol by the chain rule through the fp64 kernel derivative, as the model's autograd does in fp32
         rv = p["raw_vol"].clone().requires_grad_(True)
         dK = torch.autograd.functional.jacobian(lambda r: R.data_cov(x, r, kernel), rv).reshape(N, N)
