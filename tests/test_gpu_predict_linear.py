@@ -178,7 +178,8 @@ def test_vk_forms_validates_shapes():
 @pytest.mark.parametrize("B,n", [(3, 65), (65, 399), (2, 4096)])
 def test_vk_forms_quadratic_form_and_logdet_are_the_vk_steps(B, n):
     """With jitter = sigma2, out[:, 2] and out[:, 3] are the r'A^-1 r and logdet ops.vk_step returns on the same inputs (the
-    same pivot chain): to the bound for the fp64 step, plus one fp32 rounding of the step's outputs for the fp32 step."""
+    same pivot chain): to the bound for the fp64 step, plus one fp32 rounding of the step's outputs for the fp32 step.  The two
+    kernels run the same pivot, z chain and log-determinant (csrc/chain.h), so the fp64 step's two numbers are the forms' bit for bit."""
     from volt_amd import ops
     V, s2, r, want = case(n) if n != 4096 else case(n, B=2, seed=3)
     V, s2, r, want = V[:B], s2[:B], r[:B], want[:B]
@@ -189,6 +190,8 @@ def test_vk_forms_quadratic_form_and_logdet_are_the_vk_steps(B, n):
         assert not info.any() and not sinfo.any()
         err = np.abs(host(out)[:, 2:] - host(o)[:, 2:4])
         assert (err <= scale + eps * np.abs(want[:, 2:])).all(), (dtype, (err / scale).max())
+        if dtype == torch.float64:
+            assert host(out)[:, 2:].tobytes() == host(o)[:, 2:4].tobytes(), (host(out)[:, 2:], host(o)[:, 2:4])
 
 
 # ------------------------------------------------------------------------------------------------ 2: the ladder

@@ -16,17 +16,14 @@
 //                     conflict-free column per lane out of LDS); the next tile's rows are requested into registers before the
 //                     current tile's chain runs.  1/d_i and z_i go to the workspace series-fastest for the backward sweep,
 //                     which reads them sixteen steps ahead and sends alpha back through the same LDS tile.
-//                     The chain: d_i = fma(-s^2, 1/d_{i-1}, v delta_i + 2 s), then v_rcp_f64 + two Newton steps -- one
-//                     reciprocal and one FMA; the log (a running product of v_frexp mantissas and a sum of exponents: ONE
-//                     log per series), the z chain and the sums hang off it.
+//                     The chain is one FMA and one reciprocal per step (chain.h); the log, the z chain and the sums hang off it.
 //                     VK = true (volt_vk_step_*, the volatility-kernel data model: K_b = V_b[min(i,k)], v = 1): every series
 //                     has its OWN grid V_b, staged like resid through a second transposed LDS tile; the lane carries
 //                     V_{b,i-1} and forms delta in fp64.  Both arrays then travel in tiles of BM_VT = 32 steps (two rows per
 //                     load: the half-waves take neighbouring series), so that the two register prefetches together are as
 //                     deep as the one of the shared-grid kernel.  Chain, sums and the backward sweep are the same code.
-//   bm_forms_kernel   (volt_vk_forms_*, the forecast's conditioning: DESIGN 4.15) the VK forward sweep with a second z chain over
-//                     D V = delta next to the one over D r, on the same pivots and the same staged tiles: V'A^-1 V, V'A^-1 r,
-//                     r'A^-1 r and logdet A in doubles.  No workspace, no backward sweep; the "noise" is a jitter rung, 0 allowed.
+//   bm_forms_kernel   (volt_vk_forms_*, the forecast's conditioning: DESIGN 4.15) the VK forward sweep with a second z chain over D V
+//                     next to the one over D r: V'A^-1 V, V'A^-1 r, r'A^-1 r, logdet A in doubles.  No workspace; jitter 0 allowed.
 //   bm_post_kernel    (volt_bm_post_*, the vol forecaster's posterior: DESIGN 4.16) one wave per (series, 64 sorted test points):
 //                     the pivot chain and z^r wave-uniform off broadcast LDS reads, per lane the z chains of its test point and
 //                     of the next one over clipped grid increments, and the sums m, p, q.  Forward sweep only, no workspace.
@@ -34,6 +31,7 @@
 //   bm_solve_kernel   one lane per (series, right-hand side): R [B,N,H] with H contiguous, so the lanes of a series load and
 //                     store whole rows.  Forward z -> workspace, backward X = D'w.  Its chains are one FMA per step.
 #include "common.h"
+#include "chain.h"
 #include "host.h"
 #include "../../include/volt_hip.h"
 
@@ -45,19 +43,7 @@ constexpr int BM_VLD = BM_VT + 1;          // LDS row stride of its V tile
 constexpr int BM_LD = BM_T + 1;            // LDS row stride (doubles): a column read by 64 lanes touches every bank pair once
 constexpr int BM_PF = 16;                  // steps per register-prefetched block of the workspace sweeps
 constexpr int BM_FB = 8;                   // steps per block of the step kernel's forward chain (divides BM_T)
-constexpr double BM_LN2 = 0.693147180559945309417232121458;
 constexpr double BM_LOG_2PI = 1.837877066409345483560659472811;
-
-// 1 / d: v_rcp_f64 and two Newton steps (d is a positive normal number wherever info stays 0; anything else comes out as
-// NaN / inf and is reported through info)
-__device__ __forceinline__ double bm_rcp(double d) {
-    double r = __builtin_amdgcn_rcp(d);
-    double e = __builtin_fma(-d, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-d, r, 1.0);
-    return __builtin_fma(r, e, r);
-}
-__device__ __forceinline__ bool bm_pivot_ok(double d) { return d > 0.0 && d < __builtin_inf(); }     // false for NaN
 
 template <typename T>
 struct BmStepParams {
@@ -100,8 +86,7 @@ template <typename T>
 __device__ __forceinline__ void bm_fetch_grid(const BmStepParams<T>& p, int64_t i0, T& px, T& pxm) {
     const int64_t i = i0 + threadIdx.x;
     const bool in = i < p.N;
-    px = (T)0;
-    pxm = (T)0;
+    px = pxm = (T)0;
     if (in) px = p.x[i];
     if (in && i > 0) pxm = p.x[i - 1];
 }
@@ -118,7 +103,7 @@ __global__ __launch_bounds__(BM_T) void bm_step_kernel(BmStepParams<T> p) {
     const bool act = lane < nb;
     const int64_t b = b0 + lane;
     const double v = act && !VK ? (double)p.vol[b] : 1.0, s = act ? (double)p.sigma2[b] : 1.0;
-    const double ss = s * s, s2 = 2.0 * s;
+    const ChainBm ch(s);
 
     // ---- forward sweep
     T pre[TS], pg[VK ? TS : 2];                                        // pg: (VK) the V tile's rows; else x_i, x_{i-1} of this lane's step
@@ -160,15 +145,12 @@ __global__ __launch_bounds__(BM_T) void bm_step_kernel(BmStepParams<T> p) {
             for (int u = 0; u < BM_FB; ++u) {
                 const int64_t i = i0 + j0 + u;
                 const bool on = j0 + u < cnt;
-                const double base = __builtin_fma(v, dd[u], i == 0 ? s : s2);
-                const double d = __builtin_fma(-ss, inv_prev, base);           // the chain: this FMA and the reciprocal
-                const double c = s * inv_prev;
-                const double inv = bm_rcp(d);
-                const double z = __builtin_fma(c, zprev, rr[u] - rprev);
+                const ChainPivot pv = ch.pivot(inv_prev, ch.base(v, dd[u], i));   // the chain: one FMA and the reciprocal
+                const double d = pv.d, inv = pv.inv, z = chain_z_fwd(pv.c, zprev, rr[u] - rprev);
                 quad = on ? __builtin_fma(z * z, inv, quad) : quad;
-                P = on ? P * __builtin_amdgcn_frexp_mant(d) : P;
-                e += on ? __builtin_amdgcn_frexp_exp(d) : 0;
-                if (on && !bm_pivot_ok(d) && info == 0) info = (int)(i + 1 < 0x7fffffff ? i + 1 : 0x7fffffff);
+                P = ChainLogDet::mul(P, d, on);
+                e += ChainLogDet::exp(d, on);
+                if (on && !chain_pivot_ok(d) && info == 0) info = chain_fail_code(i);
                 iv[u] = inv;
                 zz[u] = z;
                 inv_prev = on ? inv : inv_prev;
@@ -185,12 +167,12 @@ __global__ __launch_bounds__(BM_T) void bm_step_kernel(BmStepParams<T> p) {
                     }
             }
         }
-        e += __builtin_amdgcn_frexp_exp(P);                                    // (at most BM_T mantissas in [1/2, 1) since the last time)
-        P = __builtin_amdgcn_frexp_mant(P);
+        e += ChainLogDet::exp(P);                                              // (at most BM_T mantissas in [1/2, 1) since the last time)
+        P = ChainLogDet::mant(P);
         E += e;
         __syncthreads();
     }
-    const double logdet = info ? __builtin_nan("") : log(P) + (double)E * BM_LN2;
+    const double logdet = info ? __builtin_nan("") : ChainLogDet::value(P, E);
     const double nd = (double)N;
     if (act) {
         T* o = p.out + b * 8;
@@ -231,7 +213,7 @@ __global__ __launch_bounds__(BM_T) void bm_step_kernel(BmStepParams<T> p) {
             // w = g = alpha = 0, adds nothing to the sums, and lands in a tile column that is never sent out
             const int64_t i = q * BM_PF + j;
             const double inv = ci[j], e = s * inv;
-            const double w = __builtin_fma(e, wn, cz[j] * inv);
+            const double w = chain_z_back(e, wn, cz[j], inv);
             const double a = w - wn;
             aa = __builtin_fma(a, a, aa);
             const double g = __builtin_fma(e * e, gn, inv);
@@ -270,6 +252,7 @@ struct BmFormsParams {
 // The conditioning scalars of a forecast from the volatility-kernel data model (volt_vk_forms_*): per series, with
 // A = V[min(i,k)] + j I, the forms V'A^-1 V, V'A^-1 r, r'A^-1 r and logdet A.  The forward sweep of the VK step with TWO z
 // chains on the one pivot chain -- z^V over D V = delta, z^r over D r -- and nothing else: no workspace, no backward sweep.
+// (Written out next to bm_step_kernel's, not shared with it: either way of sharing the sweep cost these chains ~1 %)
 // j = 0 is legal (c_i = 0, d_i = delta_i: the forms are then V_{N-1}, r_{N-1}, sum (D r)_i^2 / delta_i, sum log delta_i).
 template <typename T>
 __global__ __launch_bounds__(BM_T) void bm_forms_kernel(BmFormsParams<T> p) {
@@ -282,8 +265,7 @@ __global__ __launch_bounds__(BM_T) void bm_forms_kernel(BmFormsParams<T> p) {
     const int nb = (int)(B - b0 < BM_T ? B - b0 : BM_T);
     const bool act = lane < nb;
     const int64_t b = b0 + lane;
-    const double s = act ? p.jitter[b] : 1.0;
-    const double ss = s * s, s2 = 2.0 * s;
+    const ChainBm ch(act ? p.jitter[b] : 1.0);
 
     T pre[TS], pg[TS];
     auto fetch = [&](int64_t i0) {
@@ -318,25 +300,23 @@ __global__ __launch_bounds__(BM_T) void bm_forms_kernel(BmFormsParams<T> p) {
             for (int u = 0; u < BM_FB; ++u) {
                 const int64_t i = i0 + j0 + u;
                 const bool on = j0 + u < cnt;
-                const double d = __builtin_fma(-ss, inv_prev, dd[u] + (i == 0 ? s : s2));
-                const double c = s * inv_prev;
-                const double inv = bm_rcp(d);
-                const double a = __builtin_fma(c, zv, dd[u]);                  // z^V_i = delta_i + c_i z^V_{i-1}
-                const double z = __builtin_fma(c, zr, rr[u] - rprev);          // z^r_i = (r_i - r_{i-1}) + c_i z^r_{i-1}
+                const ChainPivot pv = ch.pivot(inv_prev, ch.base(1.0, dd[u], i)); // (v = 1: fma(1.0, delta, s) is folded to delta + s)
+                const double d = pv.d, inv = pv.inv, a = chain_z_fwd(pv.c, zv, dd[u]);   // z^V_i = delta_i + c_i z^V_{i-1}
+                const double z = chain_z_fwd(pv.c, zr, rr[u] - rprev);         // z^r_i = (r_i - r_{i-1}) + c_i z^r_{i-1}
                 rho = on ? __builtin_fma(a * a, inv, rho) : rho;
                 tau = on ? __builtin_fma(a * z, inv, tau) : tau;
                 quad = on ? __builtin_fma(z * z, inv, quad) : quad;
-                P = on ? P * __builtin_amdgcn_frexp_mant(d) : P;
-                e += on ? __builtin_amdgcn_frexp_exp(d) : 0;
-                if (on && !bm_pivot_ok(d) && info == 0) info = (int)(i + 1 < 0x7fffffff ? i + 1 : 0x7fffffff);
+                P = ChainLogDet::mul(P, d, on);
+                e += ChainLogDet::exp(d, on);
+                if (on && !chain_pivot_ok(d) && info == 0) info = chain_fail_code(i);
                 inv_prev = on ? inv : inv_prev;
                 zv = on ? a : zv;
                 zr = on ? z : zr;
                 rprev = on ? rr[u] : rprev;
             }
         }
-        e += __builtin_amdgcn_frexp_exp(P);
-        P = __builtin_amdgcn_frexp_mant(P);
+        e += ChainLogDet::exp(P);
+        P = ChainLogDet::mant(P);
         E += e;
         __syncthreads();
     }
@@ -346,7 +326,7 @@ __global__ __launch_bounds__(BM_T) void bm_forms_kernel(BmFormsParams<T> p) {
         o[0] = info ? nan : rho;
         o[1] = info ? nan : tau;
         o[2] = info ? nan : quad;
-        o[3] = info ? nan : log(P) + (double)E * BM_LN2;
+        o[3] = info ? nan : ChainLogDet::value(P, E);
         p.info[b] = info;
     }
 }
@@ -391,8 +371,8 @@ __global__ __launch_bounds__(BM_T) void bm_post_kernel(BmPostParams<T> p) {
     }
 
     const double xa = act ? (double)p.xs[h] : 0.0, xb = act ? (double)p.xs[h + 1 < H ? h + 1 : h] : 0.0;
-    const double v = (double)p.vol[b], s = (double)p.sigma2[b];
-    const double ss = s * s, s2 = 2.0 * s;
+    const double v = (double)p.vol[b];
+    const ChainBm ch((double)p.sigma2[b]);
     const T* xg = p.x + b * p.bsx;
     const T* rg = p.resid + b * N;
 
@@ -407,20 +387,18 @@ __global__ __launch_bounds__(BM_T) void bm_post_kernel(BmPostParams<T> p) {
     double inv_prev = 0.0, zr = 0.0, za = 0.0, zb = 0.0, m = 0.0, pp = 0.0, q = 0.0;
     int info = 0;
     auto step = [&](int64_t i, double dl, double xp, double dr) {
-        const double base = __builtin_fma(v, dl, i == 0 ? s : s2);
-        const double d = __builtin_fma(-ss, inv_prev, base);
-        const double c = s * inv_prev;
-        const double inv = bm_rcp(d);
-        zr = __builtin_fma(c, zr, dr);
+        const ChainPivot pv = ch.pivot(inv_prev, ch.base(v, dl, i));
+        const double c = pv.c;
+        zr = chain_z_fwd(c, zr, dr);
         // (D k)_i by selects: v delta_i up to the bracket, the partial increment at it, 0 after; xi >= x_i gives delta_i exactly
-        za = __builtin_fma(c, za, v * __builtin_fmin(__builtin_fmax(xa - xp, 0.0), dl));
-        zb = __builtin_fma(c, zb, v * __builtin_fmin(__builtin_fmax(xb - xp, 0.0), dl));
-        const double w = za * inv;
+        za = chain_z_fwd(c, za, v * __builtin_fmin(__builtin_fmax(xa - xp, 0.0), dl));
+        zb = chain_z_fwd(c, zb, v * __builtin_fmin(__builtin_fmax(xb - xp, 0.0), dl));
+        const double w = za * pv.inv;
         m = __builtin_fma(w, zr, m);
         pp = __builtin_fma(w, za, pp);
         q = __builtin_fma(w, zb, q);
-        if (!bm_pivot_ok(d) && info == 0) info = (int)(i + 1 < 0x7fffffff ? i + 1 : 0x7fffffff);
-        inv_prev = inv;
+        if (!chain_pivot_ok(pv.d) && info == 0) info = chain_fail_code(i);
+        inv_prev = pv.inv;
     };
     for (int64_t i0 = 0; i0 < N; i0 += BM_T) {
         sd[lane] = (double)px - (double)pxm;
@@ -459,8 +437,8 @@ __global__ __launch_bounds__(BM_T) void bm_factor_kernel(BmSolveParams<T> p) {
     const int64_t b = (int64_t)blockIdx.x * BM_T + threadIdx.x;
     const int64_t N = p.N, B = p.B;
     const bool act = b < B;
-    const double v = act ? (double)p.vol[b] : 1.0, s = act ? (double)p.sigma2[b] : 1.0;
-    const double ss = s * s, s2 = 2.0 * s;
+    const double v = act ? (double)p.vol[b] : 1.0;
+    const ChainBm ch(act ? (double)p.sigma2[b] : 1.0);
     double inv_prev = 0.0, xprev = 0.0;
     int info = 0;
     for (int64_t i0 = 0; i0 < N; i0 += BM_PF) {
@@ -471,12 +449,10 @@ __global__ __launch_bounds__(BM_T) void bm_factor_kernel(BmSolveParams<T> p) {
         for (int j = 0; j < BM_PF; ++j) {
             const int64_t i = i0 + j;
             if (i < N) {
-                const double base = __builtin_fma(v, xs[j] - xprev, i == 0 ? s : s2);
-                const double d = __builtin_fma(-ss, inv_prev, base);
-                const double inv = bm_rcp(d);
-                if (!bm_pivot_ok(d) && info == 0) info = (int)(i + 1 < 0x7fffffff ? i + 1 : 0x7fffffff);
-                if (act) p.inv[i * B + b] = inv;
-                inv_prev = inv;
+                const ChainPivot pv = ch.pivot(inv_prev, ch.base(v, xs[j] - xprev, i));
+                if (!chain_pivot_ok(pv.d) && info == 0) info = chain_fail_code(i);
+                if (act) p.inv[i * B + b] = pv.inv;
+                inv_prev = pv.inv;
                 xprev = xs[j];
             }
         }
@@ -520,7 +496,7 @@ __global__ __launch_bounds__(BM_T) void bm_solve_kernel(BmSolveParams<T> p) {
         for (int j = 0; j < BM_PF; ++j) {
             const int64_t i = q * BM_PF + j;
             if (i < N) {
-                const double z = __builtin_fma(s * ci[j], zprev, cr[j] - rprev);
+                const double z = chain_z_fwd(s * ci[j], zprev, cr[j] - rprev);
                 if (act) p.zs[i * BH + g] = z;
                 zprev = z;
                 rprev = cr[j];
@@ -552,7 +528,7 @@ __global__ __launch_bounds__(BM_T) void bm_solve_kernel(BmSolveParams<T> p) {
         for (int j = BM_PF - 1; j >= 0; --j) {
             const int64_t i = q * BM_PF + j;
             if (i < N) {
-                const double w = __builtin_fma(s * ci[j], wn, cr[j] * ci[j]);
+                const double w = chain_z_back(s * ci[j], wn, cr[j], ci[j]);
                 if (act) X[i * H] = (T)(w - wn);
                 wn = w;
             }
@@ -562,11 +538,12 @@ __global__ __launch_bounds__(BM_T) void bm_solve_kernel(BmSolveParams<T> p) {
 
 inline size_t bm_inv_bytes(int64_t B, int64_t N) { return al256((size_t)B * (size_t)N * sizeof(double)); }
 
-template <typename T>
-int bm_step(const T* x, const T* vol, const T* sigma2, const T* resid, T* out, T* alpha, int* info, void* workspace, int B,
-            int N, int flags, void* stream) {
+// the checked launch of both steps; VK (volt_vk_step_*): x the per-series grids V [B,N] with batch stride bsx (0: one grid), no vol
+template <typename T, bool VK>
+int bm_step(const T* x, int64_t bsx, const T* vol, const T* sigma2, const T* resid, T* out, T* alpha, int* info, void* workspace,
+            int B, int N, int flags, void* stream) {
     if (!x) return -1;
-    if (!vol) return -2;
+    if (VK ? (bsx < 0 || (bsx > 0 && bsx < N)) : !vol) return -2;
     if (!sigma2) return -3;
     if (!resid) return -4;
     if (!out) return -5;
@@ -578,35 +555,10 @@ int bm_step(const T* x, const T* vol, const T* sigma2, const T* resid, T* out, T
     if (N < 1) return -10;
     if (flags & ~VOLT_WANT_GRAD) return -11;
     BmStepParams<T> p{x, vol, sigma2, resid, out, alpha, info, (double*)workspace,
-                      (double*)((char*)workspace + (grad ? bm_inv_bytes(B, N) : 0)), B, N, 0};
+                      (double*)((char*)workspace + (grad ? bm_inv_bytes(B, N) : 0)), B, N, bsx};
     const dim3 grid((unsigned)((B + BM_T - 1) / BM_T));
-    if (grad) hipLaunchKernelGGL((bm_step_kernel<T, true, false>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((bm_step_kernel<T, false, false>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
-    VOLT_LAUNCH_CHECK();
-    return 0;
-}
-
-// the step for K_b = V_b[min(i,k)]: per-series grids V [B,N] with batch stride bsv (0: one grid for all), v = 1
-template <typename T>
-int vk_step(const T* V, int64_t bsv, const T* sigma2, const T* resid, T* out, T* alpha, int* info, void* workspace, int B, int N,
-            int flags, void* stream) {
-    if (!V) return -1;
-    if (bsv < 0 || (bsv > 0 && bsv < N)) return -2;
-    if (!sigma2) return -3;
-    if (!resid) return -4;
-    if (!out) return -5;
-    const bool grad = (flags & VOLT_WANT_GRAD) != 0;
-    if (grad && !alpha) return -6;
-    if (!info) return -7;
-    if (grad && (!workspace || ((uintptr_t)workspace & 255))) return -8;
-    if (B < 1) return -9;
-    if (N < 1) return -10;
-    if (flags & ~VOLT_WANT_GRAD) return -11;
-    BmStepParams<T> p{V, nullptr, sigma2, resid, out, alpha, info, (double*)workspace,
-                      (double*)((char*)workspace + (grad ? bm_inv_bytes(B, N) : 0)), B, N, bsv};
-    const dim3 grid((unsigned)((B + BM_T - 1) / BM_T));
-    if (grad) hipLaunchKernelGGL((bm_step_kernel<T, true, true>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((bm_step_kernel<T, false, true>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
+    if (grad) hipLaunchKernelGGL((bm_step_kernel<T, true, VK>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((bm_step_kernel<T, false, VK>), grid, dim3(BM_T), 0, (hipStream_t)stream, p);
     VOLT_LAUNCH_CHECK();
     return 0;
 }
@@ -687,19 +639,19 @@ size_t volt_bm_workspace_bytes(int B, int N, int H) {
 
 int volt_bm_step_f32(const float* x, const float* vol, const float* sigma2, const float* resid, float* out, float* alpha,
                      int* info, void* workspace, int B, int N, int flags, void* stream) {
-    return volt::bm_step<float>(x, vol, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
+    return volt::bm_step<float, false>(x, 0, vol, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
 }
 int volt_bm_step_f64(const double* x, const double* vol, const double* sigma2, const double* resid, double* out, double* alpha,
                      int* info, void* workspace, int B, int N, int flags, void* stream) {
-    return volt::bm_step<double>(x, vol, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
+    return volt::bm_step<double, false>(x, 0, vol, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
 }
 int volt_vk_step_f32(const float* V, int64_t bsv, const float* sigma2, const float* resid, float* out, float* alpha, int* info,
                      void* workspace, int B, int N, int flags, void* stream) {
-    return volt::vk_step<float>(V, bsv, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
+    return volt::bm_step<float, true>(V, bsv, nullptr, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
 }
 int volt_vk_step_f64(const double* V, int64_t bsv, const double* sigma2, const double* resid, double* out, double* alpha,
                      int* info, void* workspace, int B, int N, int flags, void* stream) {
-    return volt::vk_step<double>(V, bsv, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
+    return volt::bm_step<double, true>(V, bsv, nullptr, sigma2, resid, out, alpha, info, workspace, B, N, flags, stream);
 }
 int volt_vk_forms_f32(const float* V, int64_t bsv, const double* jitter, const float* resid, double* out, int* info, int B,
                       int N, void* stream) {

@@ -22,6 +22,7 @@
 // bytes) otherwise -- never a load per lane per step at stride H.  The draw overwrites its z in the tile and the tile goes
 // back the same way.  No workspace, no atomics, one launch, fixed order of every sum: bitwise repeatable.
 #include "common.h"
+#include "chain.h"
 #include "../../include/volt_hip.h"
 
 namespace volt {
@@ -37,16 +38,7 @@ struct ChainCoef {
     double d, r;                          // d_i and e_i / d_i
 };
 
-// 1 / sqrt(t): the hardware estimate and two Newton steps (the estimate's ~2^-26 becomes rounding level after the second), as
-// bm.hip's bm_rcp does for the reciprocal -- a library square root followed by a division is ~5 x the dependent instructions,
-// and this pair sits on the one serial chain of the Markov kernel.  t <= 0, inf or NaN gives inf / NaN: a failed pivot anyway.
-__device__ __forceinline__ double chain_rsqrt(double t) {
-    double y = __builtin_amdgcn_rsq(t);
-    const double h = 0.5 * t;
-    y = __builtin_fma(y, __builtin_fma(-h * y, y, 0.5), y);
-    return __builtin_fma(y, __builtin_fma(-h * y, y, 0.5), y);
-}
-// (c_i, m_i, jitter) -> (d_i, e_i / d_i); false where e_i + j is not a positive finite number
+// (c_i, m_i, jitter) -> (d_i, e_i / d_i); false where e_i + j is not a positive finite number (chain_rsqrt: chain.h; on the serial chain)
 __device__ __forceinline__ bool chain_coef(double c, double m, double jit, ChainCoef& k) {
     const double e = c - m, t = e + jit;
     const double rs = chain_rsqrt(t);
@@ -182,7 +174,7 @@ __global__ __launch_bounds__(MD_WAVES * 64) void markov_draw_kernel(MarkovDrawPa
 #pragma unroll
                 for (int u = 0; u < MD_FB; ++u) {
                     const bool ok = chain_coef(ci[u], m, jit, k[u]);
-                    if (!ok && bad == 0 && i0 + u < cnt) bad = (int)(c0 + i0 + u + 1 < 0x7fffffff ? c0 + i0 + u + 1 : 0x7fffffff);
+                    if (!ok && bad == 0 && i0 + u < cnt) bad = chain_fail_code(c0 + i0 + u);
                     m = chain_next_m(gi[u], m, k[u]);
                 }
 #pragma unroll
@@ -285,7 +277,7 @@ __global__ __launch_bounds__(64) void vk_draw_kernel(VkDrawParams<T> p) {
             const double W = (run - run0) + vlr;
             double y;
             const bool ok = chain_step(W, 1.0, jit, mu, (double)tz[lane * CD_LD + i], m, s, y);
-            if (!ok && bad == 0) bad = (int)(c0 + i + 1 < 0x7fffffff ? c0 + i + 1 : 0x7fffffff);
+            if (!ok && bad == 0) bad = chain_fail_code(c0 + i);
             tz[lane * CD_LD + i] = bad ? nan : (T)y;
         }
         __syncthreads();

@@ -2,7 +2,7 @@
 //
 // The dense step (gpcv.hip) factors K + j I and forms G = K^-1 Lq with two structured GEMMs: 5 N^3 / 3 flop per series.  For
 // K = v min(x, x') none of it is needed: A = v M + j I = D^-1 T D^-T with T tridiagonal, T = L diag(d) L' (bm.hip has the
-// recurrences: d_i, c_i = j / d_{i-1}, rho_i = j / d_i), so every column of G is one chain solve:
+// algebra, chain.h the recurrences: d_i, c_i = j / d_{i-1}, rho_i = j / d_i), so every column of G is one chain solve:
 //     forward   z_i = (Lq_ij - Lq_{i-1,j}) + c_i z_{i-1}    from i = j (column j of Lq is zero above row j)
 //               tr(A^-1 S) = sum_j sum_{i>=j} z_ij^2 / d_i
 //     backward  w_i = z_i / d_i + rho_i w_{i+1},  G_ij = w_i - w_{i+1}    from N-1 down to j: only tril(G) enters dKL/dLq
@@ -25,6 +25,7 @@
 //                          over the chunks), the three column sums in a fixed order, dF/dm and dF/dmu.
 // No atomics; every reduction has a fixed order: the step is bitwise repeatable.
 #include "common.h"
+#include "chain.h"
 #include "host.h"
 #include "../../include/volt_hip.h"
 
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(GB_W) void gpcv_bm_cols_kernel(const float* __restr
             const int64_t i = i0 + u;
             const bool on = col && i >= j && i < n;
             const double l = (double)cl[u];
-            double z = __builtin_fma(s_c[u], zprev, l - lprev);
+            double z = chain_z_fwd(s_c[u], zprev, l - lprev);
             z = on ? z : 0.0;
             tr = on ? __builtin_fma(z * z, s_iv[u], tr) : tr;
             zprev = on ? z : zprev;
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(GB_W) void gpcv_bm_cols_kernel(const float* __restr
             const int64_t i = i0 + u;
             const bool on = col && i >= j && i < n;
             const double iv = s_iv[u];
-            const double w = __builtin_fma(jit * iv, wn, cz[u] * iv);
+            const double w = chain_z_back(jit * iv, wn, cz[u], iv);
             const double g = w - wn;
             const double kl = g - (i == j ? rdiag : 0.0);
             const double f = we * 2.0 * (double)s_gv[u] * (double)cl[u] - wk * kl;
