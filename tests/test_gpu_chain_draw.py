@@ -462,6 +462,53 @@ def test_shuffled_and_duplicated_points_on_the_chain_posterior():
     # (the twin adds d z with d <= sqrt(1e-6); e / d against d at the rung and the outputs' roundings are within the 1e-4)
 
 
+@pytest.mark.parametrize("H", [1, 20, 65])
+@pytest.mark.parametrize("model", ["bmgp_f32", "bmgp_f64", "multitask"])
+def test_sweep_is_the_chain_posterior_evaluated(model, H):
+    """posterior="sweep" is posterior="chain" with its lazy covariance evaluated (one sweep, one gp._MarkovCov): the mean and the
+    covariance are equal BITWISE, for BMGP at T x N = 3 x 65 in fp32 and fp64 and MultitaskBMGP at N x T = 65 x 3, the test
+    points shuffled (inside, on and beyond the grid)."""
+    N, T = 65, 3
+    rng = np.random.default_rng(H)
+    if model == "multitask":
+        from test_gpu_multitask import make_case, model_params
+        from volt_amd.gp import MultitaskGaussianLikelihood
+        from volt_amd.models import MultitaskBMGP
+        p, x, Y = make_case(N, T, 1, seed=N + T + H)
+        x = x.numpy()
+    else:
+        import bm_chain_ref as chain
+        from test_gpu_bm_post import _bmgp as build
+        dtype = torch.float32 if model == "bmgp_f32" else torch.float64
+        x = np.asarray(chain.grids(N)["uniform_dt"], dtype=np.float32)
+        y = np.asarray(np.cumsum(rng.standard_normal((T, N)) * 0.05, axis=1) - 2.0, dtype=np.float32)
+    xs = x[-1] + (1 + np.arange(H)) / 252.0
+    if H >= 20:
+        xs[:3] = [0.5 * (x[10] + x[11]), x[40], 0.5 * (x[50] + x[51])]
+        xs = rng.permutation(xs)
+        assert not (np.diff(xs) >= 0).all()
+    xs = xs.astype(np.float32)
+    posts = {}
+    for posterior in ("chain", "sweep"):
+        if model == "multitask":
+            lh = MultitaskGaussianLikelihood(num_tasks=T).cuda()
+            m = MultitaskBMGP(dev(x), Y.cuda(), lh, solver="linear", posterior=posterior).cuda()
+            with torch.no_grad():
+                for k, prm in model_params(m, lh).items():
+                    prm.copy_(p[k])
+            posts[posterior] = m.eval()(dev(xs))
+        else:
+            posts[posterior] = build(x, y, dtype, posterior)[0](dev(xs, dtype))
+    pc, ps = posts["chain"], posts["sweep"]
+    assert pc.mean.dtype == ps.mean.dtype and torch.isfinite(ps.mean).all()
+    assert torch.equal(ps.mean, pc.mean)
+    assert torch.equal(ps.covariance_matrix, pc.covariance_matrix)
+    if model != "multitask":
+        from volt_amd import gp
+        assert isinstance(pc.lazy_covariance_matrix, gp._MarkovCov) and (pc.lazy_covariance_matrix.order is None) == (H == 1)
+        assert tuple(ps.covariance_matrix.shape) == (T, H, H) and ps.mean.dtype == dtype
+
+
 # ------------------------------------------------------------------------------------------------ 4: the data model
 @pytest.mark.parametrize("N,T,S", vkref.DRAW_SHAPES)
 def test_chain_draw_is_at_least_as_accurate_as_the_factor_draw(N, T, S):

@@ -108,8 +108,8 @@ def _standard_mean_prediction(model, train_x, log_y, vol, test_x, pred_vol, z, s
 
 def _check_vol_posterior(vol_posterior, vol_solver):
     """Before any window trains: the vol forecaster's constructor would raise the same, one GPCV fit later."""
-    from .models.BMGP import _check_posterior
-    _check_posterior("vol_posterior", vol_posterior, vol_solver)
+    from .models._posterior import check_options
+    check_options("vol_posterior", vol_solver, vol_posterior)
 
 
 def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator,

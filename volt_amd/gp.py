@@ -196,23 +196,36 @@ class Kernel(Module):
 
 
 class _Evaluated:
-    """Already-dense "lazy tensor"."""
+    """Already-dense "lazy tensor", and the base of the lazy ones: a subclass defines `_build(detach=False)` -- the dense
+    tensor, from detached parameters when asked -- and ``shape``; ``tensor`` (read-only), ``evaluate``, ``to_dense`` and
+    ``detach`` all come from that one hook, so nothing is formed before one of them is asked for."""
 
     def __init__(self, t):
-        self.tensor = t
+        self._t = t
+
+    def _build(self, detach=False):
+        return self._t.detach() if detach else self._t
+
+    @property
+    def tensor(self):
+        return self._build()
+
+    @tensor.setter
+    def tensor(self, v):
+        raise AttributeError("read-only")
 
     def evaluate(self):
-        return self.tensor
+        return self._build()
 
     def to_dense(self):
-        return self.tensor
+        return self._build()
 
     def detach(self):
-        return self.tensor.detach()
+        return self._build(detach=True)
 
     @property
     def shape(self):
-        return self.tensor.shape
+        return self._build().shape
 
 
 class _ScaledDense(_Evaluated):
@@ -223,26 +236,10 @@ class _ScaledDense(_Evaluated):
     def __init__(self, scale, base):
         self.scale, self.base = scale, base
 
-    def _product(self, scale):
+    def _build(self, detach=False):
+        scale = self.scale.detach() if detach else self.scale
         # a batched kernel carries scale [T,1] over one shared base [N,N]
         return (scale.unsqueeze(-1) if scale.ndim > 1 else scale) * self.base
-
-    @property
-    def tensor(self):
-        return self._product(self.scale)
-
-    @tensor.setter
-    def tensor(self, v):
-        raise AttributeError("read-only")
-
-    def evaluate(self):
-        return self._product(self.scale)
-
-    def to_dense(self):
-        return self.evaluate()
-
-    def detach(self):
-        return self._product(self.scale.detach())
 
     @property
     def shape(self):
@@ -291,7 +288,7 @@ def _markov_cov(diag, off):
 class _MarkovCov(_Evaluated):
     """Lazy covariance of a Markov posterior over H points (BMGP / MultitaskBMGP(posterior="chain")):
     ``scale`` * _markov_cov(diag, off) over the points in ASCENDING order, with ``order`` the permutation that sorted the
-    caller's points (None: they were ascending) -- what `_posterior_sweep` builds at once.  diag, off [..,H] fp64; scale None
+    caller's points (None: they were ascending) -- what posterior="sweep" evaluates at once.  diag, off [..,H] fp64; scale None
     or [T] (the eigen-directions' kappa_j).  The [..,H,H] matrix is formed, through `_markov_cov`, only when ``.evaluate()`` /
     ``.to_dense()`` / ``.tensor`` is asked for, and rounded to ``dtype``; draws go through `draw`, which never forms it.
 
@@ -304,8 +301,7 @@ class _MarkovCov(_Evaluated):
         self.diag, self.off, self.order, self.scale, self.dtype = diag, off, order, scale, dtype
         self.mean = mean                  # the posterior mean before its rounding to ``dtype`` (fp64, the caller's order), or None
 
-    @property
-    def tensor(self):
+    def _build(self, detach=False):                # (formed under no_grad from detached forms: nothing to detach)
         cov = _markov_cov(self.diag, self.off)
         if self.scale is not None:
             cov = self.scale.reshape(-1, 1, 1) * cov
@@ -314,19 +310,6 @@ class _MarkovCov(_Evaluated):
             full[..., self.order.unsqueeze(-1), self.order.unsqueeze(0)] = cov
             cov = full
         return cov.to(self.dtype)
-
-    @tensor.setter
-    def tensor(self, v):
-        raise AttributeError("read-only")
-
-    def evaluate(self):
-        return self.tensor
-
-    def to_dense(self):
-        return self.tensor
-
-    def detach(self):
-        return self.tensor
 
     @property
     def shape(self):
@@ -373,22 +356,8 @@ class _VolPrior(_Evaluated):
     def __init__(self, V):
         self.x = V
 
-    @property
-    def tensor(self):
-        return ops.fill(self.x)
-
-    @tensor.setter
-    def tensor(self, v):
-        raise AttributeError("read-only")
-
-    def evaluate(self):
-        return ops.fill(self.x)
-
-    def to_dense(self):
-        return ops.fill(self.x)
-
-    def detach(self):
-        return ops.fill(self.x.detach())
+    def _build(self, detach=False):
+        return ops.fill(self.x.detach() if detach else self.x)
 
     @property
     def shape(self):
@@ -1036,7 +1005,7 @@ class ExactMarginalLogLikelihood(Module):
             scale = None
             if isinstance(lazy, _ScaledDense):
                 scale = lazy.scale
-                K = lazy._product(lazy.scale.detach())
+                K = lazy.detach()
             else:
                 K = function_dist.covariance_matrix
             cov = K.reshape(-1, n, n)

@@ -14,42 +14,12 @@ parameter, noise and posterior) -- what the batched forecast driver trains inste
 import torch
 
 from .. import ops
-from ..gp import (ExactGP, MultitaskMultivariateNormal, MultivariateNormal, NanError, NotPSDError, _BrownianPrior, _KroneckerPrior,
-                  _MarkovCov, _markov_cov, _safe_factor, check_grid, same_values)
+from ..gp import (ExactGP, MultitaskMultivariateNormal, MultivariateNormal, _BrownianPrior, _dense, _KroneckerPrior,
+                  same_values)
 from ..kernels.BMKernel import BMKernel
 from ..kernels.FBMKernel import FBMKernel
 from ..kernels.MultitaskKernel import MultitaskKernel
-
-
-def _check_posterior(who, posterior, solver):
-    if posterior not in BMGP.POSTERIORS:
-        raise ValueError(f"{who}: posterior must be one of {BMGP.POSTERIORS}, got {posterior!r}")
-    if posterior != "solve" and solver != "linear":
-        raise ValueError(f"{who}: posterior={posterior!r} needs solver='linear' (the dense solver has one posterior)")
-
-
-def _sort_order(xs, order):
-    """``order`` (the permutation that sorted xs), or None where xs was ascending already (ONE host read): the chain draw then
-    skips the gather of z and the scatter of the result."""
-    if xs.shape[0] < 2 or bool((xs[1:] >= xs[:-1]).all()):
-        return None
-    return order
-
-
-def _check_post_info(info, order, who, params, not_psd):
-    """ONE host read of ops.bm_post's info.  NaN / inf parameters (``params``: tensors looked at only on failure) are a
-    NanError before a failed pivot is a NotPSDError; a negative code names the offending test point by its index in the
-    caller's order (``order``: the sort's permutation)."""
-    info = info.tolist()
-    if not any(info):
-        return
-    if not all(bool(torch.isfinite(p).all()) for p in params):
-        raise NanError(f"{who} posterior: NaN / inf in the targets or the parameters")
-    code = next(i for i in info if i)
-    if code < 0:
-        raise ValueError(f"{who} posterior: test point {int(order[-code - 1])} is NaN / inf or negative "
-                         "(Brownian motion starts at x = 0)")
-    raise NotPSDError(f"{who} posterior: {not_psd}")
+from ._posterior import POSTERIORS, SOLVERS, Chains, check_info, check_options, dense_products, sweep
 
 
 class BMGP(ExactGP):
@@ -62,20 +32,12 @@ class BMGP(ExactGP):
     rebuilds the H x H covariance from its diagonal and first off-diagonal (the posterior is Markov): nothing is N x H;
     "chain" is the same sweep with the covariance left lazy (gp._MarkovCov): samples come from ops.markov_draw in O(S H) and
     the H x H matrix is built only when ``.covariance_matrix`` / ``.variance`` is asked for."""
-    SOLVERS = ("dense", "linear")
-    POSTERIORS = ("solve", "sweep", "chain")
+    SOLVERS = SOLVERS
+    POSTERIORS = POSTERIORS
     _POST_CHUNK = 4096                        # rows of K_t* per fp64 product of the linear posterior (bounds its temporaries)
 
     def __init__(self, train_x, train_y, likelihood, kernel="bm", solver="dense", posterior="solve"):
-        if solver not in self.SOLVERS:
-            raise ValueError(f"BMGP: solver must be one of {self.SOLVERS}, got {solver!r}")
-        _check_posterior("BMGP", posterior, solver)
-        if solver == "linear" and kernel != "bm":
-            raise ValueError(f"BMGP: solver='linear' needs kernel='bm' (Brownian motion is Markov; kernel {kernel!r} is not)")
-        if solver == "linear":
-            if train_x.ndim != 1:
-                raise ValueError(f"BMGP(solver='linear'): the grid must be 1-D [N], got shape {tuple(train_x.shape)}")
-            check_grid(train_x, "BMGP(solver='linear')")
+        check_options("BMGP", solver, posterior, train_x, kernel)
         super().__init__(train_x, train_y, likelihood)
         kw = {"batch_shape": train_y.shape[:-1]} if train_y.ndim > 1 else {}
         if kernel == "bm":
@@ -98,111 +60,75 @@ class BMGP(ExactGP):
             return MultivariateNormal(self.mean_module(x), _BrownianPrior(self.covar_module.vol, self.train_inputs[0][:, 0]))
         return MultivariateNormal(self.mean_module(x), self.covar_module(x))
 
-    def _posterior_linear(self, x):
-        """mean* = m(x*) + K_*t alpha and cov = K_** - K_*t A^-1 K_t* with alpha from the linear-time step (fp64) and
-        A^-1 K_t* from the linear-time solve in the model's dtype (R = K_t* [T,N,H]); the two products over N are
-        accumulated in fp64, a block of rows at a time.  Returned in the model's dtype."""
-        with torch.no_grad():
-            xt = self.train_inputs[0][:, 0]
-            y = self.train_targets
-            batched = y.ndim > 1
-            T = y.shape[0] if batched else 1
-            n = xt.shape[0]
-            xs = x[:, 0] if x.ndim > 1 else x
-            H = xs.shape[0]
-            dt = torch.float64 if y.dtype == torch.float64 else torch.float32
-            vol = self.covar_module.vol.reshape(-1).expand(T)
-            noise = self.likelihood.noise.reshape(-1).expand(T)
-            resid = (y - self.mean_module(xt)).reshape(T, n)
-            # alpha in fp64 (the residual upcast) and K_*t rebuilt in fp64 block by block below: K_*t alpha sums N terms of
-            # either sign, so an fp32 rounding of alpha or of K_*t would come back multiplied by sum |alpha_i| K_i
-            x64, xs64, vol64 = xt.double(), xs.double(), vol.double().reshape(T, 1, 1)
-            # (the workspaces, (1 + H) T N doubles, live for this call only: a forecast takes one posterior per fit)
-            _, alpha, info = ops.bm_step(x64, vol, noise, resid.double())
-            if int((info != 0).sum().item()):
-                if not bool(torch.isfinite(vol).all()) or not bool(torch.isfinite(noise).all()):
-                    raise NanError("BMGP posterior: NaN / inf in the kernel's vol or the noise")
-                raise NotPSDError("BMGP posterior: vol min(x, x') + sigma^2 I is not positive definite (the noise must be positive)")
-            Kts = vol.to(dt).reshape(T, 1, 1) * torch.minimum(xt.to(dt).unsqueeze(-1), xs.to(dt).unsqueeze(-2))     # [T,N,H]
-            X, _ = ops.bm_solve(xt, vol, noise, Kts)
-            mean_c = torch.zeros(T, H, dtype=torch.float64, device=xt.device)
-            S = torch.zeros(T, H, H, dtype=torch.float64, device=xt.device)
-            for lo in range(0, n, self._POST_CHUNK):
-                Kc = vol64 * torch.minimum(x64[lo:lo + self._POST_CHUNK].unsqueeze(-1), xs64.unsqueeze(-2))    # [T,c,H]
-                mean_c += torch.einsum("tnh,tn->th", Kc, alpha[:, lo:lo + self._POST_CHUNK])
-                S += Kc.mT @ X[:, lo:lo + self._POST_CHUNK].double()
-            Kss = vol64 * torch.minimum(xs64.unsqueeze(-1), xs64.unsqueeze(-2))
-            mean = (self.mean_module(x).double().reshape(T, H) + mean_c).to(dt)
-            cov = (Kss - S).to(dt)
-            if not batched:
-                mean, cov = mean[0], cov[0]
-            return MultivariateNormal(mean, cov)
+    def _chains(self):
+        """The T series as chains (models/_posterior.py): the kernel's vol, the likelihood's noise, the residual in fp64."""
+        xt = self.train_inputs[0][:, 0]
+        y = self.train_targets
+        T = y.shape[0] if y.ndim > 1 else 1
+        vol = self.covar_module.vol.reshape(-1).expand(T)
+        noise = self.likelihood.noise.reshape(-1).expand(T)
+        resid = (y - self.mean_module(xt)).reshape(T, xt.shape[0])
+        if self.posterior == "solve":             # (this route looks at the parameters only, and says so)
+            looked, nan = (vol, noise), "NaN / inf in the kernel's vol or the noise"
+        else:
+            looked, nan = (vol, noise, y), "NaN / inf in the targets or the parameters"
+        return Chains(xt.double(), vol, noise, resid.double(), "BMGP", looked, nan,
+                      "vol min(x, x') + sigma^2 I is not positive definite (the noise must be positive)")
 
-    def _posterior_sweep(self, x):
-        """The same posterior from ONE ops.bm_post launch over the sorted test points (any order and duplicates accepted:
-        sorted on the device, the order restored on the way out) and one host read of its info: mean* = m(x*) + m_h,
-        var = v xi_h - p_h, cov of neighbours = v xi_h - q_h, the rest by gp._markov_cov; fp64 throughout (the upcasts of
-        `_posterior_linear`), rounded once to the model's dtype."""
-        with torch.no_grad():
-            xt = self.train_inputs[0][:, 0]
-            y = self.train_targets
-            batched = y.ndim > 1
-            T = y.shape[0] if batched else 1
-            n = xt.shape[0]
-            xs = x[:, 0] if x.ndim > 1 else x
-            H = xs.shape[0]
-            dt = torch.float64 if y.dtype == torch.float64 else torch.float32
-            vol = self.covar_module.vol.reshape(-1).expand(T)
-            noise = self.likelihood.noise.reshape(-1).expand(T)
-            resid = (y - self.mean_module(xt)).reshape(T, n)
-            xs64, order = torch.sort(xs.double())
-            out, info = ops.bm_post(xt.double(), xs64, vol, noise, resid.double())
-            _check_post_info(info, order, "BMGP", (vol, noise, y),
-                             "vol min(x, x') + sigma^2 I is not positive definite (the noise must be positive)")
-            prior = vol.double().reshape(T, 1) * xs64
-            mean_s = self.mean_module(xs64).reshape(T, H) + out[:, 0]
-            if self.posterior == "chain":                      # the same forms, the covariance left lazy
-                mean = torch.empty_like(mean_s)
-                mean[:, order] = mean_s
-                diag, off = prior - out[:, 1], prior - out[:, 2]
-                if not batched:
-                    mean, diag, off = mean[0], diag[0], off[0]
-                return MultivariateNormal(mean.to(dt), _MarkovCov(diag, off, _sort_order(xs, order), dtype=dt, mean=mean))
-            cov_s = _markov_cov(prior - out[:, 1], prior - out[:, 2])
-            mean = torch.empty_like(mean_s)
-            mean[:, order] = mean_s
-            cov = torch.empty_like(cov_s)
-            cov[:, order.unsqueeze(-1), order.unsqueeze(0)] = cov_s
-            mean, cov = mean.to(dt), cov.to(dt)
-            if not batched:
-                mean, cov = mean[0], cov[0]
-            return MultivariateNormal(mean, cov)
+    def _solve(self, x, ch, dt):
+        """mean* = m(x*) + K_*t alpha and cov = K_** - K_*t A^-1 K_t* with alpha from the linear-time step (fp64: the residual
+        upcast) and A^-1 K_t* from the linear-time solve in the model's dtype (R = K_t* [T,N,H]); the two products over N are
+        accumulated in fp64, a block of rows at a time."""
+        xt = self.train_inputs[0][:, 0]
+        xs = x[:, 0] if x.ndim > 1 else x
+        (T, n), H = ch.resid.shape, xs.shape[0]
+        # alpha in fp64 and K_*t rebuilt in fp64 block by block below: K_*t alpha sums N terms of either sign, so an fp32
+        # rounding of alpha or of K_*t would come back multiplied by sum |alpha_i| K_i
+        x64, xs64, vol64 = ch.x, xs.double(), ch.vol.double().reshape(T, 1, 1)
+        # (the workspaces, (1 + H) T N doubles, live for this call only: a forecast takes one posterior per fit)
+        _, alpha, info = ops.bm_step(x64, ch.vol, ch.sigma2, ch.resid)
+        check_info(info, ch)
+        Kts = ch.vol.to(dt).reshape(T, 1, 1) * torch.minimum(xt.to(dt).unsqueeze(-1), xs.to(dt).unsqueeze(-2))     # [T,N,H]
+        X, _ = ops.bm_solve(xt, ch.vol, ch.sigma2, Kts)
+        mean_c = torch.zeros(T, H, dtype=torch.float64, device=xt.device)
+        S = torch.zeros(T, H, H, dtype=torch.float64, device=xt.device)
+        for lo in range(0, n, self._POST_CHUNK):
+            Kc = vol64 * torch.minimum(x64[lo:lo + self._POST_CHUNK].unsqueeze(-1), xs64.unsqueeze(-2))    # [T,c,H]
+            mean_c += torch.einsum("tnh,tn->th", Kc, alpha[:, lo:lo + self._POST_CHUNK])
+            S += Kc.mT @ X[:, lo:lo + self._POST_CHUNK].double()
+        Kss = vol64 * torch.minimum(xs64.unsqueeze(-1), xs64.unsqueeze(-2))
+        return (self.mean_module(x).double().reshape(T, H) + mean_c).to(dt), (Kss - S).to(dt)
+
+    def _posterior_dense(self, x, ch):
+        """K_s = L L' on the HIP potrf, K_s^-1 = Y Y' with Y = L^-T from the HIP triangular inverse, every product on the library
+        GEMM (_posterior.dense_products)."""
+        xt = self.train_inputs[0]
+        (T, n), H = ch.resid.shape, x.shape[0]
+        A = _dense(self.covar_module(xt, xt)).reshape(T, n, n) + ch.sigma2.reshape(T, 1, 1) * torch.eye(n, device=xt.device)
+        Kst = _dense(self.covar_module(x, xt)).reshape(T, H, n)
+        m, S = dense_products(A, Kst, ch.resid.to(torch.float32).reshape(T, 1, n))
+        return self.mean_module(x).reshape(T, H) + m.reshape(T, H), _dense(self.covar_module(x, x)).reshape(T, H, H) - S
 
     def posterior_call(self, x):
-        """Exact-GP posterior at the test points: K_s = L L' on the HIP potrf, K_s^-1 = Y Y' with Y = L^-T from the HIP
-        triangular inverse, every product on the library GEMM.  One series -> MultivariateNormal(mean [H], cov [H,H]);
-        T series over the shared grid -> (mean [T,H], cov [T,H,H]).  solver="linear": _posterior_linear, or _posterior_sweep
-        with posterior="sweep" / "chain"."""
-        if self.solver == "linear":
-            return self._posterior_linear(x) if self.posterior == "solve" else self._posterior_sweep(x)
+        """Exact-GP posterior at the test points.  One series -> MultivariateNormal(mean [H], cov [H,H]); T series over the
+        shared grid -> (mean [T,H], cov [T,H,H]).  solver="dense": `_posterior_dense`; solver="linear": `_solve`, or with
+        posterior="sweep" / "chain" _posterior.sweep -- mean* = m(x*) + m_h in fp64 (the upcasts of `_solve`), rounded once to the
+        model's dtype."""
         with torch.no_grad():
-            from ..gp import _dense
-            xt = self.train_inputs[0]
-            y = self.train_targets
-            batched = y.ndim > 1
-            T = y.shape[0] if batched else 1
-            n, H = xt.shape[0], x.shape[0]
-            Ktt = _dense(self.covar_module(xt, xt)).reshape(T, n, n)
-            noise = self.likelihood.noise.reshape(-1).expand(T)
-            A = Ktt + noise.reshape(T, 1, 1) * torch.eye(n, device=xt.device)
-            f, _ = _safe_factor(A)
-            Linv = ops.trtri(f).mT.contiguous()                                            # L^-1, rows K-contiguous
-            Kst = _dense(self.covar_module(x, xt)).reshape(T, H, n)
-            G = ops.gemm_nt(Kst, Linv, uplo_b=1)                                           # K_*t L^-T
-            r = (y - self.mean_module(xt)).to(torch.float32).reshape(T, 1, n)
-            w = ops.gemm_nt(r, Linv, uplo_b=1)                                             # (L^-1 r)'
-            mean = self.mean_module(x).reshape(T, H) + ops.gemm_nt(G, w).reshape(T, H)
-            cov = _dense(self.covar_module(x, x)).reshape(T, H, H) - ops.gemm_nt(G, G)
+            ch = self._chains()
+            batched = self.train_targets.ndim > 1
+            dt = torch.float64 if self.train_targets.dtype == torch.float64 else torch.float32
+            if self.solver == "linear" and self.posterior != "solve":
+                xs64 = (x[:, 0] if x.ndim > 1 else x).double()
+                lazy = self.posterior == "chain"
+                m, cov = sweep(ch, xs64, lazy, dt, batched=batched)
+                mean = self.mean_module(xs64).reshape(m.shape) + m
+                if not batched:
+                    mean = mean[0]
+                if lazy:
+                    cov.mean = mean               # (fp64: a chain draw rounds once, at its output)
+                return MultivariateNormal(mean.to(dt), cov)
+            mean, cov = self._solve(x, ch, dt) if self.solver == "linear" else self._posterior_dense(x, ch)
             if not batched:
                 mean, cov = mean[0], cov[0]
             return MultivariateNormal(mean, cov)
@@ -233,19 +159,13 @@ class MultitaskBMGP(ExactGP):
     ``posterior`` (solver="linear" only): "solve" (default) or "sweep", as for BMGP -- one ops.bm_post launch for all
     eigen-directions instead of a chain solve per group of test points -- or "chain": the sweep with the blocks
     C_j left lazy, every L_j z_j of a draw from one ops.markov_draw launch."""
-    SOLVERS = BMGP.SOLVERS
-    POSTERIORS = BMGP.POSTERIORS
+    SOLVERS = SOLVERS
+    POSTERIORS = POSTERIORS
     _POST_CHUNK = BMGP._POST_CHUNK
     _POST_SOLVE_ELEMS = 1 << 19               # directions x N x points per solve of the linear posterior (bounds its three buffers)
 
     def __init__(self, train_x, train_y, likelihood, base_mean=None, solver="dense", posterior="solve", **kwargs):
-        if solver not in self.SOLVERS:
-            raise ValueError(f"MultitaskBMGP: solver must be one of {self.SOLVERS}, got {solver!r}")
-        _check_posterior("MultitaskBMGP", posterior, solver)
-        if solver == "linear":
-            if train_x.ndim != 1:
-                raise ValueError(f"MultitaskBMGP(solver='linear'): the grid must be 1-D [N], got shape {tuple(train_x.shape)}")
-            check_grid(train_x, "MultitaskBMGP(solver='linear')")
+        check_options("MultitaskBMGP", solver, posterior, train_x)
         super().__init__(train_x, train_y, likelihood)
         if train_y.ndim != 2:
             raise ValueError("MultitaskBMGP: train_y must be [N, T]")
@@ -279,125 +199,79 @@ class MultitaskBMGP(ExactGP):
             M = torch.minimum(xs.unsqueeze(-1), xs.unsqueeze(-2))
         return MultitaskMultivariateNormal(self.mean_module(xs), _KroneckerPrior(self.covar_module, xs, M))
 
-    def _posterior_linear(self, x):
-        """`posterior_call` without any N x N matrix: the cold fp64 prologue as there; alpha_j from the linear-time step in
-        fp64; X_j = (M + sigma_j^2 I)^-1 M_x* from the linear-time solve; m~_j = sqrt(kappa_j) M_*x alpha_j and
-        C_j = kappa_j (M_** - M_*x X_j), the two products over N accumulated in fp64 over blocks of rows as
-        BMGP._posterior_linear does.  Returned in fp32, like the dense posterior."""
-        with torch.no_grad():
-            xt = self.train_inputs[0][:, 0]
-            Y = self.train_targets
-            n, T = Y.shape
-            xs = x[..., 0] if x.ndim > 1 else x
-            H = xs.shape[0]
-            dev = xt.device
-            if self._post_ws is None or not self._post_ws.fits(n, T, dev, torch.float64, "linear"):
-                self._post_ws = ops.KronWorkspace(n, T, dev, torch.float64, "linear")
-            ws = self._post_ws
-            task, data = self.covar_module.task_covar_module, self.covar_module.data_covar_module
-            params = (data.raw_vol, task.covar_factor, task.raw_var, self.likelihood.raw_task_noises, self.likelihood.raw_noise)
-            x64, xs64 = xt.double(), xs.double()
-            ops.kron_prologue(params, x64, Y, ws)
-            kap = ws.state[0] * ws.lam()                                                   # [T], fp64
-            _, alpha, info = ops.bm_step(x64, ws.ones, ws.sigma2, ws.resid, ws.bm, want_grad=True)
-            if int((info != 0).sum().item()):
-                if not all(bool(torch.isfinite(p).all()) for p in params) or not bool(torch.isfinite(Y).all()):
-                    raise NanError("MultitaskBMGP posterior: NaN / inf in the targets or the parameters")
-                raise NotPSDError("MultitaskBMGP posterior: M + sigma_j^2 I is not positive definite")
-            mt = torch.zeros(T, H, dtype=torch.float64, device=dev)
-            S = torch.zeros(T, H, H, dtype=torch.float64, device=dev)
-            m_sx = lambda lo, hi, h0=0, h1=H: torch.minimum(xs64[h0:h1].unsqueeze(-1), x64[lo:hi].unsqueeze(-2))   # M_*x block
-            for lo in range(0, n, self._POST_CHUNK):
-                mt += alpha[:, lo:lo + self._POST_CHUNK] @ m_sx(lo, lo + self._POST_CHUNK).t()
-            # the solve in groups of test points (at a large T, of directions too): its right-hand sides, X and workspace are
-            # each [directions, N, points] doubles, and a solve costs the length of the chain however many columns ride on it
-            jb = max(1, min(T, self._POST_SOLVE_ELEMS // n))
-            hb = max(1, min(H, self._POST_SOLVE_ELEMS // (n * jb)))
-            for j in range(0, T, jb):
-                for h in range(0, H, hb):
-                    rhs = m_sx(0, n, h, h + hb).t().unsqueeze(0).expand(min(jb, T - j), n, min(hb, H - h))
-                    X, _ = ops.bm_solve(x64, ws.ones[j:j + jb], ws.sigma2[j:j + jb], rhs)
-                    for lo in range(0, n, self._POST_CHUNK):
-                        S[j:j + jb, :, h:h + hb] += m_sx(lo, lo + self._POST_CHUNK).unsqueeze(0) @ X[:, lo:lo + self._POST_CHUNK]
-                    del X
-            mt = kap.sqrt().reshape(T, 1) * mt                                             # m~_j
-            Mss = torch.minimum(xs64.unsqueeze(-1), xs64.unsqueeze(-2))
-            C = (kap.reshape(T, 1, 1) * (Mss.unsqueeze(0) - S)).to(torch.float32)
-            V64 = ws.d().sqrt().unsqueeze(-1) * ws.Q()                                     # D^1/2 Q
-            mean = (self.mean_module(xs).double() + mt.t() @ V64.t()).to(torch.float32)
-            return MultitaskMultivariateNormal(mean, blocks=(V64.to(torch.float32), C))
+    def _chains(self):
+        """The cold fp64 prologue on the model's cached workspace -> (the workspace: d, Q; kappa [T] fp64; the T
+        eigen-directions as chains (models/_posterior.py): unit vol -- the linear workspace's ones --, sigma_j^2, r_j)."""
+        xt = self.train_inputs[0][:, 0]
+        Y = self.train_targets
+        n, T = Y.shape
+        if self._post_ws is None or not self._post_ws.fits(n, T, xt.device, torch.float64, self.solver):
+            self._post_ws = ops.KronWorkspace(n, T, xt.device, torch.float64, self.solver)
+        ws = self._post_ws
+        task, data = self.covar_module.task_covar_module, self.covar_module.data_covar_module
+        params = (data.raw_vol, task.covar_factor, task.raw_var, self.likelihood.raw_task_noises, self.likelihood.raw_noise)
+        ops.kron_prologue(params, xt, Y, ws)
+        ones = ws.ones if self.solver == "linear" else None                   # (the dense blocks fill M themselves)
+        return ws, ws.state[0] * ws.lam(), Chains(xt.double(), ones, ws.sigma2, ws.resid, "MultitaskBMGP", params + (Y,),
+                                                  "NaN / inf in the targets or the parameters",
+                                                  "M + sigma_j^2 I is not positive definite")
 
-    def _posterior_sweep(self, x):
-        """`_posterior_linear` with the T chain solves and the products over N replaced by ONE ops.bm_post launch over the
-        sorted test points (unit vol, the directions' sigma_j^2 and residuals of the cold fp64 prologue) and one host read of
-        its info: m~_j = sqrt(kappa_j) m_j and C_j = kappa_j markov_cov(xi - p_j, xi - q_j); the assembly is unchanged."""
-        with torch.no_grad():
-            xt = self.train_inputs[0][:, 0]
-            Y = self.train_targets
-            n, T = Y.shape
-            xs = x[..., 0] if x.ndim > 1 else x
-            dev = xt.device
-            if self._post_ws is None or not self._post_ws.fits(n, T, dev, torch.float64, "linear"):
-                self._post_ws = ops.KronWorkspace(n, T, dev, torch.float64, "linear")
-            ws = self._post_ws
-            task, data = self.covar_module.task_covar_module, self.covar_module.data_covar_module
-            params = (data.raw_vol, task.covar_factor, task.raw_var, self.likelihood.raw_task_noises, self.likelihood.raw_noise)
-            x64 = xt.double()
-            ops.kron_prologue(params, x64, Y, ws)
-            kap = ws.state[0] * ws.lam()                                                   # [T], fp64
-            xs64, order = torch.sort(xs.double())
-            out, info = ops.bm_post(x64, xs64, ws.ones, ws.sigma2, ws.resid)
-            _check_post_info(info, order, "MultitaskBMGP", params + (Y,), "M + sigma_j^2 I is not positive definite")
-            mt_s = kap.sqrt().reshape(T, 1) * out[:, 0]                                    # m~_j over the sorted points
-            V64 = ws.d().sqrt().unsqueeze(-1) * ws.Q()                                     # D^1/2 Q
-            if self.posterior == "chain":                      # the same forms, the blocks C_j left lazy
-                mt = torch.empty_like(mt_s)
-                mt[:, order] = mt_s
-                mean = (self.mean_module(xs).double() + mt.t() @ V64.t()).to(torch.float32)
-                C = _MarkovCov(xs64 - out[:, 1], xs64 - out[:, 2], _sort_order(xs, order), scale=kap, dtype=torch.float32)
-                return MultitaskMultivariateNormal(mean, blocks=(V64.to(torch.float32), C))
-            C_s = kap.reshape(T, 1, 1) * _markov_cov(xs64 - out[:, 1], xs64 - out[:, 2])
-            mt = torch.empty_like(mt_s)
-            mt[:, order] = mt_s
-            C = torch.empty_like(C_s)
-            C[:, order.unsqueeze(-1), order.unsqueeze(0)] = C_s
-            mean = (self.mean_module(xs).double() + mt.t() @ V64.t()).to(torch.float32)
-            return MultitaskMultivariateNormal(mean, blocks=(V64.to(torch.float32), C.to(torch.float32)))
+    def _solve(self, xs, ws, ch):
+        """Without any N x N matrix: alpha_j from the linear-time step in fp64; X_j = (M + sigma_j^2 I)^-1 M_x* from the
+        linear-time solve; m_j = M_*x alpha_j and M_** - M_*x X_j, the two products over N accumulated in fp64 over blocks of
+        rows as BMGP._solve does."""
+        (T, n), H = ch.resid.shape, xs.shape[0]
+        x64, xs64 = ch.x, xs.double()
+        _, alpha, info = ops.bm_step(x64, ch.vol, ch.sigma2, ch.resid, ws.bm, want_grad=True)
+        check_info(info, ch)
+        mt = torch.zeros(T, H, dtype=torch.float64, device=x64.device)
+        S = torch.zeros(T, H, H, dtype=torch.float64, device=x64.device)
+        m_sx = lambda lo, hi, h0=0, h1=H: torch.minimum(xs64[h0:h1].unsqueeze(-1), x64[lo:hi].unsqueeze(-2))   # M_*x block
+        for lo in range(0, n, self._POST_CHUNK):
+            mt += alpha[:, lo:lo + self._POST_CHUNK] @ m_sx(lo, lo + self._POST_CHUNK).t()
+        # the solve in groups of test points (at a large T, of directions too): its right-hand sides, X and workspace are
+        # each [directions, N, points] doubles, and a solve costs the length of the chain however many columns ride on it
+        jb = max(1, min(T, self._POST_SOLVE_ELEMS // n))
+        hb = max(1, min(H, self._POST_SOLVE_ELEMS // (n * jb)))
+        for j in range(0, T, jb):
+            for h in range(0, H, hb):
+                rhs = m_sx(0, n, h, h + hb).t().unsqueeze(0).expand(min(jb, T - j), n, min(hb, H - h))
+                X, _ = ops.bm_solve(x64, ch.vol[j:j + jb], ch.sigma2[j:j + jb], rhs)
+                for lo in range(0, n, self._POST_CHUNK):
+                    S[j:j + jb, :, h:h + hb] += m_sx(lo, lo + self._POST_CHUNK).unsqueeze(0) @ X[:, lo:lo + self._POST_CHUNK]
+                del X
+        return mt, torch.minimum(xs64.unsqueeze(-1), xs64.unsqueeze(-2)).unsqueeze(0) - S
 
     def posterior_call(self, x):
         """Exact latent posterior at x [H] (gpytorch's eval-mode ExactGP call): a MultitaskMultivariateNormal with mean [H,T].
         Block by block in the eigenbasis of the task covariance: the prologue (fp64) gives W, Lambda and
         r_j; then per block m~_j = sqrt(kappa_j) M_*x (M + sigma_j^2 I)^-1 r_j and C_j = kappa_j [M_** - M_*x (M +
-        sigma_j^2 I)^-1 M_x*] on the HIP potrf / triangular inverse / GEMM, as BMGP.posterior_call does; finally
-        mean = mu_* + m~ V' and cov = (I (x) V) blockdiag(C_j) (I (x) V'), V = D^1/2 Q.  solver="linear": _posterior_linear, or
-        _posterior_sweep with posterior="sweep" / "chain"."""
-        if self.solver == "linear":
-            return self._posterior_linear(x) if self.posterior == "solve" else self._posterior_sweep(x)
+        sigma_j^2 I)^-1 M_x*]; finally mean = mu_* + m~ V' and cov = (I (x) V) blockdiag(C_j) (I (x) V'), V = D^1/2 Q.
+        solver="dense": the blocks in fp32 on the HIP potrf / triangular inverse / GEMM (_posterior.dense_products), as
+        BMGP's.  solver="linear": in fp64 from `_solve`, or with posterior="sweep" / "chain" from ONE ops.bm_post launch for all
+        directions (_posterior.sweep; "chain": the blocks C_j left lazy), rounded once to fp32 like the dense posterior."""
         with torch.no_grad():
-            xt = self.train_inputs[0][:, 0]
-            Y = self.train_targets
-            n, T = Y.shape
             xs = x[..., 0] if x.ndim > 1 else x
-            H = xs.shape[0]
-            dev = xt.device
-            if self._post_ws is None or self._post_ws.state.device != dev:
-                self._post_ws = ops.KronWorkspace(n, T, dev, torch.float64)
-            ws = self._post_ws
-            task, data = self.covar_module.task_covar_module, self.covar_module.data_covar_module
-            params = (data.raw_vol, task.covar_factor, task.raw_var, self.likelihood.raw_task_noises, self.likelihood.raw_noise)
-            ops.kron_prologue(params, xt, Y, ws)
-            kap = (ws.state[0] * ws.lam()).to(torch.float32)                               # [T]
-            M = self._base.to(torch.float32)
-            A = M.unsqueeze(0) + ws.sigma2.to(torch.float32).reshape(T, 1, 1) * torch.eye(n, device=dev)
-            f, _ = _safe_factor(A)
-            Linv = ops.trtri(f).mT.contiguous()                                            # L_j^-1
-            xs32, xt32 = xs.to(torch.float32), xt.to(torch.float32)
+            ws, kap, ch = self._chains()
+            (T, n), H = ch.resid.shape, xs.shape[0]
+            V = ws.d().sqrt().unsqueeze(-1) * ws.Q()                                       # D^1/2 Q, fp64
+            if self.solver == "linear":
+                if self.posterior == "solve":
+                    m, C = self._solve(xs, ws, ch)
+                    C = (kap.reshape(T, 1, 1) * C).to(torch.float32)
+                else:
+                    m, C = sweep(ch, xs, self.posterior == "chain", torch.float32, scale=kap)
+                mt = kap.sqrt().reshape(T, 1) * m                                          # m~_j
+                mean = (self.mean_module(xs).double() + mt.t() @ V.t()).to(torch.float32)
+                return MultitaskMultivariateNormal(mean, blocks=(V.to(torch.float32), C))
+            kap, V = kap.to(torch.float32), V.to(torch.float32)
+            s32 = ch.sigma2.to(torch.float32).reshape(T, 1, 1)
+            A = self._base.to(torch.float32).unsqueeze(0) + s32 * torch.eye(n, device=xs.device)
+            xs32, xt32 = xs.to(torch.float32), self.train_inputs[0][:, 0].to(torch.float32)
             Mst = torch.minimum(xs32.unsqueeze(-1), xt32.unsqueeze(-2)).expand(T, H, n).contiguous()
-            G = ops.gemm_nt(Mst, Linv, uplo_b=1)                                           # M_*x L^-T
-            w = ops.gemm_nt(ws.resid.to(torch.float32).reshape(T, 1, n), Linv, uplo_b=1)   # (L^-1 r)'
-            mt = kap.sqrt().reshape(T, 1) * ops.gemm_nt(G, w).reshape(T, H)               # m~_j
+            m, S = dense_products(A, Mst, ch.resid.to(torch.float32).reshape(T, 1, n))
+            mt = kap.sqrt().reshape(T, 1) * m.reshape(T, H)                                # m~_j
             Mss = torch.minimum(xs32.unsqueeze(-1), xs32.unsqueeze(-2))
-            C = kap.reshape(T, 1, 1) * (Mss.unsqueeze(0) - ops.gemm_nt(G, G))
-            V = (ws.d().sqrt().unsqueeze(-1) * ws.Q()).to(torch.float32)                   # D^1/2 Q
+            C = kap.reshape(T, 1, 1) * (Mss.unsqueeze(0) - S)
             mean = self.mean_module(xs).to(torch.float32) + ops.gemm_nt(mt.t().contiguous(), V)
             return MultitaskMultivariateNormal(mean, blocks=(V, C))

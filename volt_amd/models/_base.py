@@ -8,7 +8,8 @@ from .. import ops
 from ..gp import (ExactGP, ExactMarginalLogLikelihood, GaussianLikelihood, MultitaskGaussianLikelihood, MultivariateNormal,
                   _VolPrior, same_values)
 from ..kernels import VolatilityKernel
-from .BMGP import BMGP, MultitaskBMGP, _check_posterior
+from ._posterior import check_options
+from .BMGP import BMGP, MultitaskBMGP
 
 
 class VolGP(ExactGP):
@@ -51,7 +52,7 @@ class VolGP(ExactGP):
         # solver (BMGP(solver="linear"), csrc/bm.hip), and MultitaskBMGP on the linear-time Kronecker step (csrc/kron_chain.hip).
         if vol_solver not in BMGP.SOLVERS:
             raise ValueError(f"vol_solver must be one of {BMGP.SOLVERS}, got {vol_solver!r}")
-        _check_posterior("vol_posterior", vol_posterior, vol_solver)
+        check_options("vol_posterior", vol_solver, vol_posterior)
         self.vol_solver = vol_solver          # Volt.Train refits the vol forecaster: with the solver the model was built with
         self.vol_posterior = vol_posterior    # ... and with the same posterior
         if multitask_vol:
