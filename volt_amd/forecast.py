@@ -21,9 +21,9 @@ import warnings
 import torch
 
 from . import rollout_engine
-from .gp import NanError, NotPSDError, NumericalWarning
 from .distributed import shard_range
 from .rollout_utils import _linear_draw, _posterior_draw, _resolve_draw, _resolve_solver
+from .safe import NanError, NotPSDError, NumericalWarning, _safe_draw, _safe_forms
 from .train_utils import LearnGPCV, TrainVoltMagpieBatch, TrainVolModelBatch, TrainVolModelMultitask
 
 _MODES = {"ewma": 0, "dewma": 1, "tewma": 2}
@@ -43,7 +43,7 @@ def realised_vol(train_x, prices, span=20, floor=1e-3):
 def _standard_mean_prediction_linear(train_x, resid, m_te, vol, test_x, pred_vol, z, jitter=1e-4, max_blocks=4096,
                                      draw="factor"):
     """`_standard_mean_prediction` with solver="linear" (DESIGN 4.15): the train blocks of all B series are conditioned on by
-    ONE volt_vk_forms_* launch (gp._safe_forms) instead of B x S factorisations, and nothing is N x N or N x H.  The stacked
+    ONE volt_vk_forms_* launch (safe._safe_forms) instead of B x S factorisations, and nothing is N x N or N x H.  The stacked
     integrated path of rollout_utils.py:17-26 splits at the last train point: its train part U [B,N] keeps the full weight
     on point N-1 (the halved last weight sits on the last test point), and what the H appended points add on top of U[N-1] is
     the CumTrapz of [vol_{N-1}, pred_vol] less its first entry -- both from ops.cumtrapz in fp64.  The H x H predictive
@@ -52,7 +52,6 @@ def _standard_mean_prediction_linear(train_x, resid, m_te, vol, test_x, pred_vol
     is formed inside the kernel, so there is no ``tail`` / ``V_te`` tensor, no H x H block and no ``max_blocks`` loop: nothing
     beyond the inputs and the [B,S,H] result."""
     from . import ops
-    from .gp import _safe_draw, _safe_forms
     B, S, H = pred_vol.shape
     N = train_x.numel()
     f64 = torch.float64

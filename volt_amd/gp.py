@@ -18,13 +18,14 @@ from __future__ import annotations
 
 import math
 import threading
-import warnings
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import ops
+from . import ops, safe
+from .safe import (NanError, NotPSDError, NumericalWarning, deferred_checks,                  # noqa: F401 -- re-exported: the
+                   psd_safe_cholesky, _safe_draw, _safe_factor, _safe_forms)                  # failure policy lives in safe.py
 
 
 def same_values(a: torch.Tensor, b: torch.Tensor) -> bool:
@@ -55,101 +56,6 @@ class EqualMemo:
             import weakref
             self._ref, self._ver = weakref.ref(x), (x._version, stored._version)
         return ok
-
-
-class NotPSDError(RuntimeError):
-    pass
-
-
-class deferred_checks:
-    """Context in which the factorisation's per-matrix ``info`` is NOT read back on the host after every step (that
-    read is a device synchronisation, and it makes a training iteration impossible to capture in a hipGraph) but
-    OR-ed into a device-side accumulator; ``any_bad()`` / ``raise_if_bad()`` read it when the caller chooses.  The
-    training loops of train_utils use it (graph-captured loops, and the batched eager loops, which check every few
-    iterations and replay from a snapshot with gpytorch's jitter ladder when a step failed).
-
-    ``immediate = True`` keeps the per-step host check (and the ladder) while still sizing the accumulators: one
-    accumulator per (length, device) of ``info``, so an iteration that factors batches of different shapes (an MLL
-    step and a GPCV step, two models) keeps every flag, and nothing is allocated -- or re-zeroed on replay -- inside
-    a graph capture: run one iteration with ``immediate = True`` under the context first."""
-    _active = None
-
-    def __init__(self, immediate=False):
-        self.immediate = immediate
-        self._acc = {}
-
-    def __enter__(self):
-        self._prev = deferred_checks._active
-        deferred_checks._active = self
-        return self
-
-    def __exit__(self, *exc):
-        deferred_checks._active = self._prev
-        return False
-
-    @classmethod
-    def deferring(cls):
-        """The active context if it is deferring the check, else None."""
-        a = cls._active
-        return a if a is not None and not a.immediate else None
-
-    def _slot(self, info):
-        flat = info.reshape(-1)
-        key = (flat.shape[0], flat.device)
-        acc = self._acc.get(key)
-        if acc is None:
-            if flat.is_cuda and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("deferred_checks: no accumulator for this info shape yet -- run one iteration with "
-                                   "immediate=True under the context before capturing")
-            acc = self._acc[key] = torch.zeros_like(flat)
-        return acc, flat
-
-    def reserve(self, info):
-        self._slot(info)
-
-    def note(self, info):
-        acc, flat = self._slot(info)
-        acc.bitwise_or_(flat)                            # one launch per step; non-zero once any step failed
-
-    @classmethod
-    def settle(cls, *infos) -> bool:
-        """The protocol every step follows once its ``info`` words are on the device.  While deferring: OR each into its
-        accumulator and return False -- no allocation and no host read, so the step can be captured.  Otherwise: size the
-        accumulators if a context is active (``immediate``) and return True -- the caller reads ``info`` on the host now."""
-        chk = cls._active
-        if chk is not None:
-            for info in infos:
-                (chk.reserve if chk.immediate else chk.note)(info)
-        return chk is None or chk.immediate
-
-    def clear(self):
-        for acc in self._acc.values():
-            acc.zero_()
-
-    def any_bad(self) -> int:
-        """Number of matrices with a failed factorisation since the last clear() -- ONE host read."""
-        if not self._acc:
-            return 0
-        return int(torch.stack([(a != 0).sum() for a in self._acc.values()]).sum().item())
-
-    def raise_if_bad(self):
-        nbad = self.any_bad()
-        if nbad and any(bool((a < 0).any().item()) for a in self._acc.values()):
-            # (the accumulators OR the steps' info words: a negative one holds an internal code -- INT_MIN, INT_MIN + 1 --, not a pivot)
-            raise ops._lib.VoltHipError("a factorisation reported an INTERNAL error (hand-off time-out / workspace table) while "
-                                        "the check was deferred; rerun without deferral: the step is then re-run on the "
-                                        "launch-per-column schedule")
-        if nbad:
-            raise NotPSDError(f"{nbad} matrices failed a factorisation while the check was deferred (not positive "
-                              "definite); rerun without deferral to get gpytorch's jitter-retry behaviour")
-
-
-class NanError(RuntimeError):
-    pass
-
-
-class NumericalWarning(RuntimeWarning):
-    pass
 
 
 # ------------------------------------------------------------------------------------ modules
@@ -769,39 +675,30 @@ class _ExactMLL(torch.autograd.Function):
         ws = holder.workspace(B, n, need_grad, K.device, dt)
         resid = (target - mean).to(dt)
         noise = noise.to(dt)
-        # gpytorch factors through psd_safe_cholesky: plain first, then jitter 1e-6 * 10^i (fp32 default) with a
-        # NumericalWarning, then NotPSDError.  Same ladder here; the jitter is added inside the fused step.
-        out, alpha, info = ops.mll_step(K, resid, noise, ws, want_grad=need_grad, jitter=0.0, refine_alpha=refine_alpha.active())
+        # gpytorch factors through psd_safe_cholesky: plain first, then its jitter ladder (safe.py), the jitter added inside
+        # the fused step.  Unlike `_safe_factor`, the rungs go back to the one-launch schedule after a table-free re-run.
+        run = lambda jitter=0.0, **kw: ops.mll_step(K, resid, noise, ws, want_grad=need_grad, jitter=jitter,
+                                                    refine_alpha=refine_alpha.active(), **kw)
+        out, alpha, info = run()
         bad = int((info != 0).sum().item()) if deferred_checks.settle(info) else 0
         if bad and ops.info_internal(info):
-            # NOT "not positive definite": a one-launch step's hand-off timed out or its workspace table is not what the init
-            # wrote (include/volt_hip.h: info <= INT_MIN + 1).  gpytorch's ladder is for pivots; this is re-run ONCE on the
-            # launch-per-column schedule (fp32: the table-free path of the same entry point) and reported.
+            # an internal code (include/volt_hip.h), not a pivot.  The fp64 step has no table-free schedule to re-run on.
             codes = sorted({int(v) & 0xffffffff for v in info[info <= ops._lib.INFO_INTERNAL_MAX].tolist()})
             if dt != torch.float32:
                 raise ops._lib.VoltHipError(f"volt_mll_step_f64: internal error, info = {[hex(c) for c in codes]}")
-            warnings.warn(f"volt_mll_step_f32 reported an internal error (info = {[hex(c) for c in codes]}) on its one-launch "
-                          "schedule; the step was re-run on the launch-per-column schedule", ops._lib.VoltHipWarning)
-            out, alpha, info = ops.mll_step(K, resid, noise, ws, want_grad=need_grad, jitter=0.0,
-                                            refine_alpha=refine_alpha.active(), tables=False)
-            if ops.info_internal(info):
-                raise ops._lib.VoltHipError(f"volt_mll_step_f32: internal error on both schedules, info = {info.tolist()}")
+            out, alpha, info = safe.rerun_table_free(
+                run, lambda res: res[2],
+                f"volt_mll_step_f32 reported an internal error (info = {[hex(c) for c in codes]}) on its one-launch "
+                "schedule; the step was re-run on the launch-per-column schedule",
+                lambda info: f"volt_mll_step_f32: internal error on both schedules, info = {info.tolist()}")
             bad = int((info != 0).sum().item())
         if bad:
-            if torch.isnan(K).any() or torch.isnan(resid).any() or torch.isnan(noise).any():
-                raise NanError("cholesky: NaN in the covariance, the noise or the residual")
-            first = int(info[info != 0][0].item())
-            for i in range(3):
-                jitter = (1e-6 if dt == torch.float32 else 1e-8) * (10 ** i)      # gpytorch's defaults per dtype
-                out, alpha, info = ops.mll_step(K, resid, noise, ws, want_grad=need_grad, jitter=jitter, refine_alpha=refine_alpha.active())
-                if ops.info_internal(info):
-                    raise ops._lib.VoltHipError(f"volt_mll_step: internal error, info = {info.tolist()}")
-                if not bool((info != 0).any().item()):
-                    warnings.warn(f"A not p.d., added jitter of {jitter:.1e} to the diagonal", NumericalWarning)
-                    break
-            else:
-                raise NotPSDError(f"K + sigma^2 I not positive definite for {bad} of {B} series after jitter "
-                                  f"(first failing pivot {first})")
+            safe.check_nan((K, resid, noise), "cholesky: NaN in the covariance, the noise or the residual")
+            internal = lambda info: f"volt_mll_step: internal error, info = {info.tolist()}"
+            (out, alpha, info), _ = safe.jitter_ladder(
+                run, lambda res: safe.info_failed(res[2], internal), safe.default_jitter(dt != torch.float32),
+                exhausted=f"K + sigma^2 I not positive definite for {bad} of {B} series after jitter "
+                          f"(first failing pivot {int(info[info != 0][0].item())})")
         ctx.n = n
         ctx.has_scale = scale is not None
         ctx.want_dk = want_dk
@@ -869,8 +766,7 @@ class _ChainMLL(torch.autograd.Function):
                     what, K, inputs = "volatility-kernel", "V[min(i, j)]", "the integrated vol path"
                 else:
                     what, K, inputs = "Brownian-motion", "vol min(x, x')", "the grid, the scale"
-                if any(torch.isnan(t).any() for t in (resid, noise, grid) + (() if scale is None else (scale,))):
-                    raise NanError(f"{what} MLL: NaN in {inputs}, the noise or the residual")
+                safe.check_nan((resid, noise, grid, scale), f"{what} MLL: NaN in {inputs}, the noise or the residual")
                 raise NotPSDError(f"{K} + sigma^2 I not positive definite for {bad} of {B} series "
                                   f"(first failing pivot {int(info[info != 0][0].item())}): the noise must be positive")
         ctx.n = n
@@ -1019,95 +915,6 @@ class ExactMarginalLogLikelihood(Module):
         res = step(mean2.to(dt), noise.to(dt), t2.to(dt))
         res = res.reshape(mean.shape[:-1]) if mean.ndim > 1 else res.reshape(())
         return self._add_log_priors(res, n)
-
-
-# -------------------------------------------------------------------------- psd_safe_cholesky
-def psd_safe_cholesky(A, upper=False, out=None, jitter=None, max_tries=3):
-    """gpytorch.utils.cholesky.psd_safe_cholesky on the HIP potrf: try once; on a non-positive
-    pivot add jitter * 10^i (i = 0..max_tries-1; default 1e-6 fp32 / 1e-8 fp64) to the diagonal and
-    retry, warning like gpytorch; raise NanError / NotPSDError otherwise.  Returns dense L."""
-    f, _ = _safe_factor(A, jitter, max_tries)
-    L = f.L.reshape(A.shape)
-    return L.transpose(-1, -2) if upper else L
-
-
-def _safe_factor(A, jitter=None, max_tries=3):
-    """psd_safe_cholesky's retry policy around the HIP potrf, in A's own dtype (fp32 or fp64; anything else is
-    computed in fp32)."""
-    n = A.shape[-1]
-    A3 = A.reshape(-1, n, n)
-    if A3.dtype != torch.float64:
-        A3 = A3.to(torch.float32)
-    f = ops.potrf(A3)
-    if not bool((f.info != 0).any().item()):
-        return f, 0.0
-    tables = True
-    if ops.info_internal(f.info):
-        # an internal error of the one-launch factorisation (time-out / workspace table), not a pivot: once more on the
-        # launch-per-column schedule, and that schedule for the rest of this call
-        warnings.warn(f"volt_potrf reported an internal error (info = {f.info.tolist()[:4]} ...) on its one-launch schedule; "
-                      "re-run on the launch-per-column schedule", ops._lib.VoltHipWarning)
-        tables = False
-        f = ops.potrf(A3, tables=False)
-        if ops.info_internal(f.info):
-            raise ops._lib.VoltHipError(f"volt_potrf: internal error on both schedules, info = {f.info.tolist()[:8]}")
-        if not bool((f.info != 0).any().item()):
-            return f, 0.0
-    if torch.isnan(A3).any():
-        raise NanError(f"cholesky_cpu: {int(torch.isnan(A3).sum())} of {A3.numel()} elements of the {tuple(A.shape)} tensor are NaN.")
-    if jitter is None:
-        jitter = 1e-6 if A.dtype == torch.float32 else 1e-8
-    for i in range(max_tries):
-        jitter_new = jitter * (10 ** i)
-        f = ops.potrf(A3, jitter=jitter_new, tables=tables)
-        if ops.info_internal(f.info):
-            raise ops._lib.VoltHipError(f"volt_potrf: internal error, info = {f.info.tolist()[:8]}")
-        if not bool((f.info != 0).any().item()):
-            warnings.warn(f"A not p.d., added jitter of {jitter_new:.1e} to the diagonal", NumericalWarning)
-            return f, jitter_new
-    raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitter_new:.1e}.")
-
-
-def _safe_forms(V, resid, jitter=None, max_tries=3):
-    """`_safe_factor`'s retry policy around ops.vk_forms: the conditioning scalars of the train block A = V[min(i,j)] + j I that
-    the dense route gets from a factorisation, in O(N).  Plain first (j = 0), then jitter * 10^i for the whole batch; the
-    default rung is 1e-6 for fp32 input and 1e-8 for fp64 input.  V [N] or [G,N], resid [G,N].  Returns
-    (out [G,4] fp64 = V'A^-1 V, V'A^-1 r, r'A^-1 r, logdet A; the jitter used)."""
-    out, info = ops.vk_forms(V, 0.0, resid)
-    if not bool((info != 0).any().item()):
-        return out, 0.0
-    if torch.isnan(V).any():
-        raise NanError(f"cholesky_cpu: {int(torch.isnan(V).sum())} of {V.numel()} elements of the {tuple(V.shape)} tensor are NaN.")
-    if jitter is None:
-        jitter = 1e-6 if resid.dtype != torch.float64 else 1e-8
-    for i in range(max_tries):
-        jitter_new = jitter * (10 ** i)
-        out, info = ops.vk_forms(V, jitter_new, resid)
-        if not bool((info != 0).any().item()):
-            warnings.warn(f"A not p.d., added jitter of {jitter_new:.1e} to the diagonal", NumericalWarning)
-            return out, jitter_new
-    raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitter_new:.1e}.")
-
-
-def _safe_draw(draw, inputs=(), jitter=None, max_tries=3, f64=False):
-    """`_safe_forms`'s retry policy around a chain draw (ops.markov_draw / ops.vk_draw): ``draw(j) -> (out, info)`` is tried
-    plain first (j = 0), then with jitter * 10^i for the whole batch; the default rung is 1e-6, or 1e-8 for an fp64 model
-    (``f64``), as in `_safe_factor`.  ``inputs``: the tensors looked at for NaN on a failure.  Returns (out, the jitter used)."""
-    out, info = draw(0.0)
-    if not bool((info != 0).any().item()):
-        return out, 0.0
-    for t in inputs:
-        if torch.is_tensor(t) and torch.isnan(t).any():
-            raise NanError(f"cholesky_cpu: {int(torch.isnan(t).sum())} of {t.numel()} elements of the {tuple(t.shape)} tensor are NaN.")
-    if jitter is None:
-        jitter = 1e-8 if f64 else 1e-6
-    for i in range(max_tries):
-        jitter_new = jitter * (10 ** i)
-        out, info = draw(jitter_new)
-        if not bool((info != 0).any().item()):
-            warnings.warn(f"A not p.d., added jitter of {jitter_new:.1e} to the diagonal", NumericalWarning)
-            return out, jitter_new
-    raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitter_new:.1e}.")
 
 
 LOG_2PI = math.log(2 * math.pi)

@@ -7,7 +7,8 @@ from typing import NamedTuple
 import torch
 
 from .. import ops
-from ..gp import NanError, NotPSDError, _MarkovCov, _safe_factor, check_grid
+from ..gp import _MarkovCov, check_grid
+from ..safe import NanError, NotPSDError, _safe_factor
 
 SOLVERS = ("dense", "linear")
 POSTERIORS = ("solve", "sweep", "chain")

@@ -15,7 +15,8 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..gp import ConstantMean, EqualMemo, Module, MultitaskMean, _dense, _safe_factor
+from ..gp import ConstantMean, EqualMemo, Module, MultitaskMean, _dense
+from ..safe import _safe_factor
 from ..kernels.MultitaskKernel import IndexKernel
 from ..variational import MIN_VARIANCE, PRIOR_JITTER, MultitaskVariationalLatent, _gauss_hermite
 

@@ -8,7 +8,8 @@ factorisations of ``initialize_variational_parameters`` -- runs through the HIP 
 import torch
 
 from .. import ops
-from ..gp import ConstantMean, EqualMemo, Module, MultivariateNormal, _BrownianPrior, _dense, _safe_factor, check_grid
+from ..gp import ConstantMean, EqualMemo, Module, MultivariateNormal, _BrownianPrior, _dense, check_grid
+from ..safe import _safe_factor
 from ..kernels.BMKernel import BMKernel
 from ..likelihoods import VolatilityGaussianLikelihood  # noqa: F401  (re-exported like the reference's module namespace)
 from ..variational import CholeskyVariationalDistribution, UnwhitenedVariationalStrategy, VariationalLatent

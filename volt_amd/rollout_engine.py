@@ -13,8 +13,9 @@ import warnings
 import torch
 
 from . import _lib, ops
-from .gp import NotPSDError, NumericalWarning, _safe_factor, _safe_forms, _dense as _dense_cov
+from .gp import _dense as _dense_cov
 from .means import DEWMAMean, EWMAMean, MeanRevertingEMAMean, TEWMAMean
+from .safe import NotPSDError, NumericalWarning, _safe_factor, _safe_forms
 
 _MODES = {EWMAMean: 0, DEWMAMean: 1, TEWMAMean: 2, MeanRevertingEMAMean: 3}
 
@@ -72,7 +73,7 @@ def train_block_terms(U, r_tr, solve="factor", jitter=1e-4):
     condition number 1e6 (N = 400) .. 1e8 (N = 4096) and an fp32 factor cannot carry it.  The closed form is one of the
     min-structure identities SURVEY 4 reserves for testing: it stays available (and the tests hold the two against each
     other), but the product path no longer leans on it.
-    solve="chain" takes the same general jittered route in O(N) per series, with no N x N block: gp._safe_forms, the ladder
+    solve="chain" takes the same general jittered route in O(N) per series, with no N x N block: safe._safe_forms, the ladder
     of `_safe_factor` around volt_vk_forms_* (csrc/bm.hip; fp64 arithmetic on U as stored, one launch for all G series).  It
     is what a model with predict_solver="linear" runs."""
     U64 = U.double()

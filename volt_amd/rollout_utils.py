@@ -21,27 +21,11 @@ O(N) instead: `_posterior_draw_linear`, ``train_block_terms(solve="chain")`` -- 
 from __future__ import annotations
 
 import os
-import warnings
 
 import torch
 
 from . import ops
-from .gp import NanError, NotPSDError, NumericalWarning, _safe_draw, _safe_factor
-
-
-def _chol_1x1(pc: torch.Tensor, jitter):
-    """psd_safe_cholesky of a [...,1,1] matrix (rollout_utils.py:46): sqrt, with the jitter ladder."""
-    if bool((pc > 0).all()):
-        return pc.sqrt()
-    if torch.isnan(pc).any():
-        raise NanError("cholesky: NaN in the predictive covariance")
-    jitter = 1e-6 if jitter is None else jitter
-    for i in range(3):
-        pj = pc + jitter * (10 ** i)
-        if bool((pj > 0).all()):
-            warnings.warn(f"A not p.d., added jitter of {jitter * 10 ** i:.1e} to the diagonal", NumericalWarning)
-            return pj.sqrt()
-    raise NotPSDError("predictive covariance not positive definite after adding jitter")
+from .safe import _chol_1x1, _safe_draw, _safe_factor, _safe_forms, default_jitter
 
 
 def _posterior_draw(covar_module, full_x, full_vol, idx_cut, train_diffs, test_mean_term, z, jitter,
@@ -134,8 +118,7 @@ def _linear_draw(rho, tau, V_last, V_te, test_mean_term, z, jitter, latent_mean,
         mean = pred_mean.expand(G, T, 1).reshape(G, T)
         zc = z.to(dt).mT.reshape(G, Sg * n, T)                                             # [S,n,T]: the n columns are `reps`
         pv = pred_vol.to(dt).reshape(G, Sg, T)
-        if T == 1 and jitter is None:
-            jitter = 1e-6                                                                  # `_chol_1x1`'s first rung, whatever the dtype
+        jitter = default_jitter(False) if T == 1 and jitter is None else jitter           # `_chol_1x1`'s first rung, whatever the dtype
         out, _ = _safe_draw(lambda j: ops.vk_draw(pv, vol_last, vlr, dx, mean, zc, j, reps=n), (pv, vlr, mean, zc), jitter,
                             f64=dt == f64)
         return out.reshape(S, n, T).mT
@@ -159,12 +142,11 @@ def _posterior_draw_linear(covar_module, full_x, full_vol, idx_cut, train_diffs,
     """`_posterior_draw` without any N x N or N x T array (solver="linear"): same arguments, same result to
     rounding.  The stacked integrated path V comes from ops.cumtrapz in fp64; its first N entries are the train block
     K = V[min(i,j)] (they do not depend on the test vols: CumTrapz's halved last weight sits on the last test point), and the
-    train block enters only through the two scalars of gp._safe_forms (volt_vk_forms_*, one O(N) sweep per grid, the
+    train block enters only through the two scalars of safe._safe_forms (volt_vk_forms_*, one O(N) sweep per grid, the
     project's jitter ladder around it).  One grid serves all S samples when their train rows are shared; per-sample histories
     (the dense Rollouts engine after its first step) run as S grids in one launch.
     ``draw="chain"``: the integrated path is formed over the train part alone (the same products in the same order: its N
     entries are bit for bit those of the stacked path) and the test part inside ops.vk_draw -- `_linear_draw`."""
-    from .gp import _safe_forms
     from .kernels import VolatilityKernel
     if not isinstance(covar_module, VolatilityKernel):
         raise TypeError("solver='linear' conditions on the volatility kernel's min structure; "
@@ -178,23 +160,16 @@ def _posterior_draw_linear(covar_module, full_x, full_vol, idx_cut, train_diffs,
     td = train_diffs.reshape(-1, N) if train_diffs.ndim > 1 else train_diffs.reshape(1, N)
     one_x = _rows_shared(x)
     G = 1 if one_x and _rows_shared(vol[:, :N]) and _rows_shared(td) else S              # grids: one for all samples, or one each
+    first = default_jitter(dt == f64, jitter)                       # by what came in: the forms are fp64 whatever the input
     if draw == "chain":
         xg = (x[0] if one_x else x[:G]).to(f64)
         U = ops.cumtrapz(torch.cat((vol[:G, :N], vol[:G, N - 1:N]), -1).to(f64), xg[..., :N + 1], square=True)[:, :N]   # [G,N]
-        out, _ = _safe_forms(U, td.to(f64).expand(S, N)[:G], _ladder_start(jitter, dt))
+        out, _ = _safe_forms(U, td.to(f64).expand(S, N)[:G], first)
         return _linear_draw(out[:, 0], out[:, 1], U[:, N - 1], None, test_mean_term, z, jitter, latent_mean, theta, dt, "chain",
                             (vol[:G, N - 1], vol[:, N:], xg[..., 1] - xg[..., 0]))
     V = ops.cumtrapz(vol.to(f64), (x[0] if one_x else x).to(f64), square=True)             # [S,N+T]
-    out, _ = _safe_forms(V[:G, :N], td.to(f64).expand(S, N)[:G], _ladder_start(jitter, dt))
+    out, _ = _safe_forms(V[:G, :N], td.to(f64).expand(S, N)[:G], first)
     return _linear_draw(out[:, 0], out[:, 1], V[:, N - 1], V[:, N:], test_mean_term, z, jitter, latent_mean, theta, dt)
-
-
-def _ladder_start(jitter, dt):
-    """The first rung of the train block's jitter ladder: the caller's, or `_safe_factor`'s default for the input dtype (the
-    linear route computes in fp64 whatever the input, so the default goes by what came in)."""
-    if jitter is not None:
-        return jitter
-    return 1e-8 if dt == torch.float64 else 1e-6
 
 
 def GeneratePrediction(train_x, train_y, test_x, pred_vol, model, latent_mean=None, theta=0.5, *, z=None, solver=None,

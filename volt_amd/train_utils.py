@@ -19,6 +19,7 @@ from . import gp
 from .gp import ExactMarginalLogLikelihood, GaussianLikelihood
 from .means import DEWMAMean, EWMAMean, LogLinearMean, MeanRevertingEMAMean, TEWMAMean
 from .models import VoltMagpie, VoltronGP
+from .safe import NumericalWarning, deferred_checks
 
 LR_DATA, LR_VOL, LR_GPCV = 0.1, 0.01, 0.01          # train_utils.py:238 / :81 / :43
 PRINT_EVERY = 50
@@ -109,7 +110,7 @@ def _run_iterations(iteration, optimizer, train_iters, printing, graph=False, sc
 
     Plain (graph=False, defer=False): eagerly, with the factorisation's ``info`` read back every step (a device
     synchronisation) so that gpytorch's jitter ladder can run at once.
-    defer=True: the read-back moves to one check per CHECK_EVERY iterations (gp.deferred_checks); when a check finds a
+    defer=True: the read-back moves to one check per CHECK_EVERY iterations (safe.deferred_checks); when a check finds a
     failed factorisation the parameters and the optimiser state return to the last clean snapshot and those
     iterations are replayed with the per-step check -- the trajectory is the plain loop's, without its host round trips.
     graph=True: after `warm` eager iterations ONE iteration (every HIP launch of the step, the torch glue, the Adam
@@ -137,7 +138,7 @@ def _run_iterations(iteration, optimizer, train_iters, printing, graph=False, sc
             one(i)
         return loss
 
-    with gp.deferred_checks(immediate=True) as chk:
+    with deferred_checks(immediate=True) as chk:
         # warm-up with the per-step check: creates the optimiser state, sizes the deferred accumulators
         side = torch.cuda.Stream() if graph else None
         if graph:
@@ -172,7 +173,7 @@ def _run_iterations(iteration, optimizer, train_iters, printing, graph=False, sc
             loss = static_loss
             if any_bad():
                 warnings.warn("a factorisation failed inside the captured loop: rerunning it eagerly with the jitter ladder",
-                              gp.NumericalWarning)
+                              NumericalWarning)
                 replay_eagerly(warm, train_iters)                     # (`one` rebinds `loss`: what is returned is the eager loop's)
             return loss
         i = warm

@@ -25,8 +25,9 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import gp, ops
-from .gp import Module, MultivariateNormal, NotPSDError, NanError, _BrownianPrior, _ScaledDense, _dense
+from . import ops
+from .gp import Module, MultivariateNormal, _BrownianPrior, _ScaledDense, _dense
+from .safe import NotPSDError, check_nan, deferred_checks
 
 PRIOR_JITTER = 1e-3        # LazyTensor.add_jitter() default on the inducing prior
 MIN_VARIANCE = 1e-6        # gpytorch.settings.min_variance for fp32
@@ -171,7 +172,7 @@ class _GPCVElbo(torch.autograd.Function):
             ops.gpcv_cv_step(K.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y, abc, gh_x, gh_w, **step_args)
         else:
             ops.gpcv_step(K.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y, gh_x, gh_w, **step_args)
-        if gp.deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
+        if deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
             _raise_step_failure("GPCV cv step" if cv else "GPCV step", ws.info, (K, m, Lq) + ((abc,) if cv else ()),
                                 "prior covariance K + 1e-3 I")
         ctx.n, ctx.w_kl, ctx.has_scale, ctx.want_dk, ctx.cv = n, w_kl, scale is not None, want_dk, cv
@@ -214,7 +215,7 @@ class _GPCVBmElbo(torch.autograd.Function):
         abc, jac = _cv_transform(raw_a, raw_b, raw_c, B) if cv else (None, None)
         ops.gpcv_bm_step(x, scale.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y, gh_x, gh_w, ws, abc=abc,
                          jitter=PRIOR_JITTER, min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
-        if gp.deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
+        if deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
             _raise_step_failure("GPCV step (linear prior)", ws.info, (scale, m, Lq) + ((abc,) if cv else ()),
                                 "prior covariance K + 1e-3 I")
         ctx.n, ctx.w_kl, ctx.cv = n, w_kl, cv
@@ -282,8 +283,7 @@ class MultitaskVariationalLatent(MultivariateNormal):
 def _raise_step_failure(what, info, tensors, which):
     if ops.info_internal(info):
         raise ops._lib.VoltHipError(f"{what}: internal error, info = {info.tolist()[:8]}")
-    if any(torch.isnan(t).any() for t in tensors):
-        raise NanError(f"{what}: NaN in the prior covariance or the variational parameters")
+    check_nan(tensors, f"{what}: NaN in the prior covariance or the variational parameters")
     raise NotPSDError(f"{what}: {which} is not positive definite")
 
 
@@ -305,7 +305,7 @@ class _GPCVMtElbo(torch.autograd.Function):
         ws = holder.mt_workspace(n, T, want_dk, M.device)
         ops.gpcv_mt_step(K.detach(), M, c, Lx, Lt, cf, rv, y, gh_x, gh_w, ws, want_dk=want_dk, jitter=PRIOR_JITTER,
                          min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
-        if gp.deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
+        if deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
             info = ws.info.cpu()
             # info[0]: K_x + jitter I (LAPACK-style or an internal code);  info[1]: a pivot of K_t;  info[2]: F not finite
             which = "prior covariance K_x + 1e-3 I" if int(info[0]) != 0 else "task covariance K_t"
