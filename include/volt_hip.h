@@ -25,7 +25,10 @@
  *     failed launch.  A matrix that is not positive definite is NOT an error return: LAPACK-style
  *     `info[b]` (0, or the 1-based index of the first non-positive / NaN pivot) is written to a
  *     caller buffer and the jitter-retry policy (gpytorch psd_safe_cholesky, used at
- *     voltron/rollout_utils.py:35,46) stays in the host wrapper.
+ *     voltron/rollout_utils.py:35,46) stays in the host wrapper.  Where info[b] > 0 the failed pivot's own L[i,i] is NaN,
+ *     and so are out[b,0] and (with VOLT_WANT_GRAD) all of alpha[b,:] of the fp32 step; the other matrices of the batch
+ *     are not touched by it, and nothing in the call waits out a hand-off time-out for it (tests/test_gpu_failed_pivot.py,
+ *     every dispatch path).
  *   - Matrices are row-major fp32 (the reference is fp32 throughout; voltron/means/EWMA.py:37 even
  *     forces FloatTensor) or fp64 where a *_f64 twin exists.  `ld` = leading dimension in
  *     elements, `bs` = batch stride in elements.

@@ -88,32 +88,45 @@ def test_one_launch_fp64_reports_a_matrix_that_is_not_pd(ops):
     assert float((f.L[[0, 1, 3]] - Lr).abs().amax() / Lr.abs().amax()) < 1e-10
 
 
-@pytest.mark.parametrize("kind", ["negative", "zero", "nan"])
+@pytest.mark.parametrize("kind", ["negative", "zero", "nan", "nan_off"])
 @pytest.mark.parametrize("at", [0, 31, 32, 63, 127, 128, 300])
 def test_fp64_first_bad_pivot_is_lapacks_at_every_lane_of_the_pivot_wave(ops, kind, at):
     """Round 6: the pivot phase no longer tests d > 0 pivot by pivot -- lane j keeps 1/sqrt(d_j) and the first lane whose value is
     not > 0 names the pivot (csrc/tiles64.h pivot_phase64).  A pivot that is <= 0 or NaN must be reported at LAPACK's index
     (torch.linalg.cholesky_ex) wherever it sits in a 32-pivot phase, with later pivots' NaNs not taking its place; both the
-    one launch and the launch-per-column path."""
+    one launch and the launch-per-column path.
+    An exactly zero pivot at any index: row `at` is zeroed below the diagonal, so row `at` of L is exactly 0 by induction and the
+    pivot is K[at,at] + s2 = 0 - 0 whatever the order of the sums (s2 = 1/16 and K[at,at] = -1/16: exact).  nan_off: a NaN below
+    the diagonal of row `at` (column at // 2) must surface as the pivot of ITS row -- the rows between never read it; row 0
+    has nothing below the diagonal, so there the NaN sits in row 1."""
     from volt_amd import _lib
     L = _lib.lib()
     B, n = 2, 384
-    K, r, s2 = _problem(ops, B, n)
+    K, r, s2 = _problem(ops, B, n, s2v=0.0625 if kind == "zero" else 0.05)
     K = K.clone()
     M = K[1] + torch.diag(s2[1].expand(n))
     if kind == "nan":
         M[at, at] = float("nan")
         want = at + 1
+    elif kind == "nan_off":
+        row = max(at, 1)
+        M[row, row // 2] = float("nan")
+        want = row + 1
     elif kind == "zero":
-        if at != 0: pytest.skip("an exactly zero pivot can only be placed at index 0 (elsewhere its sign is a matter of summation order)")
-        M[0, 0] = 0.0
-        want = 1
+        M[at, :at] = 0.0
+        M[at, at] = 0.0
+        want = at + 1
+        Mz = M.clone()
+        Mz[:at, at] = 0.0                                         # (LAPACK may read either triangle: symmetric for the cross-check)
+        assert int(torch.linalg.cholesky_ex(Mz).info) == want
     else:
         Lr = torch.linalg.cholesky(M)
         M[at, at] -= 1.5 * Lr[at, at] ** 2                        # the Schur complement's pivot `at` becomes -0.5 d
         want = int(torch.linalg.cholesky_ex(M).info)
         assert want == at + 1
     K[1] = M - torch.diag(s2[1].expand(n))
+    if kind == "zero":
+        assert float(K[1, at, at] + s2[1]) == 0.0 and float(K[1, at, :at].abs().sum()) == 0.0
     f = ops.potrf(K, s2)
     info = f.info.cpu().tolist()
     assert info[0] == 0 and info[1] == want, (info, want)

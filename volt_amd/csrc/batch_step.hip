@@ -210,7 +210,10 @@ __device__ __forceinline__ void batch_piece(const BatchArgs a, const int w, cons
     }
     if (kind == BK_TRTRI_DIAG) {
         const int i = d.y;
-        batch_wait<LOCAL>(reinterpret_cast<const int*>(Winv + ((int64_t)b * n + i) * TS * TS), 1, nullptr, 0, info_b);
+        // W_i's first word is not a progress word but a float's bits (diag_body): up means NON-ZERO.  As a signed `>= 1` it was
+        // never up for a matrix that is not positive definite, whose W_i[0][0] is a NaN of either sign -- every such tile of a
+        // failed series then sat out the 3 s of the hand-off time-out (tests/test_gpu_failed_pivot.py)
+        batch_wait<LOCAL, IsSet>(reinterpret_cast<const int*>(Winv + ((int64_t)b * n + i) * TS * TS), 0, nullptr, 0, info_b);
         trtri_diag_body(Winv, Y, Np, i, b, red, smem);
         publish_release<LOCAL>(tcol + i, 1);
         return;

@@ -168,13 +168,14 @@ __device__ __forceinline__ bool flag_wait_one_lane(const int* flag, int want = 0
 }
 // Thread 0 waits on up to two words, acquires once, reports a time-out; a barrier for the rest.  Two of them, because one
 // template would put a test for nullptr on a word that one of its callers never leaves out:
-//   batch_wait: the one-launch batched steps -- progress words (>=), either may be nullptr
+//   batch_wait: the one-launch batched steps -- progress words (>=), either may be nullptr; Cmp0 = IsSet with want0 = 0: the
+//               first word is a flag that carries a value (W_k's first word, a float's bits: tiles.h diag_body), up when non-zero
 //   small_wait: the short-series step -- flags that equal the number of the step, a growing pause; f1 may be nullptr
-template <bool LOCALP>
+template <bool LOCALP, class Cmp0 = AtLeast>
 __device__ __forceinline__ void batch_wait(const int* p0, int want0, const int* p1, int want1, int* info_b) {
     if (threadIdx.x == 0) {
         bool ok = true;
-        if (p0) ok = wait_word<AtLeast>(p0, want0);
+        if (p0) ok = wait_word<Cmp0>(p0, want0);
         if (p1) ok = wait_word<AtLeast>(p1, want1) && ok;
         acquire_unless_local<LOCALP>();
         if (!ok) report_timeout(info_b);
