@@ -338,6 +338,30 @@ int volt_gpcv_mt_step_f32(const float* K, int64_t ldk, float jitter, const float
                           float* grad_covar_factor, float* grad_raw_var, float* grad_K, int* info, void* workspace, int N,
                           int T, int ws_flags, void* stream);
 
+/* The same step for the copula-process ("cv") likelihood with ONE WARP PER TASK -- the call sites it replaces are
+ * multi_task_variational_gp.py:58-69 and the batched likelihood of volatility_likelihood.py:19-22,45-47 ([T,K] parameters):
+ *     scale_t(f) = sum_k a_tk log(1 + exp(b_tk f + c_tk)),  k < Kc,   y_nt | f ~ N(0, max(scale_t(f), min_scale))
+ * abc [T,3,Kc]: the TRANSFORMED a, b, c of every task (rows a, b, c; the constraints' chain rule is the caller's).
+ * Everything else is volt_gpcv_mt_step_f32's: the same arguments, out[0..15], gradients and info[0..2] with the same meaning
+ * (a NaN in abc shows as info[2] = 1), the same launches after the quadrature pass;
+ *     grad_abc [T,3,Kc] = dF/d(a,b,c) = w_ell d ell / d(a,b,c)      (the KL does not see the likelihood).
+ * The sums behind grad_abc are per-workgroup partials added in one fixed-order fp64 pass: no float atomics, bitwise
+ * repeatable.  1 <= Kc <= VOLT_GPCV_CV_K_MAX (defined with volt_gpcv_cv_step_f32 above).
+ * Argument codes (the negative return names the first offending argument, counted from 1 as for every entry):
+ *     1 K, 2 ldk, 4 M, 5 c, 6 Lx, 7 Lt, 8 covar_factor, 9 raw_var, 10 y, 11 abc, 12 Kc, 13 gh_x, 14 gh_w, 15 Q,
+ *     20 out, 21 grad_M, 22 grad_c, 23 grad_Lx, 24 grad_Lt, 25 grad_covar_factor, 26 grad_raw_var, (27 grad_K is nullable),
+ *     28 grad_abc, 29 info, 30 workspace (null or not 256-byte aligned), 31 N, 32 T.  No launch is made before all pass.
+ * workspace: volt_gpcv_mt_cv_workspace_bytes(N, T, want_dk, Kc) bytes (0 if T or Kc is out of range): the workspace of
+ * volt_gpcv_mt_step_f32 for the same (N, T, want_dk), unchanged, with the partials [T, ceil(N/16), 3 Kc] appended;
+ * initialised the same way. */
+size_t volt_gpcv_mt_cv_workspace_bytes(int N, int T, int want_dk, int Kc);
+int volt_gpcv_mt_cv_step_f32(const float* K, int64_t ldk, float jitter, const float* M, const float* c, const float* Lx,
+                             const float* Lt, const float* covar_factor, const float* raw_var, const float* y,
+                             const float* abc, int Kc, const float* gh_x, const float* gh_w, int Q, float min_var,
+                             float min_scale, float w_ell, float w_kl, float* out, float* grad_M, float* grad_c,
+                             float* grad_Lx, float* grad_Lt, float* grad_covar_factor, float* grad_raw_var, float* grad_K,
+                             float* grad_abc, int* info, void* workspace, int N, int T, int ws_flags, void* stream);
+
 /* ---- Kronecker multi-task vol forecaster  (MultitaskBMGP, voltron/models/BMGP.py:30-56: botorch KroneckerMultiTaskGP with
  * MultitaskKernel(BMKernel(), T) and MultitaskGaussianLikelihood(T); built by the batched constructors VoltMagpie.py:51-55,
  * VoltronGP.py:46-50, Volt.py:67-71, trained through ExactMarginalLogLikelihood + loss.backward()).

@@ -64,6 +64,9 @@ _SIGS = {
     "volt_gpcv_mt_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "volt_gpcv_mt_step_f32": (C.c_int, [_ptr, _i64, _f32] + [_ptr] * 9 + [_i32, _f32, _f32, _f32, _f32] + [_ptr] * 10
                               + [_i32, _i32, _i32, _ptr]),
+    "volt_gpcv_mt_cv_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "volt_gpcv_mt_cv_step_f32": (C.c_int, [_ptr, _i64, _f32] + [_ptr] * 8 + [_i32, _ptr, _ptr, _i32, _f32, _f32, _f32, _f32]
+                                 + [_ptr] * 11 + [_i32, _i32, _i32, _ptr]),
     "volt_syev_small_f64": (C.c_int, [_ptr, _i64, _ptr, _ptr, _ptr, _i32, _i32, _ptr]),
     "volt_kron_state_bytes": (_sz, [_i32]),
     "volt_kron_prologue_f32": (C.c_int, [_ptr] * 7 + [_i64] + [_ptr] * 4 + [_i32, _i32, _ptr]),

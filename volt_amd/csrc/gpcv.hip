@@ -268,6 +268,12 @@ __global__ __launch_bounds__(256) void cv_abc_reduce_kernel(const float* __restr
     }
 }
 
+int launch_cv_abc_reduce(const float* part, int nblk, int n3, float we, float* grad_abc, int B, hipStream_t s) {
+    hipLaunchKernelGGL(cv_abc_reduce_kernel, dim3(B), dim3(256), 0, s, part, nblk, n3, we, grad_abc);
+    VOLT_LAUNCH_CHECK();
+    return 0;
+}
+
 // Gradient of F = we ell - wk KL:
 //   dF/dLq[i,j] = we 2 gv_i Lq_ij - wk (G_ij - [i == j] / Lq_ii)   (j <= i, zero above),
 //   dF/dm = we gm - wk beta,  dF/dmu = wk beta.

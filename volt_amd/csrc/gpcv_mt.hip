@@ -10,6 +10,8 @@
 // logdet, tr K^-1), T' = Lx' L^-T and G = K^-1 Lx on the structured GEMM (gpcv.hip).  The T right-hand sides ride on the
 // same MFMA core as one 128-row tile: V = R' L^-T, A' = V Y'.  New here: the N x T quadrature pass, the deterministic
 // partial sums of R'A / A'A, ONE fp64 workgroup for everything T x T, and the gradient kernels.
+// The copula-process ("cv") likelihood with one warp per task (volt_gpcv_mt_cv_step_f32) is the same launch sequence with
+// the quadrature pass of gpcv_mt_cv.hip in place of mt_gh_kernel.
 #include "common.h"
 #include "gpcv_shared.h"
 #include "../../include/volt_hip.h"
@@ -17,10 +19,8 @@
 
 namespace volt {
 
-constexpr int MT_MAX = 64;            // largest T: the task algebra is LDS resident, the T rows fit half a 128-row tile
-constexpr int MLD = MT_MAX + 1;       // LDS row stride in doubles (odd: column walks spread over the banks)
+// (MT_MAX, MLD and GH_ROWS are in gpcv_shared.h: the "cv" quadrature pass of gpcv_mt_cv.hip has the same layout)
 constexpr int MNT = 1024;             // threads of the task-algebra workgroup
-constexpr int GH_ROWS = 16;           // rows n per quadrature workgroup
 constexpr int RT_CH = 64;             // columns n staged per pass of the partial sums of R'A / A'A
 constexpr int RT_PASSES = 1;          // passes per workgroup: RT_CH * RT_PASSES columns per partial
 
@@ -467,13 +467,14 @@ __global__ __launch_bounds__(256) void mt_dk_kernel(const float* __restrict__ P1
 
 struct MtWs {
     float *LxT, *W, *Tt, *G, *P1, *P2, *Bm, *Rt, *V, *At, *mllout, *beta, *vx, *logd, *rowred, *gm, *colpart, *ellpart,
-        *part, *frobT, *frobG, *kti, *cinv, *tsc;
+        *part, *frobT, *frobG, *kti, *cinv, *tsc, *cvpart;
     void* mll;
     int ngh, nch;
     size_t bytes;
 };
 
-static MtWs carve_mt(void* base, int N, int T, int want_dk) {
+// Kc > 0: the "cv" step's layout, the "exp" one with the parameter partials [T, ngh, 3 Kc] appended.
+static MtWs carve_mt(void* base, int N, int T, int want_dk, int Kc = 0) {
     const size_t Np = (size_t)volt_padded_n(N), n = Np / TS;
     Carver c{base};
     MtWs w;
@@ -505,8 +506,74 @@ static MtWs carve_mt(void* base, int N, int T, int want_dk) {
     w.kti = c.take<float>((size_t)T * T);
     w.cinv = c.take<float>((size_t)T * T);
     w.tsc = c.take<float>(8);
+    w.cvpart = c.take<float>(Kc > 0 ? (size_t)T * w.ngh * 3 * Kc : 0);
     w.bytes = c.off;
     return w;
+}
+
+// Both multi-task steps: abc == nullptr is the "exp" likelihood (volt_gpcv_mt_step_f32, whose launch sequence this is),
+// otherwise the "cv" one -- only the quadrature pass differs.
+static int mt_step_impl(const float* K, int64_t ldk, float jitter, const float* M, const float* c, const float* Lx,
+                        const float* Lt, const float* covar_factor, const float* raw_var, const float* y, const float* abc,
+                        int Kc, const float* gh_x, const float* gh_w, int Q, float min_var, float min_scale, float w_ell,
+                        float w_kl, float* out, float* grad_M, float* grad_c, float* grad_Lx, float* grad_Lt,
+                        float* grad_covar_factor, float* grad_raw_var, float* grad_K, float* grad_abc, int* info,
+                        void* workspace, int N, int T, int ws_flags, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const int Np = volt_padded_n(N), n = Np / TS;
+    const int64_t mat = (int64_t)Np * Np;
+    const int want_dk = grad_K != nullptr;
+    MtWs w = carve_mt(workspace, N, T, want_dk, abc ? Kc : 0);
+    int rc;
+
+    // what does not depend on the factorisation goes first: R', the row sums of squares, the quadrature pass, Lx'
+    hipLaunchKernelGGL(mt_resid_kernel, dim3((Np + 255) / 256, TS), dim3(256), 0, s, M, c, w.Rt, N, Np, T);
+    hipLaunchKernelGGL(mt_rowsq_kernel, dim3((N + 3) / 4), dim3(256), 0, s, Lx, w.vx, w.logd, N);
+    if (abc) {
+        if ((rc = launch_mt_cv_pass(M, Lt, y, w.vx, abc, Kc, gh_x, gh_w, Q, min_var, min_scale, w_ell, w.gm, w.rowred, w.colpart,
+                                    w.ellpart, w.cvpart, grad_abc, N, T, s)))        // gpcv_mt_cv.hip
+            return rc;
+    } else {
+        hipLaunchKernelGGL(mt_gh_kernel, dim3(w.ngh), dim3(256), 0, s, M, Lt, y, w.vx, gh_x, gh_w, Q, min_var, min_scale, w.gm,
+                           w.rowred, w.colpart, w.ellpart, N, T);
+    }
+    if ((rc = launch_transpose_tri(Lx, N, 0, w.LxT, N, Np, 1, 1, s))) return rc;
+    // K_x + jitter I = L L',  Y = L^-T,  logdet K, tr K^-1: the exact-GP step at B = 1, ONCE for all T series
+    // (its own right-hand side is row 0 of R'; the T solves run on the GEMM below)
+    rc = volt_mll_step_f32(K, ldk, 0, w.Rt, nullptr, jitter, w.mllout, w.beta, info, w.mll, 1, N,
+                           VOLT_WANT_GRAD | (ws_flags & VOLT_WS_INITIALISED), stream);
+    if (rc) return rc;
+    const float* Y = volt_internal_mll_y(workspace, 1, N);
+    if ((rc = launch_transpose_tri(Y, Np, mat, w.W, Np, Np, 2, 1, s))) return rc;
+    // T' = Lx' L^-T (upper tiles; |T'|_F^2 = tau_x),  G = K^-1 Lx = Y T
+    GemmArgs g1{w.LxT, w.W, w.Tt, Np, mat, Np, mat, Np, mat, n, n, n, 2, 1, 2, 1.f, 0.f, w.frobT};
+    if ((rc = launch_gemm(g1, 1, s))) return rc;
+    GemmArgs g2{Y, w.Tt, w.G, Np, mat, Np, mat, Np, mat, n, n, n, 2, 2, 0, 1.f, 0.f, w.frobG};
+    if ((rc = launch_gemm(g2, 1, s))) return rc;
+    // V = R' L^-T: rows of R' against rows of W = L^-1 (lower);  A' = V Y': rows of V against rows of Y (upper)
+    GemmArgs g3{w.Rt, w.W, w.V, Np, 0, Np, 0, Np, 0, 1, n, n, 0, 1, 0, 1.f, 0.f, nullptr};
+    if ((rc = launch_gemm(g3, 1, s))) return rc;
+    GemmArgs g4{w.V, Y, w.At, Np, 0, Np, 0, Np, 0, 1, n, n, 0, 2, 0, 1.f, 0.f, nullptr};
+    if ((rc = launch_gemm(g4, 1, s))) return rc;
+    hipLaunchKernelGGL(mt_rta_kernel, dim3(w.nch), dim3(256), 0, s, w.Rt, w.At, w.part, N, Np, T);
+    MtTaskArgs ta{covar_factor, raw_var, Lt, w.part, w.colpart, w.ellpart, w.logd, w.frobT, w.frobG, w.mllout,
+                  out, grad_c, grad_Lt, grad_covar_factor, grad_raw_var, w.kti, w.cinv, w.tsc,
+                  info + 1, w.nch, w.ngh, n * n, N, T, jitter, w_ell, w_kl};
+    hipLaunchKernelGGL(mt_task_kernel, dim3(1), dim3(T <= 16 ? 256 : MNT), 0, s, ta);
+    hipLaunchKernelGGL(mt_grad_kernel, dim3((N + 255) / 256, N > T ? N : T), dim3(256), 0, s, Lx, w.G, w.rowred, w.gm, w.At, w.kti,
+                       w.tsc, grad_Lx, grad_M, N, Np, T, w_ell, w_kl);
+    if (want_dk) {
+        hipLaunchKernelGGL(mt_bmat_kernel, dim3(Np * TS / 256), dim3(256), 0, s, w.At, w.cinv, w.Bm, N, Np, T);
+        GemmArgs g5{Y, Y, w.P1, Np, mat, Np, mat, Np, mat, n, n, n, 2, 2, 0, (float)T, 0.f, nullptr};        // T K^-1 = T Y Y'
+        if ((rc = launch_gemm(g5, 1, s))) return rc;
+        GemmArgs g6{w.Bm, w.Bm, w.P1, TS, 0, TS, 0, Np, mat, n, n, 1, 0, 0, 0, -1.f, 1.f, nullptr};        // - Bm Bm'
+        if ((rc = launch_gemm(g6, 1, s))) return rc;
+        GemmArgs g7{w.G, w.G, w.P2, Np, mat, Np, mat, Np, mat, n, n, n, 0, 0, 0, 1.f, 0.f, nullptr};       // G G'
+        if ((rc = launch_gemm(g7, 1, s))) return rc;
+        hipLaunchKernelGGL(mt_dk_kernel, dim3((N + 255) / 256, N), dim3(256), 0, s, w.P1, w.P2, w.tsc, grad_K, N, Np, w_kl);
+    }
+    VOLT_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // namespace volt
@@ -549,55 +616,51 @@ int volt_gpcv_mt_step_f32(const float* K, int64_t ldk, float jitter, const float
     if (!workspace || ((uintptr_t)workspace & 255)) return -27;
     if (N < 1) return -28;
     if (T < 1 || T > MT_MAX) return -29;
-    hipStream_t s = (hipStream_t)stream;
-    const int Np = volt_padded_n(N), n = Np / TS;
-    const int64_t mat = (int64_t)Np * Np;
-    const int want_dk = grad_K != nullptr;
-    MtWs w = carve_mt(workspace, N, T, want_dk);
-    int rc;
+    return mt_step_impl(K, ldk, jitter, M, c, Lx, Lt, covar_factor, raw_var, y, nullptr, 0, gh_x, gh_w, Q, min_var, min_scale,
+                        w_ell, w_kl, out, grad_M, grad_c, grad_Lx, grad_Lt, grad_covar_factor, grad_raw_var, grad_K, nullptr,
+                        info, workspace, N, T, ws_flags, stream);
+}
 
-    // what does not depend on the factorisation goes first: R', the row sums of squares, the quadrature pass, Lx'
-    hipLaunchKernelGGL(mt_resid_kernel, dim3((Np + 255) / 256, TS), dim3(256), 0, s, M, c, w.Rt, N, Np, T);
-    hipLaunchKernelGGL(mt_rowsq_kernel, dim3((N + 3) / 4), dim3(256), 0, s, Lx, w.vx, w.logd, N);
-    hipLaunchKernelGGL(mt_gh_kernel, dim3(w.ngh), dim3(256), 0, s, M, Lt, y, w.vx, gh_x, gh_w, Q, min_var, min_scale, w.gm,
-                       w.rowred, w.colpart, w.ellpart, N, T);
-    if ((rc = launch_transpose_tri(Lx, N, 0, w.LxT, N, Np, 1, 1, s))) return rc;
-    // K_x + jitter I = L L',  Y = L^-T,  logdet K, tr K^-1: the exact-GP step at B = 1, ONCE for all T series
-    // (its own right-hand side is row 0 of R'; the T solves run on the GEMM below)
-    rc = volt_mll_step_f32(K, ldk, 0, w.Rt, nullptr, jitter, w.mllout, w.beta, info, w.mll, 1, N,
-                           VOLT_WANT_GRAD | (ws_flags & VOLT_WS_INITIALISED), stream);
-    if (rc) return rc;
-    const float* Y = volt_internal_mll_y(workspace, 1, N);
-    if ((rc = launch_transpose_tri(Y, Np, mat, w.W, Np, Np, 2, 1, s))) return rc;
-    // T' = Lx' L^-T (upper tiles; |T'|_F^2 = tau_x),  G = K^-1 Lx = Y T
-    GemmArgs g1{w.LxT, w.W, w.Tt, Np, mat, Np, mat, Np, mat, n, n, n, 2, 1, 2, 1.f, 0.f, w.frobT};
-    if ((rc = launch_gemm(g1, 1, s))) return rc;
-    GemmArgs g2{Y, w.Tt, w.G, Np, mat, Np, mat, Np, mat, n, n, n, 2, 2, 0, 1.f, 0.f, w.frobG};
-    if ((rc = launch_gemm(g2, 1, s))) return rc;
-    // V = R' L^-T: rows of R' against rows of W = L^-1 (lower);  A' = V Y': rows of V against rows of Y (upper)
-    GemmArgs g3{w.Rt, w.W, w.V, Np, 0, Np, 0, Np, 0, 1, n, n, 0, 1, 0, 1.f, 0.f, nullptr};
-    if ((rc = launch_gemm(g3, 1, s))) return rc;
-    GemmArgs g4{w.V, Y, w.At, Np, 0, Np, 0, Np, 0, 1, n, n, 0, 2, 0, 1.f, 0.f, nullptr};
-    if ((rc = launch_gemm(g4, 1, s))) return rc;
-    hipLaunchKernelGGL(mt_rta_kernel, dim3(w.nch), dim3(256), 0, s, w.Rt, w.At, w.part, N, Np, T);
-    MtTaskArgs ta{covar_factor, raw_var, Lt, w.part, w.colpart, w.ellpart, w.logd, w.frobT, w.frobG, w.mllout,
-                  out, grad_c, grad_Lt, grad_covar_factor, grad_raw_var, w.kti, w.cinv, w.tsc,
-                  info + 1, w.nch, w.ngh, n * n, N, T, jitter, w_ell, w_kl};
-    hipLaunchKernelGGL(mt_task_kernel, dim3(1), dim3(T <= 16 ? 256 : MNT), 0, s, ta);
-    hipLaunchKernelGGL(mt_grad_kernel, dim3((N + 255) / 256, N > T ? N : T), dim3(256), 0, s, Lx, w.G, w.rowred, w.gm, w.At, w.kti,
-                       w.tsc, grad_Lx, grad_M, N, Np, T, w_ell, w_kl);
-    if (want_dk) {
-        hipLaunchKernelGGL(mt_bmat_kernel, dim3(Np * TS / 256), dim3(256), 0, s, w.At, w.cinv, w.Bm, N, Np, T);
-        GemmArgs g5{Y, Y, w.P1, Np, mat, Np, mat, Np, mat, n, n, n, 2, 2, 0, (float)T, 0.f, nullptr};        // T K^-1 = T Y Y'
-        if ((rc = launch_gemm(g5, 1, s))) return rc;
-        GemmArgs g6{w.Bm, w.Bm, w.P1, TS, 0, TS, 0, Np, mat, n, n, 1, 0, 0, 0, -1.f, 1.f, nullptr};        // - Bm Bm'
-        if ((rc = launch_gemm(g6, 1, s))) return rc;
-        GemmArgs g7{w.G, w.G, w.P2, Np, mat, Np, mat, Np, mat, n, n, n, 0, 0, 0, 1.f, 0.f, nullptr};       // G G'
-        if ((rc = launch_gemm(g7, 1, s))) return rc;
-        hipLaunchKernelGGL(mt_dk_kernel, dim3((N + 255) / 256, N), dim3(256), 0, s, w.P1, w.P2, w.tsc, grad_K, N, Np, w_kl);
-    }
-    VOLT_LAUNCH_CHECK();
-    return 0;
+size_t volt_gpcv_mt_cv_workspace_bytes(int N, int T, int want_dk, int Kc) {
+    if (N <= 0 || T < 1 || T > MT_MAX || Kc < 1 || Kc > VOLT_GPCV_CV_K_MAX) return 0;
+    return carve_mt(nullptr, N, T, want_dk, Kc).bytes;
+}
+
+int volt_gpcv_mt_cv_step_f32(const float* K, int64_t ldk, float jitter, const float* M, const float* c, const float* Lx,
+                             const float* Lt, const float* covar_factor, const float* raw_var, const float* y,
+                             const float* abc, int Kc, const float* gh_x, const float* gh_w, int Q, float min_var,
+                             float min_scale, float w_ell, float w_kl, float* out, float* grad_M, float* grad_c,
+                             float* grad_Lx, float* grad_Lt, float* grad_covar_factor, float* grad_raw_var, float* grad_K,
+                             float* grad_abc, int* info, void* workspace, int N, int T, int ws_flags, void* stream) {
+    if (!K) return -1;
+    if (ldk < N) return -2;
+    if (!M) return -4;
+    if (!c) return -5;
+    if (!Lx) return -6;
+    if (!Lt) return -7;
+    if (!covar_factor) return -8;
+    if (!raw_var) return -9;
+    if (!y) return -10;
+    if (!abc) return -11;
+    if (Kc < 1 || Kc > VOLT_GPCV_CV_K_MAX) return -12;
+    if (!gh_x) return -13;
+    if (!gh_w) return -14;
+    if (Q < 1 || Q > 1024) return -15;
+    if (!out) return -20;
+    if (!grad_M) return -21;
+    if (!grad_c) return -22;
+    if (!grad_Lx) return -23;
+    if (!grad_Lt) return -24;
+    if (!grad_covar_factor) return -25;
+    if (!grad_raw_var) return -26;
+    if (!grad_abc) return -28;
+    if (!info) return -29;
+    if (!workspace || ((uintptr_t)workspace & 255)) return -30;
+    if (N < 1) return -31;
+    if (T < 1 || T > MT_MAX) return -32;
+    return mt_step_impl(K, ldk, jitter, M, c, Lx, Lt, covar_factor, raw_var, y, abc, Kc, gh_x, gh_w, Q, min_var, min_scale, w_ell,
+                        w_kl, out, grad_M, grad_c, grad_Lx, grad_Lt, grad_covar_factor, grad_raw_var, grad_K, grad_abc, info,
+                        workspace, N, T, ws_flags, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
-// What the two variational steps (gpcv.hip: one series per batch entry; gpcv_mt.hip: T series behind ONE prior) share:
-// the structured NT GEMM on the 128x128 MFMA core and the triangle-keeping transpose.  The kernels live in gpcv.hip;
-// these are their host-side launchers.
+// What the two variational steps (gpcv.hip: one series per batch entry; gpcv_mt.hip + gpcv_mt_cv.hip: T series behind ONE
+// prior) share:
+// the structured NT GEMM on the 128x128 MFMA core, the triangle-keeping transpose and the fixed-order reduction of the
+// "cv" likelihood's parameter sums.  The kernels live in gpcv.hip; these are their host-side launchers.
 #pragma once
 #include "common.h"
 #include "host.h"
@@ -25,5 +26,19 @@ int launch_gemm(const GemmArgs& g, int B, hipStream_t s);
 // keep = 1: src lower (col <= row), keep = 2: src upper (col >= row), 0: everything.
 int launch_transpose_tri(const float* src, int64_t lds, int64_t bss, float* dst, int N, int Np, int keep, int B,
                          hipStream_t s);
+// grad_abc[b][j] = we * sum_k part[b][k][j], k < nblk, j < n3 = 3 Kc (cv_abc_reduce_kernel of gpcv.hip: fp64, fixed order).
+int launch_cv_abc_reduce(const float* part, int nblk, int n3, float we, float* grad_abc, int B, hipStream_t s);
+
+// ---- the multi-task step's N x T quadrature pass: mt_gh_kernel (gpcv_mt.hip, "exp") and mt_gh_cv_kernel (gpcv_mt_cv.hip)
+constexpr int MT_MAX = 64;            // largest T: the task algebra is LDS resident, the T rows fit half a 128-row tile
+constexpr int MLD = MT_MAX + 1;       // LDS row stride in doubles (odd: column walks spread over the banks)
+constexpr int GH_ROWS = 16;           // rows n per quadrature workgroup
+// The "cv" pass for Kc warp terms per task (abc [T,3,Kc]) on the multi-task workspace's buffers -- what mt_gh_kernel writes
+// (gm, rowred, colpart, ellpart) plus the parameter partials cvpart [T, ceil(N / GH_ROWS), 3 Kc] -- and their fixed-order
+// reduction into grad_abc [T,3,Kc] = w_ell d ell / d(a,b,c).
+int launch_mt_cv_pass(const float* M, const float* Lt, const float* y, const float* vx, const float* abc, int Kc,
+                      const float* gh_x, const float* gh_w, int Q, float min_var, float min_scale, float w_ell, float* gm,
+                      float* rowred, float* colpart, float* ellpart, float* cvpart, float* grad_abc, int N, int T,
+                      hipStream_t s);
 
 }  // namespace volt

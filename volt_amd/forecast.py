@@ -24,7 +24,7 @@ from . import rollout_engine
 from .distributed import shard_range
 from .rollout_utils import _linear_draw, _posterior_draw, _resolve_draw, _resolve_solver
 from .safe import NanError, NotPSDError, NumericalWarning, _safe_draw, _safe_forms
-from .train_utils import LearnGPCV, TrainVoltMagpieBatch, TrainVolModelBatch, TrainVolModelMultitask
+from .train_utils import LearnGPCV, LearnGPCVMultitask, TrainVoltMagpieBatch, TrainVolModelBatch, TrainVolModelMultitask
 
 _MODES = {"ewma": 0, "dewma": 1, "tewma": 2}
 _STANDARD = ("constant", "loglinear", "linear")
@@ -111,16 +111,39 @@ def _check_vol_posterior(vol_posterior, vol_solver):
     check_options("vol_posterior", vol_solver, vol_posterior)
 
 
+GPCV_OPTIONS = ("param", "K", "train_likelihood")      # what gpcv_options may carry to the GPCV fit
+
+
+def _check_gpcv_options(gpcv_options, multitask_gpcv, gpcv_solver, nseries, vol_fn):
+    """Before any window trains.  Returns the options as a dict."""
+    opts = dict(gpcv_options or {})
+    unknown = sorted(set(opts) - set(GPCV_OPTIONS))
+    if unknown:
+        raise ValueError(f"gpcv_options: unknown keys {unknown}; it takes {list(GPCV_OPTIONS)}")
+    if multitask_gpcv and vol_fn is None:
+        from . import ops
+        if gpcv_solver == "linear":
+            raise ValueError('multitask_gpcv=True runs the dense multi-task step: it does not combine with gpcv_solver="linear" '
+                             "(the multi-task model has no lazy Brownian prior)")
+        if nseries > ops.GPCV_MT_T_MAX:
+            raise ValueError(f"multitask_gpcv=True takes at most {ops.GPCV_MT_T_MAX} series per rank (got {nseries})")
+    return opts
+
+
 def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator,
                  graph, vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False,
-                 predict_solver="dense", vol_posterior="solve", predict_draw="factor", debug=None):
+                 predict_solver="dense", vol_posterior="solve", predict_draw="factor", multitask_gpcv=False,
+                 gpcv_options=None, debug=None):
     """One window for the series in train_y [b, ntrain] (prices): GPCV -> data model -> vol forecasters -> rollouts,
     every stage for all b series at once.  Returns samples [b, S, H] on the device."""
     dev = train_y.device
     b, H = train_y.shape[0], test_x.numel()
     predict_solver = _resolve_solver(predict_solver)
-    if vol_fn is None:
-        vol = LearnGPCV(train_x, train_y, train_iters=gpcv_iters, graph=graph, solver=gpcv_solver)   # all series at once
+    if vol_fn is None and multitask_gpcv:                # ONE joint model over the rank's series: the prior is factored once
+        vol = LearnGPCVMultitask(train_x, train_y, train_iters=gpcv_iters, graph=graph, **(gpcv_options or {}))
+    elif vol_fn is None:
+        vol = LearnGPCV(train_x, train_y, train_iters=gpcv_iters, graph=graph, solver=gpcv_solver,
+                        **(gpcv_options or {}))                                          # all series at once
     else:
         vol = vol_fn(train_x, train_y)                                                   # [b, ntrain-1]
     # the shards are independent series and the ranks may run different numbers of fits (a failed window is redone series
@@ -167,7 +190,8 @@ def _window_summary(samples, series, last_day, spec):
 def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample, mean, k, gpcv_iters, vol_iters,
                       data_iters, theta, vol_fn, generator, save, path_fn, debug=None, graph=None, summary=None,
                       keep_samples=True, vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False,
-                      predict_solver="dense", vol_posterior="solve", predict_draw="factor"):
+                      predict_solver="dense", vol_posterior="solve", predict_draw="factor", multitask_gpcv=False,
+                      gpcv_options=None):
     """One batched pass per window (series [B,T] prices; the window ending at index e trains on series[:, e-ntrain:e]).
     A numerical failure anywhere in the batched pass (NotPSDError / NanError after the jitter ladders) must not take the
     other series down with it: the window is then redone one series at a time, and a series that still fails gets NaN
@@ -181,10 +205,11 @@ def _forecast_windows(names, series, end_idxs, ntrain, train_x, test_x, nsample,
     if not keep_samples and summary is None:
         raise ValueError("keep_samples=False leaves nothing to return without summary=")
     B = series.shape[0]
+    gpcv_options = _check_gpcv_options(gpcv_options, multitask_gpcv, gpcv_solver, B, vol_fn)
     summaries = []
     H = test_x.numel()
     args = (nsample, mean, k, gpcv_iters, vol_iters, data_iters, theta, vol_fn, generator, graph, vol_solver, gpcv_solver,
-            data_solver, multitask_vol, predict_solver, vol_posterior, predict_draw)
+            data_solver, multitask_vol, predict_solver, vol_posterior, predict_draw, multitask_gpcv, gpcv_options)
     last = None
     for last_day in end_idxs:
         train_y = series[:, last_day - ntrain:last_day].float()                          # [B, ntrain] prices
@@ -222,7 +247,7 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
                                   vol_iters=None, par_dir="./saved-outputs/", generator=None, debug=None, graph=None,
                                   summary=None, keep_samples=True, vol_solver="dense", gpcv_solver="dense",
                                   data_solver="dense", multitask_vol=False, predict_solver="dense",
-                                  vol_posterior="solve", predict_draw="factor"):
+                                  vol_posterior="solve", predict_draw="factor", multitask_gpcv=False, gpcv_options=None):
     """closes [B, T] prices for B tickers on a common calendar (device tensor).  Same window schedule,
     model name and file layout as GenerateStockPredictions (GenerateMultiMeanPreds.py:69-83,128); ``mean`` in
     ewma / dewma / tewma takes the Rollouts branch (:110-112), constant / loglinear / linear the "VOLT + standard
@@ -252,7 +277,12 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
     H x H covariance (ops.markov_draw).
     ``predict_draw="chain"`` (with ``predict_solver="linear"``): the joint draw of the standard-mean branch from ONE ops.vk_draw
     launch for all tickers, with no H x H block per path; the Rollouts branch has its own recursion and is not
-    changed by it; the default "factor" changes nothing."""
+    changed by it; the default "factor" changes nothing.
+    ``multitask_gpcv=True``: the window's vol paths come from ONE LearnGPCVMultitask call over the rank's series (the joint
+    Kronecker variational GP: one prior factorisation for all of them, T <= 64 per rank) instead of the batched single-task
+    LearnGPCV; not with ``gpcv_solver="linear"``.  The series-by-series redo after a failed window then runs T = 1.
+    ``gpcv_options``: a dict with keys out of ``param``, ``K``, ``train_likelihood``, forwarded to whichever GPCV fit runs
+    (FitGPCV / FitGPCVMultitask); unknown keys raise.  Both are ignored with a ``vol_fn``; the defaults change nothing."""
     _check_vol_posterior(vol_posterior, vol_solver)
     _resolve_draw(predict_draw, predict_solver)
     if mean not in _MODES and mean not in _STANDARD:
@@ -277,20 +307,21 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
     return _forecast_windows(tickers, closes, end_idxs.tolist(), ntrain, train_x, test_x, nsample, mean, k,
                              train_iters, vol_iters, train_iters, None, vol_fn, generator, save, path_fn, debug, graph,
                              summary, keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol, predict_solver,
-                             vol_posterior, predict_draw)
+                             vol_posterior, predict_draw, multitask_gpcv, gpcv_options)
 
 
 def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=400, n_test_times=10, nsample=1000, k=400,
                                  theta=0.01, gpcv_iters=200, vol_iters=500, data_iters=0, save=False, vol_fn=None,
                                  par_dir="./saved-outputs/", generator=None, graph=None, summary=None, keep_samples=True,
                                  vol_solver="dense", gpcv_solver="dense", data_solver="dense", multitask_vol=False,
-                                 predict_solver="dense", vol_posterior="solve", predict_draw="factor"):
+                                 predict_solver="dense", vol_posterior="solve", predict_draw="factor", multitask_gpcv=False,
+                                 gpcv_options=None):
     """The ``--kernel volt --mean ewma`` branch of experiments/weather/GPGenerator.py:20-112 for B stations at once:
     data [B,T] wind speeds (missing = -99 -> 0, then +1 as at :47,55), dt = 1/365 (:38-41), the schedule of test
     windows of :33-34, GPCV 200 / vol model 500 / data model 0 iterations (:64-67,89-92), EWMA(k=400) mean and
     mean-reverting rollouts with theta = 0.01 (:96-102), files ``stn<idx>/volt_ema<k>_theta<theta>_<last_day>.pt``
     (:103-106).  Stations shard across ranks like tickers.  Returns the last window's samples [B_local,S,H] (CPU).
-    ``summary`` / ``keep_samples`` / ``vol_solver`` / ``gpcv_solver`` / ``data_solver`` / ``multitask_vol`` / ``predict_solver`` / ``vol_posterior`` / ``predict_draw``: as for GenerateStockPredictionsBatch (the truth is the shifted series,
+    ``summary`` / ``keep_samples`` / ``vol_solver`` / ``gpcv_solver`` / ``data_solver`` / ``multitask_vol`` / ``predict_solver`` / ``vol_posterior`` / ``predict_draw`` / ``multitask_gpcv`` / ``gpcv_options``: as for GenerateStockPredictionsBatch (the truth is the shifted series,
     data + 1)."""
     _check_vol_posterior(vol_posterior, vol_solver)
     _resolve_draw(predict_draw, predict_solver)
@@ -310,4 +341,4 @@ def GenerateWindPredictionsBatch(stations, data, forecast_horizon=100, ntrain=40
     return _forecast_windows(stations, data, end_idxs, ntrain, train_x, test_x, nsample, "ewma", k, gpcv_iters,
                              vol_iters, data_iters, theta, vol_fn, generator, save, path_fn, None, graph, summary,
                              keep_samples, vol_solver, gpcv_solver, data_solver, multitask_vol, predict_solver, vol_posterior,
-                             predict_draw)
+                             predict_draw, multitask_gpcv, gpcv_options)

@@ -1,16 +1,20 @@
 """MultitaskVariationalGP, voltron/models/multi_task_variational_gp.py:11-146 -- the joint GPCV model of T series that
 share one time grid: q(F) = N(M, S_x (x) S_t) against the Kronecker prior N(mu, K_x (x) K_t), inducing points fixed at
 the inputs.  Parameter names, shapes, registration order and start values are the reference's; the ELBO and all of its
-gradients come from ONE HIP step (volt_gpcv_mt_step_f32) that factors K_x once for all T series.
+gradients come from ONE HIP step that factors K_x once for all T series: volt_gpcv_mt_step_f32 for the "exp" likelihood,
+volt_gpcv_mt_cv_step_f32 for the copula-process ("cv") one with one warp per task (a likelihood built with
+``batch_shape=[num_tasks]``).
 
 Stated differences from the reference file (README, quirk table):
 * ``model(x)`` is defined at the inducing points only, where the reference's three-term covariance (:113-146) collapses
   to S_x (x) S_t and its mean to M (K_uu^-1 K_ux = I); anything else raises NotImplementedError.
 * the prior's data block carries the single-task path's jitter 1e-3 (variational.PRIOR_JITTER); the reference adds none
   (:95-111) and leans on gpytorch's jitter ladder when x[0] = 0 makes K_x[0,0] = 0.
-* only param="exp", rank=1, fp32.
+* rank=1, fp32; param="cv" with one warp per task only (an unbatched "cv" likelihood, one warp shared by all tasks, has no
+  accelerated ELBO), and its start-up values for K = 1 only, as for SingleTaskVariationalGP.
 The reference has no trainer for this class; train_utils.FitGPCVMultitask is LearnGPCV's loop over it.  gpytorch is not
-installed here, so none of this is pinned by executing the reference's class."""
+installed here; both branches of ``initialize_variational_parameters`` are pinned to the reference's own code, executed
+over stand-ins, by tests/golden/mt_gpcv_cv.npz."""
 import torch
 from torch import nn
 
@@ -81,12 +85,26 @@ class MultitaskVariationalGP(Module):
         return self.forward(x, **kwargs)
 
     def initialize_variational_parameters(self, likelihood, x, f=None, y=None):
-        """:38-88 for the "exp" likelihood.  y [N,T]: mean = log running std of each column, S_root = L C^-T with
-        L = chol(K_uu), C = chol(L' H L + I), H the mean over tasks of the clamped inverse Hessians (whose off-diagonal
-        1e-4 survives the mean); stored as the reference stores it -- 10 * S_root, a FULL matrix of which only tril() is
-        ever used.  (gpytorch's root_inv_decomposition is taken on its Cholesky route.)"""
-        if getattr(likelihood, "param", "exp") != "exp":
-            raise NotImplementedError('the "cv" initialisation (multi_task_variational_gp.py:58-69) is not implemented')
+        """:38-88.  y [N,T]: S_root = L C^-T with L = chol(K_uu), C = chol(L' H L + I), H the mean over tasks of the inverse
+        Hessians; stored as the reference stores it -- 10 * S_root, a FULL matrix of which only tril() is ever used.
+        (gpytorch's root_inv_decomposition is taken on its Cholesky route.)
+        "exp": mean = log running std of each column, H clamped to [1e-4, 1000] AFTER diag_embed, so its off-diagonal 1e-4
+        survives the mean.
+        "cv" (:58-69, one warp per task, K = 1 only) with the reference's quirks kept: ``y = f.t()`` replaces the returns by
+        the log running std, mean = ((y/a).exp() - 1 - c)/b, sigma from the likelihood's own forward, and NO clamp on the
+        diag_embed-ed inverse Hessian, so the mean over tasks keeps zeros off the diagonal.  The reference's ``y / trans_a``
+        divides [T,N] by [T,K], a broadcast that only works for K = 1: K > 1 raises here."""
+        param = getattr(likelihood, "param", "exp")
+        if param not in ("exp", "cv"):
+            raise NotImplementedError(f"unknown volatility likelihood parameterisation {param!r}")
+        if param == "cv":
+            if tuple(likelihood.raw_a.shape[:-1]) != (self.num_tasks,):
+                raise NotImplementedError('the multi-task "cv" start-up needs one warp per task: build the likelihood with '
+                                          f"batch_shape=[num_tasks] = [{self.num_tasks}]")
+            if likelihood.raw_a.shape[-1] != 1:
+                raise NotImplementedError('the "cv" initialisation divides y [T,N] by trans_a [T,K] '
+                                          "(multi_task_variational_gp.py:60: `y / likelihood.trans_a`), a broadcast that only "
+                                          f"works for K = 1; K = {likelihood.raw_a.shape[-1]} has no start-up values")
         assert y is not None
         with torch.no_grad():
             kuu = _dense(self.data_kernel(self.inducing_points)).to(torch.float32)
@@ -102,9 +120,20 @@ class MultitaskVariationalGP(Module):
             running_std[:10] = running_std[10]
             if f is None:
                 f = running_std.clamp(min=1e-4).log()
-            # torch.diag_embed(...).clamp(min=1e-4, max=1000.).mean(0): diagonal = mean of the clamped entries, elsewhere 1e-4
-            h = (0.5 * y2.pow(-2.0) * (f * 2.0).exp()).T.clamp(min=1e-4, max=1000.0).mean(0)
-            ih = torch.full((N, N), 1e-4, device=y2.device)
+            if param == "exp":
+                # torch.diag_embed(...).clamp(min=1e-4, max=1000.).mean(0): diagonal = mean of the clamped entries, elsewhere 1e-4
+                h = (0.5 * y2.pow(-2.0) * (f * 2.0).exp()).T.clamp(min=1e-4, max=1000.0).mean(0)
+                ih = torch.full((N, N), 1e-4, device=y2.device)
+            else:
+                a, b, c = (p.detach().to(y2.device, torch.float32) for p in
+                           (likelihood.trans_a, likelihood.trans_b, likelihood.trans_c))     # [T,1]
+                yl = f.t()                                                                   # `y = f.t()`: the returns are gone
+                ft = ((yl / a).exp() - 1 - c) / b                                            # [T,N]
+                sigma = likelihood(ft).scale                         # plain-tensor forward: parameter set t meets row t
+                scaling = ((2 + 3 * yl.pow(2.0)) * (a * b.pow(2.0) / 2)).pow(-1.0)
+                h = (scaling * sigma.pow(2.0) * (1 + torch.cosh(b * yl + c))).mean(0)       # diag of diag_embed(.).mean(0)
+                ih = torch.zeros(N, N, device=y2.device)
+                f = ft.t()
             ih.diagonal().copy_(h)
             L = _safe_factor(kuu.reshape(1, N, N))[0].L[0]                                   # kuu.cholesky()
             Lt = L.mT.contiguous()

@@ -728,13 +728,20 @@ GPCV_MT_T_MAX = 64                 # include/volt_hip.h: volt_gpcv_mt_step_f32 t
 
 class GpcvMtWorkspace:
     """Caller-owned scratch and outputs of volt_gpcv_mt_step_f32, reusable across steps of the same (N, T).
+    Kc > 0: the workspace of volt_gpcv_mt_cv_step_f32 for Kc warp terms per task (adds .grad_abc [T,3,Kc]).
     info[0]: the factorisation of K + jitter I; info[1]: a non-positive pivot of K_t; info[2]: F is not finite."""
 
-    def __init__(self, N: int, T: int, want_dk: bool, device):
+    def __init__(self, N: int, T: int, want_dk: bool, device, Kc: int = 0):
         if T < 1 or T > GPCV_MT_T_MAX:
             raise ValueError(f"the multi-task GPCV step takes 1 <= T <= {GPCV_MT_T_MAX} series (got T = {T})")
-        self.N, self.T, self.want_dk = N, T, bool(want_dk)
-        nbytes = _lib.lib().volt_gpcv_mt_workspace_bytes(N, T, int(want_dk))
+        self.N, self.T, self.want_dk, self.Kc = N, T, bool(want_dk), int(Kc)
+        if Kc:
+            if Kc < 1 or Kc > GPCV_CV_K_MAX:
+                raise _lib.VoltHipError(f'the "cv" multi-task GPCV step takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms '
+                                        f"(got Kc = {Kc})")
+            nbytes = _lib.lib().volt_gpcv_mt_cv_workspace_bytes(N, T, int(want_dk), int(Kc))
+        else:
+            nbytes = _lib.lib().volt_gpcv_mt_workspace_bytes(N, T, int(want_dk))
         self.buf, self.ptr = _scratch(nbytes, device)
         with torch.cuda.device(self.buf.device):        # it begins with an MLL workspace for ONE series
             _lib.check(_lib.lib().volt_mll_workspace_init_f32(self.ptr, 1, N, 1, _lib.stream_ptr()), "volt_mll_workspace_init")
@@ -747,21 +754,24 @@ class GpcvMtWorkspace:
         self.grad_covar_factor = torch.empty(T, **f32)
         self.grad_raw_var = torch.empty(T, **f32)
         self.grad_K = torch.empty(N, N, **f32) if want_dk else None
+        self.grad_abc = torch.empty(T, 3, Kc, **f32) if Kc else None
         self.info = torch.empty(3, dtype=torch.int32, device=device)
 
-    def fits(self, N, T, want_dk, device):
-        return (self.N, self.T, self.want_dk, self.buf.device) == (N, T, bool(want_dk), device)
+    def fits(self, N, T, want_dk, device, Kc=0):
+        return (self.N, self.T, self.want_dk, self.buf.device, self.Kc) == (N, T, bool(want_dk), device, Kc)
 
 
 def gpcv_mt_step(K, M, c, Lx, Lt, covar_factor, raw_var, y, gh_x, gh_w, ws: GpcvMtWorkspace | None = None,
                  want_dk: bool = False, jitter: float = 1e-3, min_var: float = 1e-6, min_scale: float = 1e-3,
-                 w_ell: float = 1.0, w_kl: float = 1.0):
+                 w_ell: float = 1.0, w_kl: float = 1.0, abc=None):
     """One ELBO + gradient evaluation of the multi-task GPCV variational GP (include/volt_hip.h, volt_gpcv_mt_step_f32).
     K [N,N] data prior covariance without jitter; M, y [N,T]; c, covar_factor ([T] or [T,1]), raw_var [T]; Lx [N,N],
     Lt [T,T] (what lies above their diagonals is ignored).  Gradients are those of F = w_ell * ell - w_kl * KL (out[12]).
+    abc None: the "exp" likelihood.  abc [T,3,Kc]: the copula-process ("cv") likelihood with the TRANSFORMED a, b, c of
+    every task, scale_t(f) = sum_k a_tk softplus(b_tk f + c_tk) (volt_gpcv_mt_cv_step_f32).
     Returns the workspace: .out [16], .grad_M, .grad_c, .grad_Lx, .grad_Lt, .grad_covar_factor, .grad_raw_var
-    (.grad_K if want_dk), .info [3]."""
-    _need_gpu(K, M, c, Lx, Lt, covar_factor, raw_var, y, gh_x, gh_w)
+    (.grad_K if want_dk, .grad_abc [T,3,Kc] = dF/d(a,b,c) with abc), .info [3]."""
+    _need_gpu(K, M, c, Lx, Lt, covar_factor, raw_var, y, abc, gh_x, gh_w)
     if K.ndim != 2 or K.dtype != torch.float32:
         raise ValueError("K must be [N,N] fp32")
     n = K.shape[0]
@@ -772,15 +782,28 @@ def gpcv_mt_step(K, M, c, Lx, Lt, covar_factor, raw_var, y, gh_x, gh_w, ws: Gpcv
     M, y, Lx, Lt = f(M, (n, T)), f(y, (n, T)), f(Lx, (n, n)), f(Lt, (T, T))
     c, cf, rv = f(c, (T,)), f(covar_factor, (T,)), f(raw_var, (T,))
     gh_x, gh_w = gh_x.to(torch.float32).contiguous(), gh_w.to(torch.float32).contiguous()
-    if ws is None or not ws.fits(n, T, want_dk, K.device):
-        ws = GpcvMtWorkspace(n, T, want_dk, K.device)
-    _lib.check(_lib.lib().volt_gpcv_mt_step_f32(
-        K.data_ptr(), K.stride(0), float(jitter), M.data_ptr(), c.data_ptr(), Lx.data_ptr(), Lt.data_ptr(), cf.data_ptr(),
-        rv.data_ptr(), y.data_ptr(), gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var), float(min_scale),
-        float(w_ell), float(w_kl), ws.out.data_ptr(), ws.grad_M.data_ptr(), ws.grad_c.data_ptr(), ws.grad_Lx.data_ptr(),
-        ws.grad_Lt.data_ptr(), ws.grad_covar_factor.data_ptr(), ws.grad_raw_var.data_ptr(),
-        ws.grad_K.data_ptr() if want_dk else None, ws.info.data_ptr(), ws.ptr, n, T, _lib.WS_INITIALISED,
-        _lib.stream_ptr()), "volt_gpcv_mt_step")
+    Kc = 0
+    if abc is not None:
+        if abc.ndim != 3 or abc.shape[0] != T or abc.shape[1] != 3:
+            raise ValueError("abc must be [T,3,Kc]")
+        Kc = abc.shape[2]
+        if not 1 <= Kc <= GPCV_CV_K_MAX:
+            raise _lib.VoltHipError(f'the "cv" multi-task GPCV step takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms '
+                                    f"(got Kc = {Kc})")
+        abc = f(abc, (T, 3, Kc))
+    if ws is None or not ws.fits(n, T, want_dk, K.device, Kc):
+        ws = GpcvMtWorkspace(n, T, want_dk, K.device, Kc)
+    prior = (K.data_ptr(), K.stride(0), float(jitter), M.data_ptr(), c.data_ptr(), Lx.data_ptr(), Lt.data_ptr(), cf.data_ptr(),
+             rv.data_ptr(), y.data_ptr())
+    quad = (gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var), float(min_scale), float(w_ell), float(w_kl))
+    grads = (ws.out.data_ptr(), ws.grad_M.data_ptr(), ws.grad_c.data_ptr(), ws.grad_Lx.data_ptr(), ws.grad_Lt.data_ptr(),
+             ws.grad_covar_factor.data_ptr(), ws.grad_raw_var.data_ptr(), ws.grad_K.data_ptr() if want_dk else None)
+    tail = (ws.info.data_ptr(), ws.ptr, n, T, _lib.WS_INITIALISED, _lib.stream_ptr())
+    if abc is None:
+        _lib.check(_lib.lib().volt_gpcv_mt_step_f32(*prior, *quad, *grads, *tail), "volt_gpcv_mt_step")
+    else:
+        _lib.check(_lib.lib().volt_gpcv_mt_cv_step_f32(*prior, abc.data_ptr(), Kc, *quad, *grads, ws.grad_abc.data_ptr(), *tail),
+                   "volt_gpcv_mt_cv_step")
     return ws
 
 

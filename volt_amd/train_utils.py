@@ -332,11 +332,15 @@ def LearnGPCV(train_x, train_y, train_iters=1000, printing=False, early_stopping
     return likelihood(model(train_x), return_gaussian=False).scale.mean(0).detach()      # :60-67
 
 
-def FitGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None):
+def FitGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None, *, param="exp", K=1,
+                     train_likelihood=False):
     """LearnGPCV's fit (train_utils.py:15-58) over the JOINT model of T series that share the time grid
     (MultitaskVariationalGP, voltron/models/multi_task_variational_gp.py; the reference has no trainer for it):
     train_y [T,N+1] prices -> (model, likelihood, losses).  One HIP ELBO step per iteration factors the N x N prior ONCE
-    for all T series (the batched FitGPCV factors it T times and keeps T variational roots)."""
+    for all T series (the batched FitGPCV factors it T times and keeps T variational roots).
+    ``param``, ``K``, ``train_likelihood`` have FitGPCV's meaning: ``param="cv"`` fits the copula-process likelihood with
+    one warp of K terms PER TASK (``batch_shape=[T]``; start-up values for K = 1 only), and its raw_a, raw_b, raw_c join
+    the one Adam group at LR_GPCV only with ``train_likelihood=True``.  The defaults are the "exp" loop."""
     from .kernels import BMKernel, FBMKernel
     from .likelihoods import VolatilityGaussianLikelihood
     from .models import MultitaskVariationalGP
@@ -345,14 +349,23 @@ def FitGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel=
         raise ValueError("FitGPCVMultitask: train_y must be [T,N+1] (one row of prices per series)")
     dt = train_x[1] - train_x[0]
     yy = ((train_y[..., 1:] - train_y[..., :-1]) / train_y[..., :-1] / dt ** 0.5).t().contiguous()   # :16-18, [N,T]
-    likelihood = VolatilityGaussianLikelihood(param="exp")
+    if param == "exp":
+        likelihood = VolatilityGaussianLikelihood(param="exp")
+    else:
+        likelihood = VolatilityGaussianLikelihood(K=K, param=param, batch_shape=torch.Size([yy.shape[-1]])).to(train_x.device)
     covar_module = {"bm": BMKernel, "fbm": FBMKernel}[kernel]()
     model = MultitaskVariationalGP(train_x, num_tasks=yy.shape[-1], covar_module=covar_module)
     model.initialize_variational_parameters(likelihood, train_x, y=yy)
     model.train()
     likelihood.train()
     graph = bool(graph)                                  # (this entry returns the per-iteration losses: captured only on request)
-    optimizer = _adam([{"params": model.parameters()}], LR_GPCV, graph)
+    params = model.parameters()
+    if param != "exp":                                   # (this model does not register its likelihood)
+        for p in likelihood.parameters():
+            p.requires_grad_(bool(train_likelihood))
+        if train_likelihood:
+            params = list(params) + list(likelihood.parameters())
+    optimizer = _adam([{"params": params}], LR_GPCV, graph)
     elbo = VariationalELBO(likelihood, model, yy.numel(), combine_terms=True)
     losses = []
 
@@ -372,13 +385,14 @@ def FitGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel=
     return model, likelihood, losses
 
 
-def LearnGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None):
+def LearnGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None, *, param="exp", K=1,
+                       train_likelihood=False):
     """LearnGPCV for T series through the joint model: train_y [T,N+1] prices -> pred_scale [T,N] (the 10-sample
-    predictive scale of train_utils.py:60-67, per series)."""
+    predictive scale of train_utils.py:60-67, per series).  ``param``, ``K``, ``train_likelihood``: see FitGPCVMultitask."""
     # one series' N^3 chain whatever T is: the capture gate sees ONE [N] target
     graph = _auto_graph(graph, train_y[0, 1:], n3_coeff=5.0 / 3.0)
     model, likelihood, _ = FitGPCVMultitask(train_x, train_y, train_iters=train_iters, printing=printing, kernel=kernel,
-                                            graph=graph)
+                                            graph=graph, param=param, K=K, train_likelihood=train_likelihood)
     return likelihood(model(train_x), return_gaussian=False).scale.mean(0).t().detach()
 
 

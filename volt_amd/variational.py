@@ -1,6 +1,7 @@
 """Variational-GP plumbing of the GPCV stage, backed by volt_gpcv_step_f32 ("exp" likelihood),
 volt_gpcv_cv_step_f32 ("cv"), volt_gpcv_bm_step_f32 (either likelihood under the lazy Brownian-motion prior of
-``SingleTaskVariationalGP(prior_solver="linear")``) and volt_gpcv_mt_step_f32 (the multi-task model).
+``SingleTaskVariationalGP(prior_solver="linear")``), volt_gpcv_mt_step_f32 (the multi-task model, "exp") and
+volt_gpcv_mt_cv_step_f32 (the multi-task model, "cv" with one warp per task).
 
 The reference builds this stage from gpytorch parts (voltron/train_utils.py:20-44,
 voltron/models/single_task_variational_gp.py:69-122): ``CholeskyVariationalDistribution`` +
@@ -295,25 +296,33 @@ def mt_dkl_dscale(out, scale, n, T, jitter=PRIOR_JITTER):
 
 
 class _GPCVMtElbo(torch.autograd.Function):
-    """F = w_ell ell - w_kl KL of the multi-task model with the analytic gradients the HIP step returns."""
+    """F = w_ell ell - w_kl KL of the multi-task model with the analytic gradients the HIP step returns.  raw_a, raw_b, raw_c
+    None: the "exp" likelihood; given ([T,Kc]): the copula-process ("cv") likelihood, one warp per task -- the step returns
+    dF/d(a,b,c), the constraints' chain rule is applied here, as in ``_GPCVElbo``."""
 
     @staticmethod
-    def forward(ctx, M, Lx, Lt, c, cf, rv, K, y, holder, scale, num_gh, w_ell, w_kl):
+    def forward(ctx, M, Lx, Lt, c, cf, rv, K, y, raw_a, raw_b, raw_c, holder, scale, num_gh, w_ell, w_kl):
         n, T = M.shape
         want_dk = bool(ctx.needs_input_grad[6])
         gh_x, gh_w = _gauss_hermite(num_gh, M.device)
-        ws = holder.mt_workspace(n, T, want_dk, M.device)
+        cv = raw_a is not None
+        ws = holder.mt_workspace(n, T, want_dk, M.device, Kc=raw_a.shape[-1] if cv else 0)
+        abc, jac = _cv_transform(raw_a, raw_b, raw_c, T) if cv else (None, None)
         ops.gpcv_mt_step(K.detach(), M, c, Lx, Lt, cf, rv, y, gh_x, gh_w, ws, want_dk=want_dk, jitter=PRIOR_JITTER,
-                         min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
+                         min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl, abc=abc)
         if deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
             info = ws.info.cpu()
             # info[0]: K_x + jitter I (LAPACK-style or an internal code);  info[1]: a pivot of K_t;  info[2]: F not finite
             which = "prior covariance K_x + 1e-3 I" if int(info[0]) != 0 else "task covariance K_t"
-            _raise_step_failure("multi-task GPCV step", info[:1], (K, M, Lx, Lt, c, cf, rv, y), which)
-        ctx.n, ctx.T, ctx.w_kl, ctx.has_scale, ctx.want_dk = n, T, w_kl, scale is not None, want_dk
+            _raise_step_failure("multi-task GPCV cv step" if cv else "multi-task GPCV step", info[:1],
+                                (K, M, Lx, Lt, c, cf, rv, y) + ((abc,) if cv else ()), which)
+        ctx.n, ctx.T, ctx.w_kl, ctx.has_scale, ctx.want_dk, ctx.cv = n, T, w_kl, scale is not None, want_dk, cv
         ctx.cf_shape = cf.shape
         saved = [ws.grad_M.clone(), ws.grad_Lx.clone(), ws.grad_Lt.clone(), ws.grad_c.clone(),
                  ws.grad_covar_factor.clone(), ws.grad_raw_var.clone()]
+        if cv:
+            ctx.raw_shape = raw_a.shape
+            saved.append(ws.grad_abc * jac)
         if want_dk:
             saved.append(ws.grad_K.clone())
         if scale is not None:
@@ -325,14 +334,15 @@ class _GPCVMtElbo(torch.autograd.Function):
     def backward(ctx, g):
         sv = list(ctx.saved_tensors)
         gM, gLx, gLt, gc, gcf, grv = sv[:6]
-        gK = g * sv[6] if ctx.want_dk else None
+        gK = g * sv[7 if ctx.cv else 6] if ctx.want_dk else None
         gscale = None
         if ctx.has_scale:
             dkl = mt_dkl_dscale(sv[-2], sv[-1], ctx.n, ctx.T)
             s = sv[-1]
             gscale = (-ctx.w_kl * g * dkl).reshape(s.shape)
-        return (g * gM, g * gLx, g * gLt, g * gc, (g * gcf).reshape(ctx.cf_shape), g * grv, gK, None, None, gscale,
-                None, None, None)
+        ga, gb, gcc = _cv_raw_grads(g, sv[6], ctx.raw_shape) if ctx.cv else (None, None, None)
+        return (g * gM, g * gLx, g * gLt, g * gc, (g * gcf).reshape(ctx.cf_shape), g * grv, gK, None, ga, gb, gcc, None,
+                gscale, None, None, None)
 
 
 class VariationalELBO(Module):
@@ -346,9 +356,14 @@ class VariationalELBO(Module):
         param = getattr(likelihood, "param", "exp")
         if param not in ("exp", "cv"):
             raise NotImplementedError(f"unknown volatility likelihood parameterisation {param!r}")
-        if param == "cv" and hasattr(model, "variational_task_covar_root"):      # MultitaskVariationalGP
-            raise NotImplementedError('the multi-task model has an accelerated ELBO for the "exp" volatility likelihood only; '
-                                      '"cv" runs on SingleTaskVariationalGP')
+        if param == "cv" and hasattr(model, "variational_task_covar_root"):      # MultitaskVariationalGP: one warp per task
+            T = model.num_tasks
+            if likelihood.raw_a.ndim != 2:
+                raise NotImplementedError('the multi-task model has an accelerated "cv" ELBO with one warp per task only: '
+                                          f"build the likelihood with batch_shape=[num_tasks] = [{T}]")
+            if likelihood.raw_a.shape[0] != T:
+                raise ValueError(f"VariationalELBO: the likelihood's batch shape {tuple(likelihood.raw_a.shape[:-1])} does "
+                                 f"not match the model's num_tasks = {T}")
         if param == "cv" and not 1 <= likelihood.raw_a.shape[-1] <= ops.GPCV_CV_K_MAX:
             raise NotImplementedError(f'the accelerated "cv" ELBO takes 1 <= K <= {ops.GPCV_CV_K_MAX} warp terms')
         object.__setattr__(self, "likelihood", likelihood)
@@ -364,8 +379,8 @@ class VariationalELBO(Module):
     def workspace(self, B, n, want_dk, device, Kc=0):
         return ops.cached_workspace(self, "_ws", ops.GpcvWorkspace, B, n, want_dk, device, Kc)
 
-    def mt_workspace(self, n, T, want_dk, device):
-        return ops.cached_workspace(self, "_mt_ws", ops.GpcvMtWorkspace, n, T, want_dk, device)
+    def mt_workspace(self, n, T, want_dk, device, Kc=0):
+        return ops.cached_workspace(self, "_mt_ws", ops.GpcvMtWorkspace, n, T, want_dk, device, Kc)
 
     def _forward_multitask(self, latent, target):
         """VariationalELBO over a MultitaskMultivariateNormal (event shape [N,T]): the likelihood term is summed over
@@ -385,8 +400,10 @@ class VariationalELBO(Module):
         else:
             K = _dense(lazy)
         c, cf, rv = model._task_params()
+        lik = self.likelihood
+        raws = [lik.raw_a, lik.raw_b, lik.raw_c] if getattr(lik, "param", "exp") == "cv" else [None, None, None]
         return _GPCVMtElbo.apply(M, model.variational_covar_root, model.variational_task_covar_root, c, cf, rv,
-                                 K.to(torch.float32), target.to(torch.float32), self, scale,
+                                 K.to(torch.float32), target.to(torch.float32), *raws, self, scale,
                                  num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data)
 
     @staticmethod
