@@ -619,6 +619,42 @@ int volt_gpcv_bm_step_f32(const float* x, const float* vol, float jitter, const 
                           float min_scale, float w_ell, float w_kl, float* out, float* grad_m, float* grad_mu, float* grad_Lq,
                           float* grad_abc, int* info, void* workspace, int B, int N, void* stream);
 
+/* ---- GPCV ELBO step in O(N) for the Brownian-motion prior with a Markov variational family
+ * (SingleTaskVariationalGP(prior_solver="markov"); csrc/gpcv_markov.hip has the recurrences).
+ * Prior: f - mu is Brownian motion started from an N(0, jitter) level over the grid x [N] (0 <= x_0 < x_1 < .., shared by the
+ * batch): K_M = vol min(x, x') + jitter 1 1', increments of variance q_0 = vol x_0 + jitter, q_i = vol (x_i - x_{i-1}).  This is
+ * NOT the other steps' K + jitter I: a jitter on the starting level keeps K_M^-1 exactly tridiagonal (and x_0 = 0 valid).
+ * Family: q = N(m, P^-1), P = Lp Lp', Lp lower bidiagonal: diagonal exp(rho_i), entry (i+1, i) gamma_i exp(rho_i).
+ * rho, gamma [B,N]; gamma[., N-1] is never read.  resid = m - mu.  abc == NULL (and Kc == 0): the "exp" likelihood;
+ * abc [B,3,Kc], 1 <= Kc <= VOLT_GPCV_CV_K_MAX: the "cv" one.  Arithmetic of the recurrences fp64, quadrature and I/O fp32.
+ *     out[b,0..11] = ell, KL, quad, logdet K_M, logdet S, tr(K_M^-1 S), dF/dvol, 0, 0, F = w_ell ell - w_kl KL, jitter, 0
+ *     grad_m, grad_mu, grad_rho, grad_gamma [B,N] (grad_gamma[., N-1] = 0), grad_abc [B,3,Kc] = dF/d(a,b,c)
+ * info[b]: 0, or 1 where F is not finite (there is no pivot that can fail).
+ * workspace: volt_gpcv_markov_workspace_bytes(B, N, Kc) bytes (0 for a shape out of range), 256-byte aligned, O(B N); it needs
+ * no initialisation call and is fully written before it is read.  On return its first 8 B N bytes hold diag S [B,N] in fp64.
+ * ONE launch, one workgroup per series; no host synchronisation, no allocation, no atomics: every reduction has a fixed
+ * order, results are bitwise repeatable, and the launch replays from a hipGraph.  1 <= B <= 65535, N >= 1; 64-bit indices.
+ * Argument errors (before the launch, in the order of their numbers): -1 x, -2 vol, -4 resid, -5 m, -6 rho, -7 gamma, -8 y
+ * NULL; -10 Kc out of range with abc, or Kc != 0 without; -11 gh_x, -12 gh_w NULL; -13 Q outside 1 .. 1024; -18 out,
+ * -19 grad_m, -20 grad_mu, -21 grad_rho, -22 grad_gamma NULL; -23 grad_abc NULL with abc; -24 info NULL; -25 workspace NULL
+ * or not 256-byte aligned; -26 B outside 1 .. 65535; -27 N < 1.
+ *
+ * volt_markov_root_draw_f32: out[b,r,:] = m[b] + Lp[b]^-T eps[b,r,:] (u_{N-1} = eps_{N-1} e^{-rho_{N-1}},
+ * u_i = eps_i e^{-rho_i} - gamma_i u_{i+1}): `reps` draws per series, eps, out [B,reps,N]; fp64 arithmetic, rounded once.
+ * One launch, one workgroup per draw.  Argument errors: -1 m, -2 rho, -3 gamma, -4 eps, -5 out NULL; -6 B < 1; -7 reps < 1 (or
+ * B reps >= 2^24 draws: a launch of 256-thread workgroups holds fewer than 2^32 threads); -8 N < 1.
+ * volt_markov_root_var_f32: var [B,N] (fp64) = diag (Lp Lp')^-1, the step's s.  Argument errors: -1 rho, -2 gamma, -3 var
+ * NULL; -4 B < 1; -5 N < 1. */
+size_t volt_gpcv_markov_workspace_bytes(int B, int N, int Kc);
+int volt_gpcv_markov_step_f32(const float* x, const float* vol, float jitter, const float* resid, const float* m, const float* rho,
+                              const float* gamma, const float* y, const float* abc, int Kc, const float* gh_x, const float* gh_w,
+                              int Q, float min_var, float min_scale, float w_ell, float w_kl, float* out, float* grad_m,
+                              float* grad_mu, float* grad_rho, float* grad_gamma, float* grad_abc, int* info, void* workspace,
+                              int B, int N, void* stream);
+int volt_markov_root_draw_f32(const float* m, const float* rho, const float* gamma, const float* eps, float* out, int B, int reps,
+                              int N, void* stream);
+int volt_markov_root_var_f32(const float* rho, const float* gamma, double* var, int B, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,9 @@ def _check_gpcv_options(gpcv_options, multitask_gpcv, gpcv_solver, nseries, vol_
         raise ValueError(f"gpcv_options: unknown keys {unknown}; it takes {list(GPCV_OPTIONS)}")
     if multitask_gpcv and vol_fn is None:
         from . import ops
+        if gpcv_solver == "markov":
+            raise ValueError('multitask_gpcv=True runs the dense multi-task step: it does not combine with gpcv_solver="markov" '
+                             "(the multi-task model has no Markov variational family)")
         if gpcv_solver == "linear":
             raise ValueError('multitask_gpcv=True runs the dense multi-task step: it does not combine with gpcv_solver="linear" '
                              "(the multi-task model has no lazy Brownian prior)")
@@ -259,6 +262,7 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
     come to the host (no sample files either) and the first element is None.
     ``vol_solver="linear"``: the vol forecaster's fit and posterior on the linear-time Brownian-motion solver
     (TrainVolModelBatch(solver=...), csrc/bm.hip); the default "dense" changes nothing.
+    ``gpcv_solver="markov"``: the GPCV stage in O(N) with the Markov variational family (csrc/gpcv_markov.hip).
     ``gpcv_solver="linear"``: the GPCV stage's ELBO step in O(N^2) (LearnGPCV(solver=...), csrc/gpcv_bm.hip); independent of
     ``vol_solver``, ignored with a ``vol_fn``, and "dense" changes nothing.
     ``data_solver="linear"``: the data model's fit on the linear-time step over each series' integrated vol path

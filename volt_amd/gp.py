@@ -170,6 +170,19 @@ class _BrownianPrior(_ScaledDense):
         return torch.Size((n, n))
 
 
+class _BrownianLevelPrior(_BrownianPrior):
+    """Lazy prior of SingleTaskVariationalGP(prior_solver="markov"): Brownian motion started from an N(0, level) level,
+    K_M = scale * min(x, x') + level 1 1' (increments of variance q_0 = scale x_0 + level, q_i = scale (x_i - x_{i-1})), never
+    formed -- VariationalELBO hands (scale, x) to the O(N) step of csrc/gpcv_markov.hip.  NOT K + level I: a jitter on the
+    starting level keeps K_M^-1 exactly tridiagonal.  Dense only when ``.evaluate()`` / ``.to_dense()`` is asked for."""
+
+    def __init__(self, scale, x, level):
+        self.scale, self.x, self.level = scale, x, level
+
+    def _build(self, detach=False):
+        return super()._build(detach) + self.level
+
+
 def _markov_cov(diag, off):
     """The covariance [..,H,H] of a Markov process over H ordered points from its diagonal ``diag`` [..,H] and its first
     off-diagonal ``off`` [..,H] (off[.., j] = cov(j, j+1); the last entry is not read): cov(a, c) = diag_a prod_{a <= j < c} g_j

@@ -43,7 +43,7 @@ class Volt(VolGP):
               vol_model=None, vol_lh=None, *, gpcv_solver="dense"):
         """Volt.py:95-146: GPCV + vol model (:103-104), then the data model (:108-146).  ``vol`` (and optionally a
         trained ``vol_model`` / ``vol_lh``) skips the first stage.  ``gpcv_solver="linear"``: the GPCV stage on the O(N^2)
-        ELBO step (LearnGPCV(solver=...)); the vol forecaster keeps the solver and posterior the model was built with (``vol_solver``, ``vol_posterior``), and so does the data
+        ELBO step, ``"markov"``: on the O(N) step with the Markov variational family (LearnGPCV(solver=...)); the vol forecaster keeps the solver and posterior the model was built with (``vol_solver``, ``vol_posterior``), and so does the data
         model (``data_solver``: UpdateVolPath rebuilds the lazy prior, the fit below steps on it)."""
         from ..train_utils import LR_DATA, LearnGPCV, TrainVolModel, _attach_vol, _fit_exact, _train_noise_and_mean
         x = self.train_x.squeeze()

@@ -723,6 +723,107 @@ def gpcv_bm_step(x, vol, resid, m, Lq, y, gh_x, gh_w, ws: GpcvBmWorkspace | None
     return ws
 
 
+class GpcvMarkovWorkspace:
+    """Caller-owned scratch and outputs of volt_gpcv_markov_step_f32, reusable across steps of the same (B, N, Kc): O(B N)
+    bytes, no initialisation call.  After a step ``.s`` [B,N] (fp64, a view of the scratch) holds diag S = diag P^-1.
+    Kc > 0 adds .grad_abc [B,3,Kc] (the "cv" likelihood)."""
+
+    def __init__(self, B: int, N: int, device, Kc: int = 0):
+        self.B, self.N, self.Kc = B, N, int(Kc)
+        if Kc < 0 or Kc > GPCV_CV_K_MAX:
+            raise _lib.VoltHipError(f'the "cv" GPCV step takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms (got Kc = {Kc})')
+        self.nbytes = int(_lib.lib().volt_gpcv_markov_workspace_bytes(B, N, int(Kc)))
+        self.buf, self.ptr = _scratch(self.nbytes, device)
+        off = self.ptr - self.buf.data_ptr()
+        self.s = self.buf[off:off + 8 * B * N].view(torch.float64).view(B, N)
+        f32 = dict(dtype=torch.float32, device=device)
+        self.out = torch.empty(B, 12, **f32)
+        self.grad_m = torch.empty(B, N, **f32)
+        self.grad_mu = torch.empty(B, N, **f32)
+        self.grad_rho = torch.empty(B, N, **f32)
+        self.grad_gamma = torch.empty(B, N, **f32)
+        self.grad_abc = torch.empty(B, 3, Kc, **f32) if Kc else None
+        self.info = torch.empty(B, dtype=torch.int32, device=device)
+
+    def fits(self, B, N, device, Kc=0):
+        return (self.B, self.N, self.buf.device, self.Kc) == (B, N, device, Kc)
+
+
+def gpcv_markov_step(x, vol, resid, m, rho, gamma, y, gh_x, gh_w, ws: GpcvMarkovWorkspace | None = None, abc=None,
+                     jitter: float = 1e-3, min_var: float = 1e-6, min_scale: float = 1e-3, w_ell: float = 1.0,
+                     w_kl: float = 1.0):
+    """The GPCV ELBO step in O(N) for the Markov variational family q = N(m, (Lp Lp')^-1), Lp lower bidiagonal with diagonal
+    exp(rho) and sub-diagonal gamma exp(rho), under the Brownian prior started from an N(0, jitter) level,
+    K_M = vol min(x, x') + jitter 1 1' -- NOT the other steps' K + jitter I (include/volt_hip.h, volt_gpcv_markov_step_f32).
+    x [N] the grid (0 <= x_0 < x_1 < ..), vol [B] (or one value), resid = m - mu, m, rho, gamma, y [B,N] (gamma[:, N-1] is
+    not read); abc [B,3,Kc] given: the "cv" likelihood.  Returns the workspace: .out [B,12] (out[:, 6] = dF/dvol,
+    out[:, 9] = F), .grad_m, .grad_mu, .grad_rho, .grad_gamma (.grad_abc with abc), .info, .s = diag S."""
+    _need_gpu(x, vol, resid, m, rho, gamma, y, gh_x, gh_w, abc)
+    if m.ndim != 2:
+        raise ValueError("m must be [B,N]")
+    B, n = m.shape
+    if x.shape[-1] != n:
+        raise ValueError("x and m disagree on N")
+    x, vol, _ = _bm_args(x, vol, vol, B, torch.float32)
+    c = lambda t, shape: t.reshape(shape).to(torch.float32).contiguous()
+    resid, m, y, rho, gamma = (c(t, (B, n)) for t in (resid, m, y, rho, gamma))
+    gh_x, gh_w = gh_x.to(torch.float32).contiguous(), gh_w.to(torch.float32).contiguous()
+    Kc = 0
+    if abc is not None:
+        if abc.ndim != 3 or abc.shape[0] != B or abc.shape[1] != 3:
+            raise ValueError("abc must be [B,3,Kc]")
+        Kc = abc.shape[2]
+        abc = c(abc, (B, 3, Kc))
+    if abc is not None and not 1 <= Kc <= GPCV_CV_K_MAX:      # no workspace can be sized: let the entry name the argument
+        ws = None
+    elif ws is None or not ws.fits(B, n, m.device, Kc):
+        ws = GpcvMarkovWorkspace(B, n, m.device, Kc)
+    o = lambda name: getattr(ws, name).data_ptr() if ws is not None and getattr(ws, name) is not None else None
+    with torch.cuda.device(m.device):
+        _lib.check(_lib.lib().volt_gpcv_markov_step_f32(
+            x.data_ptr(), vol.data_ptr(), float(jitter), resid.data_ptr(), m.data_ptr(), rho.data_ptr(), gamma.data_ptr(),
+            y.data_ptr(), abc.data_ptr() if abc is not None else None, Kc, gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(),
+            float(min_var), float(min_scale), float(w_ell), float(w_kl), o("out"), o("grad_m"), o("grad_mu"), o("grad_rho"),
+            o("grad_gamma"), o("grad_abc"), o("info"), ws.ptr if ws is not None else None, B, n, _lib.stream_ptr()),
+            "volt_gpcv_markov_step")
+    return ws
+
+
+def _markov_root_args(rho, gamma):
+    _need_gpu(rho, gamma)
+    if rho.ndim != 2 or gamma.shape != rho.shape:
+        raise ValueError("rho and gamma must both be [B,N]")
+    return rho.to(torch.float32).contiguous(), gamma.to(torch.float32).contiguous()
+
+
+def markov_root_draw(m: torch.Tensor, rho: torch.Tensor, gamma: torch.Tensor, eps: torch.Tensor) -> torch.Tensor:
+    """m + Lp^-T eps for the bidiagonal precision root Lp of (rho, gamma) (volt_markov_root_draw_f32): m, rho, gamma [B,N],
+    eps [B,reps,N] -> [B,reps,N]; one backward affine recurrence per draw, fp64 arithmetic rounded once."""
+    rho, gamma = _markov_root_args(rho, gamma)
+    _need_gpu(m, eps)
+    B, n = rho.shape
+    if eps.ndim != 3 or eps.shape[0] != B or eps.shape[2] != n or eps.shape[1] < 1 or tuple(m.shape) != (B, n):
+        raise ValueError(f"m must be [B,N] = {(B, n)} and eps [B,reps,N]")
+    m, eps = m.to(torch.float32).contiguous(), eps.to(torch.float32).contiguous()
+    out = torch.empty_like(eps)
+    with torch.cuda.device(eps.device):
+        _lib.check(_lib.lib().volt_markov_root_draw_f32(m.data_ptr(), rho.data_ptr(), gamma.data_ptr(), eps.data_ptr(),
+                                                        out.data_ptr(), B, eps.shape[1], n, _lib.stream_ptr()),
+                   "volt_markov_root_draw")
+    return out
+
+
+def markov_root_var(rho: torch.Tensor, gamma: torch.Tensor) -> torch.Tensor:
+    """diag (Lp Lp')^-1 [B,N] in fp64 (volt_markov_root_var_f32): the s of ``gpcv_markov_step``."""
+    rho, gamma = _markov_root_args(rho, gamma)
+    B, n = rho.shape
+    var = torch.empty(B, n, dtype=torch.float64, device=rho.device)
+    with torch.cuda.device(rho.device):
+        _lib.check(_lib.lib().volt_markov_root_var_f32(rho.data_ptr(), gamma.data_ptr(), var.data_ptr(), B, n,
+                                                       _lib.stream_ptr()), "volt_markov_root_var")
+    return var
+
+
 GPCV_MT_T_MAX = 64                 # include/volt_hip.h: volt_gpcv_mt_step_f32 takes 1 <= T <= 64 series
 
 

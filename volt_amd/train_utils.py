@@ -255,14 +255,14 @@ def _fit_exact(model, lh, train_x, target, params, lr, train_iters, printing, gr
 
 
 # ------------------------------------------------------------------------------------------------ (f)4: GPCV
-GPCV_SOLVERS = ("dense", "linear")
+GPCV_SOLVERS = ("dense", "linear", "markov")
 
 
 def _check_gpcv_solver(solver, kernel):
     if solver not in GPCV_SOLVERS:
         raise ValueError(f"GPCV: solver must be one of {GPCV_SOLVERS}, got {solver!r}")
-    if solver == "linear" and kernel != "bm":
-        raise ValueError(f"GPCV: solver='linear' needs kernel='bm' (Brownian motion is Markov; kernel {kernel!r} is not)")
+    if solver != "dense" and kernel != "bm":
+        raise ValueError(f"GPCV: solver={solver!r} needs kernel='bm' (Brownian motion is Markov; kernel {kernel!r} is not)")
 
 
 def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None, *, param="exp", K=1,
@@ -273,7 +273,10 @@ def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", gra
     Adam group at LR_GPCV (the reference's loop trains the model's parameters only, :37-43; its commented-out
     likelihood group is not reference behaviour).  The defaults are the reference's loop.
     ``solver="linear"`` (kernel "bm" only): the ELBO step of csrc/gpcv_bm.hip, O(N^2) instead of the dense step's O(N^3)
-    (``SingleTaskVariationalGP(prior_solver="linear")``; the start-up values stay dense)."""
+    (``SingleTaskVariationalGP(prior_solver="linear")``; the start-up values stay dense).
+    ``solver="markov"`` (kernel "bm" only): the Markov variational family and the level-jitter Brownian prior of
+    ``SingleTaskVariationalGP(prior_solver="markov")`` -- one launch per step, O(N) time and memory, start-up values included
+    (csrc/gpcv_markov.hip).  A different model from the other two solvers' (another prior jitter, another family)."""
     _check_gpcv_solver(solver, kernel)
     from .kernels import BMKernel, FBMKernel
     from .likelihoods import VolatilityGaussianLikelihood
@@ -323,10 +326,11 @@ def LearnGPCV(train_x, train_y, train_iters=1000, printing=False, early_stopping
     log-vol, ``y | f ~ N(0, exp f)``) fitted to the scaled returns; one HIP ELBO step per iteration.
     train_y [N+1] prices -> pred_scale [N]; train_y [T,N+1] fits T series at once (batched parameters).
     ``param``, ``K``, ``train_likelihood``: the copula-process likelihood, see FitGPCV.  ``solver="linear"``: the O(N^2) step
-    (FitGPCV); until its capture gate has been measured it is treated like the linear BM step (``launch_bound=True``)."""
+    (FitGPCV); until its capture gate has been measured it is treated like the linear BM step (``launch_bound=True``).
+    ``solver="markov"``: the O(N) step (FitGPCV), one launch per iteration and so launch-bound at every N."""
     _check_gpcv_solver(solver, kernel)
     # (only the fitted scale is returned: nothing per-iteration is lost by capturing)
-    graph = _auto_graph(graph, train_y[..., 1:], n3_coeff=5.0 / 3.0, launch_bound=solver == "linear")
+    graph = _auto_graph(graph, train_y[..., 1:], n3_coeff=5.0 / 3.0, launch_bound=solver in ("linear", "markov"))
     model, likelihood, _ = FitGPCV(train_x, train_y, train_iters=train_iters, printing=printing, kernel=kernel, graph=graph,
                                    param=param, K=K, train_likelihood=train_likelihood, solver=solver)
     return likelihood(model(train_x), return_gaussian=False).scale.mean(0).detach()      # :60-67

@@ -1,6 +1,7 @@
 """Variational-GP plumbing of the GPCV stage, backed by volt_gpcv_step_f32 ("exp" likelihood),
 volt_gpcv_cv_step_f32 ("cv"), volt_gpcv_bm_step_f32 (either likelihood under the lazy Brownian-motion prior of
-``SingleTaskVariationalGP(prior_solver="linear")``), volt_gpcv_mt_step_f32 (the multi-task model, "exp") and
+``SingleTaskVariationalGP(prior_solver="linear")``), volt_gpcv_markov_step_f32 (either likelihood, the Markov variational
+family of ``prior_solver="markov"``: O(N) time and memory), volt_gpcv_mt_step_f32 (the multi-task model, "exp") and
 volt_gpcv_mt_cv_step_f32 (the multi-task model, "cv" with one warp per task).
 
 The reference builds this stage from gpytorch parts (voltron/train_utils.py:20-44,
@@ -27,7 +28,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .gp import Module, MultivariateNormal, _BrownianPrior, _ScaledDense, _dense
+from .gp import Module, MultivariateNormal, _BrownianLevelPrior, _BrownianPrior, _ScaledDense, _dense
 from .safe import NotPSDError, check_nan, deferred_checks
 
 PRIOR_JITTER = 1e-3        # LazyTensor.add_jitter() default on the inducing prior
@@ -124,6 +125,70 @@ class VariationalLatent(MultivariateNormal):
         S = eps.reshape(-1, *self.loc.shape)                          # [S,B,N]
         f = ops.gemm_nt(S.transpose(0, 1).contiguous(), self.chol.detach(), uplo_b=1)   # [B,S,N]
         return self.loc.detach() + f.transpose(0, 1).reshape(base_samples.shape)
+
+
+class MarkovVariationalDistribution(Module):
+    """q(u) = N(variational_mean, P^-1) with a TRIDIAGONAL precision P = Lp Lp', Lp lower bidiagonal: diagonal
+    exp(log_diag_precision_root), entry (i+1, i) coupling_i exp(log_diag_precision_root_i) -- 3 N numbers instead of the
+    Cholesky family's N^2 / 2.  Under a Brownian prior and a likelihood that factorises over points the optimal Gaussian q has
+    precision K^-1 + diag(lambda), which is tridiagonal: the family contains it.  No positivity constraint, no sign ambiguity,
+    no pivot.  ``coupling`` is stored [.., N]; its last entry is unused and never read.  Initialised 0 / I like gpytorch."""
+
+    def __init__(self, num_inducing_points, batch_shape=torch.Size(), **kwargs):
+        super().__init__()
+        self.variational_mean = nn.Parameter(torch.zeros(*batch_shape, num_inducing_points))
+        self.log_diag_precision_root = nn.Parameter(torch.zeros(*batch_shape, num_inducing_points))
+        self.coupling = nn.Parameter(torch.zeros(*batch_shape, num_inducing_points))
+
+
+class MarkovVariationalLatent(MultivariateNormal):
+    """What ``SingleTaskVariationalGP(prior_solver="markov")(train_x)`` returns: q(u) of ``MarkovVariationalDistribution``,
+    tied to its model.  ``variance`` and ``rsample`` are O(N) recurrences on the device (csrc/gpcv_markov.hip); the dense
+    covariance is built only when ``_covar`` is asked for."""
+
+    def __init__(self, model):
+        dist = model.variational_strategy._variational_distribution
+        self.model = model
+        self.loc = dist.variational_mean
+        self._rho, self._gamma = dist.log_diag_precision_root, dist.coupling
+
+    def _flat(self):
+        n = self.loc.shape[-1]
+        return (t.detach().reshape(-1, n) for t in (self.loc, self._rho, self._gamma))
+
+    @property
+    def precision_root(self):
+        """Lp [.., N, N], dense (tests and small problems only)."""
+        d = self._rho.detach().double().exp()
+        Lp = torch.diag_embed(d)
+        if d.shape[-1] > 1:
+            Lp = Lp + torch.diag_embed(self._gamma.detach().double()[..., :-1] * d[..., :-1], offset=-1)
+        return Lp
+
+    @property
+    def _covar(self):
+        Lp = self.precision_root
+        return torch.linalg.inv(Lp @ Lp.mT).to(self.loc.dtype)
+
+    @property
+    def variance(self):
+        """diag P^-1, clamped at MIN_VARIANCE.  DETACHED: unlike ``VariationalLatent.variance`` it carries no gradient to
+        log_diag_precision_root / coupling (the recurrence runs in the HIP library) -- a direct caller of
+        ``likelihood.expected_log_prob(y, latent)`` differentiates through the mean only; the gradients of the variational
+        parameters come from ``VariationalELBO``, which is what the trainers use."""
+        _, rho, gamma = self._flat()
+        return ops.markov_root_var(rho, gamma).to(self.loc.dtype).reshape(self.loc.shape).clamp_min(MIN_VARIANCE)
+
+    def rsample(self, sample_shape=torch.Size(), base_samples=None):
+        """m + Lp^-T eps, eps ~ N(0, I) of shape sample_shape + loc.shape: one backward recurrence per draw."""
+        if base_samples is None:
+            base_samples = torch.randn(torch.Size(sample_shape) + self.loc.shape, dtype=self.loc.dtype,
+                                       device=self.loc.device)
+        m, rho, gamma = self._flat()
+        B, n = m.shape
+        eps = base_samples.reshape(-1, B, n).transpose(0, 1)                                   # [B,S,N]
+        f = ops.markov_root_draw(m, rho, gamma, eps)
+        return f.transpose(0, 1).reshape(base_samples.shape).to(self.loc.dtype)
 
 
 def _dkl_dscale_grad(o, c, n, w_kl, g):
@@ -237,6 +302,47 @@ class _GPCVBmElbo(torch.autograd.Function):
         return g1 * gm, g2 * gL, g1 * gmu, gscale, None, None, ga, gb, gc, None, None, None, None
 
 
+class _GPCVMarkovElbo(torch.autograd.Function):
+    """F[b] = w_ell ell_b - w_kl KL_b for the Markov family (m, rho, gamma) under the level-jitter Brownian prior
+    K_M = scale min(x, x') + j 1 1' (csrc/gpcv_markov.hip: one launch, O(N)).  The step returns dF/dscale itself
+    (out[:, 6]); scale = sigmoid(raw_vol) stays in the graph, so its chain rule is autograd's."""
+
+    @staticmethod
+    def forward(ctx, m, rho, gamma, mean, scale, x, y, raw_a, raw_b, raw_c, holder, num_gh, w_ell, w_kl):
+        B, n = m.shape
+        gh_x, gh_w = _gauss_hermite(num_gh, m.device)
+        cv = raw_a is not None
+        ws = holder.markov_workspace(B, n, m.device, raw_a.shape[-1] if cv else 0)
+        abc, jac = _cv_transform(raw_a, raw_b, raw_c, B) if cv else (None, None)
+        ops.gpcv_markov_step(x, scale.detach(), (m - mean).detach(), m.detach(), rho.detach(), gamma.detach(), y, gh_x, gh_w,
+                             ws, abc=abc, jitter=PRIOR_JITTER, min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
+        if deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
+            # info = 1: F is not finite.  There is no pivot in this family: a NaN input, or parameters whose variances overflow
+            _raise_step_failure("GPCV step (markov family)", ws.info,
+                                (scale, m, rho, gamma[..., :-1], mean, y) + ((abc,) if cv else ()), None,
+                                message="F is not finite although no input is NaN (info = "
+                                        f"{ws.info.tolist()[:8]}): the variances exp(-2 log_diag_precision_root) or the products "
+                                        "of coupling^2 overflow, or the prior's increments are not positive")
+        ctx.cv, ctx.scale_shape = cv, scale.shape
+        saved = [ws.grad_m.clone(), ws.grad_rho.clone(), ws.grad_gamma.clone(), ws.grad_mu.clone(), ws.out[:, 6].clone()]
+        if cv:
+            ctx.raw_shape = raw_a.shape
+            saved.append(ws.grad_abc * jac)
+        ctx.save_for_backward(*saved)
+        return ws.out[:, 9].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        sv = list(ctx.saved_tensors)
+        gm, grho, ggam, gmu, gv = sv[:5]
+        g1, g2 = g.reshape(-1, 1), g.reshape(-1, 1, 1)
+        gscale = g * gv
+        gscale = gscale.reshape(ctx.scale_shape) if gscale.numel() == math.prod(ctx.scale_shape) else \
+            gscale.sum().reshape(ctx.scale_shape)
+        ga, gb, gc = _cv_raw_grads(g2, sv[5], ctx.raw_shape) if ctx.cv else (None, None, None)
+        return g1 * gm, g1 * grho, g1 * ggam, g1 * gmu, gscale, None, None, ga, gb, gc, None, None, None, None
+
+
 class MultitaskVariationalLatent(MultivariateNormal):
     """What ``MultitaskVariationalGP(inducing_points)`` returns: q(F) = N(M, S_x (x) S_t) itself (event shape [N,T]), tied
     to its model so the ELBO can reach the prior."""
@@ -281,11 +387,12 @@ class MultitaskVariationalLatent(MultivariateNormal):
         return self.loc.detach() + Z.transpose(1, 2).reshape(base_samples.shape)
 
 
-def _raise_step_failure(what, info, tensors, which):
+def _raise_step_failure(what, info, tensors, which, message=None):
+    """``message``: what NotPSDError says where the step has no factorisation to blame (the Markov family)."""
     if ops.info_internal(info):
         raise ops._lib.VoltHipError(f"{what}: internal error, info = {info.tolist()[:8]}")
     check_nan(tensors, f"{what}: NaN in the prior covariance or the variational parameters")
-    raise NotPSDError(f"{what}: {which} is not positive definite")
+    raise NotPSDError(f"{what}: {message}" if message else f"{what}: {which} is not positive definite")
 
 
 def mt_dkl_dscale(out, scale, n, T, jitter=PRIOR_JITTER):
@@ -372,6 +479,10 @@ class VariationalELBO(Module):
         self._ws = None
         self._mt_ws = None
         self._bm_ws = None
+        self._markov_ws = None
+
+    def markov_workspace(self, B, n, device, Kc=0):
+        return ops.cached_workspace(self, "_markov_ws", ops.GpcvMarkovWorkspace, B, n, device, Kc)
 
     def bm_workspace(self, B, n, device, Kc=0):
         return ops.cached_workspace(self, "_bm_ws", ops.GpcvBmWorkspace, B, n, device, Kc)
@@ -417,9 +528,31 @@ class VariationalELBO(Module):
             raws = [r.reshape(B, Kc) for r in raws]
         return raws
 
+    def _forward_markov(self, latent, target):
+        """prior_solver="markov": the O(N) step over (m, rho, gamma); nothing N x N is formed."""
+        model = latent.model
+        m = latent.loc
+        if not m.is_cuda:
+            raise ops._lib.VoltHipError("VariationalELBO: tensors must live on the MI355X; no CPU fallback")
+        prior = model.forward(model.variational_strategy.inducing_points)
+        lazy = prior.lazy_covariance_matrix
+        if not isinstance(lazy, _BrownianLevelPrior):
+            raise TypeError("VariationalELBO: the Markov variational family needs the prior of prior_solver='markov'")
+        n = m.shape[-1]
+        f32 = lambda t: t.reshape(-1, n).to(torch.float32)
+        B = m.numel() // n
+        lik = self.likelihood
+        raws = self._cv_raws(lik, B, m) if getattr(lik, "param", "exp") == "cv" else [None, None, None]
+        res = _GPCVMarkovElbo.apply(f32(m), f32(latent._rho), f32(latent._gamma), f32(prior.mean.expand(m.shape)), lazy.scale,
+                                    lazy.x, f32(target), *raws, self, num_gauss_hermite_locs.value(), 1.0 / n,
+                                    self.beta / self.num_data)
+        return res.reshape(m.shape[:-1]) if m.ndim > 1 else res.reshape(())
+
     def forward(self, approximate_dist_f, target):
         if isinstance(approximate_dist_f, MultitaskVariationalLatent):
             return self._forward_multitask(approximate_dist_f, target)
+        if isinstance(approximate_dist_f, MarkovVariationalLatent):
+            return self._forward_markov(approximate_dist_f, target)
         if not isinstance(approximate_dist_f, VariationalLatent):
             raise TypeError("VariationalELBO expects the output of SingleTaskVariationalGP(train_x)")
         model = approximate_dist_f.model
