@@ -280,7 +280,12 @@ int volt_gemm_nt_f32(const float* A, int64_t lda, int64_t bsa, int uplo_a, const
  *     out[b,0..11] = ell, KL, r'K^-1 r, logdet K, logdet S, tr(K^-1 S), tr K^-1, |K^-1 Lq|_F^2, |K^-1 r|^2,
  *                    F, jitter, 0
  *     grad_m, grad_mu [B,N], grad_Lq [B,N,N]: gradients of F;  grad_K [B,N,N] (nullable) = dF/dK.
- * info[b] LAPACK-style for the factorisation of K + jitter I.  workspace: volt_gpcv_workspace_bytes. */
+ * info[b] LAPACK-style for the factorisation of K + jitter I.  A series whose factorisation fails (info[b] > 0) is a
+ * reported result, not an error return: its KL and F (out[b,1], out[b,9]) are not finite and grad_m[b,:], grad_mu[b,:] are
+ * NaN throughout (the MLL step's contract for out[b,0] and alpha, carried on); its grad_Lq[b] and grad_K[b] have no meaning;
+ * out[b,0] = ell and out[b,4] = logdet S, which do not involve K, are the series' own.  The other series of the batch are
+ * not touched by it, and the workspace needs nothing before its next step (tests/test_gpu_gpcv_dense_edges.py).
+ * workspace: volt_gpcv_workspace_bytes. */
 size_t volt_gpcv_workspace_bytes(int B, int N, int want_dk);
 int volt_gpcv_step_f32(const float* K, int64_t ldk, int64_t bsk, float jitter, const float* resid, const float* m,
                        const float* Lq, const float* y, const float* gh_x, const float* gh_w, int Q, float min_var,
