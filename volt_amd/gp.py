@@ -369,11 +369,15 @@ class MultivariateNormal:
     def variance(self):
         return torch.diagonal(self.covariance_matrix, dim1=-2, dim2=-1)
 
-    def rsample(self, sample_shape=torch.Size(), base_samples=None):
-        shape = torch.Size(sample_shape) + self.loc.shape
+    def _base_samples(self, sample_shape, base_samples):
+        """``base_samples`` as given, else N(0, I) draws of shape sample_shape + loc.shape."""
         if base_samples is None:
-            base_samples = torch.randn(shape, dtype=self.loc.dtype, device=self.loc.device)
-        if isinstance(self._covar, _MarkovCov):              # posterior="chain": O(S H), no H x H matrix (ops.markov_draw)
+            base_samples = torch.randn(torch.Size(sample_shape) + self.loc.shape, dtype=self.loc.dtype, device=self.loc.device)
+        return base_samples
+
+    def rsample(self, sample_shape=torch.Size(), base_samples=None):
+        base_samples = self._base_samples(sample_shape, base_samples)
+        if isinstance(self._covar, _MarkovCov):             # posterior="chain": O(S H), no H x H matrix (ops.markov_draw)
             H = self.loc.shape[-1]
             G = self.loc.numel() // H
             zb = base_samples.reshape(-1, G, H).transpose(0, 1).to(self.loc.dtype)         # [G,S,H] (a view when G = 1)

@@ -581,32 +581,89 @@ def gemm_nt(A: torch.Tensor, B: torch.Tensor, uplo_a: int = 0, uplo_b: int = 0) 
 GPCV_CV_K_MAX = 8                   # include/volt_hip.h: VOLT_GPCV_CV_K_MAX, volt_gpcv_cv_step_f32 takes 1 <= Kc <= 8 warp terms
 
 
-class GpcvWorkspace:
+def _f32(t, shape):
+    return t.detach().reshape(shape).to(torch.float32).contiguous()
+
+
+def _quad_args(gh_x, gh_w, min_var, min_scale, w_ell, w_kl):
+    """The Gauss-Hermite table as the steps read it and the argument run every GPCV entry takes after its prior.  Returns
+    (gh_x, gh_w, run): the caller holds the two tensors until its launch is queued."""
+    gh_x, gh_w = gh_x.to(torch.float32).contiguous(), gh_w.to(torch.float32).contiguous()
+    return gh_x, gh_w, (gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var), float(min_scale), float(w_ell),
+                        float(w_kl))
+
+
+def _abc_arg(abc, lead, letter, reject=None):
+    """The "cv" likelihood's abc checked as [lead,3,Kc] (``letter`` names ``lead`` in the message) and made fp32 contiguous.
+    Returns (abc, Kc, whether a workspace can be sized); no abc: (None, 0, True).
+    An out-of-range Kc is behaviour and differs by family.  ``reject`` None (the single-task steps): no workspace can be sized, so
+    the caller passes none and the C entry returns its argument code ("invalid argument ...", pinned by
+    tests/test_gpu_gpcv_cv.py).  ``reject`` a step's name (the multi-task step): VoltHipError from here."""
+    if abc is None:
+        return None, 0, True
+    if abc.ndim != 3 or abc.shape[0] != lead or abc.shape[1] != 3:
+        raise ValueError(f"abc must be [{letter},3,Kc]")
+    Kc = abc.shape[2]
+    ok = 1 <= Kc <= GPCV_CV_K_MAX
+    if not ok and reject is not None:
+        raise _lib.VoltHipError(f"{reject} takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms (got Kc = {Kc})")
+    return _f32(abc, (lead, 3, Kc)), Kc, ok
+
+
+def _step_workspace(cls, ws, sizeable, *key):
+    """``ws`` if it fits ``key``, else a new ``cls(*key)``; None where ``_abc_arg`` found nothing to size one for."""
+    if not sizeable:
+        return None
+    return ws if ws is not None and ws.fits(*key) else cls(*key)
+
+
+def _ptrs(ws, *names):
+    """The addresses of the workspace's ``names`` in that order; None for an output it does not have, or without a workspace."""
+    vals = (getattr(ws, name) if ws is not None else None for name in names)
+    return tuple(v.data_ptr() if torch.is_tensor(v) else v for v in vals)
+
+
+class _GpcvStepWorkspace:
+    """What the four GPCV workspaces share: the scratch, the MLL workspace some of them begin with, the fp32 outputs, ``info``
+    and ``fits``.  A subclass states its constructor key, its byte count and its outputs; the names it sets are its own."""
+    _STEP = 'the "cv" GPCV step'
+
+    def _checked_kc(self, Kc):
+        if Kc < 0 or Kc > GPCV_CV_K_MAX:
+            raise _lib.VoltHipError(f"{self._STEP} takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms (got Kc = {Kc})")
+        return int(Kc)
+
+    def _allocate(self, key, device, nbytes, outputs, n_info, mll_init=None):
+        """``key``: the constructor's arguments without the device (what ``fits`` compares); ``outputs``: name -> shape, None
+        for an output this workspace does not have; ``mll_init``: (B, N) of the MLL workspace the scratch begins with."""
+        self._key, self.nbytes = key, int(nbytes)
+        self.buf, self.ptr = _scratch(self.nbytes, device)
+        if mll_init is not None:                         # the launch-schedule table of that step
+            with torch.cuda.device(self.buf.device):
+                _lib.check(_lib.lib().volt_mll_workspace_init_f32(self.ptr, *mll_init, 1, _lib.stream_ptr()),
+                           "volt_mll_workspace_init")
+        for name, shape in outputs.items():
+            setattr(self, name, None if shape is None else torch.empty(shape, dtype=torch.float32, device=device))
+        self.info = torch.empty(n_info, dtype=torch.int32, device=device)
+
+    def _fits(self, device, *key):
+        return (self.buf.device, *self._key) == (device, *key)
+
+
+class GpcvWorkspace(_GpcvStepWorkspace):
     """Caller-owned scratch and outputs of volt_gpcv_step_f32, reusable across steps of the same (B,N).
     Kc > 0: the workspace of volt_gpcv_cv_step_f32 for Kc warp terms (adds .grad_abc [B,3,Kc])."""
 
     def __init__(self, B: int, N: int, want_dk: bool, device, Kc: int = 0):
-        self.B, self.N, self.want_dk, self.Kc = B, N, bool(want_dk), int(Kc)
-        if Kc:
-            if Kc < 1 or Kc > GPCV_CV_K_MAX:
-                raise _lib.VoltHipError(f'the "cv" GPCV step takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms (got Kc = {Kc})')
-            nbytes = _lib.lib().volt_gpcv_cv_workspace_bytes(B, N, int(want_dk), int(Kc))
-        else:
-            nbytes = _lib.lib().volt_gpcv_workspace_bytes(B, N, int(want_dk))
-        self.buf, self.ptr = _scratch(nbytes, device)
-        with torch.cuda.device(self.buf.device):        # it begins with an MLL workspace: the schedule table of that step
-            _lib.check(_lib.lib().volt_mll_workspace_init_f32(self.ptr, B, N, 1, _lib.stream_ptr()), "volt_mll_workspace_init")
-        f32 = dict(dtype=torch.float32, device=device)
-        self.out = torch.empty(B, 12, **f32)
-        self.grad_m = torch.empty(B, N, **f32)
-        self.grad_mu = torch.empty(B, N, **f32)
-        self.grad_Lq = torch.empty(B, N, N, **f32)
-        self.grad_K = torch.empty(B, N, N, **f32) if want_dk else None
-        self.grad_abc = torch.empty(B, 3, Kc, **f32) if Kc else None
-        self.info = torch.empty(B, dtype=torch.int32, device=device)
+        self.B, self.N, self.want_dk, self.Kc = B, N, bool(want_dk), self._checked_kc(Kc)
+        L = _lib.lib()
+        nbytes = L.volt_gpcv_cv_workspace_bytes(B, N, int(want_dk), self.Kc) if Kc else L.volt_gpcv_workspace_bytes(B, N, int(want_dk))
+        self._allocate((B, N, self.want_dk, self.Kc), device, nbytes, mll_init=(B, N), n_info=B, outputs={
+            "out": (B, 12), "grad_m": (B, N), "grad_mu": (B, N), "grad_Lq": (B, N, N),
+            "grad_K": (B, N, N) if want_dk else None, "grad_abc": (B, 3, Kc) if Kc else None})
 
     def fits(self, B, N, want_dk, device, Kc=0):
-        return (self.B, self.N, self.want_dk, self.buf.device, self.Kc) == (B, N, bool(want_dk), device, Kc)
+        return self._fits(device, B, N, bool(want_dk), Kc)
 
 
 def gpcv_step(K, resid, m, Lq, y, gh_x, gh_w, ws: GpcvWorkspace | None = None, want_dk: bool = False,
@@ -635,55 +692,34 @@ def _gpcv_dense_step(K, resid, m, Lq, y, abc, gh_x, gh_w, ws, want_dk, jitter, m
     if K.ndim != 3 or K.dtype != torch.float32:
         raise ValueError("K must be [B,N,N] fp32")
     B, n, _ = K.shape
-    Kc = 0
-    if abc is not None:
-        if abc.ndim != 3 or abc.shape[0] != B or abc.shape[1] != 3:
-            raise ValueError("abc must be [B,3,Kc]")
-        Kc = abc.shape[2]
+    abc, Kc, sizeable = _abc_arg(abc, B, "B")
     if K.stride(-1) != 1:
         K = K.contiguous()
-    c = lambda t, shape: t.reshape(shape).to(torch.float32).contiguous()
-    resid, m, y, Lq = c(resid, (B, n)), c(m, (B, n)), c(y, (B, n)), c(Lq, (B, n, n))
-    if abc is not None:
-        abc = c(abc, (B, 3, Kc))
-    gh_x, gh_w = gh_x.to(torch.float32).contiguous(), gh_w.to(torch.float32).contiguous()
-    if abc is not None and not 1 <= Kc <= GPCV_CV_K_MAX:      # no workspace can be sized: let the entry name the argument
-        ws = None
-    elif ws is None or not ws.fits(B, n, want_dk, K.device, Kc):
-        ws = GpcvWorkspace(B, n, want_dk, K.device, Kc)
-    o = lambda name: getattr(ws, name).data_ptr() if ws is not None and getattr(ws, name) is not None else None
+    resid, m, y, Lq = _f32(resid, (B, n)), _f32(m, (B, n)), _f32(y, (B, n)), _f32(Lq, (B, n, n))
+    gh_x, gh_w, quad = _quad_args(gh_x, gh_w, min_var, min_scale, w_ell, w_kl)
+    ws = _step_workspace(GpcvWorkspace, ws, sizeable, B, n, want_dk, K.device, Kc)
     prior = (K.data_ptr(), K.stride(1), K.stride(0), float(jitter), resid.data_ptr(), m.data_ptr(), Lq.data_ptr(), y.data_ptr())
-    quad = (gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var), float(min_scale), float(w_ell), float(w_kl))
-    grads = (o("out"), o("grad_m"), o("grad_mu"), o("grad_Lq"), o("grad_K"))
-    tail = (o("info"), ws.ptr if ws is not None else None, B, n, _lib.WS_INITIALISED if ws is not None else 0, _lib.stream_ptr())
+    grads = _ptrs(ws, "out", "grad_m", "grad_mu", "grad_Lq", "grad_K")
+    tail = (*_ptrs(ws, "info", "ptr"), B, n, _lib.WS_INITIALISED if ws is not None else 0, _lib.stream_ptr())
     if abc is None:
         _lib.check(_lib.lib().volt_gpcv_step_f32(*prior, *quad, *grads, *tail), "volt_gpcv_step")
     else:
-        _lib.check(_lib.lib().volt_gpcv_cv_step_f32(*prior, abc.data_ptr(), Kc, *quad, *grads, o("grad_abc"), *tail),
+        _lib.check(_lib.lib().volt_gpcv_cv_step_f32(*prior, abc.data_ptr(), Kc, *quad, *grads, *_ptrs(ws, "grad_abc"), *tail),
                    "volt_gpcv_cv_step")
     return ws
 
 
-class GpcvBmWorkspace:
+class GpcvBmWorkspace(_GpcvStepWorkspace):
     """Caller-owned scratch and outputs of volt_gpcv_bm_step_f32, reusable across steps of the same (B, N, Kc): one packed
     fp64 triangle per series plus O(B N); no initialisation call.  Kc > 0 adds .grad_abc [B,3,Kc] (the "cv" likelihood)."""
 
     def __init__(self, B: int, N: int, device, Kc: int = 0):
-        self.B, self.N, self.Kc = B, N, int(Kc)
-        if Kc < 0 or Kc > GPCV_CV_K_MAX:
-            raise _lib.VoltHipError(f'the "cv" GPCV step takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms (got Kc = {Kc})')
-        nbytes = int(_lib.lib().volt_gpcv_bm_workspace_bytes(B, N, int(Kc)))
-        self.buf, self.ptr = _scratch(nbytes, device)
-        f32 = dict(dtype=torch.float32, device=device)
-        self.out = torch.empty(B, 12, **f32)
-        self.grad_m = torch.empty(B, N, **f32)
-        self.grad_mu = torch.empty(B, N, **f32)
-        self.grad_Lq = torch.empty(B, N, N, **f32)
-        self.grad_abc = torch.empty(B, 3, Kc, **f32) if Kc else None
-        self.info = torch.empty(B, dtype=torch.int32, device=device)
+        self.B, self.N, self.Kc = B, N, self._checked_kc(Kc)
+        self._allocate((B, N, self.Kc), device, _lib.lib().volt_gpcv_bm_workspace_bytes(B, N, self.Kc), n_info=B, outputs={
+            "out": (B, 12), "grad_m": (B, N), "grad_mu": (B, N), "grad_Lq": (B, N, N), "grad_abc": (B, 3, Kc) if Kc else None})
 
     def fits(self, B, N, device, Kc=0):
-        return (self.B, self.N, self.buf.device, self.Kc) == (B, N, device, Kc)
+        return self._fits(device, B, N, Kc)
 
 
 def gpcv_bm_step(x, vol, resid, m, Lq, y, gh_x, gh_w, ws: GpcvBmWorkspace | None = None, abc=None, jitter: float = 1e-3,
@@ -699,54 +735,34 @@ def gpcv_bm_step(x, vol, resid, m, Lq, y, gh_x, gh_w, ws: GpcvBmWorkspace | None
     if x.shape[-1] != n:
         raise ValueError("x and Lq disagree on N")
     x, vol, _ = _bm_args(x, vol, vol, B, torch.float32)
-    c = lambda t, shape: t.reshape(shape).to(torch.float32).contiguous()
-    resid, m, y, Lq = c(resid, (B, n)), c(m, (B, n)), c(y, (B, n)), c(Lq, (B, n, n))
-    gh_x, gh_w = gh_x.to(torch.float32).contiguous(), gh_w.to(torch.float32).contiguous()
-    Kc = 0
-    if abc is not None:
-        if abc.ndim != 3 or abc.shape[0] != B or abc.shape[1] != 3:
-            raise ValueError("abc must be [B,3,Kc]")
-        Kc = abc.shape[2]
-        abc = c(abc, (B, 3, Kc))
-    if abc is not None and not 1 <= Kc <= GPCV_CV_K_MAX:      # no workspace can be sized: let the entry name the argument
-        ws = None
-    elif ws is None or not ws.fits(B, n, Lq.device, Kc):
-        ws = GpcvBmWorkspace(B, n, Lq.device, Kc)
-    o = lambda name: getattr(ws, name).data_ptr() if ws is not None and getattr(ws, name) is not None else None
+    resid, m, y, Lq = _f32(resid, (B, n)), _f32(m, (B, n)), _f32(y, (B, n)), _f32(Lq, (B, n, n))
+    gh_x, gh_w, quad = _quad_args(gh_x, gh_w, min_var, min_scale, w_ell, w_kl)
+    abc, Kc, sizeable = _abc_arg(abc, B, "B")
+    ws = _step_workspace(GpcvBmWorkspace, ws, sizeable, B, n, Lq.device, Kc)
     with torch.cuda.device(Lq.device):
         _lib.check(_lib.lib().volt_gpcv_bm_step_f32(
             x.data_ptr(), vol.data_ptr(), float(jitter), resid.data_ptr(), m.data_ptr(), Lq.data_ptr(), y.data_ptr(),
-            abc.data_ptr() if abc is not None else None, Kc, gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var),
-            float(min_scale), float(w_ell), float(w_kl), o("out"), o("grad_m"), o("grad_mu"), o("grad_Lq"), o("grad_abc"),
-            o("info"), ws.ptr if ws is not None else None, B, n,
-            _lib.stream_ptr()), "volt_gpcv_bm_step")
+            abc.data_ptr() if abc is not None else None, Kc, *quad,
+            *_ptrs(ws, "out", "grad_m", "grad_mu", "grad_Lq", "grad_abc", "info", "ptr"), B, n, _lib.stream_ptr()),
+            "volt_gpcv_bm_step")
     return ws
 
 
-class GpcvMarkovWorkspace:
+class GpcvMarkovWorkspace(_GpcvStepWorkspace):
     """Caller-owned scratch and outputs of volt_gpcv_markov_step_f32, reusable across steps of the same (B, N, Kc): O(B N)
     bytes, no initialisation call.  After a step ``.s`` [B,N] (fp64, a view of the scratch) holds diag S = diag P^-1.
     Kc > 0 adds .grad_abc [B,3,Kc] (the "cv" likelihood)."""
 
     def __init__(self, B: int, N: int, device, Kc: int = 0):
-        self.B, self.N, self.Kc = B, N, int(Kc)
-        if Kc < 0 or Kc > GPCV_CV_K_MAX:
-            raise _lib.VoltHipError(f'the "cv" GPCV step takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms (got Kc = {Kc})')
-        self.nbytes = int(_lib.lib().volt_gpcv_markov_workspace_bytes(B, N, int(Kc)))
-        self.buf, self.ptr = _scratch(self.nbytes, device)
+        self.B, self.N, self.Kc = B, N, self._checked_kc(Kc)
+        self._allocate((B, N, self.Kc), device, _lib.lib().volt_gpcv_markov_workspace_bytes(B, N, self.Kc), n_info=B, outputs={
+            "out": (B, 12), "grad_m": (B, N), "grad_mu": (B, N), "grad_rho": (B, N), "grad_gamma": (B, N),
+            "grad_abc": (B, 3, Kc) if Kc else None})
         off = self.ptr - self.buf.data_ptr()
         self.s = self.buf[off:off + 8 * B * N].view(torch.float64).view(B, N)
-        f32 = dict(dtype=torch.float32, device=device)
-        self.out = torch.empty(B, 12, **f32)
-        self.grad_m = torch.empty(B, N, **f32)
-        self.grad_mu = torch.empty(B, N, **f32)
-        self.grad_rho = torch.empty(B, N, **f32)
-        self.grad_gamma = torch.empty(B, N, **f32)
-        self.grad_abc = torch.empty(B, 3, Kc, **f32) if Kc else None
-        self.info = torch.empty(B, dtype=torch.int32, device=device)
 
     def fits(self, B, N, device, Kc=0):
-        return (self.B, self.N, self.buf.device, self.Kc) == (B, N, device, Kc)
+        return self._fits(device, B, N, Kc)
 
 
 def gpcv_markov_step(x, vol, resid, m, rho, gamma, y, gh_x, gh_w, ws: GpcvMarkovWorkspace | None = None, abc=None,
@@ -765,27 +781,16 @@ def gpcv_markov_step(x, vol, resid, m, rho, gamma, y, gh_x, gh_w, ws: GpcvMarkov
     if x.shape[-1] != n:
         raise ValueError("x and m disagree on N")
     x, vol, _ = _bm_args(x, vol, vol, B, torch.float32)
-    c = lambda t, shape: t.reshape(shape).to(torch.float32).contiguous()
-    resid, m, y, rho, gamma = (c(t, (B, n)) for t in (resid, m, y, rho, gamma))
-    gh_x, gh_w = gh_x.to(torch.float32).contiguous(), gh_w.to(torch.float32).contiguous()
-    Kc = 0
-    if abc is not None:
-        if abc.ndim != 3 or abc.shape[0] != B or abc.shape[1] != 3:
-            raise ValueError("abc must be [B,3,Kc]")
-        Kc = abc.shape[2]
-        abc = c(abc, (B, 3, Kc))
-    if abc is not None and not 1 <= Kc <= GPCV_CV_K_MAX:      # no workspace can be sized: let the entry name the argument
-        ws = None
-    elif ws is None or not ws.fits(B, n, m.device, Kc):
-        ws = GpcvMarkovWorkspace(B, n, m.device, Kc)
-    o = lambda name: getattr(ws, name).data_ptr() if ws is not None and getattr(ws, name) is not None else None
+    resid, m, y, rho, gamma = (_f32(t, (B, n)) for t in (resid, m, y, rho, gamma))
+    gh_x, gh_w, quad = _quad_args(gh_x, gh_w, min_var, min_scale, w_ell, w_kl)
+    abc, Kc, sizeable = _abc_arg(abc, B, "B")
+    ws = _step_workspace(GpcvMarkovWorkspace, ws, sizeable, B, n, m.device, Kc)
     with torch.cuda.device(m.device):
         _lib.check(_lib.lib().volt_gpcv_markov_step_f32(
             x.data_ptr(), vol.data_ptr(), float(jitter), resid.data_ptr(), m.data_ptr(), rho.data_ptr(), gamma.data_ptr(),
-            y.data_ptr(), abc.data_ptr() if abc is not None else None, Kc, gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(),
-            float(min_var), float(min_scale), float(w_ell), float(w_kl), o("out"), o("grad_m"), o("grad_mu"), o("grad_rho"),
-            o("grad_gamma"), o("grad_abc"), o("info"), ws.ptr if ws is not None else None, B, n, _lib.stream_ptr()),
-            "volt_gpcv_markov_step")
+            y.data_ptr(), abc.data_ptr() if abc is not None else None, Kc, *quad,
+            *_ptrs(ws, "out", "grad_m", "grad_mu", "grad_rho", "grad_gamma", "grad_abc", "info", "ptr"), B, n,
+            _lib.stream_ptr()), "volt_gpcv_markov_step")
     return ws
 
 
@@ -827,39 +832,25 @@ def markov_root_var(rho: torch.Tensor, gamma: torch.Tensor) -> torch.Tensor:
 GPCV_MT_T_MAX = 64                 # include/volt_hip.h: volt_gpcv_mt_step_f32 takes 1 <= T <= 64 series
 
 
-class GpcvMtWorkspace:
+class GpcvMtWorkspace(_GpcvStepWorkspace):
     """Caller-owned scratch and outputs of volt_gpcv_mt_step_f32, reusable across steps of the same (N, T).
     Kc > 0: the workspace of volt_gpcv_mt_cv_step_f32 for Kc warp terms per task (adds .grad_abc [T,3,Kc]).
     info[0]: the factorisation of K + jitter I; info[1]: a non-positive pivot of K_t; info[2]: F is not finite."""
+    _STEP = 'the "cv" multi-task GPCV step'
 
     def __init__(self, N: int, T: int, want_dk: bool, device, Kc: int = 0):
         if T < 1 or T > GPCV_MT_T_MAX:
             raise ValueError(f"the multi-task GPCV step takes 1 <= T <= {GPCV_MT_T_MAX} series (got T = {T})")
-        self.N, self.T, self.want_dk, self.Kc = N, T, bool(want_dk), int(Kc)
-        if Kc:
-            if Kc < 1 or Kc > GPCV_CV_K_MAX:
-                raise _lib.VoltHipError(f'the "cv" multi-task GPCV step takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms '
-                                        f"(got Kc = {Kc})")
-            nbytes = _lib.lib().volt_gpcv_mt_cv_workspace_bytes(N, T, int(want_dk), int(Kc))
-        else:
-            nbytes = _lib.lib().volt_gpcv_mt_workspace_bytes(N, T, int(want_dk))
-        self.buf, self.ptr = _scratch(nbytes, device)
-        with torch.cuda.device(self.buf.device):        # it begins with an MLL workspace for ONE series
-            _lib.check(_lib.lib().volt_mll_workspace_init_f32(self.ptr, 1, N, 1, _lib.stream_ptr()), "volt_mll_workspace_init")
-        f32 = dict(dtype=torch.float32, device=device)
-        self.out = torch.empty(16, **f32)
-        self.grad_M = torch.empty(N, T, **f32)
-        self.grad_c = torch.empty(T, **f32)
-        self.grad_Lx = torch.empty(N, N, **f32)
-        self.grad_Lt = torch.empty(T, T, **f32)
-        self.grad_covar_factor = torch.empty(T, **f32)
-        self.grad_raw_var = torch.empty(T, **f32)
-        self.grad_K = torch.empty(N, N, **f32) if want_dk else None
-        self.grad_abc = torch.empty(T, 3, Kc, **f32) if Kc else None
-        self.info = torch.empty(3, dtype=torch.int32, device=device)
+        self.N, self.T, self.want_dk, self.Kc = N, T, bool(want_dk), self._checked_kc(Kc)
+        L = _lib.lib()
+        nbytes = L.volt_gpcv_mt_cv_workspace_bytes(N, T, int(want_dk), self.Kc) if Kc else L.volt_gpcv_mt_workspace_bytes(N, T, int(want_dk))
+        # (the MLL workspace it begins with is for ONE series)
+        self._allocate((N, T, self.want_dk, self.Kc), device, nbytes, mll_init=(1, N), n_info=3, outputs={
+            "out": (16,), "grad_M": (N, T), "grad_c": (T,), "grad_Lx": (N, N), "grad_Lt": (T, T), "grad_covar_factor": (T,),
+            "grad_raw_var": (T,), "grad_K": (N, N) if want_dk else None, "grad_abc": (T, 3, Kc) if Kc else None})
 
     def fits(self, N, T, want_dk, device, Kc=0):
-        return (self.N, self.T, self.want_dk, self.buf.device, self.Kc) == (N, T, bool(want_dk), device, Kc)
+        return self._fits(device, N, T, bool(want_dk), Kc)
 
 
 def gpcv_mt_step(K, M, c, Lx, Lt, covar_factor, raw_var, y, gh_x, gh_w, ws: GpcvMtWorkspace | None = None,
@@ -879,31 +870,19 @@ def gpcv_mt_step(K, M, c, Lx, Lt, covar_factor, raw_var, y, gh_x, gh_w, ws: Gpcv
     T = M.shape[-1]
     if K.stride(-1) != 1:
         K = K.contiguous()
-    f = lambda t, shape: t.detach().reshape(shape).to(torch.float32).contiguous()
-    M, y, Lx, Lt = f(M, (n, T)), f(y, (n, T)), f(Lx, (n, n)), f(Lt, (T, T))
-    c, cf, rv = f(c, (T,)), f(covar_factor, (T,)), f(raw_var, (T,))
-    gh_x, gh_w = gh_x.to(torch.float32).contiguous(), gh_w.to(torch.float32).contiguous()
-    Kc = 0
-    if abc is not None:
-        if abc.ndim != 3 or abc.shape[0] != T or abc.shape[1] != 3:
-            raise ValueError("abc must be [T,3,Kc]")
-        Kc = abc.shape[2]
-        if not 1 <= Kc <= GPCV_CV_K_MAX:
-            raise _lib.VoltHipError(f'the "cv" multi-task GPCV step takes 1 <= Kc <= {GPCV_CV_K_MAX} warp terms '
-                                    f"(got Kc = {Kc})")
-        abc = f(abc, (T, 3, Kc))
-    if ws is None or not ws.fits(n, T, want_dk, K.device, Kc):
-        ws = GpcvMtWorkspace(n, T, want_dk, K.device, Kc)
+    M, y, Lx, Lt = _f32(M, (n, T)), _f32(y, (n, T)), _f32(Lx, (n, n)), _f32(Lt, (T, T))
+    c, cf, rv = _f32(c, (T,)), _f32(covar_factor, (T,)), _f32(raw_var, (T,))
+    gh_x, gh_w, quad = _quad_args(gh_x, gh_w, min_var, min_scale, w_ell, w_kl)
+    abc, Kc, sizeable = _abc_arg(abc, T, "T", reject=GpcvMtWorkspace._STEP)
+    ws = _step_workspace(GpcvMtWorkspace, ws, sizeable, n, T, want_dk, K.device, Kc)
     prior = (K.data_ptr(), K.stride(0), float(jitter), M.data_ptr(), c.data_ptr(), Lx.data_ptr(), Lt.data_ptr(), cf.data_ptr(),
              rv.data_ptr(), y.data_ptr())
-    quad = (gh_x.data_ptr(), gh_w.data_ptr(), gh_x.numel(), float(min_var), float(min_scale), float(w_ell), float(w_kl))
-    grads = (ws.out.data_ptr(), ws.grad_M.data_ptr(), ws.grad_c.data_ptr(), ws.grad_Lx.data_ptr(), ws.grad_Lt.data_ptr(),
-             ws.grad_covar_factor.data_ptr(), ws.grad_raw_var.data_ptr(), ws.grad_K.data_ptr() if want_dk else None)
-    tail = (ws.info.data_ptr(), ws.ptr, n, T, _lib.WS_INITIALISED, _lib.stream_ptr())
+    grads = _ptrs(ws, "out", "grad_M", "grad_c", "grad_Lx", "grad_Lt", "grad_covar_factor", "grad_raw_var", "grad_K")
+    tail = (*_ptrs(ws, "info", "ptr"), n, T, _lib.WS_INITIALISED, _lib.stream_ptr())
     if abc is None:
         _lib.check(_lib.lib().volt_gpcv_mt_step_f32(*prior, *quad, *grads, *tail), "volt_gpcv_mt_step")
     else:
-        _lib.check(_lib.lib().volt_gpcv_mt_cv_step_f32(*prior, abc.data_ptr(), Kc, *quad, *grads, ws.grad_abc.data_ptr(), *tail),
+        _lib.check(_lib.lib().volt_gpcv_mt_cv_step_f32(*prior, abc.data_ptr(), Kc, *quad, *grads, *_ptrs(ws, "grad_abc"), *tail),
                    "volt_gpcv_mt_cv_step")
     return ws
 

@@ -281,7 +281,6 @@ def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", gra
     from .kernels import BMKernel, FBMKernel
     from .likelihoods import VolatilityGaussianLikelihood
     from .models import SingleTaskVariationalGP
-    from .variational import VariationalELBO, num_gauss_hermite_locs
     dt = train_x[1] - train_x[0]
     yy = (train_y[..., 1:] - train_y[..., :-1]) / train_y[..., :-1] / dt ** 0.5        # scaled returns, :16-18
     kw = {"batch_shape": yy.shape[:-1]} if yy.ndim > 1 else {}
@@ -294,13 +293,24 @@ def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", gra
                                     mean_module=gp.ConstantMean(**kw), covar_module=covar_module,
                                     learn_inducing_locations=False, use_whitened_var_strat=False, prior_solver=solver)
     model.initialize_variational_parameters(likelihood, train_x, y=yy)
+    # the model registers its likelihood: model.parameters() holds its raw_a, raw_b, raw_c, and Adam steps the ones that
+    # receive a gradient
+    return _fit_gpcv(model, likelihood, model.parameters(), train_x, yy, yy.shape[-1], train_iters, printing, graph,
+                     train_likelihood)
+
+
+def _fit_gpcv(model, likelihood, params, train_x, yy, num_data, train_iters, printing, graph, train_likelihood):
+    """The fit FitGPCV and FitGPCVMultitask share once the model, the likelihood and the scaled returns ``yy`` exist: Adam at
+    LR_GPCV on ``params`` over -ELBO under 75 Gauss-Hermite nodes; the likelihood's parameters receive a gradient only with
+    ``train_likelihood``.  Returns (model, likelihood, losses)."""
+    from .variational import VariationalELBO, num_gauss_hermite_locs
     model.train()
     likelihood.train()
-    graph = bool(graph)                                  # (this entry returns the per-iteration losses: captured only on request)
-    for p in likelihood.parameters():                    # the model registers its likelihood: model.parameters() holds these,
-        p.requires_grad_(bool(train_likelihood))         # and Adam steps the ones that receive a gradient
-    optimizer = _adam([{"params": model.parameters()}], LR_GPCV, graph)
-    elbo = VariationalELBO(likelihood, model, yy.shape[-1], combine_terms=True)
+    graph = bool(graph)                                  # (these entries return the per-iteration losses: captured only on request)
+    for p in likelihood.parameters():
+        p.requires_grad_(bool(train_likelihood))
+    optimizer = _adam([{"params": params}], LR_GPCV, graph)
+    elbo = VariationalELBO(likelihood, model, num_data, combine_terms=True)
     losses = []
 
     def iteration():                                     # :50-54
@@ -348,7 +358,6 @@ def FitGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel=
     from .kernels import BMKernel, FBMKernel
     from .likelihoods import VolatilityGaussianLikelihood
     from .models import MultitaskVariationalGP
-    from .variational import VariationalELBO, num_gauss_hermite_locs
     if train_y.ndim != 2:
         raise ValueError("FitGPCVMultitask: train_y must be [T,N+1] (one row of prices per series)")
     dt = train_x[1] - train_x[0]
@@ -360,33 +369,10 @@ def FitGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel=
     covar_module = {"bm": BMKernel, "fbm": FBMKernel}[kernel]()
     model = MultitaskVariationalGP(train_x, num_tasks=yy.shape[-1], covar_module=covar_module)
     model.initialize_variational_parameters(likelihood, train_x, y=yy)
-    model.train()
-    likelihood.train()
-    graph = bool(graph)                                  # (this entry returns the per-iteration losses: captured only on request)
-    params = model.parameters()
-    if param != "exp":                                   # (this model does not register its likelihood)
-        for p in likelihood.parameters():
-            p.requires_grad_(bool(train_likelihood))
-        if train_likelihood:
-            params = list(params) + list(likelihood.parameters())
-    optimizer = _adam([{"params": params}], LR_GPCV, graph)
-    elbo = VariationalELBO(likelihood, model, yy.numel(), combine_terms=True)
-    losses = []
-
-    def iteration():                                     # :50-54
-        with num_gauss_hermite_locs(75):
-            loss = -elbo(model(train_x), yy)
-            if not graph:
-                losses.append(loss.detach())
-            loss.backward()
-        return loss
-
-    last = _run_iterations(iteration, optimizer, train_iters, printing, graph)
-    if graph and last is not None:
-        losses.append(last.detach())
-    model.eval()
-    likelihood.eval()
-    return model, likelihood, losses
+    params = list(model.parameters())
+    if train_likelihood:                                 # (this model does not register its likelihood)
+        params += list(likelihood.parameters())
+    return _fit_gpcv(model, likelihood, params, train_x, yy, yy.numel(), train_iters, printing, graph, train_likelihood)
 
 
 def LearnGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None, *, param="exp", K=1,

@@ -21,6 +21,8 @@ K^-1 Lq, all gradients -- runs in libvolt_hip.so through one ``torch.autograd.Fu
 """
 from __future__ import annotations
 
+import functools
+import inspect
 import math
 
 import numpy as np
@@ -115,9 +117,7 @@ class VariationalLatent(MultivariateNormal):
 
     def rsample(self, sample_shape=torch.Size(), base_samples=None):
         """m + L eps, eps ~ N(0, I) of shape sample_shape + [N] (one series) -- CholLazyTensor's root is L itself."""
-        if base_samples is None:
-            base_samples = torch.randn(torch.Size(sample_shape) + self.loc.shape, dtype=self.loc.dtype,
-                                       device=self.loc.device)
+        base_samples = self._base_samples(sample_shape, base_samples)
         eps = base_samples.reshape(-1, self.loc.shape[-1]) if self.loc.ndim == 1 else base_samples
         if self.loc.ndim == 1:
             f = ops.gemm_nt(eps, self.chol.detach(), uplo_b=1)       # [S,N] = eps L'
@@ -181,9 +181,7 @@ class MarkovVariationalLatent(MultivariateNormal):
 
     def rsample(self, sample_shape=torch.Size(), base_samples=None):
         """m + Lp^-T eps, eps ~ N(0, I) of shape sample_shape + loc.shape: one backward recurrence per draw."""
-        if base_samples is None:
-            base_samples = torch.randn(torch.Size(sample_shape) + self.loc.shape, dtype=self.loc.dtype,
-                                       device=self.loc.device)
+        base_samples = self._base_samples(sample_shape, base_samples)
         m, rho, gamma = self._flat()
         B, n = m.shape
         eps = base_samples.reshape(-1, B, n).transpose(0, 1)                                   # [B,S,N]
@@ -219,6 +217,47 @@ def _cv_raw_grads(g2, graw, raw_shape):
     return tuple(graw[i].reshape(raw_shape) for i in range(3))
 
 
+@functools.lru_cache(maxsize=None)
+def _inputs(function):
+    """The names of ``function.forward``'s inputs, in order: ``backward`` returns one gradient (or None) for each."""
+    return tuple(inspect.signature(function.forward).parameters)[1:]
+
+
+def _elbo_forward(ctx, ws, device, num_gh, raws, lead, step, failed, grad_fields, keep, value):
+    """The forward all four ELBO functions share, around one ops step into the workspace ``ws``.
+    ``raws``: (raw_a, raw_b, raw_c) of the "cv" likelihood, or three None ("exp"); ``lead``: B or T of the step's abc.
+    ``step(gh_x, gh_w, abc)`` runs the family's step; ``failed(abc)`` raises for a nonzero ``ws.info``.
+    ``grad_fields``: input name -> the workspace field that is dF/d(that input); a field the workspace lacks is skipped.
+    ``keep``: name -> a further tensor ``backward`` needs; ``value``: the view of ``ws.out`` that holds F (views of the
+    workspace are cloned AFTER the step; the next step overwrites it).  What ``backward`` reads is saved under its name: the
+    gradients under their inputs', ``keep`` under its own, dF/d(a,b,c) * Jacobian under "graw"."""
+    gh_x, gh_w = _gauss_hermite(num_gh, device)
+    cv = raws[0] is not None
+    abc, jac = _cv_transform(*raws, lead) if cv else (None, None)
+    step(gh_x, gh_w, abc)
+    if deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
+        failed(abc)
+    saved = {name: getattr(ws, field).clone() for name, field in grad_fields.items() if getattr(ws, field) is not None}
+    ctx.grad_names = tuple(saved)
+    saved.update((name, t.clone()) for name, t in keep.items())
+    if cv:
+        ctx.raw_shape = raws[0].shape
+        saved["graw"] = ws.grad_abc * jac
+    ctx.saved_names = tuple(saved)
+    ctx.save_for_backward(*saved.values())
+    return value.clone()
+
+
+def _elbo_backward(ctx, g):
+    """The backward all four share.  Returns ({input name: g * its saved gradient, g broadcast over the leading (series)
+    dimension; raw_a, raw_b, raw_c with the "cv" likelihood}, {name: saved tensor}): the caller adds its scale rule."""
+    sv = dict(zip(ctx.saved_names, ctx.saved_tensors))
+    grads = {name: g.reshape((-1,) + (1,) * (sv[name].ndim - 1)) * sv[name] for name in ctx.grad_names}
+    if "graw" in sv:
+        grads["raw_a"], grads["raw_b"], grads["raw_c"] = _cv_raw_grads(g.reshape(-1, 1, 1), sv["graw"], ctx.raw_shape)
+    return grads, sv
+
+
 class _GPCVElbo(torch.autograd.Function):
     """F[b] = w_ell ell_b - w_kl KL_b over a dense prior K, with the analytic gradient the HIP step returns.  raw_a, raw_b,
     raw_c None: the "exp" likelihood (ops.gpcv_step); given ([Kc] or [B,Kc]): the copula-process ("cv") likelihood,
@@ -228,42 +267,29 @@ class _GPCVElbo(torch.autograd.Function):
     @staticmethod
     def forward(ctx, m, Lq, mean, K, y, raw_a, raw_b, raw_c, holder, scale, num_gh, w_ell, w_kl):
         B, n = m.shape
-        want_dk = bool(ctx.needs_input_grad[3])
-        gh_x, gh_w = _gauss_hermite(num_gh, m.device)
+        want_dk = bool(ctx.needs_input_grad[_inputs(_GPCVElbo).index("K")])
         cv = raw_a is not None
-        ws = holder.workspace(B, n, want_dk, m.device, Kc=raw_a.shape[-1] if cv else 0)
-        step_args = dict(ws=ws, want_dk=want_dk, jitter=PRIOR_JITTER, min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
-        if cv:
-            abc, jac = _cv_transform(raw_a, raw_b, raw_c, B)
-            ops.gpcv_cv_step(K.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y, abc, gh_x, gh_w, **step_args)
-        else:
-            ops.gpcv_step(K.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y, gh_x, gh_w, **step_args)
-        if deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
+        ws = holder.workspace(ops.GpcvWorkspace, B, n, want_dk, m.device, raw_a.shape[-1] if cv else 0)
+
+        def step(gh_x, gh_w, abc):
+            fn, lik = (ops.gpcv_cv_step, (abc,)) if cv else (ops.gpcv_step, ())
+            fn(K.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y, *lik, gh_x, gh_w, ws=ws, want_dk=want_dk,
+               jitter=PRIOR_JITTER, min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
+
+        def failed(abc):
             _raise_step_failure("GPCV cv step" if cv else "GPCV step", ws.info, (K, m, Lq) + ((abc,) if cv else ()),
                                 "prior covariance K + 1e-3 I")
-        ctx.n, ctx.w_kl, ctx.has_scale, ctx.want_dk, ctx.cv = n, w_kl, scale is not None, want_dk, cv
-        saved = [ws.grad_m.clone(), ws.grad_Lq.clone(), ws.grad_mu.clone()]
-        if cv:
-            ctx.raw_shape = raw_a.shape
-            saved.append(ws.grad_abc * jac)
-        if want_dk:
-            saved.append(ws.grad_K.clone())
-        if scale is not None:
-            saved += [ws.out[:, 2:9].clone(), scale.detach().clone()]
-        ctx.save_for_backward(*saved)
-        return ws.out[:, 9].clone()
+        ctx.n, ctx.w_kl = n, w_kl
+        keep = {"o": ws.out[:, 2:9], "prior_scale": scale.detach()} if scale is not None else {}
+        return _elbo_forward(ctx, ws, m.device, num_gh, (raw_a, raw_b, raw_c), B, step, failed,
+                             {"m": "grad_m", "Lq": "grad_Lq", "mean": "grad_mu", "K": "grad_K"}, keep, ws.out[:, 9])
 
     @staticmethod
     def backward(ctx, g):
-        sv = list(ctx.saved_tensors)
-        gm, gL, gmu = sv[:3]
-        g1, g2 = g.reshape(-1, 1), g.reshape(-1, 1, 1)
-        gK = g2 * sv[4 if ctx.cv else 3] if ctx.want_dk else None
-        gscale = None
-        if ctx.has_scale:
-            gscale = _dkl_dscale_grad(sv[-2], sv[-1], ctx.n, ctx.w_kl, g)
-        ga, gb, gc = _cv_raw_grads(g2, sv[3], ctx.raw_shape) if ctx.cv else (None, None, None)
-        return g1 * gm, g2 * gL, g1 * gmu, gK, None, ga, gb, gc, None, gscale, None, None, None
+        grads, sv = _elbo_backward(ctx, g)
+        if "prior_scale" in sv:
+            grads["scale"] = _dkl_dscale_grad(sv["o"], sv["prior_scale"], ctx.n, ctx.w_kl, g)
+        return tuple(grads.get(name) for name in _inputs(_GPCVElbo))
 
 
 class _GPCVBmElbo(torch.autograd.Function):
@@ -275,31 +301,25 @@ class _GPCVBmElbo(torch.autograd.Function):
     @staticmethod
     def forward(ctx, m, Lq, mean, scale, x, y, raw_a, raw_b, raw_c, holder, num_gh, w_ell, w_kl):
         B, n = m.shape
-        gh_x, gh_w = _gauss_hermite(num_gh, m.device)
-        cv = raw_a is not None
-        ws = holder.bm_workspace(B, n, m.device, raw_a.shape[-1] if cv else 0)
-        abc, jac = _cv_transform(raw_a, raw_b, raw_c, B) if cv else (None, None)
-        ops.gpcv_bm_step(x, scale.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y, gh_x, gh_w, ws, abc=abc,
-                         jitter=PRIOR_JITTER, min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
-        if deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
-            _raise_step_failure("GPCV step (linear prior)", ws.info, (scale, m, Lq) + ((abc,) if cv else ()),
+        ws = holder.workspace(ops.GpcvBmWorkspace, B, n, m.device, raw_a.shape[-1] if raw_a is not None else 0)
+
+        def step(gh_x, gh_w, abc):
+            ops.gpcv_bm_step(x, scale.detach(), (m - mean).detach(), m.detach(), Lq.detach(), y, gh_x, gh_w, ws, abc=abc,
+                             jitter=PRIOR_JITTER, min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
+
+        def failed(abc):
+            _raise_step_failure("GPCV step (linear prior)", ws.info, (scale, m, Lq) + ((abc,) if abc is not None else ()),
                                 "prior covariance K + 1e-3 I")
-        ctx.n, ctx.w_kl, ctx.cv = n, w_kl, cv
-        saved = [ws.grad_m.clone(), ws.grad_Lq.clone(), ws.grad_mu.clone(), ws.out[:, 2:9].clone(), scale.detach().clone()]
-        if cv:
-            ctx.raw_shape = raw_a.shape
-            saved.append(ws.grad_abc * jac)
-        ctx.save_for_backward(*saved)
-        return ws.out[:, 9].clone()
+        ctx.n, ctx.w_kl = n, w_kl
+        return _elbo_forward(ctx, ws, m.device, num_gh, (raw_a, raw_b, raw_c), B, step, failed,
+                             {"m": "grad_m", "Lq": "grad_Lq", "mean": "grad_mu"},
+                             {"o": ws.out[:, 2:9], "prior_scale": scale.detach()}, ws.out[:, 9])
 
     @staticmethod
     def backward(ctx, g):
-        sv = list(ctx.saved_tensors)
-        gm, gL, gmu, o, scale = sv[:5]
-        g1, g2 = g.reshape(-1, 1), g.reshape(-1, 1, 1)
-        gscale = _dkl_dscale_grad(o, scale, ctx.n, ctx.w_kl, g)
-        ga, gb, gc = _cv_raw_grads(g2, sv[5], ctx.raw_shape) if ctx.cv else (None, None, None)
-        return g1 * gm, g2 * gL, g1 * gmu, gscale, None, None, ga, gb, gc, None, None, None, None
+        grads, sv = _elbo_backward(ctx, g)
+        grads["scale"] = _dkl_dscale_grad(sv["o"], sv["prior_scale"], ctx.n, ctx.w_kl, g)
+        return tuple(grads.get(name) for name in _inputs(_GPCVBmElbo))
 
 
 class _GPCVMarkovElbo(torch.autograd.Function):
@@ -310,37 +330,31 @@ class _GPCVMarkovElbo(torch.autograd.Function):
     @staticmethod
     def forward(ctx, m, rho, gamma, mean, scale, x, y, raw_a, raw_b, raw_c, holder, num_gh, w_ell, w_kl):
         B, n = m.shape
-        gh_x, gh_w = _gauss_hermite(num_gh, m.device)
-        cv = raw_a is not None
-        ws = holder.markov_workspace(B, n, m.device, raw_a.shape[-1] if cv else 0)
-        abc, jac = _cv_transform(raw_a, raw_b, raw_c, B) if cv else (None, None)
-        ops.gpcv_markov_step(x, scale.detach(), (m - mean).detach(), m.detach(), rho.detach(), gamma.detach(), y, gh_x, gh_w,
-                             ws, abc=abc, jitter=PRIOR_JITTER, min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
-        if deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
+        ws = holder.workspace(ops.GpcvMarkovWorkspace, B, n, m.device, raw_a.shape[-1] if raw_a is not None else 0)
+
+        def step(gh_x, gh_w, abc):
+            ops.gpcv_markov_step(x, scale.detach(), (m - mean).detach(), m.detach(), rho.detach(), gamma.detach(), y, gh_x,
+                                 gh_w, ws, abc=abc, jitter=PRIOR_JITTER, min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
+
+        def failed(abc):
             # info = 1: F is not finite.  There is no pivot in this family: a NaN input, or parameters whose variances overflow
             _raise_step_failure("GPCV step (markov family)", ws.info,
-                                (scale, m, rho, gamma[..., :-1], mean, y) + ((abc,) if cv else ()), None,
+                                (scale, m, rho, gamma[..., :-1], mean, y) + ((abc,) if abc is not None else ()), None,
                                 message="F is not finite although no input is NaN (info = "
                                         f"{ws.info.tolist()[:8]}): the variances exp(-2 log_diag_precision_root) or the products "
                                         "of coupling^2 overflow, or the prior's increments are not positive")
-        ctx.cv, ctx.scale_shape = cv, scale.shape
-        saved = [ws.grad_m.clone(), ws.grad_rho.clone(), ws.grad_gamma.clone(), ws.grad_mu.clone(), ws.out[:, 6].clone()]
-        if cv:
-            ctx.raw_shape = raw_a.shape
-            saved.append(ws.grad_abc * jac)
-        ctx.save_for_backward(*saved)
-        return ws.out[:, 9].clone()
+        ctx.scale_shape = scale.shape
+        return _elbo_forward(ctx, ws, m.device, num_gh, (raw_a, raw_b, raw_c), B, step, failed,
+                             {"m": "grad_m", "rho": "grad_rho", "gamma": "grad_gamma", "mean": "grad_mu"},
+                             {"dF_dscale": ws.out[:, 6]}, ws.out[:, 9])
 
     @staticmethod
     def backward(ctx, g):
-        sv = list(ctx.saved_tensors)
-        gm, grho, ggam, gmu, gv = sv[:5]
-        g1, g2 = g.reshape(-1, 1), g.reshape(-1, 1, 1)
-        gscale = g * gv
-        gscale = gscale.reshape(ctx.scale_shape) if gscale.numel() == math.prod(ctx.scale_shape) else \
+        grads, sv = _elbo_backward(ctx, g)
+        gscale = g * sv["dF_dscale"]
+        grads["scale"] = gscale.reshape(ctx.scale_shape) if gscale.numel() == math.prod(ctx.scale_shape) else \
             gscale.sum().reshape(ctx.scale_shape)
-        ga, gb, gc = _cv_raw_grads(g2, sv[5], ctx.raw_shape) if ctx.cv else (None, None, None)
-        return g1 * gm, g1 * grho, g1 * ggam, g1 * gmu, gscale, None, None, ga, gb, gc, None, None, None, None
+        return tuple(grads.get(name) for name in _inputs(_GPCVMarkovElbo))
 
 
 class MultitaskVariationalLatent(MultivariateNormal):
@@ -376,9 +390,7 @@ class MultitaskVariationalLatent(MultivariateNormal):
     def rsample(self, sample_shape=torch.Size(), base_samples=None):
         """M + Lx E Lt', E ~ N(0, I) of shape sample_shape + [N,T] (the Kronecker root applied factor by factor)."""
         n, T = self.loc.shape
-        if base_samples is None:
-            base_samples = torch.randn(torch.Size(sample_shape) + self.loc.shape, dtype=self.loc.dtype,
-                                       device=self.loc.device)
+        base_samples = self._base_samples(sample_shape, base_samples)
         Lx, Lt = (r.detach() for r in self._roots)
         E = base_samples.reshape(-1, n, T)
         S = E.shape[0]
@@ -410,46 +422,34 @@ class _GPCVMtElbo(torch.autograd.Function):
     @staticmethod
     def forward(ctx, M, Lx, Lt, c, cf, rv, K, y, raw_a, raw_b, raw_c, holder, scale, num_gh, w_ell, w_kl):
         n, T = M.shape
-        want_dk = bool(ctx.needs_input_grad[6])
-        gh_x, gh_w = _gauss_hermite(num_gh, M.device)
+        want_dk = bool(ctx.needs_input_grad[_inputs(_GPCVMtElbo).index("K")])
         cv = raw_a is not None
-        ws = holder.mt_workspace(n, T, want_dk, M.device, Kc=raw_a.shape[-1] if cv else 0)
-        abc, jac = _cv_transform(raw_a, raw_b, raw_c, T) if cv else (None, None)
-        ops.gpcv_mt_step(K.detach(), M, c, Lx, Lt, cf, rv, y, gh_x, gh_w, ws, want_dk=want_dk, jitter=PRIOR_JITTER,
-                         min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl, abc=abc)
-        if deferred_checks.settle(ws.info) and bool((ws.info != 0).any().item()):
+        ws = holder.workspace(ops.GpcvMtWorkspace, n, T, want_dk, M.device, raw_a.shape[-1] if cv else 0)
+
+        def step(gh_x, gh_w, abc):
+            ops.gpcv_mt_step(K.detach(), M, c, Lx, Lt, cf, rv, y, gh_x, gh_w, ws, want_dk=want_dk, jitter=PRIOR_JITTER,
+                             min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl, abc=abc)
+
+        def failed(abc):
             info = ws.info.cpu()
             # info[0]: K_x + jitter I (LAPACK-style or an internal code);  info[1]: a pivot of K_t;  info[2]: F not finite
             which = "prior covariance K_x + 1e-3 I" if int(info[0]) != 0 else "task covariance K_t"
             _raise_step_failure("multi-task GPCV cv step" if cv else "multi-task GPCV step", info[:1],
                                 (K, M, Lx, Lt, c, cf, rv, y) + ((abc,) if cv else ()), which)
-        ctx.n, ctx.T, ctx.w_kl, ctx.has_scale, ctx.want_dk, ctx.cv = n, T, w_kl, scale is not None, want_dk, cv
-        ctx.cf_shape = cf.shape
-        saved = [ws.grad_M.clone(), ws.grad_Lx.clone(), ws.grad_Lt.clone(), ws.grad_c.clone(),
-                 ws.grad_covar_factor.clone(), ws.grad_raw_var.clone()]
-        if cv:
-            ctx.raw_shape = raw_a.shape
-            saved.append(ws.grad_abc * jac)
-        if want_dk:
-            saved.append(ws.grad_K.clone())
-        if scale is not None:
-            saved += [ws.out.clone(), scale.detach().clone()]
-        ctx.save_for_backward(*saved)
-        return ws.out[12].clone()
+        ctx.n, ctx.T, ctx.w_kl, ctx.cf_shape = n, T, w_kl, cf.shape
+        keep = {"out": ws.out, "prior_scale": scale.detach()} if scale is not None else {}
+        return _elbo_forward(ctx, ws, M.device, num_gh, (raw_a, raw_b, raw_c), T, step, failed,
+                             {"M": "grad_M", "Lx": "grad_Lx", "Lt": "grad_Lt", "c": "grad_c", "cf": "grad_covar_factor",
+                              "rv": "grad_raw_var", "K": "grad_K"}, keep, ws.out[12])
 
     @staticmethod
     def backward(ctx, g):
-        sv = list(ctx.saved_tensors)
-        gM, gLx, gLt, gc, gcf, grv = sv[:6]
-        gK = g * sv[7 if ctx.cv else 6] if ctx.want_dk else None
-        gscale = None
-        if ctx.has_scale:
-            dkl = mt_dkl_dscale(sv[-2], sv[-1], ctx.n, ctx.T)
-            s = sv[-1]
-            gscale = (-ctx.w_kl * g * dkl).reshape(s.shape)
-        ga, gb, gcc = _cv_raw_grads(g, sv[6], ctx.raw_shape) if ctx.cv else (None, None, None)
-        return (g * gM, g * gLx, g * gLt, g * gc, (g * gcf).reshape(ctx.cf_shape), g * grv, gK, None, ga, gb, gcc, None,
-                gscale, None, None, None)
+        grads, sv = _elbo_backward(ctx, g)
+        grads["cf"] = grads["cf"].reshape(ctx.cf_shape)
+        if "prior_scale" in sv:
+            dkl = mt_dkl_dscale(sv["out"], sv["prior_scale"], ctx.n, ctx.T)
+            grads["scale"] = (-ctx.w_kl * g * dkl).reshape(sv["prior_scale"].shape)
+        return tuple(grads.get(name) for name in _inputs(_GPCVMtElbo))
 
 
 class VariationalELBO(Module):
@@ -476,30 +476,47 @@ class VariationalELBO(Module):
         object.__setattr__(self, "likelihood", likelihood)
         object.__setattr__(self, "model", model)
         self.num_data, self.beta = float(num_data), float(beta)
-        self._ws = None
-        self._mt_ws = None
-        self._bm_ws = None
-        self._markov_ws = None
+        for attr in self._WS_ATTR.values():
+            setattr(self, attr, None)
 
-    def markov_workspace(self, B, n, device, Kc=0):
-        return ops.cached_workspace(self, "_markov_ws", ops.GpcvMarkovWorkspace, B, n, device, Kc)
+    # one workspace of each kind lives from iteration to iteration (a captured graph holds their addresses)
+    _WS_ATTR = {ops.GpcvWorkspace: "_ws", ops.GpcvMtWorkspace: "_mt_ws", ops.GpcvBmWorkspace: "_bm_ws",
+                ops.GpcvMarkovWorkspace: "_markov_ws"}
 
-    def bm_workspace(self, B, n, device, Kc=0):
-        return ops.cached_workspace(self, "_bm_ws", ops.GpcvBmWorkspace, B, n, device, Kc)
+    def workspace(self, cls, *key):
+        """The cached workspace of class ``cls`` if it fits ``key`` (the constructor's arguments), else a new one."""
+        return ops.cached_workspace(self, self._WS_ATTR[cls], cls, *key)
 
-    def workspace(self, B, n, want_dk, device, Kc=0):
-        return ops.cached_workspace(self, "_ws", ops.GpcvWorkspace, B, n, want_dk, device, Kc)
+    @staticmethod
+    def _need_cuda(t):
+        if not t.is_cuda:
+            raise ops._lib.VoltHipError("VariationalELBO: tensors must live on the MI355X; no CPU fallback")
 
-    def mt_workspace(self, n, T, want_dk, device, Kc=0):
-        return ops.cached_workspace(self, "_mt_ws", ops.GpcvMtWorkspace, n, T, want_dk, device, Kc)
+    def _weights(self, n):                               # (num_gh, w_ell, w_kl): the likelihood term / N, the KL / (num_data / beta)
+        return num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data
+
+    def _likelihood_raws(self, lead, m):
+        """(raw_a, raw_b, raw_c) of a "cv" likelihood as the ELBO functions take them, three None for "exp".  A batched
+        likelihood (one parameter set per series or task) must match the model's ``lead`` = B series (batch shape
+        m.shape[:-1]) or T tasks."""
+        lik = self.likelihood
+        if getattr(lik, "param", "exp") != "cv":
+            return [None, None, None]
+        Kc = lik.raw_a.shape[-1]
+        raws = [lik.raw_a, lik.raw_b, lik.raw_c]
+        if lik.raw_a.ndim > 1:
+            if lik.raw_a.numel() != lead * Kc:
+                raise ValueError(f"VariationalELBO: the likelihood's batch shape {tuple(lik.raw_a.shape[:-1])} does not "
+                                 f"match the model's {tuple(m.shape[:-1])}")
+            raws = [r.reshape(lead, Kc) for r in raws]
+        return raws
 
     def _forward_multitask(self, latent, target):
         """VariationalELBO over a MultitaskMultivariateNormal (event shape [N,T]): the likelihood term is summed over
         tasks and divided by N, the KL by num_data / beta."""
         model = latent.model
         M = model.variational_mean
-        if not M.is_cuda:
-            raise ops._lib.VoltHipError("VariationalELBO: tensors must live on the MI355X; no CPU fallback")
+        self._need_cuda(M)
         n, T = M.shape
         if tuple(target.shape) != (n, T):
             raise ValueError(f"VariationalELBO: the multi-task target must be [N,T] = [{n},{T}] (got {tuple(target.shape)})")
@@ -511,29 +528,15 @@ class VariationalELBO(Module):
         else:
             K = _dense(lazy)
         c, cf, rv = model._task_params()
-        lik = self.likelihood
-        raws = [lik.raw_a, lik.raw_b, lik.raw_c] if getattr(lik, "param", "exp") == "cv" else [None, None, None]
         return _GPCVMtElbo.apply(M, model.variational_covar_root, model.variational_task_covar_root, c, cf, rv,
-                                 K.to(torch.float32), target.to(torch.float32), *raws, self, scale,
-                                 num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data)
-
-    @staticmethod
-    def _cv_raws(lik, B, m):
-        Kc = lik.raw_a.shape[-1]
-        raws = [lik.raw_a, lik.raw_b, lik.raw_c]
-        if lik.raw_a.ndim > 1:                                       # batched likelihood: one parameter set per series
-            if lik.raw_a.numel() != B * Kc:
-                raise ValueError(f"VariationalELBO: the likelihood's batch shape {tuple(lik.raw_a.shape[:-1])} does not "
-                                 f"match the model's {tuple(m.shape[:-1])}")
-            raws = [r.reshape(B, Kc) for r in raws]
-        return raws
+                                 K.to(torch.float32), target.to(torch.float32), *self._likelihood_raws(T, M), self, scale,
+                                 *self._weights(n))
 
     def _forward_markov(self, latent, target):
         """prior_solver="markov": the O(N) step over (m, rho, gamma); nothing N x N is formed."""
         model = latent.model
         m = latent.loc
-        if not m.is_cuda:
-            raise ops._lib.VoltHipError("VariationalELBO: tensors must live on the MI355X; no CPU fallback")
+        self._need_cuda(m)
         prior = model.forward(model.variational_strategy.inducing_points)
         lazy = prior.lazy_covariance_matrix
         if not isinstance(lazy, _BrownianLevelPrior):
@@ -541,11 +544,8 @@ class VariationalELBO(Module):
         n = m.shape[-1]
         f32 = lambda t: t.reshape(-1, n).to(torch.float32)
         B = m.numel() // n
-        lik = self.likelihood
-        raws = self._cv_raws(lik, B, m) if getattr(lik, "param", "exp") == "cv" else [None, None, None]
         res = _GPCVMarkovElbo.apply(f32(m), f32(latent._rho), f32(latent._gamma), f32(prior.mean.expand(m.shape)), lazy.scale,
-                                    lazy.x, f32(target), *raws, self, num_gauss_hermite_locs.value(), 1.0 / n,
-                                    self.beta / self.num_data)
+                                    lazy.x, f32(target), *self._likelihood_raws(B, m), self, *self._weights(n))
         return res.reshape(m.shape[:-1]) if m.ndim > 1 else res.reshape(())
 
     def forward(self, approximate_dist_f, target):
@@ -557,8 +557,7 @@ class VariationalELBO(Module):
             raise TypeError("VariationalELBO expects the output of SingleTaskVariationalGP(train_x)")
         model = approximate_dist_f.model
         m, Lq = approximate_dist_f.loc, approximate_dist_f._chol
-        if not m.is_cuda:
-            raise ops._lib.VoltHipError("VariationalELBO: tensors must live on the MI355X; no CPU fallback")
+        self._need_cuda(m)
         Z = model.variational_strategy.inducing_points
         prior = model.forward(Z)
         n = m.shape[-1]
@@ -567,9 +566,7 @@ class VariationalELBO(Module):
         B = m2.shape[0]
         mean2 = prior.mean.expand(m.shape).reshape(-1, n)
         lazy = prior.lazy_covariance_matrix
-        lik = self.likelihood
-        raws = self._cv_raws(lik, B, m) if getattr(lik, "param", "exp") == "cv" else [None, None, None]
-        weights = (num_gauss_hermite_locs.value(), 1.0 / n, self.beta / self.num_data)
+        raws, weights = self._likelihood_raws(B, m), self._weights(n)
         if isinstance(lazy, _BrownianPrior):                           # prior_solver="linear": no dense K anywhere
             res = _GPCVBmElbo.apply(m2.to(torch.float32), L3.to(torch.float32), mean2.to(torch.float32), lazy.scale, lazy.x, y2,
                                     *raws, self, *weights)
