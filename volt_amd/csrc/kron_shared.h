@@ -122,16 +122,20 @@ __device__ __forceinline__ int kron_jacobi(double* A, double* V, int T, JacobiLd
 }
 
 // After kron_jacobi: eigenvalues ascending into s.lam, the matching eigenvectors as the columns of Qout [T][KLD]
-// (ties keep their index order).
+// (ties keep their index order).  A NaN eigenvalue (a NaN parameter) ranks above every number, NaNs among themselves in
+// index order: the ranks are a permutation whatever the diagonal holds, so every slot of s.lam and every column of Qout is
+// written exactly once -- comparisons alone would rank every NaN 0, beside the smallest number, and leave the top slots
+// holding whatever the LDS held before.
 __device__ __forceinline__ void kron_sort(const double* A, const double* V, double* Qout, int T, JacobiLds& s) {
     const int tid = threadIdx.x;
     __syncthreads();
     if (tid < T) {
         const double li = A[tid * KLD + tid];
+        const bool nan_i = li != li;
         int r = 0;
         for (int k = 0; k < T; ++k) {
             const double lk = A[k * KLD + k];
-            r += (lk < li) || (lk == li && k < tid);
+            r += nan_i ? (lk == lk || k < tid) : ((lk < li) || (lk == li && k < tid));
         }
         s.rank[tid] = r;
         s.lam[r] = li;
