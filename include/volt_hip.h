@@ -660,6 +660,41 @@ int volt_markov_root_draw_f32(const float* m, const float* rho, const float* gam
                               int N, void* stream);
 int volt_markov_root_var_f32(const float* rho, const float* gamma, double* var, int B, int N, void* stream);
 
+/* ---- Multi-task GPCV ELBO step in O(N T (Q + T) + T^3): the Markov variational family under the Kronecker prior
+ * (MultitaskVariationalGP(prior_solver="markov"); csrc/gpcv_mt_markov.hip has the closed forms).
+ * Prior: p(F) = N(mu, K_M (x) K_t) over the grid x [N] (0 <= x_0 < x_1 < ..), K_M = vol min(x, x') + jitter 1 1' as in
+ * volt_gpcv_markov_step_f32 (vol [1]; NOT the dense multi-task step's K + jitter I), K_t = f f' + diag softplus(raw_var)
+ * (covar_factor f [T], raw_var [T]), mu[n,t] = c_t.
+ * Family: q(F) = N(M, P^-1 (x) S_t), P = Lp Lp' with Lp lower bidiagonal (diagonal exp(rho_i), entry (i+1, i)
+ * gamma_i exp(rho_i); rho, gamma [N], gamma[N-1] is never read), S_t = Lt Lt' (Lt [T,T]; what lies above its diagonal is
+ * ignored), M [N,T].  y [N,T].  abc == NULL (and Kc == 0): the "exp" likelihood; abc [T,3,Kc], 1 <= Kc <=
+ * VOLT_GPCV_CV_K_MAX: the "cv" one with one warp per task (the TRANSFORMED a, b, c).  Recurrences and sums fp64, the
+ * quadrature nodes and all I/O fp32.
+ *     out[0..11] = ell, KL, quad = tr(K_t^-1 G), logdet K_M, logdet K_t, logdet S_x = -2 sum rho, logdet S_t,
+ *                  tau_x = tr(K_M^-1 P^-1), tau_t = tr(K_t^-1 S_t), dF/dvol, F = w_ell ell - w_kl KL, jitter
+ *     grad_M [N,T], grad_c [T], grad_rho, grad_gamma [N] (grad_gamma[N-1] = 0), grad_Lt [T,T] (zero above the diagonal),
+ *     grad_covar_factor, grad_raw_var [T], grad_abc [T,3,Kc] = dF/d(a,b,c)
+ * info[0]: 1 where F is not finite, else 0;  info[1]: 0, or j + 1 for the first pivot j of K_t that is not positive (the
+ * outputs are then NaN).  A NaN input arrives in info; there is no data-dependent loop.
+ * workspace: volt_gpcv_mt_markov_workspace_bytes(N, T, Kc) bytes (0 for a shape out of range), 256-byte aligned,
+ * O(N T + T^2 ceil(N / 128)); it needs no initialisation call and is fully written before it is read.  On return its first
+ * 8 N bytes hold diag P^-1 [N] in fp64.
+ * Four launches (five with abc); no host synchronisation, no allocation, no atomics: every reduction has a fixed order that
+ * depends on (N, T) alone, results are bitwise repeatable, and the launch sequence replays from a hipGraph.
+ * N >= 1, 1 <= T <= 64; 64-bit indices.
+ * Argument errors (before any launch, in the order of their numbers): -1 x, -2 vol, -4 M, -5 c, -6 rho, -7 gamma, -8 Lt,
+ * -9 covar_factor, -10 raw_var, -11 y NULL; -13 Kc out of range with abc, or Kc != 0 without; -14 gh_x, -15 gh_w NULL;
+ * -16 Q outside 1 .. 1024; -21 out, -22 grad_M, -23 grad_c, -24 grad_rho, -25 grad_gamma, -26 grad_Lt, -27 grad_covar_factor,
+ * -28 grad_raw_var NULL; -29 grad_abc NULL with abc; -30 info NULL; -31 workspace NULL or not 256-byte aligned; -32 N < 1;
+ * -33 T outside 1 .. 64. */
+size_t volt_gpcv_mt_markov_workspace_bytes(int N, int T, int Kc);
+int volt_gpcv_mt_markov_step_f32(const float* x, const float* vol, float jitter, const float* M, const float* c, const float* rho,
+                                 const float* gamma, const float* Lt, const float* covar_factor, const float* raw_var,
+                                 const float* y, const float* abc, int Kc, const float* gh_x, const float* gh_w, int Q,
+                                 float min_var, float min_scale, float w_ell, float w_kl, float* out, float* grad_M,
+                                 float* grad_c, float* grad_rho, float* grad_gamma, float* grad_Lt, float* grad_covar_factor,
+                                 float* grad_raw_var, float* grad_abc, int* info, void* workspace, int N, int T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,6 +112,7 @@ def _check_vol_posterior(vol_posterior, vol_solver):
 
 
 GPCV_OPTIONS = ("param", "K", "train_likelihood")      # what gpcv_options may carry to the GPCV fit
+MULTITASK_GPCV = (False, True, "markov")               # True: the dense joint model; "markov": its Markov family
 
 
 def _check_gpcv_options(gpcv_options, multitask_gpcv, gpcv_solver, nseries, vol_fn):
@@ -120,13 +121,17 @@ def _check_gpcv_options(gpcv_options, multitask_gpcv, gpcv_solver, nseries, vol_
     unknown = sorted(set(opts) - set(GPCV_OPTIONS))
     if unknown:
         raise ValueError(f"gpcv_options: unknown keys {unknown}; it takes {list(GPCV_OPTIONS)}")
+    if multitask_gpcv not in MULTITASK_GPCV:
+        raise ValueError(f"multitask_gpcv must be one of {list(MULTITASK_GPCV)}, got {multitask_gpcv!r}")
     if multitask_gpcv and vol_fn is None:
         from . import ops
+        what = 'multitask_gpcv="markov" chooses the joint model\'s own solver' if multitask_gpcv == "markov" else \
+            "multitask_gpcv=True runs the dense multi-task step"
         if gpcv_solver == "markov":
-            raise ValueError('multitask_gpcv=True runs the dense multi-task step: it does not combine with gpcv_solver="markov" '
-                             "(the multi-task model has no Markov variational family)")
+            raise ValueError(f'{what}: it does not combine with gpcv_solver="markov" (the Markov variational family of the '
+                             'multi-task model is spelled multitask_gpcv="markov"; gpcv_solver is the single-task fit\'s)')
         if gpcv_solver == "linear":
-            raise ValueError('multitask_gpcv=True runs the dense multi-task step: it does not combine with gpcv_solver="linear" '
+            raise ValueError(f'{what}: it does not combine with gpcv_solver="linear" '
                              "(the multi-task model has no lazy Brownian prior)")
         if nseries > ops.GPCV_MT_T_MAX:
             raise ValueError(f"multitask_gpcv=True takes at most {ops.GPCV_MT_T_MAX} series per rank (got {nseries})")
@@ -143,7 +148,8 @@ def _window_pass(train_x, test_x, train_y, nsample, mean, k, gpcv_iters, vol_ite
     b, H = train_y.shape[0], test_x.numel()
     predict_solver = _resolve_solver(predict_solver)
     if vol_fn is None and multitask_gpcv:                # ONE joint model over the rank's series: the prior is factored once
-        vol = LearnGPCVMultitask(train_x, train_y, train_iters=gpcv_iters, graph=graph, **(gpcv_options or {}))
+        vol = LearnGPCVMultitask(train_x, train_y, train_iters=gpcv_iters, graph=graph,
+                                 solver="markov" if multitask_gpcv == "markov" else "dense", **(gpcv_options or {}))
     elif vol_fn is None:
         vol = LearnGPCV(train_x, train_y, train_iters=gpcv_iters, graph=graph, solver=gpcv_solver,
                         **(gpcv_options or {}))                                          # all series at once
@@ -284,7 +290,9 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
     changed by it; the default "factor" changes nothing.
     ``multitask_gpcv=True``: the window's vol paths come from ONE LearnGPCVMultitask call over the rank's series (the joint
     Kronecker variational GP: one prior factorisation for all of them, T <= 64 per rank) instead of the batched single-task
-    LearnGPCV; not with ``gpcv_solver="linear"``.  The series-by-series redo after a failed window then runs T = 1.
+    LearnGPCV; not with ``gpcv_solver="linear"`` or ``"markov"``.  The series-by-series redo after a failed window then runs
+    T = 1.  ``multitask_gpcv="markov"``: the same joint model with the Markov variational family under the level-jitter
+    Brownian prior (LearnGPCVMultitask(solver="markov"), csrc/gpcv_mt_markov.hip): O(N T), no N x N array.
     ``gpcv_options``: a dict with keys out of ``param``, ``K``, ``train_likelihood``, forwarded to whichever GPCV fit runs
     (FitGPCV / FitGPCVMultitask); unknown keys raise.  Both are ignored with a ``vol_fn``; the defaults change nothing."""
     _check_vol_posterior(vol_posterior, vol_solver)

@@ -12,6 +12,14 @@ Stated differences from the reference file (README, quirk table):
   (:95-111) and leans on gpytorch's jitter ladder when x[0] = 0 makes K_x[0,0] = 0.
 * rank=1, fp32; param="cv" with one warp per task only (an unbatched "cv" likelihood, one warp shared by all tasks, has no
   accelerated ELBO), and its start-up values for K = 1 only, as for SingleTaskVariationalGP.
+* ``prior_solver="markov"`` (keyword-only; the default "dense" is everything above, unchanged): the joint model in
+  O(N T (Q + T) + T^3) time and O(N T) memory (csrc/gpcv_mt_markov.hip, volt_gpcv_mt_markov_step_f32).  The data
+  kernel must be a BMKernel over a grid 0 <= x_0 < x_1 < .. (validated once); the prior's data block is Brownian motion
+  started from an N(0, 1e-3) LEVEL, K_M = vol min(x, x') + 1e-3 1 1' (not K_x + 1e-3 I, whose diagonal jitter destroys the
+  Markov structure), and the variational family is q(F) = N(M, P^-1 (x) S_t) with a TRIDIAGONAL precision P = Lp Lp':
+  parameters ``variational_mean`` [N,T], ``log_diag_precision_root`` [N], ``coupling`` [N] (its last entry is never read),
+  ``variational_task_covar_root`` [T,T] -- there is no ``variational_covar_root``.  The start-up values take an O(N T) route
+  (``_initialize_markov``); no N x N tensor exists anywhere on this route.
 The reference has no trainer for this class; train_utils.FitGPCVMultitask is LearnGPCV's loop over it.  gpytorch is not
 installed here; both branches of ``initialize_variational_parameters`` are pinned to the reference's own code, executed
 over stand-ins, by tests/golden/mt_gpcv_cv.npz."""
@@ -19,24 +27,44 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..gp import ConstantMean, EqualMemo, Module, MultitaskMean, _dense
+from ..gp import ConstantMean, EqualMemo, Module, MultitaskMean, _dense, check_grid
 from ..safe import _safe_factor
+from ..kernels.BMKernel import BMKernel
 from ..kernels.MultitaskKernel import IndexKernel
-from ..variational import MIN_VARIANCE, PRIOR_JITTER, MultitaskVariationalLatent, _gauss_hermite
+from ..variational import (MIN_VARIANCE, PRIOR_JITTER, MultitaskMarkovVariationalLatent, MultitaskVariationalLatent,
+                           _gauss_hermite)
+from .single_task_variational_gp import markov_startup_factor
 
 
 class MultitaskVariationalGP(Module):
-    def __init__(self, inducing_points, num_tasks, covar_module=None, rank=1, **kwargs):
+    PRIOR_SOLVERS = ("dense", "markov")
+
+    def __init__(self, inducing_points, num_tasks, covar_module=None, rank=1, *, prior_solver="dense", **kwargs):
         super().__init__()
+        if prior_solver not in self.PRIOR_SOLVERS:
+            raise ValueError(f"MultitaskVariationalGP: prior_solver must be one of {self.PRIOR_SOLVERS}, got {prior_solver!r}")
         if rank != 1:
             raise NotImplementedError("MultitaskVariationalGP: only the rank-1 IndexKernel has an accelerated ELBO")
         if covar_module is None:
             raise NotImplementedError("pass covar_module (BMKernel / FBMKernel): the data kernel of the Kronecker prior")
         ops._check_tasks(num_tasks)
         n = inducing_points.shape[-1]
+        if prior_solver == "markov":
+            if not isinstance(covar_module, BMKernel):
+                raise ValueError(f"MultitaskVariationalGP: prior_solver='markov' needs covar_module=BMKernel (Brownian motion "
+                                 f"is Markov; {type(covar_module).__name__} is not)")
+            if inducing_points.ndim != 1:
+                raise ValueError("MultitaskVariationalGP(prior_solver='markov'): the inducing grid must be [N], got shape "
+                                 f"{tuple(inducing_points.shape)}")
+            check_grid(inducing_points, "MultitaskVariationalGP(prior_solver='markov')")
+        self.prior_solver = prior_solver
         # registration and draw order of the reference's __init__ (:15-36): the mean's randn comes before IndexKernel's two
         self.register_parameter("variational_mean", nn.Parameter(0.01 * torch.randn(n, num_tasks), requires_grad=True))
-        self.register_parameter("variational_covar_root", nn.Parameter(torch.eye(n), requires_grad=True))
+        if prior_solver == "markov":                             # the tridiagonal precision root, 0 / I like the dense one
+            self.register_parameter("log_diag_precision_root", nn.Parameter(torch.zeros(n), requires_grad=True))
+            self.register_parameter("coupling", nn.Parameter(torch.zeros(n), requires_grad=True))
+        else:
+            self.register_parameter("variational_covar_root", nn.Parameter(torch.eye(n), requires_grad=True))
         self.register_parameter("variational_task_covar_root", nn.Parameter(torch.eye(num_tasks), requires_grad=True))
         self.index_kernel = IndexKernel(num_tasks=num_tasks, rank=rank, **kwargs)
         self.data_kernel = covar_module
@@ -61,6 +89,18 @@ class MultitaskVariationalGP(Module):
         if not M.is_cuda:
             raise ops._lib.VoltHipError("MultitaskVariationalGP.kl_divergence: tensors must live on the MI355X; no CPU fallback")
         n, T = M.shape
+        if self.prior_solver == "markov":
+            with torch.no_grad():
+                c, cf, rv = self._task_params()
+                gx, gw = _gauss_hermite(1, M.device)
+                ws = self._kl_ws
+                if ws is None or not ws.fits(n, T, M.device):
+                    ws = ops.GpcvMtMarkovWorkspace(n, T, M.device)
+                    object.__setattr__(self, "_kl_ws", ws)
+                ops.gpcv_mt_markov_step(self.inducing_points, self.data_kernel.vol, M, c, self.log_diag_precision_root,
+                                        self.coupling, self.variational_task_covar_root, cf, rv, torch.zeros_like(M), gx, gw,
+                                        ws, jitter=PRIOR_JITTER, min_var=MIN_VARIANCE)
+                return ws.out[1].clone()
         with torch.no_grad():
             K = _dense(self.data_kernel(self.inducing_points)).to(torch.float32)
             c, cf, rv = self._task_params()
@@ -81,7 +121,7 @@ class MultitaskVariationalGP(Module):
         Z = self.inducing_points
         xs = x.reshape(Z.shape) if x.numel() == Z.numel() else x
         if xs.shape == Z.shape and self._eq_memo.equal(x, Z, lambda: torch.equal(xs, Z)):
-            return MultitaskVariationalLatent(self)
+            return MultitaskMarkovVariationalLatent(self) if self.prior_solver == "markov" else MultitaskVariationalLatent(self)
         return self.forward(x, **kwargs)
 
     def initialize_variational_parameters(self, likelihood, x, f=None, y=None):
@@ -106,8 +146,10 @@ class MultitaskVariationalGP(Module):
                                           "(multi_task_variational_gp.py:60: `y / likelihood.trans_a`), a broadcast that only "
                                           f"works for K = 1; K = {likelihood.raw_a.shape[-1]} has no start-up values")
         assert y is not None
+        markov = self.prior_solver == "markov"
         with torch.no_grad():
-            kuu = _dense(self.data_kernel(self.inducing_points)).to(torch.float32)
+            if not markov:
+                kuu = _dense(self.data_kernel(self.inducing_points)).to(torch.float32)
             y2 = y.to(torch.float32)
             N, T = y2.shape
             # running std of y[:i] (unbiased) per column, one prefix-sum pass instead of the reference's N slices
@@ -123,7 +165,7 @@ class MultitaskVariationalGP(Module):
             if param == "exp":
                 # torch.diag_embed(...).clamp(min=1e-4, max=1000.).mean(0): diagonal = mean of the clamped entries, elsewhere 1e-4
                 h = (0.5 * y2.pow(-2.0) * (f * 2.0).exp()).T.clamp(min=1e-4, max=1000.0).mean(0)
-                ih = torch.full((N, N), 1e-4, device=y2.device)
+                ih = None if markov else torch.full((N, N), 1e-4, device=y2.device)
             else:
                 a, b, c = (p.detach().to(y2.device, torch.float32) for p in
                            (likelihood.trans_a, likelihood.trans_b, likelihood.trans_c))     # [T,1]
@@ -132,8 +174,10 @@ class MultitaskVariationalGP(Module):
                 sigma = likelihood(ft).scale                         # plain-tensor forward: parameter set t meets row t
                 scaling = ((2 + 3 * yl.pow(2.0)) * (a * b.pow(2.0) / 2)).pow(-1.0)
                 h = (scaling * sigma.pow(2.0) * (1 + torch.cosh(b * yl + c))).mean(0)       # diag of diag_embed(.).mean(0)
-                ih = torch.zeros(N, N, device=y2.device)
+                ih = None if markov else torch.zeros(N, N, device=y2.device)
                 f = ft.t()
+            if markov:
+                return self._initialize_markov(h, f, running_std)
             ih.diagonal().copy_(h)
             L = _safe_factor(kuu.reshape(1, N, N))[0].L[0]                                   # kuu.cholesky()
             Lt = L.mT.contiguous()
@@ -142,11 +186,31 @@ class MultitaskVariationalGP(Module):
             inner = inner + torch.eye(N, device=y2.device)                                   # .add_jitter(1.0)
             Yi = ops.trtri(_safe_factor(inner.reshape(1, N, N))[0])[0]                       # C^-T
             S_root = ops.gemm_nt(L.contiguous(), Yi.mT.contiguous(), uplo_a=1, uplo_b=1)     # L C^-T
-            self.variational_mean.data = f.to(torch.float32).contiguous()
             self.variational_covar_root.data = (S_root * 10.0).contiguous()
-            log_means = running_std.clamp(min=1e-4).mean(0).log()
-            for i, m in enumerate(self.mean_module.base_means):
-                m.constant.data.add_(log_means[i])
-            if type(self.index_kernel) is IndexKernel:
-                # (`index_kernel.var.data /= 10.` at :87 divides a temporary, as in BMGP.py:39: a no-op)
-                self.index_kernel.covar_factor.data /= 10.
+            self._initialize_mean_and_task_kernel(f, running_std)
+
+    def _initialize_mean_and_task_kernel(self, f, running_std):
+        """What both start-up routes share (:80-88): the variational mean, the mean constants, covar_factor / 10."""
+        self.variational_mean.data = f.to(torch.float32).contiguous()
+        log_means = running_std.clamp(min=1e-4).mean(0).log()
+        for i, m in enumerate(self.mean_module.base_means):
+            m.constant.data.add_(log_means[i])
+        if type(self.index_kernel) is IndexKernel:
+            # (`index_kernel.var.data /= 10.` at :87 divides a temporary, as in BMGP.py:39: a no-op)
+            self.index_kernel.covar_factor.data /= 10.
+
+    def _initialize_markov(self, h, f, running_std):
+        """The start-up values of prior_solver="markov" in O(N T).  The dense route stores 10 * S_root with S_root S_root' =
+        L (L'HL + I)^-1 L' = (K^-1 + H)^-1 for a diagonal H, so under the Markov prior K_M the precision of S_x is tridiagonal:
+        P0 = (K_M^-1 + diag h) / 100, and (log_diag_precision_root, coupling) is its bidiagonal Cholesky factor
+        (single_task_variational_gp.markov_startup_factor: one fp64 host loop over N).  h [N]: the mean over tasks that
+        ``initialize_variational_parameters`` computed.  One quirk cannot be carried: the "exp" branch's clamp leaves 1e-4 OFF the
+        diagonal of H, a dense rank-one term; here H is its diagonal only (DESIGN 4.19 says the same of the single-task model)."""
+        Z = self.inducing_points
+        x = Z.reshape(-1).double().cpu().numpy()
+        vol = self.data_kernel.vol.detach().double().reshape(-1).cpu().numpy()            # [1]
+        rho, gamma = markov_startup_factor(x, vol, PRIOR_JITTER, h.double().reshape(1, -1).cpu().numpy())
+        put = lambda a: torch.as_tensor(a[0], dtype=torch.float32).to(Z.device)
+        self.log_diag_precision_root.data = put(rho)
+        self.coupling.data = put(gamma)
+        self._initialize_mean_and_task_kernel(f, running_std)

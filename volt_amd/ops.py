@@ -624,7 +624,7 @@ def _ptrs(ws, *names):
 
 
 class _GpcvStepWorkspace:
-    """What the four GPCV workspaces share: the scratch, the MLL workspace some of them begin with, the fp32 outputs, ``info``
+    """What the GPCV workspaces share: the scratch, the MLL workspace some of them begin with, the fp32 outputs, ``info``
     and ``fits``.  A subclass states its constructor key, its byte count and its outputs; the names it sets are its own."""
     _STEP = 'the "cv" GPCV step'
 
@@ -884,6 +884,59 @@ def gpcv_mt_step(K, M, c, Lx, Lt, covar_factor, raw_var, y, gh_x, gh_w, ws: Gpcv
     else:
         _lib.check(_lib.lib().volt_gpcv_mt_cv_step_f32(*prior, abc.data_ptr(), Kc, *quad, *grads, *_ptrs(ws, "grad_abc"), *tail),
                    "volt_gpcv_mt_cv_step")
+    return ws
+
+
+class GpcvMtMarkovWorkspace(_GpcvStepWorkspace):
+    """Caller-owned scratch and outputs of volt_gpcv_mt_markov_step_f32, reusable across steps of the same (N, T, Kc):
+    O(N T + T^2 N / 128) bytes, no initialisation call.  After a step ``.s`` [N] (fp64, a view of the scratch) holds
+    diag P^-1.  Kc > 0 adds .grad_abc [T,3,Kc] (the "cv" likelihood, one warp per task).
+    info[0]: F is not finite; info[1]: a non-positive pivot of K_t."""
+    _STEP = 'the "cv" multi-task GPCV step (markov family)'
+
+    def __init__(self, N: int, T: int, device, Kc: int = 0):
+        if T < 1 or T > GPCV_MT_T_MAX:
+            raise ValueError(f"the multi-task GPCV step takes 1 <= T <= {GPCV_MT_T_MAX} series (got T = {T})")
+        self.N, self.T, self.Kc = N, T, self._checked_kc(Kc)
+        self._allocate((N, T, self.Kc), device, _lib.lib().volt_gpcv_mt_markov_workspace_bytes(N, T, self.Kc), n_info=2, outputs={
+            "out": (12,), "grad_M": (N, T), "grad_c": (T,), "grad_rho": (N,), "grad_gamma": (N,), "grad_Lt": (T, T),
+            "grad_covar_factor": (T,), "grad_raw_var": (T,), "grad_abc": (T, 3, Kc) if Kc else None})
+        off = self.ptr - self.buf.data_ptr()
+        self.s = self.buf[off:off + 8 * N].view(torch.float64)
+
+    def fits(self, N, T, device, Kc=0):
+        return self._fits(device, N, T, Kc)
+
+
+def gpcv_mt_markov_step(x, vol, M, c, rho, gamma, Lt, covar_factor, raw_var, y, gh_x, gh_w,
+                        ws: GpcvMtMarkovWorkspace | None = None, abc=None, jitter: float = 1e-3, min_var: float = 1e-6,
+                        min_scale: float = 1e-3, w_ell: float = 1.0, w_kl: float = 1.0):
+    """The multi-task GPCV ELBO step in O(N T) for the Markov family q(F) = N(M, (Lp Lp')^-1 (x) Lt Lt') under the prior
+    N(1 c', K_M (x) K_t), K_M = vol min(x, x') + jitter 1 1' (include/volt_hip.h, volt_gpcv_mt_markov_step_f32).
+    x [N] the grid (0 <= x_0 < x_1 < ..), vol one value, M, y [N,T], c, covar_factor ([T] or [T,1]), raw_var [T], rho, gamma [N]
+    (gamma[N-1] is not read), Lt [T,T] (what lies above its diagonal is ignored); abc [T,3,Kc] given: the "cv" likelihood
+    with the TRANSFORMED a, b, c of every task.  Gradients are those of F = w_ell * ell - w_kl * KL (out[10]).
+    Returns the workspace: .out [12] (out[9] = dF/dvol), .grad_M, .grad_c, .grad_rho, .grad_gamma, .grad_Lt,
+    .grad_covar_factor, .grad_raw_var (.grad_abc with abc), .info [2], .s = diag P^-1."""
+    _need_gpu(x, vol, M, c, rho, gamma, Lt, covar_factor, raw_var, y, abc, gh_x, gh_w)
+    if M.ndim != 2:
+        raise ValueError("M must be [N,T]")
+    n, T = M.shape
+    if x.shape[-1] != n or x.numel() != n:
+        raise ValueError("x and M disagree on N")
+    x, vol, _ = _bm_args(x, vol, vol, 1, torch.float32)
+    M, y, Lt = _f32(M, (n, T)), _f32(y, (n, T)), _f32(Lt, (T, T))
+    rho, gamma = _f32(rho, (n,)), _f32(gamma, (n,))
+    c, cf, rv = _f32(c, (T,)), _f32(covar_factor, (T,)), _f32(raw_var, (T,))
+    gh_x, gh_w, quad = _quad_args(gh_x, gh_w, min_var, min_scale, w_ell, w_kl)
+    abc, Kc, sizeable = _abc_arg(abc, T, "T", reject=GpcvMtMarkovWorkspace._STEP)
+    ws = _step_workspace(GpcvMtMarkovWorkspace, ws, sizeable, n, T, M.device, Kc)
+    with torch.cuda.device(M.device):
+        _lib.check(_lib.lib().volt_gpcv_mt_markov_step_f32(
+            x.data_ptr(), vol.data_ptr(), float(jitter), M.data_ptr(), c.data_ptr(), rho.data_ptr(), gamma.data_ptr(),
+            Lt.data_ptr(), cf.data_ptr(), rv.data_ptr(), y.data_ptr(), abc.data_ptr() if abc is not None else None, Kc, *quad,
+            *_ptrs(ws, "out", "grad_M", "grad_c", "grad_rho", "grad_gamma", "grad_Lt", "grad_covar_factor", "grad_raw_var",
+                   "grad_abc", "info", "ptr"), n, T, _lib.stream_ptr()), "volt_gpcv_mt_markov_step")
     return ws
 
 

@@ -346,15 +346,28 @@ def LearnGPCV(train_x, train_y, train_iters=1000, printing=False, early_stopping
     return likelihood(model(train_x), return_gaussian=False).scale.mean(0).detach()      # :60-67
 
 
+GPCV_MT_SOLVERS = ("dense", "markov")
+
+
+def _check_gpcv_mt_solver(solver, kernel):
+    if solver not in GPCV_MT_SOLVERS:
+        raise ValueError(f"multi-task GPCV: solver must be one of {GPCV_MT_SOLVERS}, got {solver!r}")
+    _check_gpcv_solver(solver, kernel)
+
+
 def FitGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None, *, param="exp", K=1,
-                     train_likelihood=False):
+                     train_likelihood=False, solver="dense"):
     """LearnGPCV's fit (train_utils.py:15-58) over the JOINT model of T series that share the time grid
     (MultitaskVariationalGP, voltron/models/multi_task_variational_gp.py; the reference has no trainer for it):
     train_y [T,N+1] prices -> (model, likelihood, losses).  One HIP ELBO step per iteration factors the N x N prior ONCE
     for all T series (the batched FitGPCV factors it T times and keeps T variational roots).
     ``param``, ``K``, ``train_likelihood`` have FitGPCV's meaning: ``param="cv"`` fits the copula-process likelihood with
     one warp of K terms PER TASK (``batch_shape=[T]``; start-up values for K = 1 only), and its raw_a, raw_b, raw_c join
-    the one Adam group at LR_GPCV only with ``train_likelihood=True``.  The defaults are the "exp" loop."""
+    the one Adam group at LR_GPCV only with ``train_likelihood=True``.  The defaults are the "exp" loop.
+    ``solver="markov"`` (kernel "bm" only): the Markov variational family under the level-jitter Brownian prior of
+    ``MultitaskVariationalGP(prior_solver="markov")`` -- O(N T) time and memory, start-up values included, no N x N array
+    (csrc/gpcv_mt_markov.hip).  A different model from the dense solver's (another prior jitter, another family)."""
+    _check_gpcv_mt_solver(solver, kernel)
     from .kernels import BMKernel, FBMKernel
     from .likelihoods import VolatilityGaussianLikelihood
     from .models import MultitaskVariationalGP
@@ -367,7 +380,7 @@ def FitGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel=
     else:
         likelihood = VolatilityGaussianLikelihood(K=K, param=param, batch_shape=torch.Size([yy.shape[-1]])).to(train_x.device)
     covar_module = {"bm": BMKernel, "fbm": FBMKernel}[kernel]()
-    model = MultitaskVariationalGP(train_x, num_tasks=yy.shape[-1], covar_module=covar_module)
+    model = MultitaskVariationalGP(train_x, num_tasks=yy.shape[-1], covar_module=covar_module, prior_solver=solver)
     model.initialize_variational_parameters(likelihood, train_x, y=yy)
     params = list(model.parameters())
     if train_likelihood:                                 # (this model does not register its likelihood)
@@ -376,13 +389,15 @@ def FitGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel=
 
 
 def LearnGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None, *, param="exp", K=1,
-                       train_likelihood=False):
+                       train_likelihood=False, solver="dense"):
     """LearnGPCV for T series through the joint model: train_y [T,N+1] prices -> pred_scale [T,N] (the 10-sample
-    predictive scale of train_utils.py:60-67, per series).  ``param``, ``K``, ``train_likelihood``: see FitGPCVMultitask."""
+    predictive scale of train_utils.py:60-67, per series).  ``param``, ``K``, ``train_likelihood``, ``solver``: see
+    FitGPCVMultitask; ``solver="markov"`` is a handful of short launches per iteration and so launch-bound at every N."""
+    _check_gpcv_mt_solver(solver, kernel)
     # one series' N^3 chain whatever T is: the capture gate sees ONE [N] target
-    graph = _auto_graph(graph, train_y[0, 1:], n3_coeff=5.0 / 3.0)
+    graph = _auto_graph(graph, train_y[0, 1:], n3_coeff=5.0 / 3.0, launch_bound=solver == "markov")
     model, likelihood, _ = FitGPCVMultitask(train_x, train_y, train_iters=train_iters, printing=printing, kernel=kernel,
-                                            graph=graph, param=param, K=K, train_likelihood=train_likelihood)
+                                            graph=graph, param=param, K=K, train_likelihood=train_likelihood, solver=solver)
     return likelihood(model(train_x), return_gaussian=False).scale.mean(0).t().detach()
 
 

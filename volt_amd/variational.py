@@ -2,7 +2,8 @@
 volt_gpcv_cv_step_f32 ("cv"), volt_gpcv_bm_step_f32 (either likelihood under the lazy Brownian-motion prior of
 ``SingleTaskVariationalGP(prior_solver="linear")``), volt_gpcv_markov_step_f32 (either likelihood, the Markov variational
 family of ``prior_solver="markov"``: O(N) time and memory), volt_gpcv_mt_step_f32 (the multi-task model, "exp") and
-volt_gpcv_mt_cv_step_f32 (the multi-task model, "cv" with one warp per task).
+volt_gpcv_mt_cv_step_f32 (the multi-task model, "cv" with one warp per task) and volt_gpcv_mt_markov_step_f32 (the multi-task
+model with the Markov family of ``MultitaskVariationalGP(prior_solver="markov")``, either likelihood: O(N T)).
 
 The reference builds this stage from gpytorch parts (voltron/train_utils.py:20-44,
 voltron/models/single_task_variational_gp.py:69-122): ``CholeskyVariationalDistribution`` +
@@ -452,6 +453,88 @@ class _GPCVMtElbo(torch.autograd.Function):
         return tuple(grads.get(name) for name in _inputs(_GPCVMtElbo))
 
 
+class MultitaskMarkovVariationalLatent(MultitaskVariationalLatent):
+    """What ``MultitaskVariationalGP(prior_solver="markov")(inducing_points)`` returns: q(F) = N(M, P^-1 (x) S_t) with the
+    tridiagonal P = Lp Lp' of (log_diag_precision_root, coupling).  ``variance`` and ``rsample`` are O(N T) recurrences on the
+    device (csrc/gpcv_markov.hip's root kernels); the dense covariance is built only when ``_covar`` is asked for."""
+
+    def _root(self):
+        m = self.model
+        return m.log_diag_precision_root.detach().reshape(1, -1), m.coupling.detach().reshape(1, -1)
+
+    @property
+    def _covar(self):
+        rho, gamma = self._root()
+        d = rho[0].double().exp()
+        Lp = torch.diag_embed(d)
+        if d.shape[-1] > 1:
+            Lp = Lp + torch.diag_embed(gamma[0].double()[:-1] * d[:-1], offset=-1)
+        Lt = self.model.variational_task_covar_root.detach().tril().double()
+        return torch.kron(torch.linalg.inv(Lp @ Lp.mT).contiguous(), (Lt @ Lt.mT).contiguous()).to(self.loc.dtype)
+
+    @property
+    def variance(self):
+        """clamp(s_n st_t), s = diag P^-1 from the step's own scan, st = diag S_t.  DETACHED, like
+        ``MarkovVariationalLatent.variance``: the gradients of the variational parameters come from ``VariationalELBO``."""
+        s = ops.markov_root_var(*self._root())[0]                                              # [N] fp64
+        st = self.model.variational_task_covar_root.detach().tril().double().pow(2).sum(-1)
+        return (s.unsqueeze(-1) * st.unsqueeze(-2)).to(self.loc.dtype).clamp_min(MIN_VARIANCE)
+
+    def rsample(self, sample_shape=torch.Size(), base_samples=None):
+        """M + (Lp^-T E) Lt', E ~ N(0, I) of shape sample_shape + [N,T]: one backward recurrence per draw and task column
+        (ops.markov_root_draw over the S T columns), then the T x T product."""
+        n, T = self.loc.shape
+        base_samples = self._base_samples(sample_shape, base_samples)
+        rho, gamma = self._root()
+        E = base_samples.reshape(-1, n, T)
+        S = E.shape[0]
+        cols = E.transpose(1, 2).reshape(1, S * T, n)                                          # a column of E per draw
+        U = ops.markov_root_draw(torch.zeros_like(rho), rho, gamma, cols).reshape(S, T, n)     # (Lp^-T E)'
+        Lt = self.model.variational_task_covar_root.detach().tril().to(torch.float32)
+        F = torch.matmul(U.transpose(1, 2), Lt.mT)                                             # [S,N,T]
+        return (self.loc.detach() + F.reshape(base_samples.shape)).to(self.loc.dtype)
+
+
+class _GPCVMtMarkovElbo(torch.autograd.Function):
+    """F = w_ell ell - w_kl KL of the multi-task model with the Markov family (M, rho, gamma, Lt) under the prior
+    K_M (x) K_t, K_M = scale min(x, x') + j 1 1' (csrc/gpcv_mt_markov.hip: O(N T)).  The step returns dF/dscale itself
+    (out[9]); scale = sigmoid(raw_vol) stays in the graph, so its chain rule is autograd's, as in ``_GPCVMarkovElbo``."""
+
+    @staticmethod
+    def forward(ctx, M, rho, gamma, Lt, c, cf, rv, scale, x, y, raw_a, raw_b, raw_c, holder, num_gh, w_ell, w_kl):
+        n, T = M.shape
+        cv = raw_a is not None
+        ws = holder.workspace(ops.GpcvMtMarkovWorkspace, n, T, M.device, raw_a.shape[-1] if cv else 0)
+
+        def step(gh_x, gh_w, abc):
+            ops.gpcv_mt_markov_step(x, scale.detach(), M.detach(), c.detach(), rho.detach(), gamma.detach(), Lt.detach(),
+                                    cf.detach(), rv.detach(), y, gh_x, gh_w, ws, abc=abc, jitter=PRIOR_JITTER,
+                                    min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl)
+
+        def failed(abc):
+            info = ws.info.cpu()
+            # info[0]: F is not finite;  info[1]: a pivot of K_t.  There is no pivot on the x side
+            tensors = (scale, M, rho, gamma[..., :-1], Lt, c, cf, rv, y) + ((abc,) if cv else ())
+            what = "multi-task GPCV cv step (markov family)" if cv else "multi-task GPCV step (markov family)"
+            if int(info[1]) != 0:
+                _raise_step_failure(what, info[1:], tensors, "task covariance K_t")
+            _raise_step_failure(what, info[:1], tensors, None,
+                                message="F is not finite although no input is NaN: the variances exp(-2 log_diag_precision_root) "
+                                        "or the products of coupling^2 overflow, the prior's increments are not positive, or the "
+                                        "task root has a zero on its diagonal")
+        ctx.cf_shape, ctx.scale_shape = cf.shape, scale.shape
+        return _elbo_forward(ctx, ws, M.device, num_gh, (raw_a, raw_b, raw_c), T, step, failed,
+                             {"M": "grad_M", "rho": "grad_rho", "gamma": "grad_gamma", "Lt": "grad_Lt", "c": "grad_c",
+                              "cf": "grad_covar_factor", "rv": "grad_raw_var"}, {"dF_dscale": ws.out[9]}, ws.out[10])
+
+    @staticmethod
+    def backward(ctx, g):
+        grads, sv = _elbo_backward(ctx, g)
+        grads["cf"] = grads["cf"].reshape(ctx.cf_shape)
+        grads["scale"] = (g * sv["dF_dscale"]).reshape(ctx.scale_shape)
+        return tuple(grads.get(name) for name in _inputs(_GPCVMtMarkovElbo))
+
+
 class VariationalELBO(Module):
     """gpytorch.mlls.VariationalELBO(likelihood, model, num_data, beta=1.0, combine_terms=True) stand-in
     (train_utils.py:44): ``mll(model(train_x), yy)`` -> scalar ELBO (or [T] for a batched model)."""
@@ -481,7 +564,7 @@ class VariationalELBO(Module):
 
     # one workspace of each kind lives from iteration to iteration (a captured graph holds their addresses)
     _WS_ATTR = {ops.GpcvWorkspace: "_ws", ops.GpcvMtWorkspace: "_mt_ws", ops.GpcvBmWorkspace: "_bm_ws",
-                ops.GpcvMarkovWorkspace: "_markov_ws"}
+                ops.GpcvMarkovWorkspace: "_markov_ws", ops.GpcvMtMarkovWorkspace: "_mt_markov_ws"}
 
     def workspace(self, cls, *key):
         """The cached workspace of class ``cls`` if it fits ``key`` (the constructor's arguments), else a new one."""
@@ -532,6 +615,19 @@ class VariationalELBO(Module):
                                  K.to(torch.float32), target.to(torch.float32), *self._likelihood_raws(T, M), self, scale,
                                  *self._weights(n))
 
+    def _forward_multitask_markov(self, latent, target):
+        """``_forward_multitask`` for prior_solver="markov": the O(N T) step over (M, rho, gamma, Lt); nothing N x N is formed."""
+        model = latent.model
+        M = model.variational_mean
+        self._need_cuda(M)
+        n, T = M.shape
+        if tuple(target.shape) != (n, T):
+            raise ValueError(f"VariationalELBO: the multi-task target must be [N,T] = [{n},{T}] (got {tuple(target.shape)})")
+        c, cf, rv = model._task_params()
+        return _GPCVMtMarkovElbo.apply(M, model.log_diag_precision_root, model.coupling, model.variational_task_covar_root, c,
+                                       cf, rv, model.data_kernel.vol, model.inducing_points.reshape(-1),
+                                       target.to(torch.float32), *self._likelihood_raws(T, M), self, *self._weights(n))
+
     def _forward_markov(self, latent, target):
         """prior_solver="markov": the O(N) step over (m, rho, gamma); nothing N x N is formed."""
         model = latent.model
@@ -549,6 +645,8 @@ class VariationalELBO(Module):
         return res.reshape(m.shape[:-1]) if m.ndim > 1 else res.reshape(())
 
     def forward(self, approximate_dist_f, target):
+        if isinstance(approximate_dist_f, MultitaskMarkovVariationalLatent):
+            return self._forward_multitask_markov(approximate_dist_f, target)
         if isinstance(approximate_dist_f, MultitaskVariationalLatent):
             return self._forward_multitask(approximate_dist_f, target)
         if isinstance(approximate_dist_f, MarkovVariationalLatent):
