@@ -660,6 +660,40 @@ int volt_markov_root_draw_f32(const float* m, const float* rho, const float* gam
                               int N, void* stream);
 int volt_markov_root_var_f32(const float* rho, const float* gamma, double* var, int B, int N, void* stream);
 
+/* ---- The Markov GPCV away from its grid in O(N + S H): mean, variance and joint path draws of f at H test points
+ * (SingleTaskVariationalGP / MultitaskVariationalGP(prior_solver="markov")(x); csrc/markov_predict.hip has the
+ * formulas and the plan's steps).  Given u ~ q, f(xi) is a Brownian bridge between the neighbouring knots of the grid x [N],
+ * free Brownian motion beyond x_{N-1}, and a bridge from (-jitter / vol, level mu, variance 0) before x_0.
+ *
+ * volt_markov_predict_plan_f32: x [N] and xs [H] (ascending, >= 0, finite; duplicates allowed) are shared by the B series;
+ * vol, mu [B]; m, rho, gamma [B,N] (gamma[., N-1] is never read).  Outputs, all fp64: mean, var_q (the q part A P^-1 A'),
+ * var_p (the bridge part K** - A K_uu A') [B,H]; the draw plan coef [B,3H+1,3] and code [B,3H+1] (8 h + op), of which
+ * steps[b] <= 3 H + 1 entries are steps (the rest no-ops); steps depends on (x, xs) alone.  var_q at a test point ON a knot is
+ * volt_markov_root_var_f32's s there bit for bit, and mean is m there.
+ * info[b]: 0; -(h + 1) for the first xs_h that is NaN, infinite, negative or below its predecessor -- the series' outputs are
+ * then NaN and steps[b] = 0; 1 where a variance (or s_0) is not finite.
+ * workspace: volt_markov_predict_workspace_bytes(B, N, H) bytes (0 for a shape out of range), 256-byte aligned, O(B (N + H)),
+ * no initialisation call, fully written before it is read.  ONE launch, one workgroup per series; no atomics, bitwise
+ * repeatable, replays from a hipGraph.  1 <= B <= 65535, N >= 1, 1 <= H <= 2^24; 64-bit indices.
+ * Argument errors: -1 x, -2 xs, -3 vol, -5 mu, -6 m, -7 rho, -8 gamma, -9 mean, -10 var_q, -11 var_p, -12 coef, -13 code,
+ * -14 steps, -15 info NULL; -16 workspace NULL or not 256-byte aligned; -17 B, -18 N, -19 H out of range.
+ *
+ * volt_markov_predict_draw_f32: out[b,s,:] = the plan run on eps[b,s,:]: eps [B,S,E] with E >= steps[b] base samples per
+ * path (N(0,1) for a joint draw; the first steps[b] of a row are read), out [B,S,H] fp32, fp64 arithmetic rounded once.
+ * flags: VOLT_DRAW_EXP writes exp(out); VOLT_PREDICT_NO_CHAIN / VOLT_PREDICT_NO_BRIDGE zero the noise of the chain steps
+ * (the q part) / of the bridge steps, the mean is added either way.  A series whose steps[b] is 0 (a failed plan) or exceeds
+ * E gets NaN.  One lane per path, one wave per 64 paths of one series, eps and out staged through LDS; ONE launch, no workspace.
+ * Argument errors: -1 mean, -2 coef, -3 code, -4 steps, -5 eps, -6 out NULL; -7 B outside 1 .. 65535; -8 S < 1; -9 H out of
+ * range; -10 E < 1; -11 an unknown flag. */
+#define VOLT_PREDICT_NO_CHAIN 2   /* flag bits of volt_markov_predict_draw_f32 (beside VOLT_DRAW_EXP) */
+#define VOLT_PREDICT_NO_BRIDGE 4
+size_t volt_markov_predict_workspace_bytes(int B, int N, int H);
+int volt_markov_predict_plan_f32(const float* x, const float* xs, const float* vol, float jitter, const float* mu, const float* m,
+                                 const float* rho, const float* gamma, double* mean, double* var_q, double* var_p, double* coef,
+                                 int* code, int* steps, int* info, void* workspace, int B, int N, int H, void* stream);
+int volt_markov_predict_draw_f32(const double* mean, const double* coef, const int* code, const int* steps, const float* eps,
+                                 float* out, int B, int S, int H, int E, int flags, void* stream);
+
 /* ---- Multi-task GPCV ELBO step in O(N T (Q + T) + T^3): the Markov variational family under the Kronecker prior
  * (MultitaskVariationalGP(prior_solver="markov"); csrc/gpcv_mt_markov.hip has the closed forms).
  * Prior: p(F) = N(mu, K_M (x) K_t) over the grid x [N] (0 <= x_0 < x_1 < ..), K_M = vol min(x, x') + jitter 1 1' as in

@@ -108,8 +108,12 @@ _SIGS = {
     "volt_gpcv_mt_markov_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "volt_gpcv_mt_markov_step_f32": (C.c_int, [_ptr, _ptr, _f32] + [_ptr] * 9 + [_i32, _ptr, _ptr, _i32, _f32, _f32, _f32, _f32]
                                      + [_ptr] * 11 + [_i32, _i32, _ptr]),
+    "volt_markov_predict_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "volt_markov_predict_plan_f32": (C.c_int, [_ptr, _ptr, _ptr, _f32] + [_ptr] * 12 + [_i32, _i32, _i32, _ptr]),
+    "volt_markov_predict_draw_f32": (C.c_int, [_ptr] * 6 + [_i32] * 5 + [_ptr]),
 }
 DRAW_EXP = 1                                            # include/volt_hip.h: VOLT_DRAW_EXP
+PREDICT_NO_CHAIN, PREDICT_NO_BRIDGE = 2, 4              # include/volt_hip.h: VOLT_PREDICT_NO_CHAIN, VOLT_PREDICT_NO_BRIDGE
 SUMMARY_MAX_S, SUMMARY_EXP = 32768, 1                   # include/volt_hip.h: VOLT_SUMMARY_MAX_S, VOLT_SUMMARY_EXP
 
 # measurement / tuning hooks: include/volt_hip_tune.h, not part of the drop-in boundary

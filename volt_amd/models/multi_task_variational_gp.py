@@ -19,7 +19,9 @@ Stated differences from the reference file (README, quirk table):
   Markov structure), and the variational family is q(F) = N(M, P^-1 (x) S_t) with a TRIDIAGONAL precision P = Lp Lp':
   parameters ``variational_mean`` [N,T], ``log_diag_precision_root`` [N], ``coupling`` [N] (its last entry is never read),
   ``variational_task_covar_root`` [T,T] -- there is no ``variational_covar_root``.  The start-up values take an O(N T) route
-  (``_initialize_markov``); no N x N tensor exists anywhere on this route.
+  (``_initialize_markov``); no N x N tensor exists anywhere on this route.  This solver alone also answers AWAY from the
+  inducing grid: ``model(x)`` for any x [H] or [H,1] >= 0 returns ``MultitaskMarkovPredictiveLatent`` over [H,T] (mean,
+  variance, joint draws; csrc/markov_predict.hip); ``prior_solver="dense"`` keeps raising there.
 The reference has no trainer for this class; train_utils.FitGPCVMultitask is LearnGPCV's loop over it.  gpytorch is not
 installed here; both branches of ``initialize_variational_parameters`` are pinned to the reference's own code, executed
 over stand-ins, by tests/golden/mt_gpcv_cv.npz."""
@@ -31,8 +33,8 @@ from ..gp import ConstantMean, EqualMemo, Module, MultitaskMean, _dense, check_g
 from ..safe import _safe_factor
 from ..kernels.BMKernel import BMKernel
 from ..kernels.MultitaskKernel import IndexKernel
-from ..variational import (MIN_VARIANCE, PRIOR_JITTER, MultitaskMarkovVariationalLatent, MultitaskVariationalLatent,
-                           _gauss_hermite)
+from ..variational import (MIN_VARIANCE, PRIOR_JITTER, MultitaskMarkovPredictiveLatent, MultitaskMarkovVariationalLatent,
+                           MultitaskVariationalLatent, _gauss_hermite, _predict_points)
 from .single_task_variational_gp import markov_startup_factor
 
 
@@ -122,6 +124,8 @@ class MultitaskVariationalGP(Module):
         xs = x.reshape(Z.shape) if x.numel() == Z.numel() else x
         if xs.shape == Z.shape and self._eq_memo.equal(x, Z, lambda: torch.equal(xs, Z)):
             return MultitaskMarkovVariationalLatent(self) if self.prior_solver == "markov" else MultitaskVariationalLatent(self)
+        if self.prior_solver == "markov":                        # away from the grid: O(N + H) on the x side
+            return MultitaskMarkovPredictiveLatent(self, _predict_points(x, "MultitaskVariationalGP(prior_solver='markov')"))
         return self.forward(x, **kwargs)
 
     def initialize_variational_parameters(self, likelihood, x, f=None, y=None):

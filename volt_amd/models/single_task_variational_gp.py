@@ -13,7 +13,8 @@ from ..safe import _safe_factor
 from ..kernels.BMKernel import BMKernel
 from ..likelihoods import VolatilityGaussianLikelihood  # noqa: F401  (re-exported like the reference's module namespace)
 from ..variational import (PRIOR_JITTER, CholeskyVariationalDistribution, MarkovVariationalDistribution,
-                           MarkovVariationalLatent, UnwhitenedVariationalStrategy, VariationalLatent)
+                           MarkovPredictiveLatent, MarkovVariationalLatent, UnwhitenedVariationalStrategy, VariationalLatent,
+                           _predict_points)
 
 
 class SingleTaskVariationalGP(Module):
@@ -27,7 +28,10 @@ class SingleTaskVariationalGP(Module):
     ``variational_mean``, ``log_diag_precision_root``, ``coupling``) and the prior is Brownian motion started from an
     N(0, 1e-3) LEVEL, K_M = vol min(x, x') + 1e-3 1 1' -- not the other solvers' K + 1e-3 I, whose diagonal jitter destroys the
     Markov structure; a jitter on the starting level keeps the precision exactly tridiagonal and x_0 = 0 valid.  The
-    start-up values take an O(N) route (``_initialize_markov``); no N x N tensor exists anywhere on this route."""
+    start-up values take an O(N) route (``_initialize_markov``); no N x N tensor exists anywhere on this route.
+    Only this solver answers AWAY from the inducing grid: ``model(x)`` for any x [H] or [H,1] >= 0, in any order, returns
+    ``MarkovPredictiveLatent`` (mean, variance, joint draws in O(N + S H); csrc/markov_predict.hip) -- between
+    two observations or beyond the last one.  "dense" and "linear" raise NotImplementedError there."""
     PRIOR_SOLVERS = ("dense", "linear", "markov")
 
     def __init__(self, init_points=None, likelihood=None, learn_inducing_locations=True, covar_module=None,
@@ -91,6 +95,8 @@ class SingleTaskVariationalGP(Module):
         # LearnGPCV passes the same train_x object on every iteration (train_utils.py:51): compare once, not 1000 times
         if x.shape == Z.shape and self._eq_memo.equal(arg, Z, lambda: torch.equal(x, Z)):
             return MarkovVariationalLatent(self) if self.prior_solver == "markov" else VariationalLatent(self)
+        if self.prior_solver == "markov":                             # away from the grid: O(N + H), csrc/markov_predict.hip
+            return MarkovPredictiveLatent(self, _predict_points(arg, 'SingleTaskVariationalGP(prior_solver="markov")'))
         raise NotImplementedError("SingleTaskVariationalGP(x) away from the inducing points is outside the accelerated "
                                   "path: LearnGPCV only evaluates the model at train_x (train_utils.py:51,60)")
 

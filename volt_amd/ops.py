@@ -829,6 +829,100 @@ def markov_root_var(rho: torch.Tensor, gamma: torch.Tensor) -> torch.Tensor:
     return var
 
 
+class MarkovPredictPlan:
+    """What ``markov_predict_plan`` returns.  In the CALLER's order of the test points: ``mean``, ``var_q`` (the q part
+    A P^-1 A'), ``var_p`` (the bridge part K** - A K_uu A') [B,H] fp64.  ``info`` [B] int32 (0; -(h + 1): the h-th point of the
+    SORTED list is NaN, infinite, negative -- the series' results are then NaN; 1: a variance is not finite).  The draw plan
+    itself (``coef``, ``code``, ``steps``, over the sorted points) is for ``markov_predict_draw``; ``E``: the base samples a
+    path consumes, <= 3 H + 1 -- read from the device once (ONE HOST SYNCHRONISATION, at the first use: code that sizes its base
+    samples by it cannot be captured in a graph unless E was read before the capture; ``steps`` depends on (x, xs) alone)."""
+
+    def __init__(self, B, N, H, mean, var_q, var_p, coef, code, steps, info, order):
+        self.B, self.N, self.H = B, N, H
+        self._mean, self._var_q, self._var_p = mean, var_q, var_p      # (over the sorted points)
+        self.coef, self.code, self.steps, self.info, self.order = coef, code, steps, info, order
+        self._E = None
+
+    def _caller_order(self, t):
+        out = torch.empty_like(t)
+        out[:, self.order] = t
+        return out
+
+    mean = property(lambda self: self._caller_order(self._mean))
+    var_q = property(lambda self: self._caller_order(self._var_q))
+    var_p = property(lambda self: self._caller_order(self._var_p))
+
+    @property
+    def E(self):
+        if self._E is None:
+            self._E = int(self.steps.max().item())
+        return self._E
+
+
+def markov_predict_plan(x, xs, vol, mu, m, rho, gamma, jitter: float = 1e-3) -> MarkovPredictPlan:
+    """The Markov GPCV's q(f(xs)) at H test points away from its grid, in O(N + H log N) per series and ONE launch
+    (volt_markov_predict_plan_f32): x [N] the grid, xs [H] the test points in ANY order (sorted here, stably; every
+    result comes back in the caller's order), >= 0; vol, mu [B] (or one value): the prior's scale and constant; m, rho, gamma
+    [B,N] the family's parameters (gamma[:, N-1] is not read); jitter: the prior's level variance.  No gradients."""
+    _need_gpu(x, xs, vol, mu, m, rho, gamma)
+    if m.ndim != 2 or rho.shape != m.shape or gamma.shape != m.shape:
+        raise ValueError("m, rho and gamma must all be [B,N]")
+    B, n = m.shape
+    if x.ndim != 1 or x.shape[0] != n:
+        raise ValueError("x must be [N] with m's N")
+    if xs.ndim != 1 or xs.shape[0] < 1:
+        raise ValueError("xs must be [H], H >= 1")
+    H = xs.shape[0]
+    nbytes = _lib.lib().volt_markov_predict_workspace_bytes(B, n, H)
+    if nbytes == 0:
+        raise ValueError(f"markov_predict_plan: (B, N, H) = {(B, n, H)} is out of range (1 <= B <= 65535, N >= 1, 1 <= H <= 2^24)")
+    dev = m.device
+    xs_sorted, order = torch.sort(xs.detach().to(torch.float32), stable=True)
+    x = x.detach().to(torch.float32).contiguous()
+    vol, mu = (torch.as_tensor(t, device=dev).detach().to(torch.float32).reshape(-1).expand(B).contiguous() for t in (vol, mu))
+    m, rho, gamma = (_f32(t, (B, n)) for t in (m, rho, gamma))
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    mean, var_q, var_p, coef = f64(B, H), f64(B, H), f64(B, H), f64(B, 3 * H + 1, 3)
+    code, steps, info = i32(B, 3 * H + 1), i32(B), i32(B)
+    _, ws = _scratch(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().volt_markov_predict_plan_f32(
+            x.data_ptr(), xs_sorted.data_ptr(), vol.data_ptr(), float(jitter), mu.data_ptr(), m.data_ptr(), rho.data_ptr(),
+            gamma.data_ptr(), mean.data_ptr(), var_q.data_ptr(), var_p.data_ptr(), coef.data_ptr(), code.data_ptr(),
+            steps.data_ptr(), info.data_ptr(), ws, B, n, H, _lib.stream_ptr()), "volt_markov_predict_plan")
+    return MarkovPredictPlan(B, n, H, mean, var_q, var_p, coef, code, steps, info, order)
+
+
+_PREDICT_PARTS = {"both": 0, "chain": _lib.PREDICT_NO_BRIDGE, "bridge": _lib.PREDICT_NO_CHAIN}
+
+
+def markov_predict_draw(plan: MarkovPredictPlan, eps: torch.Tensor, exp: bool = False, part: str = "both") -> torch.Tensor:
+    """Joint draws of f at the plan's test points in O(S H) (volt_markov_predict_draw_f32): eps [B,S,E'] with E' >= plan.E base
+    samples per path (N(0,1) for a draw; columns beyond plan.E are not read) -> [B,S,H] fp32 in the caller's order of the test
+    points.  ``exp``: the exponential of the draw, computed in double and rounded once.  ``part``: "both"; "chain": mean + the
+    q part alone (covariance A P^-1 A'); "bridge": mean + the bridge part alone (K** - A K_uu A') -- the two use disjoint
+    columns of eps.  A series whose plan failed (plan.info < 0) comes back NaN."""
+    _need_gpu(eps)
+    if part not in _PREDICT_PARTS:
+        raise ValueError(f"part must be one of {tuple(_PREDICT_PARTS)}, got {part!r}")
+    if eps.ndim != 3 or eps.shape[0] != plan.B or eps.shape[1] < 1 or eps.shape[2] < 1:
+        raise ValueError(f"eps must be [B,S,E] with B = {plan.B}")
+    _, S, E = eps.shape
+    eps = eps.detach().to(torch.float32).contiguous()
+    out = torch.empty(plan.B, S, plan.H, dtype=torch.float32, device=eps.device)
+    with torch.cuda.device(eps.device):
+        _lib.check(_lib.lib().volt_markov_predict_draw_f32(
+            plan._mean.data_ptr(), plan.coef.data_ptr(), plan.code.data_ptr(), plan.steps.data_ptr(), eps.data_ptr(),
+            out.data_ptr(), plan.B, S, plan.H, E, (_lib.DRAW_EXP if exp else 0) | _PREDICT_PARTS[part], _lib.stream_ptr()),
+            "volt_markov_predict_draw")
+    if plan.H > 1:                                                     # back to the caller's order
+        res = torch.empty_like(out)
+        res[:, :, plan.order] = out
+        return res
+    return out
+
+
 GPCV_MT_T_MAX = 64                 # include/volt_hip.h: volt_gpcv_mt_step_f32 takes 1 <= T <= 64 series
 
 

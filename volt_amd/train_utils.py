@@ -346,6 +346,18 @@ def LearnGPCV(train_x, train_y, train_iters=1000, printing=False, early_stopping
     return likelihood(model(train_x), return_gaussian=False).scale.mean(0).detach()      # :60-67
 
 
+def PredictGPCV(model, likelihood, test_x, nsample=10):
+    """Vol paths of a fitted GPCV at ``test_x`` -- between the observations or beyond the last one: [nsample, (T,) H], the
+    likelihood's ``scale`` at ``nsample`` JOINT draws of f(test_x) from the model's own q (``model(test_x).rsample``), which is
+    what LearnGPCV averages at train_x.  ``model`` from ``FitGPCV(solver="markov")`` (the only family that answers away from
+    its grid; csrc/markov_predict.hip, O(N + nsample H)); test_x [H] or [H,1], >= 0, any order.  The paths can be handed to
+    ``GeneratePrediction(..., pred_vol=...)``.  It uses NO second-stage vol model: nothing is refitted to a collapsed path, and
+    the posterior variance the GPCV computed is kept in the draws."""
+    with torch.no_grad():
+        f = model(test_x).rsample(torch.Size([int(nsample)]))
+        return likelihood(f, return_gaussian=False).scale.detach()
+
+
 GPCV_MT_SOLVERS = ("dense", "markov")
 
 

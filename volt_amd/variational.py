@@ -4,6 +4,8 @@ volt_gpcv_cv_step_f32 ("cv"), volt_gpcv_bm_step_f32 (either likelihood under the
 family of ``prior_solver="markov"``: O(N) time and memory), volt_gpcv_mt_step_f32 (the multi-task model, "exp") and
 volt_gpcv_mt_cv_step_f32 (the multi-task model, "cv" with one warp per task) and volt_gpcv_mt_markov_step_f32 (the multi-task
 model with the Markov family of ``MultitaskVariationalGP(prior_solver="markov")``, either likelihood: O(N T)).
+The two Markov models also answer AWAY from the inducing grid (``MarkovPredictiveLatent``, ``MultitaskMarkovPredictiveLatent``:
+volt_markov_predict_plan_f32 / volt_markov_predict_draw_f32, O(N + S H)).
 
 The reference builds this stage from gpytorch parts (voltron/train_utils.py:20-44,
 voltron/models/single_task_variational_gp.py:69-122): ``CholeskyVariationalDistribution`` +
@@ -188,6 +190,75 @@ class MarkovVariationalLatent(MultivariateNormal):
         eps = base_samples.reshape(-1, B, n).transpose(0, 1)                                   # [B,S,N]
         f = ops.markov_root_draw(m, rho, gamma, eps)
         return f.transpose(0, 1).reshape(base_samples.shape).to(self.loc.dtype)
+
+
+def _predict_points(x, who):
+    """The test points of a prediction away from the grid as a flat [H] tensor: [H] or [H,1], finite, >= 0, any order."""
+    if not torch.is_tensor(x) or x.ndim not in (1, 2) or (x.ndim == 2 and x.shape[-1] != 1) or x.numel() < 1:
+        raise ValueError(f"{who}: test points must be [H] or [H,1] with H >= 1, got shape "
+                         f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    xs = x.detach().reshape(-1)
+    if not bool((torch.isfinite(xs) & (xs >= 0)).all()):
+        raise ValueError(f"{who}: test points must be finite and >= 0 (the Brownian prior lives on x >= 0)")
+    return xs
+
+
+class MarkovPredictiveLatent(MultivariateNormal):
+    """What ``SingleTaskVariationalGP(prior_solver="markov")(x)`` returns for ``x`` other than the inducing grid: q(f(x)), the
+    Gauss-Markov q(u) carried through the Brownian prior's conditional -- a bridge between the neighbouring knots, free Brownian
+    motion beyond the last one (csrc/markov_predict.hip).  ``loc`` / ``variance`` [.., H] come from ONE O(N + H)
+    launch made here; ``rsample`` draws joint paths in O(H) each.  No N x N or H x H array exists unless ``_covar`` is asked for
+    (tests and small H).  NO autograd: everything is detached -- the parameters' gradients come from ``VariationalELBO``."""
+
+    def __init__(self, model, xs):
+        latent = MarkovVariationalLatent(model)
+        m, rho, gamma = latent._flat()
+        Z = model.variational_strategy.inducing_points
+        B = m.shape[0]
+        mu = model.mean_module.constant.detach().reshape(-1)
+        vol = model.covar_module.vol.detach().reshape(-1)
+        if mu.numel() not in (1, B) or vol.numel() not in (1, B):
+            raise ValueError("MarkovPredictiveLatent: the mean constant and the kernel's vol must be one value or one per series")
+        self.model, self._batch, self._xs = model, latent.loc.shape[:-1], xs
+        self.plan = ops.markov_predict_plan(Z.reshape(-1), xs, vol, mu, m, rho, gamma, jitter=PRIOR_JITTER)
+        self._dtype = latent.loc.dtype
+        self.loc = self.plan.mean.to(self._dtype).reshape(*self._batch, -1)
+
+    @property
+    def variance(self):
+        """var_q + var_p, clamped at MIN_VARIANCE; detached, like ``MarkovVariationalLatent.variance``."""
+        v = self.plan.var_q + self.plan.var_p
+        return v.to(self._dtype).reshape(self.loc.shape).clamp_min(MIN_VARIANCE)
+
+    @property
+    def _covar(self):
+        """Dense [.., H, H] from the dense definition A P^-1 A' + K** - A K_uu A' in fp64 (tests and small H only)."""
+        model = self.model
+        x = model.variational_strategy.inducing_points.reshape(-1).double()
+        xs = self._xs.double()
+        S = MarkovVariationalLatent(model)._covar.double().reshape(-1, x.shape[0], x.shape[0])
+        vol = model.covar_module.vol.detach().double().reshape(-1, 1, 1)
+        k = lambda a, b: vol * torch.minimum(a.unsqueeze(-1), b.unsqueeze(-2)) + PRIOR_JITTER
+        Kuu, Ksu, Kss = k(x, x), k(xs, x), k(xs, xs)
+        A = torch.linalg.solve(Kuu, Ksu.mT).mT
+        C = A @ S @ A.mT + Kss - A @ Kuu @ A.mT
+        return C.reshape(*self._batch, self.plan.H, self.plan.H).to(self._dtype)
+
+    def rsample(self, sample_shape=torch.Size(), base_samples=None):
+        """Joint draws of f(x), shape sample_shape + loc.shape.  ``base_samples``: N(0, 1) of shape sample_shape + [.., E],
+        E = plan.E <= 3 H + 1 numbers per path (NOT H: a path is the image of the knot chain's and the bridges' innovations).
+        E is read from the device at the first use (ops.MarkovPredictPlan.E: one host synchronisation), so
+        ``model(x).rsample(..)`` as a whole cannot be captured in a graph; with ``plan.E`` read beforehand and ``base_samples``
+        given, the draw alone can (ops.markov_predict_draw makes no host read)."""
+        E = self.plan.E
+        if base_samples is None:
+            base_samples = torch.randn(*torch.Size(sample_shape), *self._batch, E, dtype=torch.float32, device=self.loc.device)
+        elif base_samples.shape[-1] < E or tuple(base_samples.shape[base_samples.ndim - 1 - len(self._batch):-1]) != tuple(self._batch):
+            raise ValueError(f"base_samples must be sample_shape + {tuple(self._batch) + (E,)}, got {tuple(base_samples.shape)}")
+        lead = base_samples.shape[:base_samples.ndim - 1 - len(self._batch)]
+        eps = base_samples.reshape(-1, self.plan.B, base_samples.shape[-1]).transpose(0, 1)            # [B,S,E]
+        f = ops.markov_predict_draw(self.plan, eps)                                                    # [B,S,H]
+        return f.transpose(0, 1).reshape(*lead, *self._batch, self.plan.H).to(self._dtype)
 
 
 def _dkl_dscale_grad(o, c, n, w_kl, g):
@@ -493,6 +564,75 @@ class MultitaskMarkovVariationalLatent(MultitaskVariationalLatent):
         Lt = self.model.variational_task_covar_root.detach().tril().to(torch.float32)
         F = torch.matmul(U.transpose(1, 2), Lt.mT)                                             # [S,N,T]
         return (self.loc.detach() + F.reshape(base_samples.shape)).to(self.loc.dtype)
+
+
+class MultitaskMarkovPredictiveLatent(MultitaskVariationalLatent):
+    """What ``MultitaskVariationalGP(prior_solver="markov")(x)`` returns for ``x`` other than the inducing grid: q(F(x)) over
+    [H,T], covariance (A P^-1 A') (x) S_t + (K** - A K_uu A') (x) K_t with K_t = f f' + diag softplus(raw_var) as the step
+    defines it.  The x side is csrc/markov_predict.hip: one plan over the T columns of M (the mean: task t's
+    constant is the level before x_0) and one over a single zero-mean series (the variances and the draws: exact deviations,
+    no mean to subtract) -- so the three N-length scans, which do not depend on the mean, run T + 1 times instead of once, in
+    two launches; the two T x T products of ``rsample`` stay in torch.  NO autograd, like ``MarkovPredictiveLatent``."""
+
+    def __init__(self, model, xs):
+        self.model, self._xs = model, xs
+        M = model.variational_mean.detach()
+        n, T = M.shape
+        rho, gamma = model.log_diag_precision_root.detach().reshape(1, n), model.coupling.detach().reshape(1, n)
+        c, cf, rv = (t.detach().reshape(-1) for t in model._task_params())
+        x, vol = model.inducing_points.reshape(-1), model.data_kernel.vol.detach().reshape(-1)
+        self._mean_plan = ops.markov_predict_plan(x, xs, vol, c, M.mT, rho.expand(T, n), gamma.expand(T, n), jitter=PRIOR_JITTER)
+        zero = torch.zeros(1, n, dtype=torch.float32, device=M.device)
+        self.plan = ops.markov_predict_plan(x, xs, vol, zero[:, 0], zero, rho, gamma, jitter=PRIOR_JITTER)
+        self._dtype = M.dtype
+        self.loc = self._mean_plan.mean.mT.to(self._dtype).contiguous()                       # [H,T]
+        Lt = model.variational_task_covar_root.detach().tril().double()
+        self._St = Lt @ Lt.mT
+        self._Kt = torch.outer(cf.double(), cf.double()) + torch.diag(torch.nn.functional.softplus(rv.double()))
+        self._Lt = Lt
+
+    @property
+    def variance(self):
+        """var_q diag S_t + var_p diag K_t [H,T], clamped at MIN_VARIANCE; detached."""
+        v = torch.outer(self.plan.var_q[0], self._St.diagonal()) + torch.outer(self.plan.var_p[0], self._Kt.diagonal())
+        return v.to(self._dtype).clamp_min(MIN_VARIANCE)
+
+    @property
+    def _covar(self):
+        """Dense (H T) x (H T), element (h, t) at h T + t, from the dense definition in fp64 (tests and small H only)."""
+        m = self.model
+        x, xs = m.inducing_points.reshape(-1).double(), self._xs.double()
+        n = x.shape[0]
+        d = m.log_diag_precision_root.detach().double().exp()
+        Lp = torch.diag_embed(d)
+        if n > 1:
+            Lp = Lp + torch.diag_embed(m.coupling.detach().double()[:-1] * d[:-1], offset=-1)
+        S = torch.linalg.inv(Lp @ Lp.mT)
+        vol = m.data_kernel.vol.detach().double().reshape(())
+        k = lambda a, b: vol * torch.minimum(a.unsqueeze(-1), b.unsqueeze(-2)) + PRIOR_JITTER
+        Kuu, Ksu, Kss = k(x, x), k(xs, x), k(xs, xs)
+        A = torch.linalg.solve(Kuu, Ksu.mT).mT
+        C = torch.kron((A @ S @ A.mT).contiguous(), self._St) + torch.kron((Kss - A @ Kuu @ A.mT).contiguous(), self._Kt)
+        return C.to(self._dtype)
+
+    def rsample(self, sample_shape=torch.Size(), base_samples=None):
+        """Joint draws of F(x), shape sample_shape + [H,T]: T unit chains mixed by Lt' plus T unit bridges mixed by chol(K_t)'.
+        ``base_samples``: N(0, 1) of shape sample_shape + [T, E], E = plan.E <= 3 H + 1 -- the chain and the bridge steps read
+        disjoint columns of a row, so one row serves both.  E is read from the device at the first use (one host synchronisation:
+        see ``MarkovPredictiveLatent.rsample``)."""
+        H, T = self.loc.shape
+        E = self.plan.E
+        if base_samples is None:
+            base_samples = torch.randn(*torch.Size(sample_shape), T, E, dtype=torch.float32, device=self.loc.device)
+        elif base_samples.ndim < 2 or base_samples.shape[-2] != T or base_samples.shape[-1] < E:
+            raise ValueError(f"base_samples must be sample_shape + {(T, E)}, got {tuple(base_samples.shape)}")
+        lead = base_samples.shape[:-2]
+        eps = base_samples.reshape(1, -1, base_samples.shape[-1])                                      # [1, S T, E]
+        Uc = ops.markov_predict_draw(self.plan, eps, part="chain").reshape(-1, T, H)                   # (zero mean: the parts alone)
+        Ub = ops.markov_predict_draw(self.plan, eps, part="bridge").reshape(-1, T, H)
+        Ck = torch.linalg.cholesky(self._Kt).to(torch.float32)
+        F = torch.matmul(Uc.transpose(1, 2), self._Lt.to(torch.float32).mT) + torch.matmul(Ub.transpose(1, 2), Ck.mT)   # [S,H,T]
+        return (self.loc + F).reshape(*lead, H, T).to(self._dtype)
 
 
 class _GPCVMtMarkovElbo(torch.autograd.Function):
