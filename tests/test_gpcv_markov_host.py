@@ -372,9 +372,10 @@ def test_markov_kernels_cross_compile_without_scratch_or_spills(tmp_path):
             print(name, "VGPRs", re.search(r" VGPRs: (\d+)", b).group(1), "occupancy",
                   re.search(r"Occupancy \[waves/SIMD\]: (\d+)", b).group(1), "static LDS",
                   re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
-    with open(src) as fh:
-        text = fh.read()
-    assert "atomic" not in text.replace("no atomics", "")
+    for path in (src, os.path.join(ROOT, "volt_amd", "csrc", "markov_scan.h")):      # (the scan and the sums live in the header)
+        with open(path) as fh:
+            text = fh.read()
+        assert "atomic" not in text.replace("no atomics", ""), path
     lib = os.path.join(ROOT, "volt_amd", "csrc", "libvolt_hip.so")
     from volt_amd import _lib
     _lib.lib()

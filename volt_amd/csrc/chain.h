@@ -52,4 +52,44 @@ __device__ __forceinline__ double chain_z_fwd(double c, double zprev, double u) 
 // backward  w_i = z_i / d_i + rho_i w_{i+1},  rho_i = s / d_i
 __device__ __forceinline__ double chain_z_back(double rho, double wnext, double z, double inv) { return __builtin_fma(rho, wnext, z * inv); }
 
+// ---- the staged tile of the draw kernels (chain_draw.hip, markov_predict.hip): a wave moves rows [0, rows) x columns [0, cnt)
+// between global memory (row r at src(r) / dst(r), unit stride) and tile[r][CH + 1] in LDS, V elements per global access
+template <typename T, int V, int CH, typename RowPtr>
+__device__ __forceinline__ void tile_load(T* tile, RowPtr src, int rows, int cnt, int lane) {
+    typedef T vec_t __attribute__((ext_vector_type(V)));
+    constexpr int NV = CH / V, LD = CH + 1;
+    for (int idx = lane; idx < 64 * NV; idx += 64) {
+        const int r = idx / NV, c = (idx % NV) * V;
+        const T* s = src(r) + c;                     // (formed by every lane: a row pointer may come from a cross-lane read)
+        if (r < rows && c < cnt) {
+            if constexpr (V > 1) {
+                const vec_t v = *reinterpret_cast<const vec_t*>(s);
+#pragma unroll
+                for (int u = 0; u < V; ++u) tile[r * LD + c + u] = v[u];
+            } else {
+                tile[r * LD + c] = *s;
+            }
+        }
+    }
+}
+template <typename T, int V, int CH, typename RowPtr>
+__device__ __forceinline__ void tile_store(const T* tile, RowPtr dst, int rows, int cnt, int lane) {
+    typedef T vec_t __attribute__((ext_vector_type(V)));
+    constexpr int NV = CH / V, LD = CH + 1;
+    for (int idx = lane; idx < 64 * NV; idx += 64) {
+        const int r = idx / NV, c = (idx % NV) * V;
+        T* d = dst(r) + c;
+        if (r < rows && c < cnt) {
+            if constexpr (V > 1) {
+                vec_t v;
+#pragma unroll
+                for (int u = 0; u < V; ++u) v[u] = tile[r * LD + c + u];
+                *reinterpret_cast<vec_t*>(d) = v;
+            } else {
+                *d = tile[r * LD + c];
+            }
+        }
+    }
+}
+
 }  // namespace volt

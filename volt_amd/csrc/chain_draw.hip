@@ -62,45 +62,6 @@ __device__ __forceinline__ bool chain_step(double c, double g, double jit, doubl
     return ok;
 }
 
-// ---- the staged tile: rows [0, rows) x steps [0, cnt) between global memory (row r at src(r), unit stride) and tile[r][CD_LD]
-template <typename T, int V, typename RowPtr>
-__device__ __forceinline__ void tile_load(T* tile, RowPtr src, int rows, int cnt, int lane) {
-    typedef T vec_t __attribute__((ext_vector_type(V)));
-    constexpr int NV = CD_CH / V;
-    for (int idx = lane; idx < 64 * NV; idx += 64) {
-        const int r = idx / NV, c = (idx % NV) * V;
-        const T* s = src(r) + c;                     // (formed by every lane: a row pointer may come from a cross-lane read)
-        if (r < rows && c < cnt) {
-            if constexpr (V > 1) {
-                const vec_t v = *reinterpret_cast<const vec_t*>(s);
-#pragma unroll
-                for (int u = 0; u < V; ++u) tile[r * CD_LD + c + u] = v[u];
-            } else {
-                tile[r * CD_LD + c] = *s;
-            }
-        }
-    }
-}
-template <typename T, int V, typename RowPtr>
-__device__ __forceinline__ void tile_store(const T* tile, RowPtr dst, int rows, int cnt, int lane) {
-    typedef T vec_t __attribute__((ext_vector_type(V)));
-    constexpr int NV = CD_CH / V;
-    for (int idx = lane; idx < 64 * NV; idx += 64) {
-        const int r = idx / NV, c = (idx % NV) * V;
-        T* d = dst(r) + c;
-        if (r < rows && c < cnt) {
-            if constexpr (V > 1) {
-                vec_t v;
-#pragma unroll
-                for (int u = 0; u < V; ++u) v[u] = tile[r * CD_LD + c + u];
-                *reinterpret_cast<vec_t*>(d) = v;
-            } else {
-                *d = tile[r * CD_LD + c];
-            }
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ Markov posterior
 template <typename T>
 struct MarkovDrawParams {
@@ -188,7 +149,7 @@ __global__ __launch_bounds__(MD_WAVES * 64) void markov_draw_kernel(MarkovDrawPa
         for (int rd = 0; rd < MD_ROUNDS; ++rd) {
             const int64_t pb = s0 + (int64_t)(rd * MD_WAVES + wave) * 64;
             const int rows = (int)(S - pb < 64 ? (S - pb < 0 ? 0 : S - pb) : 64);
-            tile_load<T, V>(tile, [&](int r) { return zg + (pb + r) * H + c0; }, rows, cnt, lane);
+            tile_load<T, V, CD_CH>(tile, [&](int r) { return zg + (pb + r) * H + c0; }, rows, cnt, lane);
             __syncthreads();
             if (lane < rows) {
                 double s = st[rd * MD_WAVES * 64 + tid];
@@ -201,7 +162,7 @@ __global__ __launch_bounds__(MD_WAVES * 64) void markov_draw_kernel(MarkovDrawPa
                 st[rd * MD_WAVES * 64 + tid] = s;
             }
             __syncthreads();
-            tile_store<T, V>(tile, [&](int r) { return og + (pb + r) * H + c0; }, rows, cnt, lane);
+            tile_store<T, V, CD_CH>(tile, [&](int r) { return og + (pb + r) * H + c0; }, rows, cnt, lane);
             __syncthreads();
         }
     }
@@ -263,8 +224,8 @@ __global__ __launch_bounds__(64) void vk_draw_kernel(VkDrawParams<T> p) {
     const T nan = (T)__builtin_nan("");
     for (int64_t c0 = 0; c0 < H; c0 += CD_CH) {
         const int cnt = (int)(H - c0 < CD_CH ? H - c0 : CD_CH);
-        tile_load<T, V>(tz, [&](int r) { return p.z + (p0 + r) * H + c0; }, rows, cnt, lane);
-        tile_load<T, V>(tv, [&](int r) { return p.pred_vol + (vrow0 + __shfl(vrel, r)) * H + c0; }, 64, cnt, lane);
+        tile_load<T, V, CD_CH>(tz, [&](int r) { return p.z + (p0 + r) * H + c0; }, rows, cnt, lane);
+        tile_load<T, V, CD_CH>(tv, [&](int r) { return p.pred_vol + (vrow0 + __shfl(vrel, r)) * H + c0; }, 64, cnt, lane);
         if (one_series && lane < cnt) tm[lane] = mean[c0 + lane];
         double mu_next = one_series ? 0.0 : mean[c0];       // a wave across series: each lane's own mean, requested a step ahead
         __syncthreads();
@@ -281,7 +242,7 @@ __global__ __launch_bounds__(64) void vk_draw_kernel(VkDrawParams<T> p) {
             tz[lane * CD_LD + i] = bad ? nan : (T)y;
         }
         __syncthreads();
-        tile_store<T, V>(tz, [&](int r) { return p.out + (p0 + r) * H + c0; }, rows, cnt, lane);
+        tile_store<T, V, CD_CH>(tz, [&](int r) { return p.out + (p0 + r) * H + c0; }, rows, cnt, lane);
         __syncthreads();
     }
     if (__any(act && bad > 1)) {

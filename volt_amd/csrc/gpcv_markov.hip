@@ -8,10 +8,11 @@
 //     s_i   = e^{-2 rho_i} + gamma_i^2 s_{i+1}              diag P^-1, backward, positive terms only
 //     sh_i  = h_i + gamma_{i-1}^2 sh_{i-1}                  its adjoint, forward
 //     u_i   = eps_i e^{-rho_i} - gamma_i u_{i+1}            a draw m + Lp^-T eps, backward
-// so all three run through ONE device primitive, affine_scan: the maps (a, b): t -> a + b t compose associatively; a thread
-// composes a contiguous run of MK_R of them, a wave combines its 64 runs with cross-lane shuffles (six steps), the workgroup
-// combines its waves through LDS in wave order, and chunks of MK_T * MK_R points carry into each other in order.  The order
-// of every operation depends on N alone: no atomics, bitwise repeatable.  fp64 throughout, I/O fp32.
+// so all three run through ONE device primitive, affine_scan (markov_scan.h, shared with gpcv_mt_markov.hip and
+// markov_predict.hip): the maps (a, b): t -> a + b t compose associatively; a thread composes a contiguous run of 4 of them, a
+// wave combines its 64 runs with cross-lane shuffles (six steps), the workgroup combines its waves through LDS in wave order,
+// and chunks of MK_T * 4 points carry into each other in order.  The order of every operation depends on N alone: no atomics,
+// bitwise repeatable.  fp64 throughout, I/O fp32.
 // No rescaling of the coefficient products is needed: every term is positive in the s recurrence, so a product of the
 // b = gamma^2 can only overflow where s_i >= prod b * s_N, the true variance, overflows too (info then reports F not finite).
 //
@@ -19,118 +20,19 @@
 //     scan back (s -> workspace)  ->  rows (a wave per point, lanes over the quadrature nodes: the node formulas of gpcv.hip's
 //     gh_ell_kernel / gh_cv_ell_kernel with the variance read from s instead of summed from a row of Lq)  ->  scan forward
 //     (sh), with the gradients and the scalars' partial sums formed at each point as its sh arrives  ->  fixed-order sums.
-// The node loops are a private copy of gpcv.hip's, not shared code: there the loop sits between a row reduction of Lq and a
-// per-4-rows partial sum, here between two scans with per-wave fp64 sums, and the existing kernels' bits stay untouched.
+// The "cv" node is gpcv_shared.h's cv_node, the one the multi-task steps call.  The "exp" node loop is written out here: through
+// gpcv_shared.h's exp_node the compiler fuses the three accumulations of this kernel differently (other bits).
 #include "common.h"
 #include "host.h"
+#include "gpcv_shared.h"
+#include "markov_scan.h"
 #include "../../include/volt_hip.h"
 
 namespace volt {
 
-constexpr int MK_T = 512;                  // threads of the step's workgroup (8 waves)
+constexpr int MK_T = MARKOV_VAR_T;         // threads of the step's workgroup (8 waves)
 constexpr int MK_W = MK_T / 64;
-constexpr int MK_R = 4;                    // points a thread composes before the cross-lane scan
 constexpr int MK_DT = 256;                 // threads of the draw's workgroup
-
-struct Aff {                               // t -> a + b t
-    double a, b;
-};
-// g after f
-__device__ __forceinline__ Aff aff_then(const Aff& f, const Aff& g) { return Aff{__builtin_fma(g.b, f.a, g.a), g.b * f.b}; }
-
-__device__ __forceinline__ double shfl_up_d(double v, int d) { return __shfl_up(v, d, 64); }
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// Keeps a wave-uniform value in vector registers.  The step kernel's 27 arguments, the per-series bases made from them and
-// the fp64 constants of exp / log do not fit the scalar register file side by side; what only the last phase needs waits here
-// (an empty statement with a register constraint: it emits no instruction).
-template <class V>
-__device__ __forceinline__ void park_in_vgpr(V& v) {
-    asm("" : "+v"(v));
-}
-
-// value_p = a_p + b_p value_{p-1}, p = 0 .. n-1, value_{-1} = 0.  coef(p, a, b) gives the map of position p, sink(p, value_p)
-// takes the result; every thread of the workgroup (T threads, T / 64 waves) calls this with the same n.  lds: 2 (T / 64) + 1
-// doubles.  A caller that runs backward in its own index passes i = n - 1 - p to its lambdas.
-template <int T, class Coef, class Sink>
-__device__ __forceinline__ void affine_scan(int64_t n, double* lds, Coef coef, Sink sink) {
-    constexpr int W = T / 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (scalar: the loops over waves are scalar loops)
-    constexpr int64_t CH = (int64_t)T * MK_R;
-    double carry = 0.0;
-    for (int64_t c0 = 0; c0 < n; c0 += CH) {
-        const int64_t p0 = c0 + (int64_t)tid * MK_R;
-        double a[MK_R], b[MK_R];
-        Aff run{0.0, 1.0};
-#pragma unroll
-        for (int r = 0; r < MK_R; ++r) {
-            a[r] = 0.0;
-            b[r] = 1.0;
-            if (p0 + r < n) coef(p0 + r, a[r], b[r]);
-            run = aff_then(run, Aff{a[r], b[r]});
-        }
-        // inclusive scan of the runs inside the wave
-        Aff inc = run;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const Aff o{shfl_up_d(inc.a, d), shfl_up_d(inc.b, d)};
-            if (lane >= d) inc = aff_then(o, inc);
-        }
-        if (lane == 63) {
-            lds[2 * wave] = inc.a;
-            lds[2 * wave + 1] = inc.b;
-        }
-        Aff exc{shfl_up_d(inc.a, 1), shfl_up_d(inc.b, 1)};
-        if (lane == 0) exc = Aff{0.0, 1.0};
-        __syncthreads();
-        double v = carry;                                              // the value entering this wave, then this thread
-#pragma unroll 1
-        for (int w = 0; w < wave; ++w) v = __builtin_fma(lds[2 * w + 1], v, lds[2 * w]);
-        double vend = v;                                               // ... and the one leaving the chunk
-#pragma unroll 1
-        for (int w = wave; w < W; ++w) vend = __builtin_fma(lds[2 * w + 1], vend, lds[2 * w]);
-        v = __builtin_fma(exc.b, v, exc.a);
-#pragma unroll
-        for (int r = 0; r < MK_R; ++r) {
-            v = __builtin_fma(b[r], v, a[r]);
-            if (p0 + r < n) sink(p0 + r, v);
-        }
-        carry = vend;
-        __syncthreads();
-    }
-}
-
-// sum over the workgroup in a fixed order: lanes by butterfly, waves in order.  lds: T / 64 doubles.  All threads get the sum.
-template <int T>
-__device__ __forceinline__ double block_sum_d(double v, double* lds) {
-    v = wave_sum_d(v);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = 0.0;
-    for (int w = 0; w < T / 64; ++w) r += lds[w];
-    __syncthreads();
-    return r;
-}
-
-// s_i = diag P^-1 for one series into sb [N] (backward scan); eb (nullable) [N] keeps e^{-2 rho_i}
-template <int T>
-__device__ __forceinline__ void markov_var_scan(const float* __restrict__ rho, const float* __restrict__ gam, double* sb, double* eb,
-                                                int64_t n, double* lds) {
-    affine_scan<T>(
-        n, lds,
-        [&](int64_t p, double& a, double& b) {
-            const int64_t i = n - 1 - p;
-            a = exp(-2.0 * (double)rho[i]);
-            if (eb) eb[i] = a;
-            const double g = p > 0 ? (double)gam[i] : 0.0;             // gamma_{N-1} is never read
-            b = g * g;
-        },
-        [&](int64_t p, double v) { sb[n - 1 - p] = v; });
-}
 
 template <int KC>
 __global__ __launch_bounds__(MK_T) void gpcv_markov_step_kernel(
@@ -152,17 +54,14 @@ __global__ __launch_bounds__(MK_T) void gpcv_markov_step_kernel(
     park_in_vgpr(grad_m), park_in_vgpr(grad_mu), park_in_vgpr(grad_rho), park_in_vgpr(grad_gam), park_in_vgpr(grad_abc);
     park_in_vgpr(out), park_in_vgpr(info), park_in_vgpr(gmb), park_in_vgpr(eb), park_in_vgpr(db), park_in_vgpr(x);
     const double v = (double)vol[b];
-    auto qinc = [&](int64_t i) -> double {                             // the prior's increment variance q_i
-        return i == 0 ? __builtin_fma(v, (double)x[0], jit) : v * ((double)x[i] - (double)x[i - 1]);
-    };
 
     // ---- 1. s = diag P^-1; the two log-determinants
     double ldk = 0.0, srho = 0.0;
     for (int64_t i = tid; i < n; i += MK_T) {
-        ldk += log(qinc(i));
+        ldk += log(prior_inc(x, v, jit, i));
         srho += (double)rb[i];
     }
-    markov_var_scan<MK_T>(rb, gb, sb, eb, n, lds);
+    markov_var_scan<MK_T, true>(rb, gb, sb, eb, n, lds);
     __syncthreads();
 
     // ---- 2. the likelihood rows: wave w takes points w, w + MK_W, ..
@@ -205,36 +104,8 @@ __global__ __launch_bounds__(MK_T) void gpcv_markov_step_kernel(
 #pragma unroll
             for (int k = 0; k < KA; ++k) ga[k] = gbb[k] = gc[k] = 0.f;
             for (int q = lane; q < Q; q += 64) {
-                const float xq = ghx[q], wq = ghw[q];
-                const float f = mi + sd2 * xq;
-                float sp[KA], sg[KA];
-                float s = 0.f;
-#pragma unroll
-                for (int k = 0; k < KA; ++k) {
-                    const float u = pb[k] * f + pc[k];
-                    const float t = expf(-fabsf(u));
-                    const float inv = 1.f / (1.f + t);
-                    sp[k] = fmaxf(u, 0.f) + log1pf(t);
-                    sg[k] = u >= 0.f ? inv : t * inv;
-                    s += pa[k] * sp[k];
-                }
-                const bool live = s > min_scale;
-                const float sc = live ? s : min_scale;
-                const float r = yi / sc;
-                const float logp = -0.5f * r * r - logf(sc) - 0.91893853320467274f;
-                const float wg = live ? wq * (r * r - 1.f) / sc : 0.f;      // w_q g_s
-                float dsdf = 0.f;
-#pragma unroll
-                for (int k = 0; k < KA; ++k) {
-                    const float as = pa[k] * sg[k];
-                    dsdf += as * pb[k];
-                    ga[k] += wg * sp[k];
-                    gbb[k] += wg * as * f;
-                    gc[k] += wg * as;
-                }
-                e += wq * logp;
-                gm += wg * dsdf;
-                gv += wg * dsdf * xq;
+                const float xq = ghx[q];
+                cv_node<KA>(mi + sd2 * xq, xq, ghw[q], yi, min_scale, pa, pb, pc, ga, gbb, gc, e, gm, gv);
             }
 #pragma unroll
             for (int k = 0; k < KA; ++k) {                             // per lane, point after point, in fp64
@@ -280,12 +151,12 @@ __global__ __launch_bounds__(MK_T) void gpcv_markov_step_kernel(
         n, lds,
         [&](int64_t i, double& a, double& bb) {
             const double gp = i > 0 ? (double)gb[i - 1] : 0.0, o = 1.0 + gp;
-            a = we * (double)gvb[i] - wk * (i > 0 ? o * o : 1.0) / (2.0 * qinc(i));
+            a = we * (double)gvb[i] - wk * (i > 0 ? o * o : 1.0) / (2.0 * prior_inc(x, v, jit, i));
             bb = gp * gp;
         },
         [&](int64_t i, double sh) {
             const bool last = i == n - 1;
-            const double q = qinc(i), si = sb[i];
+            const double q = prior_inc(x, v, jit, i), si = sb[i];
             const double d = (double)db[i], dp = i > 0 ? (double)db[i - 1] : 0.0, dd = d - dp;
             double e = si, kd = dd / q, t = sh;
             if (i > 0) {
@@ -294,7 +165,7 @@ __global__ __launch_bounds__(MK_T) void gpcv_markov_step_kernel(
             }
             float gg = 0.f;
             if (!last) {
-                const double qn = qinc(i + 1), sn = sb[i + 1], g = (double)gb[i];
+                const double qn = prior_inc(x, v, jit, i + 1), sn = sb[i + 1], g = (double)gb[i];
                 gg = (float)(2.0 * g * sn * sh - wk * (1.0 + g) * sn / qn);
                 t -= wk / (2.0 * qn);
                 kd -= ((double)db[i + 1] - d) / qn;
@@ -303,7 +174,7 @@ __global__ __launch_bounds__(MK_T) void gpcv_markov_step_kernel(
             grad_rho[b * n + i] = (float)(-2.0 * eb[i] * t - wk);
             grad_m[b * n + i] = (float)(we * (double)gmb[i] - wk * kd);
             grad_mu[b * n + i] = (float)(wk * kd);
-            const double del = i == 0 ? (double)x[0] : (double)x[i] - (double)x[i - 1];
+            const double del = grid_step(x, i);
             tr += e / q;
             quad += dd * dd / q;
             dv += del * (1.0 / q - (e + dd * dd) / (q * q));
@@ -362,7 +233,7 @@ __global__ __launch_bounds__(MK_T) void markov_root_var_kernel(const float* __re
                                                                double* __restrict__ var, int N) {
     __shared__ double lds[2 * MK_W + 1];
     const int64_t n = N, b = blockIdx.x;
-    markov_var_scan<MK_T>(rho + b * n, gam + b * n, var + b * n, nullptr, n, lds);
+    markov_var_scan<MK_T, true>(rho + b * n, gam + b * n, var + b * n, nullptr, n, lds);
 }
 
 struct GpcvMarkovWs {

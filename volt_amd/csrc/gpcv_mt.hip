@@ -13,19 +13,16 @@
 // The copula-process ("cv") likelihood with one warp per task (volt_gpcv_mt_cv_step_f32) is the same launch sequence with
 // the quadrature pass of gpcv_mt_cv.hip in place of mt_gh_kernel.
 #include "common.h"
-#include "gpcv_shared.h"
+#include "gpcv_task.h"
 #include "../../include/volt_hip.h"
 #include <math.h>
 
 namespace volt {
 
-// (MT_MAX, MLD and GH_ROWS are in gpcv_shared.h: the "cv" quadrature pass of gpcv_mt_cv.hip has the same layout)
-constexpr int MNT = 1024;             // threads of the task-algebra workgroup
+// (MT_MAX, MLD and GH_ROWS are in gpcv_shared.h: the "cv" quadrature pass of gpcv_mt_cv.hip has the same layout; the task
+// algebra and its workgroup size TASK_NT are in gpcv_task.h)
 constexpr int RT_CH = 64;             // columns n staged per pass of the partial sums of R'A / A'A
 constexpr int RT_PASSES = 1;          // passes per workgroup: RT_CH * RT_PASSES columns per partial
-
-__device__ __forceinline__ double msoftplus(double v) { return v > 20.0 ? v : log1p(exp(v)); }
-__device__ __forceinline__ double msigmoid(double v) { return 1.0 / (1.0 + exp(-v)); }
 
 // Rt [128, Np] = (M - c)' zero padded: the T right-hand sides as rows of one MFMA tile (row 0 doubles as the exact-GP
 // step's residual).
@@ -93,16 +90,10 @@ __global__ __launch_bounds__(256) void mt_gh_kernel(const float* __restrict__ M,
             const float sd2 = sqrtf(2.f * var);
             for (int k = 0; k < Q; ++k) {
                 const float xk = ghx[k], wk = ghw[k];
-                const float f = mi + sd2 * xk;
-                const float ef = expf(f);
-                const bool live = ef > min_scale;
-                const float sc = live ? ef : min_scale;
-                const float r = yi / sc;
-                const float logp = -0.5f * r * r - (live ? f : lms) - 0.91893853320467274f;
-                const float g = live ? (r * r - 1.f) : 0.f;
-                el += wk * logp;
-                g1 += wk * g;
-                g2 += wk * g * xk;
+                const ExpNode nd = exp_node(mi + sd2 * xk, yi, min_scale, lms);
+                el += wk * nd.logp;
+                g1 += wk * nd.g;
+                g2 += wk * nd.g * xk;
             }
             g2 = floored ? 0.f : g2 / sd2;               // df/dvar = x_k / sqrt(2 var)
             gm[(int64_t)n * T + t] = g1;
@@ -197,7 +188,8 @@ struct MtTaskArgs {
     float jitter, we, wk;
 };
 
-__device__ __forceinline__ double wave_sum_d(double v) {
+// the DESCENDING butterfly (offsets 32 .. 1); markov_scan.h's wave_sum_d is the ascending one, which rounds differently
+__device__ __forceinline__ double wave_sum_d_desc(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
@@ -208,29 +200,13 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // H = dKL/dK_t pushed through to covar_factor and raw_var, grad_Lt, grad_c, and the step's scalars.  Sums over lists are
 // per-thread strided sums, a butterfly inside each wave, then the waves in order: a fixed order, three block reductions in
 // all.  Leaves K_t^-1 and C^-1 (fp32) and {tau_t, tau_x} for the kernels that follow.
-__global__ __launch_bounds__(MNT) void mt_task_kernel(MtTaskArgs a) {
+__global__ __launch_bounds__(TASK_NT) void mt_task_kernel(MtTaskArgs a) {
     __shared__ double sC[MT_MAX * MLD], sI[MT_MAX * MLD], sK[MT_MAX * MLD], sA[MT_MAX * MLD];
-    __shared__ double sgrp[MNT], sred[4 * (MNT / 64)];
+    __shared__ double sgrp[TASK_NT], sred[4 * (TASK_NT / 64)];
     __shared__ double sf[MT_MAX], scs[MT_MAX], scol[MT_MAX], spiv[MT_MAX];
     __shared__ int sbad;
     const int tid = threadIdx.x, nt = blockDim.x, T = a.T, TT = T * T, N = a.N;
-    const int lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
-    // v[0..3] <- their sums over the workgroup (two barriers)
-    auto block_sum4 = [&](double (&v)[4]) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const double w = wave_sum_d(v[k]);
-            if (lane == 0) sred[k * (MNT / 64) + wave] = w;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            double s = 0.0;
-            for (int w = 0; w < nw; ++w) s += sred[k * (MNT / 64) + w];
-            v[k] = s;
-        }
-        __syncthreads();
-    };
+    auto block_sum4 = [&](double (&v)[4]) { task_block_sum4(v, sred, [](double x) { return wave_sum_d_desc(x); }); };
     if (tid < T) sf[tid] = (double)a.cf[tid];
     if (tid == 0) sbad = 0;
     // the sums that need nothing of the T x T algebra: tau_x = |T'|_F^2, |G|_F^2, ell, logdet S_x
@@ -245,94 +221,17 @@ __global__ __launch_bounds__(MNT) void mt_task_kernel(MtTaskArgs a) {
     for (int i = tid; i < N; i += nt) r0[3] += (double)a.logd[i];
     block_sum4(r0);                                       // (its barriers publish sf and sbad)
     const double tau_x = r0[0], gg = r0[1], ell = r0[2], ld_sx = r0[3];
-    for (int e = tid; e < TT; e += nt) {
-        const int i = e / T, j = e - i * T;
-        sC[i * MLD + j] = sf[i] * sf[j] + (i == j ? msoftplus((double)a.raw_var[i]) : 0.0);
-    }
-    {   // colred[t] = sum_blk colpart[blk, t]: nw strided partial sums per task, added in order
-        const int t = lane, g = wave;
-        double acc = 0.0;
-        if (t < T) {
-#pragma unroll 8
-            for (int b = g; b < a.ngh; b += nw) acc += (double)a.colpart[(int64_t)b * T + t];
-        }
-        sgrp[g * 64 + t] = acc;
-    }
-    __syncthreads();
-    if (tid < T) {
-        double s = 0.0;
-        for (int g = 0; g < nw; ++g) s += sgrp[g * 64 + tid];
-        scol[tid] = s;
-    }
-    // C = chol(K_t) right-looking in place (strictly lower part; the pivots go to spiv) and, in the same sweep, X = C^-1 by
-    // right-looking forward substitution (row j is final once divided by its pivot, then leaves every row below it):
-    // two barriers per column.  Every thread takes the pivot's root itself, so no thread waits for thread 0.
-    for (int e = tid; e < TT; e += nt) sI[(e / T) * MLD + e % T] = e / T == e % T ? 1.0 : 0.0;
-    __syncthreads();
-    for (int j = 0; j < T; ++j) {
-        double d = sC[j * MLD + j];
-        const bool bad = !(d > 0.0);                       // <= 0 or NaN: reported, and everything downstream is NaN
-        d = bad ? __builtin_nan("") : sqrt(d);
-        if (tid == 0) {
-            if (bad && !sbad) sbad = j + 1;
-            spiv[j] = d;
-        }
-        for (int i = j + 1 + tid; i < T; i += nt) sC[i * MLD + j] /= d;
-        for (int c = nt - 1 - tid; c <= j; c += nt) sI[j * MLD + c] /= d;        // (the last threads: the first scale C)
-        __syncthreads();
-        const int m = T - j - 1, cnt = m * T;
-        for (int e = tid; e < cnt; e += nt) {
-            const int i = j + 1 + e / T, c = e % T;
-            if (c > j) {
-                if (c <= i) sC[i * MLD + c] -= sC[i * MLD + j] * sC[c * MLD + j];
-            } else {
-                sI[i * MLD + c] -= sC[i * MLD + j] * sI[j * MLD + c];
-            }
-        }
-        __syncthreads();
-    }
-    for (int e = tid; e < TT; e += nt) {                  // K_t^-1 = C^-T C^-1
-        const int s = e / T, t = e - s * T;
-        double acc = 0.0;
-        for (int k = s > t ? s : t; k < T; ++k) acc = fma(sI[k * MLD + s], sI[k * MLD + t], acc);
-        sK[s * MLD + t] = acc;
-        a.kti[e] = (float)acc;
-        a.cinv[e] = (float)sI[s * MLD + t];
-    }
-    for (int e = tid; e < TT; e += nt) {                  // sC <- tril(Lt)  (C itself is no longer needed)
-        const int t = e / T, s = e - t * T;
-        sC[t * MLD + s] = s <= t ? (double)a.Lt[e] : 0.0;
-    }
-    __syncthreads();
-    for (int e = tid; e < TT; e += nt) {                  // U = K_t^-1 Lt
-        const int s = e / T, k = e - s * T;
-        double acc = 0.0;
-        for (int t = k; t < T; ++t) acc = fma(sK[s * MLD + t], sC[t * MLD + k], acc);
-        sA[s * MLD + k] = acc;
-    }
-    __syncthreads();
-    // tau_t = tr(Lt' K_t^-1 Lt), logdet K_t, logdet S_t
+    task_build_kt(sC, sf, a.raw_var, T);
+    task_colsum<8>(a.colpart, a.ngh, T, sgrp, scol);
+    task_chol_inverse(sC, sI, spiv, &sbad, T);
     double r1[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int e = tid; e < TT; e += nt) r1[0] += sA[(e / T) * MLD + e % T] * sC[(e / T) * MLD + e % T];
-    if (tid < T) {
-        const double d = sC[tid * MLD + tid];
-        r1[1] = 2.0 * log(spiv[tid]);
-        r1[2] = log(d * d);
-    }
+    task_inverse_and_u(sC, sI, sK, sA, spiv, a.Lt, T, r1, [&](int e, int s, int t, double v) {
+        a.kti[e] = (float)v;
+        a.cinv[e] = (float)sI[s * MLD + t];
+    });
     block_sum4(r1);
     const double tau_t = r1[0], ld_kt = r1[1], ld_st = r1[2];
-    // dF/dLt = we 2 colred_t Lt - wk (tau_x tril(U) - N diag(1 / Lt_tt))
-    for (int e = tid; e < TT; e += nt) {
-        const int t = e / T, s = e - t * T;
-        double g = 0.0;
-        if (s <= t) {
-            const double l = sC[t * MLD + s];
-            double kl = tau_x * sA[t * MLD + s];
-            if (s == t) kl -= (double)N / l;
-            g = (double)a.we * 2.0 * scol[t] * l - (double)a.wk * kl;
-        }
-        a.grad_Lt[e] = (float)g;
-    }
+    task_grad_lt(sC, sA, scol, tau_x, N, (double)a.we, (double)a.wk, a.grad_Lt, T);
     __syncthreads();
     // sC <- R'A (chunks in order);  tr(K_t^-1 A'A);  colsum A
     const int pstride = 2 * TT + T;
@@ -357,35 +256,7 @@ __global__ __launch_bounds__(MNT) void mt_task_kernel(MtTaskArgs a) {
     }
     block_sum4(r2);                                       // (its barriers publish sC and scs)
     const double tr_aa = r2[0], q = r2[1];
-    for (int e = tid; e < TT; e += nt) {                  // Z = K_t^-1 R'A
-        const int s = e / T, k = e - s * T;
-        double acc = 0.0;
-        for (int t = 0; t < T; ++t) acc = fma(sK[s * MLD + t], sC[t * MLD + k], acc);
-        sI[s * MLD + k] = acc;
-    }
-    __syncthreads();
-    // H = dKL/dK_t = 1/2 (N K_t^-1 - tau_x U U' - Z K_t^-1)
-    for (int e = tid; e < TT; e += nt) {
-        const int s = e / T, t = e - s * T;
-        double uu = 0.0, zk = 0.0;
-        for (int k = 0; k < T; ++k) {
-            uu = fma(sA[s * MLD + k], sA[t * MLD + k], uu);
-            zk = fma(sI[s * MLD + k], sK[k * MLD + t], zk);
-        }
-        sC[s * MLD + t] = 0.5 * ((double)N * sK[s * MLD + t] - tau_x * uu - zk);
-    }
-    __syncthreads();
-    if (tid < T) {
-        const int t = tid;
-        double hf = 0.0, gc = 0.0;
-        for (int s = 0; s < T; ++s) {
-            hf = fma(sC[t * MLD + s] + sC[s * MLD + t], sf[s], hf);       // K_t = f f' + diag: dKL/df = (H + H') f
-            gc = fma(scs[s], sK[s * MLD + t], gc);
-        }
-        a.grad_cf[t] = (float)(-(double)a.wk * hf);
-        a.grad_rv[t] = (float)(-(double)a.wk * sC[t * MLD + t] * msigmoid((double)a.raw_var[t]));
-        a.grad_c[t] = (float)((double)a.wk * gc);                          // dKL/dc_t = - sum_n (A K_t^-1)_nt
-    }
+    task_push_through(sC, sI, sK, sA, sf, scs, tau_x, N, (double)a.wk, a.raw_var, a.grad_cf, a.grad_rv, a.grad_c, T);
     if (tid == 0) {
         const double ld_k = (double)a.mllout[3];
         const double kl = 0.5 * (tau_x * tau_t + q - (double)N * T + T * ld_k + N * ld_kt - T * ld_sx - N * ld_st);
@@ -559,7 +430,7 @@ static int mt_step_impl(const float* K, int64_t ldk, float jitter, const float* 
     MtTaskArgs ta{covar_factor, raw_var, Lt, w.part, w.colpart, w.ellpart, w.logd, w.frobT, w.frobG, w.mllout,
                   out, grad_c, grad_Lt, grad_covar_factor, grad_raw_var, w.kti, w.cinv, w.tsc,
                   info + 1, w.nch, w.ngh, n * n, N, T, jitter, w_ell, w_kl};
-    hipLaunchKernelGGL(mt_task_kernel, dim3(1), dim3(T <= 16 ? 256 : MNT), 0, s, ta);
+    hipLaunchKernelGGL(mt_task_kernel, dim3(1), dim3(T <= 16 ? 256 : TASK_NT), 0, s, ta);
     hipLaunchKernelGGL(mt_grad_kernel, dim3((N + 255) / 256, N > T ? N : T), dim3(256), 0, s, Lx, w.G, w.rowred, w.gm, w.At, w.kti,
                        w.tsc, grad_Lx, grad_M, N, Np, T, w_ell, w_kl);
     if (want_dk) {

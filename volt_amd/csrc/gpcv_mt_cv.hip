@@ -9,47 +9,6 @@
 
 namespace volt {
 
-// One Gauss-Hermite node of the copula-process ("cv") likelihood:  s(f) = sum_k a_k softplus(b_k f + c_k),
-//   sc = max(s, min_scale),  logp = -y^2 / (2 sc^2) - log sc - log sqrt(2 pi),  wg = w_q dlogp/ds = w_q (y^2/sc^2 - 1)/sc
-//   [s > min_scale].  Adds w_q logp to e, wg ds/df to gm, wg ds/df x_q to gv, and wg (softplus(u_k), a_k sigmoid(u_k) f,
-//   a_k sigmoid(u_k)) to the parameter sums ga, gb, gc.
-// This is the node body of gh_cv_ell_kernel (gpcv.hip) written a SECOND time, statement for statement: calling it from
-// there as a __forceinline__ function changed that kernel's gfx950 ISA (profiles/mt_gpcv_cv/isa_diff.txt), so the
-// single-task kernel keeps its own copy and its bits.  Whoever changes one changes the other.
-template <int KC>
-__device__ __forceinline__ void cv_node(float f, float xq, float wq, float yi, float min_scale, const float (&pa)[KC],
-                                        const float (&pb)[KC], const float (&pc)[KC], float (&ga)[KC], float (&gb)[KC],
-                                        float (&gc)[KC], float& e, float& gm, float& gv) {
-    float sp[KC], sg[KC];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < KC; ++k) {
-        const float u = pb[k] * f + pc[k];
-        const float t = expf(-fabsf(u));
-        const float inv = 1.f / (1.f + t);
-        sp[k] = fmaxf(u, 0.f) + log1pf(t);
-        sg[k] = u >= 0.f ? inv : t * inv;
-        s += pa[k] * sp[k];
-    }
-    const bool live = s > min_scale;
-    const float sc = live ? s : min_scale;
-    const float r = yi / sc;
-    const float logp = -0.5f * r * r - logf(sc) - 0.91893853320467274f;
-    const float wg = live ? wq * (r * r - 1.f) / sc : 0.f;      // w_q g_s
-    float dsdf = 0.f;
-#pragma unroll
-    for (int k = 0; k < KC; ++k) {
-        const float as = pa[k] * sg[k];
-        dsdf += as * pb[k];
-        ga[k] += wg * sp[k];
-        gb[k] += wg * as * f;
-        gc[k] += wg * as;
-    }
-    e += wq * logp;
-    gm += wg * dsdf;
-    gv += wg * dsdf * xq;
-}
-
 // mt_gh_kernel's pass (gpcv_mt.hip) for the copula-process ("cv") warp of task t, scale(f) = sum_k a_tk softplus(b_tk f +
 // c_tk) (cv_node; abc [T,3,KC]).  It writes what mt_gh_kernel writes, with the same meaning, and the parameter sums besides.
 // Here a WAVE owns a task: wave w of the workgroup's CV_WAVES takes t = w, w + CV_WAVES, ..., walks the workgroup's GH_ROWS

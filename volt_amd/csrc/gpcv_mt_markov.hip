@@ -8,10 +8,11 @@
 //     R = M - 1 c',  D_0 = R_0,  D_i = R_i - R_{i-1}  (T-vectors; c cancels for i > 0)
 //     tau_x = sum e_i / q_i,  tau_t = tr(K_t^-1 S_t),  G = sum D_i D_i' / q_i,  G2 = sum Delta_i D_i D_i' / q_i^2,  quad = tr(K_t^-1 G)
 //     KL = 1/2 [tau_x tau_t + quad - N T + T sum log q_i + N logdet K_t + 2 T sum rho_i - N logdet S_t]
-// The x side (s, its adjoint sh) is T-independent: two affine scans over N alone, gpcv_markov.hip's affine_scan in a private
-// copy (4 points a thread, 64 runs a wave, waves through LDS in order, chunks in order).  The task side is T x T: one fp64
-// workgroup, a private copy of gpcv_mt.hip's mt_task_kernel with G in the place of R'A.  Between them the N x T quadrature
-// pass runs as a grid over row tiles.  The private copies keep the existing kernels' bits.
+// The x side (s, its adjoint sh) is T-independent: two affine scans over N alone, markov_scan.h's affine_scan (4 points a
+// thread, 64 runs a wave, waves through LDS in order, chunks in order; s through its markov_var_scan, so it equals
+// volt_markov_root_var_f32's bit for bit).  The task side is T x T: one fp64 workgroup running gpcv_task.h's task algebra, the
+// one gpcv_mt.hip's mt_task_kernel runs, with G in the place of R'A.  Between them the N x T quadrature pass runs as a grid
+// over row tiles, its nodes gpcv_shared.h's exp_node / cv_node.
 //
 // Four launches (five with the "cv" likelihood):
 //   front  workgroup 0: s backward (-> workspace), tau_x, sum log q, sum rho, sum Delta/q, sum Delta e/q^2
@@ -26,103 +27,22 @@
 // No atomics, no host synchronisation; every sum has an order that depends on (N, T) alone.  Recurrences and sums fp64,
 // the quadrature nodes and all I/O fp32.
 #include "common.h"
-#include "gpcv_shared.h"
+#include "gpcv_task.h"
+#include "markov_scan.h"
 #include "../../include/volt_hip.h"
 #include <math.h>
 
 namespace volt {
 namespace mtm {
 
-constexpr int MM_T = 512;                  // threads of every workgroup but the task algebra's (8 waves)
+constexpr int MM_T = MARKOV_VAR_T;         // threads of every workgroup but the task algebra's (8 waves)
 constexpr int MM_W = MM_T / 64;
-constexpr int MM_R = 4;                    // points a thread composes before the cross-lane scan
 constexpr int MM_ROWS = 16;                // rows n per quadrature workgroup
 constexpr int MM_GCH = 128;                // rows n per partial sum of G, G2
 constexpr int MM_GST = 32;                 // ... staged in LDS per pass
 constexpr int MM_PPT = MT_MAX * MT_MAX / MM_T;   // (s, t) pairs a thread of the partial sums owns
 constexpr int MM_MROWS = 32;               // rows n per grad_M workgroup
-constexpr int MM_NT = 1024;                // threads of the task-algebra workgroup
 
-struct Aff {                               // t -> a + b t
-    double a, b;
-};
-// g after f
-__device__ __forceinline__ Aff aff_then(const Aff& f, const Aff& g) { return Aff{__builtin_fma(g.b, f.a, g.a), g.b * f.b}; }
-__device__ __forceinline__ double shfl_up_d(double v, int d) { return __shfl_up(v, d, 64); }
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ double msoftplus(double v) { return v > 20.0 ? v : log1p(exp(v)); }
-__device__ __forceinline__ double msigmoid(double v) { return 1.0 / (1.0 + exp(-v)); }
-
-// value_p = a_p + b_p value_{p-1}, p = 0 .. n-1, value_{-1} = 0 (gpcv_markov.hip's affine_scan; MM_T threads, lds: 2 MM_W + 1
-// doubles).  A caller that runs backward in its own index passes i = n - 1 - p to its lambdas.
-template <class Coef, class Sink>
-__device__ __forceinline__ void affine_scan(int64_t n, double* lds, Coef coef, Sink sink) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr int64_t CH = (int64_t)MM_T * MM_R;
-    double carry = 0.0;
-    for (int64_t c0 = 0; c0 < n; c0 += CH) {
-        const int64_t p0 = c0 + (int64_t)tid * MM_R;
-        double a[MM_R], b[MM_R];
-        Aff run{0.0, 1.0};
-#pragma unroll
-        for (int r = 0; r < MM_R; ++r) {
-            a[r] = 0.0;
-            b[r] = 1.0;
-            if (p0 + r < n) coef(p0 + r, a[r], b[r]);
-            run = aff_then(run, Aff{a[r], b[r]});
-        }
-        Aff inc = run;                                                 // inclusive scan of the runs inside the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const Aff o{shfl_up_d(inc.a, d), shfl_up_d(inc.b, d)};
-            if (lane >= d) inc = aff_then(o, inc);
-        }
-        if (lane == 63) {
-            lds[2 * wave] = inc.a;
-            lds[2 * wave + 1] = inc.b;
-        }
-        Aff exc{shfl_up_d(inc.a, 1), shfl_up_d(inc.b, 1)};
-        if (lane == 0) exc = Aff{0.0, 1.0};
-        __syncthreads();
-        double v = carry;                                              // the value entering this wave, then this thread
-#pragma unroll 1
-        for (int w = 0; w < wave; ++w) v = __builtin_fma(lds[2 * w + 1], v, lds[2 * w]);
-        double vend = v;                                               // ... and the one leaving the chunk
-#pragma unroll 1
-        for (int w = wave; w < MM_W; ++w) vend = __builtin_fma(lds[2 * w + 1], vend, lds[2 * w]);
-        v = __builtin_fma(exc.b, v, exc.a);
-#pragma unroll
-        for (int r = 0; r < MM_R; ++r) {
-            v = __builtin_fma(b[r], v, a[r]);
-            if (p0 + r < n) sink(p0 + r, v);
-        }
-        carry = vend;
-        __syncthreads();
-    }
-}
-
-// sum over the workgroup in a fixed order: lanes by butterfly, waves in order.  lds: MM_W doubles.  All threads get the sum.
-__device__ __forceinline__ double block_sum_d(double v, double* lds) {
-    v = wave_sum_d(v);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = 0.0;
-    for (int w = 0; w < MM_W; ++w) r += lds[w];
-    __syncthreads();
-    return r;
-}
-
-// the prior's increment variance q_i and the grid step Delta_i
-__device__ __forceinline__ double grid_step(const float* __restrict__ x, int64_t i) {
-    return i == 0 ? (double)x[0] : (double)x[i] - (double)x[i - 1];
-}
-__device__ __forceinline__ double prior_inc(const float* __restrict__ x, double v, double jit, int64_t i) {
-    return i == 0 ? __builtin_fma(v, (double)x[0], jit) : v * ((double)x[i] - (double)x[i - 1]);
-}
 
 // ---- front: workgroup 0 the x side's backward scan and sums (xs[0..4] = tau_x, sum log q, sum rho, sum Delta / q,
 // sum Delta e / q^2; xs[5] = q_0), workgroups 1 .. the partial sums gpart[blk][2][T,T] of G and G2 over rows blk MM_GCH .. + MM_GCH
@@ -142,16 +62,7 @@ __global__ __launch_bounds__(MM_T) void front_kernel(const float* __restrict__ x
             ldq += log(prior_inc(x, v, jit, i));
             srho += (double)rho[i];
         }
-        affine_scan(
-            n, lds,
-            [&](int64_t p, double& a, double& b) {
-                const int64_t i = n - 1 - p;
-                a = exp(-2.0 * (double)rho[i]);
-                ws_e[i] = a;
-                const double g = p > 0 ? (double)gam[i] : 0.0;         // gamma_{N-1} is never read
-                b = g * g;
-            },
-            [&](int64_t p, double val) { ws_s[n - 1 - p] = val; });
+        markov_var_scan<MM_T, false>(rho, gam, ws_s, ws_e, n, lds);
         __syncthreads();
         double tx = 0.0, x1 = 0.0, x2 = 0.0;
         for (int64_t i = tid; i < n; i += MM_T) {
@@ -165,11 +76,11 @@ __global__ __launch_bounds__(MM_T) void front_kernel(const float* __restrict__ x
             x1 += del / q;
             x2 += del * e / (q * q);
         }
-        tx = block_sum_d(tx, lds);
-        ldq = block_sum_d(ldq, lds);
-        srho = block_sum_d(srho, lds);
-        x1 = block_sum_d(x1, lds);
-        x2 = block_sum_d(x2, lds);
+        tx = block_sum_d<MM_T>(tx, lds);
+        ldq = block_sum_d<MM_T>(ldq, lds);
+        srho = block_sum_d<MM_T>(srho, lds);
+        x1 = block_sum_d<MM_T>(x1, lds);
+        x2 = block_sum_d<MM_T>(x2, lds);
         if (tid == 0) {
             xs[0] = tx;
             xs[1] = ldq;
@@ -239,41 +150,6 @@ __global__ __launch_bounds__(MM_T) void front_kernel(const float* __restrict__ x
     }
 }
 
-// One Gauss-Hermite node of the copula-process ("cv") likelihood: gpcv_mt_cv.hip's cv_node in a private copy (see there).
-template <int KC>
-__device__ __forceinline__ void cv_node(float f, float xq, float wq, float yi, float min_scale, const float (&pa)[KC],
-                                        const float (&pb)[KC], const float (&pc)[KC], float (&ga)[KC], float (&gb)[KC],
-                                        float (&gc)[KC], float& e, float& gm, float& gv) {
-    float sp[KC], sg[KC];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < KC; ++k) {
-        const float u = pb[k] * f + pc[k];
-        const float t = expf(-fabsf(u));
-        const float inv = 1.f / (1.f + t);
-        sp[k] = fmaxf(u, 0.f) + log1pf(t);
-        sg[k] = u >= 0.f ? inv : t * inv;
-        s += pa[k] * sp[k];
-    }
-    const bool live = s > min_scale;
-    const float sc = live ? s : min_scale;
-    const float r = yi / sc;
-    const float logp = -0.5f * r * r - logf(sc) - 0.91893853320467274f;
-    const float wg = live ? wq * (r * r - 1.f) / sc : 0.f;      // w_q g_s
-    float dsdf = 0.f;
-#pragma unroll
-    for (int k = 0; k < KC; ++k) {
-        const float as = pa[k] * sg[k];
-        dsdf += as * pb[k];
-        ga[k] += wg * sp[k];
-        gb[k] += wg * as * f;
-        gc[k] += wg * as;
-    }
-    e += wq * logp;
-    gm += wg * dsdf;
-    gv += wg * dsdf * xq;
-}
-
 // ---- rows: the N x T Gauss-Hermite pass over rows blockIdx.x MM_ROWS .. + MM_ROWS, variance max(s_n st_t, min_var).
 //   gm [N,T] = dE/dM;  rowred[n] = a_n = sum_t gv_nt st_t;  colpart[blk, t] = sum_{n in blk} gv_nt s_n;  ellpart[blk];
 //   KC > 0: cvpart[t][blk][3 KC].  gv = dE/dvar (0 where the variance is floored).
@@ -316,16 +192,10 @@ __global__ __launch_bounds__(MM_T) void rows_kernel(const float* __restrict__ M,
                 const float sd2 = sqrtf(2.f * var);
                 for (int k = 0; k < Q; ++k) {
                     const float xk = ghx[k], wq = ghw[k];
-                    const float f = mi + sd2 * xk;
-                    const float ef = expf(f);
-                    const bool live = ef > min_scale;
-                    const float sc = live ? ef : min_scale;
-                    const float r = yi / sc;
-                    const float logp = -0.5f * r * r - (live ? f : lms) - 0.91893853320467274f;
-                    const float g = live ? (r * r - 1.f) : 0.f;
-                    el += wq * logp;
-                    g1 += wq * g;
-                    g2 += wq * g * xk;
+                    const ExpNode nd = exp_node(mi + sd2 * xk, yi, min_scale, lms);
+                    el += wq * nd.logp;
+                    g1 += wq * nd.g;
+                    g2 += wq * nd.g * xk;
                 }
                 g2 = floored ? 0.f : g2 / sd2;               // df/dvar = x_k / sqrt(2 var)
                 gm[n * T + t] = g1;
@@ -421,33 +291,18 @@ struct TaskArgs {
     double we, wk;
 };
 
-// ---- task: everything T x T, one workgroup of MM_NT threads, fp64 in LDS -- gpcv_mt.hip's mt_task_kernel in a private copy
-// with the x side's scalars read from xs, G in the place of R'A, tr(K_t^-1 G2) in the place of tr(K_t^-1 A'A) and
-// colsum A = D_0 / q_0 (the rows of A = K_M^-1 R telescope).  The partial sums of G, G2 are added by MM_NT / T^2 groups of
-// threads striding over the chunks, then the groups in order.  Leaves K_t^-1 and tau_t (fp64) for the back kernel.
-__global__ __launch_bounds__(MM_NT) void task_kernel(TaskArgs a) {
+// ---- task: everything T x T, one workgroup of TASK_NT threads, fp64 in LDS: the task algebra of gpcv_task.h (shared with
+// gpcv_mt.hip's mt_task_kernel) with the x side's scalars read from xs, G in the place of R'A, tr(K_t^-1 G2) in the place of
+// tr(K_t^-1 A'A) and colsum A = D_0 / q_0 (the rows of A = K_M^-1 R telescope).  The partial sums of G, G2 are added by
+// TASK_NT / T^2 groups of threads striding over the chunks, then the groups in order.  Leaves K_t^-1 and tau_t (fp64) for
+// the back kernel.
+__global__ __launch_bounds__(TASK_NT) void task_kernel(TaskArgs a) {
     __shared__ double sC[MT_MAX * MLD], sI[MT_MAX * MLD], sK[MT_MAX * MLD], sA[MT_MAX * MLD];
-    __shared__ double sgrp[MM_NT], sgrp2[MM_NT], sred[4 * (MM_NT / 64)];
+    __shared__ double sgrp[TASK_NT], sgrp2[TASK_NT], sred[4 * (TASK_NT / 64)];
     __shared__ double sf[MT_MAX], scs[MT_MAX], scol[MT_MAX], spiv[MT_MAX];
     __shared__ int sbad;
     const int tid = threadIdx.x, nt = blockDim.x, T = a.T, TT = T * T, N = a.N;
-    const int lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
-    // v[0..3] <- their sums over the workgroup (two barriers)
-    auto block_sum4 = [&](double (&v)[4]) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const double w = wave_sum_d(v[k]);
-            if (lane == 0) sred[k * (MM_NT / 64) + wave] = w;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            double s = 0.0;
-            for (int w = 0; w < nw; ++w) s += sred[k * (MM_NT / 64) + w];
-            v[k] = s;
-        }
-        __syncthreads();
-    };
+    auto block_sum4 = [&](double (&v)[4]) { task_block_sum4(v, sred, [](double x) { return wave_sum_d(x); }); };
     if (tid < T) sf[tid] = (double)a.cf[tid];
     if (tid == 0) sbad = 0;
     double r0[4] = {0.0, 0.0, 0.0, 0.0};
@@ -455,92 +310,14 @@ __global__ __launch_bounds__(MM_NT) void task_kernel(TaskArgs a) {
     for (int i = tid; i < a.ngh; i += nt) r0[0] += a.ellpart[i];
     block_sum4(r0);                                       // (its barriers publish sf and sbad)
     const double ell = r0[0], tau_x = a.xs[0], ld_k = a.xs[1], ld_sx = -2.0 * a.xs[2];
-    for (int e = tid; e < TT; e += nt) {
-        const int i = e / T, j = e - i * T;
-        sC[i * MLD + j] = sf[i] * sf[j] + (i == j ? msoftplus((double)a.raw_var[i]) : 0.0);
-    }
-    {   // colred[t] = sum_blk colpart[blk, t]: nw strided partial sums per task, added in order
-        const int t = lane, g = wave;
-        double acc = 0.0;
-        if (t < T) {
-#pragma unroll 4
-            for (int b = g; b < a.ngh; b += nw) acc += a.colpart[(int64_t)b * T + t];
-        }
-        sgrp[g * 64 + t] = acc;
-    }
-    __syncthreads();
-    if (tid < T) {
-        double s = 0.0;
-        for (int g = 0; g < nw; ++g) s += sgrp[g * 64 + tid];
-        scol[tid] = s;
-    }
-    // C = chol(K_t) right-looking in place and, in the same sweep, X = C^-1 by right-looking forward substitution: two
-    // barriers per column.  Every thread takes the pivot's root itself.
-    for (int e = tid; e < TT; e += nt) sI[(e / T) * MLD + e % T] = e / T == e % T ? 1.0 : 0.0;
-    __syncthreads();
-    for (int j = 0; j < T; ++j) {
-        double d = sC[j * MLD + j];
-        const bool bad = !(d > 0.0);                       // <= 0 or NaN: reported, and everything downstream is NaN
-        d = bad ? __builtin_nan("") : sqrt(d);
-        if (tid == 0) {
-            if (bad && !sbad) sbad = j + 1;
-            spiv[j] = d;
-        }
-        for (int i = j + 1 + tid; i < T; i += nt) sC[i * MLD + j] /= d;
-        for (int cc = nt - 1 - tid; cc <= j; cc += nt) sI[j * MLD + cc] /= d;        // (the last threads: the first scale C)
-        __syncthreads();
-        const int m = T - j - 1, cnt = m * T;
-        for (int e = tid; e < cnt; e += nt) {
-            const int i = j + 1 + e / T, cc = e % T;
-            if (cc > j) {
-                if (cc <= i) sC[i * MLD + cc] -= sC[i * MLD + j] * sC[cc * MLD + j];
-            } else {
-                sI[i * MLD + cc] -= sC[i * MLD + j] * sI[j * MLD + cc];
-            }
-        }
-        __syncthreads();
-    }
-    for (int e = tid; e < TT; e += nt) {                  // K_t^-1 = C^-T C^-1
-        const int s = e / T, t = e - s * T;
-        double acc = 0.0;
-        for (int k = s > t ? s : t; k < T; ++k) acc = fma(sI[k * MLD + s], sI[k * MLD + t], acc);
-        sK[s * MLD + t] = acc;
-        a.kti[e] = acc;
-    }
-    for (int e = tid; e < TT; e += nt) {                  // sC <- tril(Lt)  (C itself is no longer needed)
-        const int t = e / T, s = e - t * T;
-        sC[t * MLD + s] = s <= t ? (double)a.Lt[e] : 0.0;
-    }
-    __syncthreads();
-    for (int e = tid; e < TT; e += nt) {                  // U = K_t^-1 Lt
-        const int s = e / T, k = e - s * T;
-        double acc = 0.0;
-        for (int t = k; t < T; ++t) acc = fma(sK[s * MLD + t], sC[t * MLD + k], acc);
-        sA[s * MLD + k] = acc;
-    }
-    __syncthreads();
-    // tau_t = tr(Lt' K_t^-1 Lt), logdet K_t, logdet S_t
+    task_build_kt(sC, sf, a.raw_var, T);
+    task_colsum<4>(a.colpart, a.ngh, T, sgrp, scol);
+    task_chol_inverse(sC, sI, spiv, &sbad, T);
     double r1[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int e = tid; e < TT; e += nt) r1[0] += sA[(e / T) * MLD + e % T] * sC[(e / T) * MLD + e % T];
-    if (tid < T) {
-        const double d = sC[tid * MLD + tid];
-        r1[1] = 2.0 * log(spiv[tid]);
-        r1[2] = log(d * d);
-    }
+    task_inverse_and_u(sC, sI, sK, sA, spiv, a.Lt, T, r1, [&](int e, int, int, double v) { a.kti[e] = v; });
     block_sum4(r1);
     const double tau_t = r1[0], ld_kt = r1[1], ld_st = r1[2];
-    // dF/dLt = we 2 b_t Lt - wk (tau_x tril(U) - N diag(1 / Lt_tt))
-    for (int e = tid; e < TT; e += nt) {
-        const int t = e / T, s = e - t * T;
-        double g = 0.0;
-        if (s <= t) {
-            const double l = sC[t * MLD + s];
-            double kl = tau_x * sA[t * MLD + s];
-            if (s == t) kl -= (double)N / l;
-            g = a.we * 2.0 * scol[t] * l - a.wk * kl;
-        }
-        a.grad_Lt[e] = (float)g;
-    }
+    task_grad_lt(sC, sA, scol, tau_x, N, a.we, a.wk, a.grad_Lt, T);
     // sC <- G (chunks by groups, groups in order);  tr(K_t^-1 G2);  quad = tr(K_t^-1 G);  colsum A = D_0 / q_0
     const int Gn = TT >= nt ? 1 : nt / TT;
     if (Gn > 1 && tid < Gn * TT) {
@@ -581,35 +358,7 @@ __global__ __launch_bounds__(MM_NT) void task_kernel(TaskArgs a) {
     }
     block_sum4(r2);                                       // (its barriers publish sC and scs)
     const double tr_g2 = r2[0], q = r2[1];
-    for (int e = tid; e < TT; e += nt) {                  // Z = K_t^-1 G
-        const int s = e / T, k = e - s * T;
-        double acc = 0.0;
-        for (int t = 0; t < T; ++t) acc = fma(sK[s * MLD + t], sC[t * MLD + k], acc);
-        sI[s * MLD + k] = acc;
-    }
-    __syncthreads();
-    // H = dKL/dK_t = 1/2 (N K_t^-1 - tau_x U U' - Z K_t^-1)
-    for (int e = tid; e < TT; e += nt) {
-        const int s = e / T, t = e - s * T;
-        double uu = 0.0, zk = 0.0;
-        for (int k = 0; k < T; ++k) {
-            uu = fma(sA[s * MLD + k], sA[t * MLD + k], uu);
-            zk = fma(sI[s * MLD + k], sK[k * MLD + t], zk);
-        }
-        sC[s * MLD + t] = 0.5 * ((double)N * sK[s * MLD + t] - tau_x * uu - zk);
-    }
-    __syncthreads();
-    if (tid < T) {
-        const int t = tid;
-        double hf = 0.0, gc = 0.0;
-        for (int s = 0; s < T; ++s) {
-            hf = fma(sC[t * MLD + s] + sC[s * MLD + t], sf[s], hf);       // K_t = f f' + diag: dKL/df = (H + H') f
-            gc = fma(scs[s], sK[s * MLD + t], gc);
-        }
-        a.grad_cf[t] = (float)(-a.wk * hf);
-        a.grad_rv[t] = (float)(-a.wk * sC[t * MLD + t] * msigmoid((double)a.raw_var[t]));
-        a.grad_c[t] = (float)(a.wk * gc);                                  // dKL/dc_t = - sum_n (A K_t^-1)_nt
-    }
+    task_push_through(sC, sI, sK, sA, sf, scs, tau_x, N, a.wk, a.raw_var, a.grad_cf, a.grad_rv, a.grad_c, T);
     if (tid == 0) {
         const double kl = 0.5 * (tau_x * tau_t + q - (double)N * T + T * ld_k + N * ld_kt - T * ld_sx - N * ld_st);
         const double F = a.we * ell - a.wk * kl;
@@ -649,7 +398,7 @@ __global__ __launch_bounds__(MM_T) void back_kernel(const float* __restrict__ x,
     const double v = (double)vol[0];
     if (blockIdx.x == 0) {
         const double wt = wk * tsc[0];                                 // w_kl tau_t
-        affine_scan(
+        affine_scan<MM_T>(
             n, lds,
             [&](int64_t i, double& a, double& b) {
                 const double gp = i > 0 ? (double)gam[i - 1] : 0.0, o = 1.0 + gp;
@@ -797,7 +546,7 @@ int volt_gpcv_mt_markov_step_f32(const float* x, const float* vol, float jitter,
     }
     mtm::TaskArgs ta{covar_factor, raw_var, Lt, M, c, w.gpart, w.colpart, w.ellpart, w.xs, out, grad_c, grad_Lt,
                      grad_covar_factor, grad_raw_var, w.kti, w.tsc, info, w.nch, w.ngh, N, T, jitter, we, wk};
-    hipLaunchKernelGGL(mtm::task_kernel, dim3(1), dim3(mtm::MM_NT), 0, s, ta);
+    hipLaunchKernelGGL(mtm::task_kernel, dim3(1), dim3(TASK_NT), 0, s, ta);
     hipLaunchKernelGGL(mtm::back_kernel, dim3(1 + w.ngm), dim3(mtm::MM_T), 0, s, x, vol, jit, M, c, gamma, w.s, w.e, w.rowred, w.gm,
                        w.kti, w.tsc, we, wk, grad_M, grad_rho, grad_gamma, N, T);
     VOLT_LAUNCH_CHECK();

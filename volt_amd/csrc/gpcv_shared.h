@@ -41,4 +41,57 @@ int launch_mt_cv_pass(const float* M, const float* Lt, const float* y, const flo
                       float* rowred, float* colpart, float* ellpart, float* cvpart, float* grad_abc, int N, int T,
                       hipStream_t s);
 
+// ---- the Gauss-Hermite node bodies of the multi-task and the Markov steps.  (gpcv.hip's gh_ell_kernel / gh_cv_ell_kernel keep
+// the same statements written out: calling these from there changed that file's gfx950 ISA)
+// One node of the "exp" likelihood:  sc = max(exp f, min_scale),  logp = -y^2 / (2 sc^2) - log sc - log sqrt(2 pi),
+//   g = dlogp/df = (y^2/sc^2 - 1) [exp f > min_scale];  lms = log min_scale.  The caller weighs and adds them up.
+struct ExpNode {
+    float logp, g;
+};
+__device__ __forceinline__ ExpNode exp_node(float f, float yi, float min_scale, float lms) {
+    const float ef = expf(f);
+    const bool live = ef > min_scale;
+    const float sc = live ? ef : min_scale;
+    const float r = yi / sc;
+    return ExpNode{-0.5f * r * r - (live ? f : lms) - 0.91893853320467274f, live ? (r * r - 1.f) : 0.f};
+}
+
+// One node of the copula-process ("cv") likelihood:  s(f) = sum_k a_k softplus(b_k f + c_k),
+//   sc = max(s, min_scale),  logp = -y^2 / (2 sc^2) - log sc - log sqrt(2 pi),  wg = w_q dlogp/ds = w_q (y^2/sc^2 - 1)/sc
+//   [s > min_scale].  Adds w_q logp to e, wg ds/df to gm, wg ds/df x_q to gv, and wg (softplus(u_k), a_k sigmoid(u_k) f,
+//   a_k sigmoid(u_k)) to the parameter sums ga, gb, gc.
+template <int KC>
+__device__ __forceinline__ void cv_node(float f, float xq, float wq, float yi, float min_scale, const float (&pa)[KC],
+                                        const float (&pb)[KC], const float (&pc)[KC], float (&ga)[KC], float (&gb)[KC],
+                                        float (&gc)[KC], float& e, float& gm, float& gv) {
+    float sp[KC], sg[KC];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+        const float u = pb[k] * f + pc[k];
+        const float t = expf(-fabsf(u));
+        const float inv = 1.f / (1.f + t);
+        sp[k] = fmaxf(u, 0.f) + log1pf(t);
+        sg[k] = u >= 0.f ? inv : t * inv;
+        s += pa[k] * sp[k];
+    }
+    const bool live = s > min_scale;
+    const float sc = live ? s : min_scale;
+    const float r = yi / sc;
+    const float logp = -0.5f * r * r - logf(sc) - 0.91893853320467274f;
+    const float wg = live ? wq * (r * r - 1.f) / sc : 0.f;      // w_q g_s
+    float dsdf = 0.f;
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+        const float as = pa[k] * sg[k];
+        dsdf += as * pb[k];
+        ga[k] += wg * sp[k];
+        gb[k] += wg * as * f;
+        gc[k] += wg * as;
+    }
+    e += wq * logp;
+    gm += wg * dsdf;
+    gv += wg * dsdf * xq;
+}
+
 }  // namespace volt

@@ -42,104 +42,27 @@
 //
 // markov_predict_draw_kernel: one lane per path, one wave per 64 paths of one series.  The plan is wave-uniform and read as
 // such; the wave's 64 x E block of eps and its 64 x H block of out pass through LDS in chunks of MP_CH columns with padded
-// rows (chain_draw.hip's data movement: the global side moves along the rows, never a lane per step at stride H or E).
+// rows (chain_draw.hip's data movement, chain.h's tile_load / tile_store: the global side moves along the rows, never a lane
+// per step at stride H or E).
 //
-// affine_scan and markov_var_scan are private copies of gpcv_markov.hip's (as gpcv_mt_markov.hip has): that file is compiled
-// alone and its text is pinned by its tests.  fp64 arithmetic, fp32 I/O; no atomics, no scratch; the order of every operation
-// depends on (N, H) alone: bitwise repeatable.
+// affine_scan and markov_var_scan are markov_scan.h's, the staged tile chain.h's.  fp64 arithmetic, fp32 I/O; no atomics, no
+// scratch; the order of every operation depends on (N, H) alone: bitwise repeatable.
 #include "common.h"
 #include "host.h"
+#include "chain.h"
+#include "markov_scan.h"
 #include "../../include/volt_hip.h"
 
 namespace volt {
 namespace mpr {
 
-constexpr int MP_T = 512;                  // threads of the plan's workgroup: gpcv_markov.hip's MK_T (the same scan order for s)
+constexpr int MP_T = MARKOV_VAR_T;         // threads of the plan's workgroup: the step's, so that markov_var_scan gives the step's s
 constexpr int MP_W = MP_T / 64;
-constexpr int MP_R = 4;                    // points a thread composes before the cross-lane scan: gpcv_markov.hip's MK_R
 constexpr int MP_CH = 32;                  // columns per staged chunk of the draw
 constexpr int MP_LD = MP_CH + 1;           // the padded row
 constexpr int MP_HMAX = 1 << 24;           // test points at most (a step's code is 8 h + op in an int)
 
 enum { OP_NOP = 0, OP_KNOT = 1, OP_OPEN = 2, OP_POINT = 3, OP_CLOSE = 4 };
-
-struct Aff {                               // t -> a + b t
-    double a, b;
-};
-// g after f
-__device__ __forceinline__ Aff aff_then(const Aff& f, const Aff& g) { return Aff{__builtin_fma(g.b, f.a, g.a), g.b * f.b}; }
-__device__ __forceinline__ double shfl_up_d(double v, int d) { return __shfl_up(v, d, 64); }
-
-// Keeps a wave-uniform value in vector registers (gpcv_markov.hip's park_in_vgpr): the plan kernel's pointers and the bases made
-// from them do not fit the scalar register file beside the fp64 constants of exp; what only the last phase needs waits here
-template <class V>
-__device__ __forceinline__ void park_in_vgpr(V& v) {
-    asm("" : "+v"(v));
-}
-
-// value_p = a_p + b_p value_{p-1}, p = 0 .. n-1, value_{-1} = 0 (gpcv_markov.hip's affine_scan, word for word; lds: 2 W + 1 doubles)
-template <int T, class Coef, class Sink>
-__device__ __forceinline__ void affine_scan(int64_t n, double* lds, Coef coef, Sink sink) {
-    constexpr int W = T / 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr int64_t CH = (int64_t)T * MP_R;
-    double carry = 0.0;
-    for (int64_t c0 = 0; c0 < n; c0 += CH) {
-        const int64_t p0 = c0 + (int64_t)tid * MP_R;
-        double a[MP_R], b[MP_R];
-        Aff run{0.0, 1.0};
-#pragma unroll
-        for (int r = 0; r < MP_R; ++r) {
-            a[r] = 0.0;
-            b[r] = 1.0;
-            if (p0 + r < n) coef(p0 + r, a[r], b[r]);
-            run = aff_then(run, Aff{a[r], b[r]});
-        }
-        Aff inc = run;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const Aff o{shfl_up_d(inc.a, d), shfl_up_d(inc.b, d)};
-            if (lane >= d) inc = aff_then(o, inc);
-        }
-        if (lane == 63) {
-            lds[2 * wave] = inc.a;
-            lds[2 * wave + 1] = inc.b;
-        }
-        Aff exc{shfl_up_d(inc.a, 1), shfl_up_d(inc.b, 1)};
-        if (lane == 0) exc = Aff{0.0, 1.0};
-        __syncthreads();
-        double v = carry;
-#pragma unroll 1
-        for (int w = 0; w < wave; ++w) v = __builtin_fma(lds[2 * w + 1], v, lds[2 * w]);
-        double vend = v;
-#pragma unroll 1
-        for (int w = wave; w < W; ++w) vend = __builtin_fma(lds[2 * w + 1], vend, lds[2 * w]);
-        v = __builtin_fma(exc.b, v, exc.a);
-#pragma unroll
-        for (int r = 0; r < MP_R; ++r) {
-            v = __builtin_fma(b[r], v, a[r]);
-            if (p0 + r < n) sink(p0 + r, v);
-        }
-        carry = vend;
-        __syncthreads();
-    }
-}
-
-// s_i = diag P^-1 into sb [N] (backward scan); eb [N] keeps e^{-2 rho_i} (gpcv_markov.hip's markov_var_scan)
-template <int T>
-__device__ __forceinline__ void markov_var_scan(const float* __restrict__ rho, const float* __restrict__ gam, double* sb, double* eb,
-                                                int64_t n, double* lds) {
-    affine_scan<T>(
-        n, lds,
-        [&](int64_t p, double& a, double& b) {
-            const int64_t i = n - 1 - p;
-            a = exp(-2.0 * (double)rho[i]);
-            eb[i] = a;
-            const double g = p > 0 ? (double)gam[i] : 0.0;             // gamma_{N-1} is never read
-            b = g * g;
-        },
-        [&](int64_t p, double v) { sb[n - 1 - p] = v; });
-}
 
 // the smallest value over the workgroup (every thread gets it).  red: MP_W ints
 __device__ __forceinline__ int block_min_i(int v, int* red) {
@@ -218,7 +141,7 @@ __global__ __launch_bounds__(MP_T) void markov_predict_plan_kernel(PlanParams p)
     }
 
     // ---- 2. s, and Phi, r segmented at the selected knots.  Knot k is selected iff k = N-1 or some idx is k-1 or k
-    markov_var_scan<MP_T>(rb, gb, sb, qb, n, lds);                     // (qb holds e^{-2 rho} until the r scan replaces it)
+    markov_var_scan<MP_T, false>(rb, gb, sb, qb, n, lds);                     // (qb holds e^{-2 rho} until the r scan replaces it)
     auto right_selected = [&](int64_t i) -> bool {                     // is knot i + 1 selected
         if (i + 1 == n - 1) return true;
         int64_t lo = 0, hi = H;                                        // the first h with idx_h >= i
@@ -327,46 +250,6 @@ __global__ __launch_bounds__(MP_T) void markov_predict_plan_kernel(PlanParams p)
     if (tid == 0) *info = notfinite;
 }
 
-// ---- the staged tile: rows [0, rows) x columns [0, cnt) between global memory (row r at src(r), unit stride) and tile[r][MP_LD]
-// (chain_draw.hip's tile_load / tile_store for fp32)
-template <int V, typename RowPtr>
-__device__ __forceinline__ void tile_load(float* tile, RowPtr src, int rows, int cnt, int lane) {
-    typedef float vec_t __attribute__((ext_vector_type(V)));
-    constexpr int NV = MP_CH / V;
-    for (int idx = lane; idx < 64 * NV; idx += 64) {
-        const int r = idx / NV, c = (idx % NV) * V;
-        if (r < rows && c < cnt) {
-            const float* s = src(r) + c;
-            if constexpr (V > 1) {
-                const vec_t v = *reinterpret_cast<const vec_t*>(s);
-#pragma unroll
-                for (int u = 0; u < V; ++u) tile[r * MP_LD + c + u] = v[u];
-            } else {
-                tile[r * MP_LD + c] = *s;
-            }
-        }
-    }
-}
-template <int V, typename RowPtr>
-__device__ __forceinline__ void tile_store(const float* tile, RowPtr dst, int rows, int cnt, int lane) {
-    typedef float vec_t __attribute__((ext_vector_type(V)));
-    constexpr int NV = MP_CH / V;
-    for (int idx = lane; idx < 64 * NV; idx += 64) {
-        const int r = idx / NV, c = (idx % NV) * V;
-        if (r < rows && c < cnt) {
-            float* d = dst(r) + c;
-            if constexpr (V > 1) {
-                vec_t v;
-#pragma unroll
-                for (int u = 0; u < V; ++u) v[u] = tile[r * MP_LD + c + u];
-                *reinterpret_cast<vec_t*>(d) = v;
-            } else {
-                *d = tile[r * MP_LD + c];
-            }
-        }
-    }
-}
-
 struct DrawParams {
     const double *mean, *coef;             // [B,H], [B,3H+1,3]
     const int *code, *steps;               // [B,3H+1], [B]
@@ -404,12 +287,12 @@ __global__ __launch_bounds__(64) void markov_predict_draw_kernel(DrawParams p) {
     auto flush = [&]() {
         __syncthreads();
         const int cnt = (int)(H - cur < MP_CH ? H - cur : MP_CH);
-        tile_store<VO>(to, [&](int r) { return ob + r * H + cur; }, rows, cnt, lane);
+        tile_store<float, VO, MP_CH>(to, [&](int r) { return ob + r * H + cur; }, rows, cnt, lane);
         __syncthreads();
     };
     for (int64_t e0 = 0; e0 < E; e0 += MP_CH) {
         const int cnt = (int)(E - e0 < MP_CH ? E - e0 : MP_CH);
-        tile_load<VE>(te, [&](int r) { return eb + r * EC + e0; }, rows, cnt, lane);
+        tile_load<float, VE, MP_CH>(te, [&](int r) { return eb + r * EC + e0; }, rows, cnt, lane);
         __syncthreads();
         for (int k = 0; k < cnt; ++k) {
             const int cd = code[e0 + k], op = cd & 7;
