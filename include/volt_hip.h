@@ -660,6 +660,35 @@ int volt_markov_root_draw_f32(const float* m, const float* rho, const float* gam
                               int N, void* stream);
 int volt_markov_root_var_f32(const float* rho, const float* gamma, double* var, int B, int N, void* stream);
 
+/* ---- Natural-gradient update of the Markov GPCV's q in O(N), ONE launch (csrc/gpcv_markov_ng.hip has the
+ * recurrences).  Prior, family and likelihood arguments as volt_gpcv_markov_step_f32, with mu [B,N] the prior mean in place of
+ * resid.  The optimum of F over q has precision K_M^-1 + diag(lam2) and mean mu + P^-1 lam1, which lies in the family; one call
+ * moves the sites lam1, lam2 [B,N] (fp64, updated IN PLACE; zeros stand for q = prior) a step in (0, 1] towards the targets the
+ * current q = (m, rho, gamma) asks for, with r = w_ell / w_kl, d = m - mu, gm = dE/dm, gv = dE/ds at the current q,
+ *     t2_i = max(-2 r gv_i, 0),  t1_i = r gm_i + t2_i d_i,  lam <- (1 - step) lam + step t,
+ * and writes the q of the new sites: (rho_out, gamma_out) the bidiagonal root of K_M^-1 + diag(lam2) (gamma_out[., N-1] = 0;
+ * gamma[., N-1] is never read), m_out = mu + P^-1 lam1.  m_out / rho_out / gamma_out may be the buffers m / rho / gamma.
+ *     out[b,0..3] (fp64) = the number of sites clamped at 0 (gv_i > 0), max |m_out - m|, max |rho_out - rho|,
+ *                          max |gamma_out - gamma| (over i < N - 1)
+ * info[b]: 0, or 1 where a site, a pivot or an output of series b is not finite (only a non-finite input can do that: every
+ * pivot of K_M^-1 + diag(lam2 >= 0) is positive); m_out, rho_out, gamma_out, lam1, lam2 and out of that series are then NaN,
+ * the other series are not affected.
+ * workspace: volt_gpcv_markov_ng_workspace_bytes(B, N, Kc) bytes (0 for a shape out of range), 256-byte aligned, 32 B N bytes;
+ * it needs no initialisation call and is fully written before it is read.  On return its first 8 B N bytes hold
+ * diag P^-1 [B,N] of the INPUT q in fp64: volt_gpcv_markov_step_f32's s bit for bit.
+ * One workgroup per series; no host synchronisation, no allocation, no atomics: every reduction has a fixed order, results are
+ * bitwise repeatable, and the launch replays from a hipGraph.  1 <= B <= 65535, N >= 1; 64-bit indices.
+ * Argument errors (before the launch, in the order of their numbers): -1 x, -2 vol, -4 mu, -5 m, -6 rho, -7 gamma, -8 y NULL;
+ * -10 Kc out of range with abc, or Kc != 0 without; -11 gh_x, -12 gh_w NULL; -13 Q outside 1 .. 1024; -17 w_kl not > 0;
+ * -18 step outside (0, 1]; -19 lam1, -20 lam2, -21 m_out, -22 rho_out, -23 gamma_out, -24 out, -25 info NULL; -26 workspace NULL
+ * or not 256-byte aligned; -27 B outside 1 .. 65535; -28 N < 1. */
+size_t volt_gpcv_markov_ng_workspace_bytes(int B, int N, int Kc);
+int volt_gpcv_markov_ng_f32(const float* x, const float* vol, float jitter, const float* mu, const float* m, const float* rho,
+                            const float* gamma, const float* y, const float* abc, int Kc, const float* gh_x, const float* gh_w,
+                            int Q, float min_var, float min_scale, float w_ell, float w_kl, double step, double* lam1,
+                            double* lam2, float* m_out, float* rho_out, float* gamma_out, double* out, int* info,
+                            void* workspace, int B, int N, void* stream);
+
 /* ---- The Markov GPCV away from its grid in O(N + S H): mean, variance and joint path draws of f at H test points
  * (SingleTaskVariationalGP / MultitaskVariationalGP(prior_solver="markov")(x); csrc/markov_predict.hip has the
  * formulas and the plan's steps).  Given u ~ q, f(xi) is a Brownian bridge between the neighbouring knots of the grid x [N],

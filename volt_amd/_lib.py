@@ -105,6 +105,9 @@ _SIGS = {
                                   + [_ptr] * 8 + [_i32, _i32, _ptr]),
     "volt_markov_root_draw_f32": (C.c_int, [_ptr] * 5 + [_i32, _i32, _i32, _ptr]),
     "volt_markov_root_var_f32": (C.c_int, [_ptr] * 3 + [_i32, _i32, _ptr]),
+    "volt_gpcv_markov_ng_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "volt_gpcv_markov_ng_f32": (C.c_int, [_ptr, _ptr, _f32] + [_ptr] * 6 + [_i32, _ptr, _ptr, _i32, _f32, _f32, _f32, _f32, _f64]
+                                + [_ptr] * 8 + [_i32, _i32, _ptr]),
     "volt_gpcv_mt_markov_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "volt_gpcv_mt_markov_step_f32": (C.c_int, [_ptr, _ptr, _f32] + [_ptr] * 9 + [_i32, _ptr, _ptr, _i32, _f32, _f32, _f32, _f32]
                                      + [_ptr] * 11 + [_i32, _i32, _ptr]),

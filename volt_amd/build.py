@@ -17,7 +17,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libvolt_hip.so")
-SOURCES = ["runtime.hip", "fill.hip", "ewma.hip", "chol.hip", "one_launch.hip", "batch_step.hip", "chol64.hip", "batch64_step.hip", "trsv.hip", "mll.hip", "mll64.hip", "rollout.hip", "gpcv.hip", "gpcv_mt.hip", "gpcv_mt_cv.hip", "adam.hip", "kron.hip", "kron_chain.hip", "summary.hip", "bm.hip", "gpcv_bm.hip", "chain_draw.hip", "gpcv_markov.hip", "gpcv_mt_markov.hip", "markov_predict.hip"]
+SOURCES = ["runtime.hip", "fill.hip", "ewma.hip", "chol.hip", "one_launch.hip", "batch_step.hip", "chol64.hip", "batch64_step.hip", "trsv.hip", "mll.hip", "mll64.hip", "rollout.hip", "gpcv.hip", "gpcv_mt.hip", "gpcv_mt_cv.hip", "adam.hip", "kron.hip", "kron_chain.hip", "summary.hip", "bm.hip", "gpcv_bm.hip", "chain_draw.hip", "gpcv_markov.hip", "gpcv_mt_markov.hip", "markov_predict.hip", "gpcv_markov_ng.hip"]
 HEADERS = ["common.h", "chain.h", "handoff.h", "tiles.h", "tiles64.h", "host.h", "table_cache.h", "sched.h", "long_sched.h", "batch_sched.h", "gpcv_shared.h", "gpcv_task.h", "markov_scan.h", "kron_shared.h", os.path.join("..", "..", "include", "volt_hip.h"),
            os.path.join("..", "..", "include", "volt_hip_tune.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",

@@ -111,7 +111,7 @@ def _check_vol_posterior(vol_posterior, vol_solver):
     check_options("vol_posterior", vol_solver, vol_posterior)
 
 
-GPCV_OPTIONS = ("param", "K", "train_likelihood")      # what gpcv_options may carry to the GPCV fit
+GPCV_OPTIONS = ("param", "K", "train_likelihood", "optimizer", "ng_step")      # what gpcv_options may carry to the GPCV fit
 MULTITASK_GPCV = (False, True, "markov")               # True: the dense joint model; "markov": its Markov family
 
 
@@ -123,6 +123,12 @@ def _check_gpcv_options(gpcv_options, multitask_gpcv, gpcv_solver, nseries, vol_
         raise ValueError(f"gpcv_options: unknown keys {unknown}; it takes {list(GPCV_OPTIONS)}")
     if multitask_gpcv not in MULTITASK_GPCV:
         raise ValueError(f"multitask_gpcv must be one of {list(MULTITASK_GPCV)}, got {multitask_gpcv!r}")
+    if vol_fn is None and ("optimizer" in opts or "ng_step" in opts):     # (natural-gradient updates: FitGPCV)
+        from .train_utils import _check_gpcv_optimizer
+        _check_gpcv_optimizer(opts.get("optimizer", "adam"), opts.get("ng_step", 1.0), gpcv_solver, multitask=bool(multitask_gpcv))
+        if multitask_gpcv:                               # (the joint fit has Adam only and takes neither key)
+            opts.pop("optimizer", None)
+            opts.pop("ng_step", None)
     if multitask_gpcv and vol_fn is None:
         from . import ops
         what = 'multitask_gpcv="markov" chooses the joint model\'s own solver' if multitask_gpcv == "markov" else \
@@ -293,8 +299,9 @@ def GenerateStockPredictionsBatch(tickers, closes, dates=None, forecast_horizon=
     LearnGPCV; not with ``gpcv_solver="linear"`` or ``"markov"``.  The series-by-series redo after a failed window then runs
     T = 1.  ``multitask_gpcv="markov"``: the same joint model with the Markov variational family under the level-jitter
     Brownian prior (LearnGPCVMultitask(solver="markov"), csrc/gpcv_mt_markov.hip): O(N T), no N x N array.
-    ``gpcv_options``: a dict with keys out of ``param``, ``K``, ``train_likelihood``, forwarded to whichever GPCV fit runs
-    (FitGPCV / FitGPCVMultitask); unknown keys raise.  Both are ignored with a ``vol_fn``; the defaults change nothing."""
+    ``gpcv_options``: a dict with keys out of ``param``, ``K``, ``train_likelihood``, ``optimizer``, ``ng_step`` (the last two:
+    ``{"optimizer": "natgrad"}`` with ``gpcv_solver="markov"`` fits q by natural-gradient updates, FitGPCV),
+    forwarded to whichever GPCV fit runs (FitGPCV / FitGPCVMultitask); unknown keys raise.  Both are ignored with a ``vol_fn``; the defaults change nothing."""
     _check_vol_posterior(vol_posterior, vol_solver)
     _resolve_draw(predict_draw, predict_solver)
     if mean not in _MODES and mean not in _STANDARD:

@@ -40,11 +40,13 @@ class Volt(VolGP):
         self._full_x, self._full_log_data = train_x, log_data    # Train's GPCV stage starts from the prices
 
     def Train(self, gpcv_iters=400, vol_mod_iters=1000, data_mod_iters=400, display=False, vol=None,
-              vol_model=None, vol_lh=None, *, gpcv_solver="dense"):
+              vol_model=None, vol_lh=None, *, gpcv_solver="dense", gpcv_optimizer="adam"):
         """Volt.py:95-146: GPCV + vol model (:103-104), then the data model (:108-146).  ``vol`` (and optionally a
         trained ``vol_model`` / ``vol_lh``) skips the first stage.  ``gpcv_solver="linear"``: the GPCV stage on the O(N^2)
         ELBO step, ``"markov"``: on the O(N) step with the Markov variational family (LearnGPCV(solver=...)); the vol forecaster keeps the solver and posterior the model was built with (``vol_solver``, ``vol_posterior``), and so does the data
-        model (``data_solver``: UpdateVolPath rebuilds the lazy prior, the fit below steps on it)."""
+        model (``data_solver``: UpdateVolPath rebuilds the lazy prior, the fit below steps on it).
+        ``gpcv_optimizer="natgrad"`` (with ``gpcv_solver="markov"``): the GPCV's q by natural-gradient updates
+        (LearnGPCV(optimizer=...))."""
         from ..train_utils import LR_DATA, LearnGPCV, TrainVolModel, _attach_vol, _fit_exact, _train_noise_and_mean
         x = self.train_x.squeeze()
         if vol is None:
@@ -52,7 +54,8 @@ class Volt(VolGP):
                 raise NotImplementedError("batched Volt.Train: fit the vol path with LearnGPCV(train_x, prices [T,N+1]) "
                                           "and pass it as vol= (the reference's GPCV + MultitaskBMGP stage is not wired into "
                                           "batched Train; TrainVolModelMultitask fits the multitask vol model)")
-            vol = LearnGPCV(self._full_x[1:], self._full_log_data.exp(), gpcv_iters, printing=display, solver=gpcv_solver)
+            vol = LearnGPCV(self._full_x[1:], self._full_log_data.exp(), gpcv_iters, printing=display, solver=gpcv_solver,
+                            optimizer=gpcv_optimizer)
             vol_model, vol_lh = TrainVolModel(self._full_x[1:], vol, vol_mod_iters, printing=display, solver=self.vol_solver,
                                               vol_posterior=self.vol_posterior)
         self.UpdateVolPath(vol)

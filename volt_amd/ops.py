@@ -794,6 +794,68 @@ def gpcv_markov_step(x, vol, resid, m, rho, gamma, y, gh_x, gh_w, ws: GpcvMarkov
     return ws
 
 
+class GpcvMarkovNgWorkspace(_GpcvStepWorkspace):
+    """Caller-owned scratch and outputs of volt_gpcv_markov_ng_f32, reusable across updates of the same (B, N, Kc): 32 B N
+    bytes, no initialisation call.  ``.m_out``, ``.rho_out``, ``.gamma_out`` [B,N] fp32 receive the new q unless the caller
+    names other buffers; ``.out`` [B,4] fp64 and ``.info`` [B]; after an update ``.s`` [B,N] (fp64, a view of the scratch)
+    holds diag P^-1 of the q that went IN."""
+    _STEP = 'the "cv" natural-gradient update'
+
+    def __init__(self, B: int, N: int, device, Kc: int = 0):
+        self.B, self.N, self.Kc = B, N, self._checked_kc(Kc)
+        self._allocate((B, N, self.Kc), device, _lib.lib().volt_gpcv_markov_ng_workspace_bytes(B, N, self.Kc), n_info=B,
+                       outputs={"m_out": (B, N), "rho_out": (B, N), "gamma_out": (B, N)})
+        self.out = torch.empty(B, 4, dtype=torch.float64, device=device)
+        off = self.ptr - self.buf.data_ptr()
+        self.s = self.buf[off:off + 8 * B * N].view(torch.float64).view(B, N)
+
+    def fits(self, B, N, device, Kc=0):
+        return self._fits(device, B, N, Kc)
+
+
+def gpcv_markov_natgrad(x, vol, mu, m, rho, gamma, y, gh_x, gh_w, lam1, lam2, ws: GpcvMarkovNgWorkspace | None = None, abc=None,
+                        into=None, jitter: float = 1e-3, min_var: float = 1e-6, min_scale: float = 1e-3, w_ell: float = 1.0,
+                        w_kl: float = 1.0, step: float = 1.0):
+    """One natural-gradient update of the Markov variational family in O(N) and ONE launch (include/volt_hip.h,
+    volt_gpcv_markov_ng_f32).  Arguments as ``gpcv_markov_step`` with the prior mean ``mu`` [B,N] in place of
+    resid, and the sites ``lam1``, ``lam2`` [B,N] fp64 contiguous, UPDATED IN PLACE (zeros: q = prior): they move ``step`` in
+    (0, 1] towards t2 = max(-2 r dE/ds, 0), t1 = r dE/dm + t2 (m - mu), r = w_ell / w_kl, and the q with precision
+    K_M^-1 + diag(lam2) and mean mu + P^-1 lam1 is written to ``into`` = (m_out, rho_out, gamma_out), fp32 contiguous [B,N]
+    -- they MAY be m, rho, gamma themselves -- or, without ``into``, to the workspace's .m_out, .rho_out, .gamma_out.
+    Returns the workspace: .out [B,4] fp64 = (clamped sites, max |dm|, max |drho|, max |dgamma|), .info (1: a non-finite
+    series, whose outputs and sites are NaN), .s = diag P^-1 of the q that went in.  No host read."""
+    _need_gpu(x, vol, mu, m, rho, gamma, y, gh_x, gh_w, lam1, lam2, abc)
+    if m.ndim != 2:
+        raise ValueError("m must be [B,N]")
+    B, n = m.shape
+    if x.shape[-1] != n:
+        raise ValueError("x and m disagree on N")
+    for name, t in (("lam1", lam1), ("lam2", lam2)):
+        if t.dtype != torch.float64 or tuple(t.shape) != (B, n) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous fp64 [B,N] = {(B, n)} tensor (it is updated in place)")
+    if not 0.0 < float(step) <= 1.0:
+        raise ValueError(f"gpcv_markov_natgrad: step must lie in (0, 1], got {step}")
+    x, vol, _ = _bm_args(x, vol, vol, B, torch.float32)
+    mu = mu.detach().to(torch.float32)                                   # [B,N], or one value per series, or one value
+    mu = (mu.reshape(B, n) if mu.numel() == B * n else mu.reshape(-1, 1).expand(B, n)).contiguous()
+    m, y, rho, gamma = (_f32(t, (B, n)) for t in (m, y, rho, gamma))
+    gh_x, gh_w, quad = _quad_args(gh_x, gh_w, min_var, min_scale, w_ell, w_kl)
+    abc, Kc, sizeable = _abc_arg(abc, B, "B", reject=GpcvMarkovNgWorkspace._STEP)
+    ws = _step_workspace(GpcvMarkovNgWorkspace, ws, sizeable, B, n, m.device, Kc)
+    if into is None:
+        into = (ws.m_out, ws.rho_out, ws.gamma_out)
+    for t in into:
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, n) or not t.is_contiguous() or t.device != m.device:
+            raise ValueError(f"gpcv_markov_natgrad: every output must be a contiguous fp32 [B,N] = {(B, n)} tensor on m's device")
+    with torch.cuda.device(m.device):
+        _lib.check(_lib.lib().volt_gpcv_markov_ng_f32(
+            x.data_ptr(), vol.data_ptr(), float(jitter), mu.data_ptr(), m.data_ptr(), rho.data_ptr(), gamma.data_ptr(),
+            y.data_ptr(), abc.data_ptr() if abc is not None else None, Kc, *quad, float(step), lam1.data_ptr(), lam2.data_ptr(),
+            *(t.data_ptr() for t in into), *_ptrs(ws, "out", "info", "ptr"), B, n, _lib.stream_ptr()),
+            "volt_gpcv_markov_natgrad")
+    return ws
+
+
 def _markov_root_args(rho, gamma):
     _need_gpu(rho, gamma)
     if rho.ndim != 2 or gamma.shape != rho.shape:

@@ -256,6 +256,7 @@ def _fit_exact(model, lh, train_x, target, params, lr, train_iters, printing, gr
 
 # ------------------------------------------------------------------------------------------------ (f)4: GPCV
 GPCV_SOLVERS = ("dense", "linear", "markov")
+GPCV_OPTIMIZERS = ("adam", "natgrad")
 
 
 def _check_gpcv_solver(solver, kernel):
@@ -265,8 +266,23 @@ def _check_gpcv_solver(solver, kernel):
         raise ValueError(f"GPCV: solver={solver!r} needs kernel='bm' (Brownian motion is Markov; kernel {kernel!r} is not)")
 
 
+def _check_gpcv_optimizer(optimizer, ng_step, solver, multitask=False):
+    if optimizer not in GPCV_OPTIMIZERS:
+        raise ValueError(f"GPCV: optimizer must be one of {GPCV_OPTIMIZERS}, got {optimizer!r}")
+    if optimizer != "natgrad":
+        return
+    if multitask:
+        raise ValueError('multi-task GPCV: optimizer="natgrad" is the single-task fit\'s (FitGPCV(solver="markov")): under the '
+                         "Kronecker family the optimal q is not in the family, so there is no fixed point to iterate to")
+    if solver != "markov":
+        raise ValueError(f'GPCV: optimizer="natgrad" needs solver="markov" (only the Markov variational family contains the '
+                         f"optimal q; got solver={solver!r})")
+    if not 0.0 < float(ng_step) <= 1.0:
+        raise ValueError(f"GPCV: ng_step must lie in (0, 1], got {ng_step}")
+
+
 def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None, *, param="exp", K=1,
-            train_likelihood=False, solver="dense"):
+            train_likelihood=False, solver="dense", optimizer="adam", ng_step=1.0):
     """The fit inside LearnGPCV (train_utils.py:15-58), returning what it builds: (model, likelihood, losses).
     ``param="cv"`` fits the copula-process likelihood with K warp terms (volatility_likelihood.py:43-51; the start-up
     values exist for K = 1 only, as in the reference); ``train_likelihood=True`` adds its raw_a, raw_b, raw_c to the one
@@ -276,8 +292,14 @@ def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", gra
     (``SingleTaskVariationalGP(prior_solver="linear")``; the start-up values stay dense).
     ``solver="markov"`` (kernel "bm" only): the Markov variational family and the level-jitter Brownian prior of
     ``SingleTaskVariationalGP(prior_solver="markov")`` -- one launch per step, O(N) time and memory, start-up values included
-    (csrc/gpcv_markov.hip).  A different model from the other two solvers' (another prior jitter, another family)."""
+    (csrc/gpcv_markov.hip).  A different model from the other two solvers' (another prior jitter, another family).
+    ``optimizer="natgrad"`` (``solver="markov"`` only; the default "adam" is the loop above, unchanged): q is fitted by
+    natural-gradient updates of ``ng_step`` in (0, 1] -- one O(N) launch each (csrc/gpcv_markov_ng.hip) -- and Adam
+    at LR_GPCV keeps every OTHER parameter.  An iteration is the update, then the ELBO step and its backward, then Adam: the
+    loss of an iteration is -ELBO at the updated q.  About ten iterations reach the ELBO Adam reaches after two hundred; with
+    ``param="cv"`` (not log-concave) use ``ng_step=0.5``, and expect losses that do not fall monotonically."""
     _check_gpcv_solver(solver, kernel)
+    _check_gpcv_optimizer(optimizer, ng_step, solver)
     from .kernels import BMKernel, FBMKernel
     from .likelihoods import VolatilityGaussianLikelihood
     from .models import SingleTaskVariationalGP
@@ -296,25 +318,36 @@ def FitGPCV(train_x, train_y, train_iters=1000, printing=False, kernel="bm", gra
     # the model registers its likelihood: model.parameters() holds its raw_a, raw_b, raw_c, and Adam steps the ones that
     # receive a gradient
     return _fit_gpcv(model, likelihood, model.parameters(), train_x, yy, yy.shape[-1], train_iters, printing, graph,
-                     train_likelihood)
+                     train_likelihood, ng_step=float(ng_step) if optimizer == "natgrad" else None)
 
 
-def _fit_gpcv(model, likelihood, params, train_x, yy, num_data, train_iters, printing, graph, train_likelihood):
+def _fit_gpcv(model, likelihood, params, train_x, yy, num_data, train_iters, printing, graph, train_likelihood, ng_step=None):
     """The fit FitGPCV and FitGPCVMultitask share once the model, the likelihood and the scaled returns ``yy`` exist: Adam at
     LR_GPCV on ``params`` over -ELBO under 75 Gauss-Hermite nodes; the likelihood's parameters receive a gradient only with
-    ``train_likelihood``.  Returns (model, likelihood, losses)."""
+    ``train_likelihood``.  ``ng_step`` given (FitGPCV(optimizer="natgrad")): every iteration begins with one natural-gradient
+    update of q (``VariationalELBO.natural_gradient_step``, no host read: it captures like the rest), and the three variational
+    parameters are kept out of Adam and of autograd for the length of the fit.  Returns (model, likelihood, losses)."""
     from .variational import VariationalELBO, num_gauss_hermite_locs
     model.train()
     likelihood.train()
     graph = bool(graph)                                  # (these entries return the per-iteration losses: captured only on request)
     for p in likelihood.parameters():
         p.requires_grad_(bool(train_likelihood))
+    variational = []
+    if ng_step is not None:
+        dist = model.variational_strategy._variational_distribution
+        variational = [dist.variational_mean, dist.log_diag_precision_root, dist.coupling]
+        params = [p for p in params if all(p is not q for q in variational)]
+        for q in variational:
+            q.requires_grad_(False)
     optimizer = _adam([{"params": params}], LR_GPCV, graph)
     elbo = VariationalELBO(likelihood, model, num_data, combine_terms=True)
     losses = []
 
     def iteration():                                     # :50-54
         with num_gauss_hermite_locs(75):
+            if ng_step is not None:
+                elbo.natural_gradient_step(yy, step=ng_step)
             loss = -elbo(model(train_x), yy)
             if not graph:
                 losses.append(loss.detach())
@@ -322,7 +355,11 @@ def _fit_gpcv(model, likelihood, params, train_x, yy, num_data, train_iters, pri
             loss.backward()
         return loss
 
-    last = _run_iterations(iteration, optimizer, train_iters, printing, graph)
+    try:
+        last = _run_iterations(iteration, optimizer, train_iters, printing, graph)
+    finally:
+        for q in variational:
+            q.requires_grad_(True)
     if graph and last is not None:
         losses.append(last.detach())
     model.eval()
@@ -331,18 +368,21 @@ def _fit_gpcv(model, likelihood, params, train_x, yy, num_data, train_iters, pri
 
 
 def LearnGPCV(train_x, train_y, train_iters=1000, printing=False, early_stopping=False, kernel="bm", graph=None, *,
-              param="exp", K=1, train_likelihood=False, solver="dense"):
+              param="exp", K=1, train_likelihood=False, solver="dense", optimizer="adam", ng_step=1.0):
     """voltron/train_utils.py:15-67: the volatility path of a price series from a variational GP (BM or FBM prior over
     log-vol, ``y | f ~ N(0, exp f)``) fitted to the scaled returns; one HIP ELBO step per iteration.
     train_y [N+1] prices -> pred_scale [N]; train_y [T,N+1] fits T series at once (batched parameters).
     ``param``, ``K``, ``train_likelihood``: the copula-process likelihood, see FitGPCV.  ``solver="linear"``: the O(N^2) step
     (FitGPCV); until its capture gate has been measured it is treated like the linear BM step (``launch_bound=True``).
-    ``solver="markov"``: the O(N) step (FitGPCV), one launch per iteration and so launch-bound at every N."""
+    ``solver="markov"``: the O(N) step (FitGPCV), one launch per iteration and so launch-bound at every N.
+    ``optimizer="natgrad"``, ``ng_step``: natural-gradient updates of q instead of Adam on it (FitGPCV; ``solver="markov"``)."""
     _check_gpcv_solver(solver, kernel)
+    _check_gpcv_optimizer(optimizer, ng_step, solver)
     # (only the fitted scale is returned: nothing per-iteration is lost by capturing)
     graph = _auto_graph(graph, train_y[..., 1:], n3_coeff=5.0 / 3.0, launch_bound=solver in ("linear", "markov"))
     model, likelihood, _ = FitGPCV(train_x, train_y, train_iters=train_iters, printing=printing, kernel=kernel, graph=graph,
-                                   param=param, K=K, train_likelihood=train_likelihood, solver=solver)
+                                   param=param, K=K, train_likelihood=train_likelihood, solver=solver, optimizer=optimizer,
+                                   ng_step=ng_step)
     return likelihood(model(train_x), return_gaussian=False).scale.mean(0).detach()      # :60-67
 
 
@@ -368,7 +408,7 @@ def _check_gpcv_mt_solver(solver, kernel):
 
 
 def FitGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel="bm", graph=None, *, param="exp", K=1,
-                     train_likelihood=False, solver="dense"):
+                     train_likelihood=False, solver="dense", optimizer="adam"):
     """LearnGPCV's fit (train_utils.py:15-58) over the JOINT model of T series that share the time grid
     (MultitaskVariationalGP, voltron/models/multi_task_variational_gp.py; the reference has no trainer for it):
     train_y [T,N+1] prices -> (model, likelihood, losses).  One HIP ELBO step per iteration factors the N x N prior ONCE
@@ -378,8 +418,10 @@ def FitGPCVMultitask(train_x, train_y, train_iters=1000, printing=False, kernel=
     the one Adam group at LR_GPCV only with ``train_likelihood=True``.  The defaults are the "exp" loop.
     ``solver="markov"`` (kernel "bm" only): the Markov variational family under the level-jitter Brownian prior of
     ``MultitaskVariationalGP(prior_solver="markov")`` -- O(N T) time and memory, start-up values included, no N x N array
-    (csrc/gpcv_mt_markov.hip).  A different model from the dense solver's (another prior jitter, another family)."""
+    (csrc/gpcv_mt_markov.hip).  A different model from the dense solver's (another prior jitter, another family).
+    ``optimizer``: "adam" only -- "natgrad" (FitGPCV) is refused: the optimum is not in the Kronecker family."""
     _check_gpcv_mt_solver(solver, kernel)
+    _check_gpcv_optimizer(optimizer, 1.0, solver, multitask=True)
     from .kernels import BMKernel, FBMKernel
     from .likelihoods import VolatilityGaussianLikelihood
     from .models import MultitaskVariationalGP

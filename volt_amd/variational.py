@@ -143,6 +143,18 @@ class MarkovVariationalDistribution(Module):
         self.log_diag_precision_root = nn.Parameter(torch.zeros(*batch_shape, num_inducing_points))
         self.coupling = nn.Parameter(torch.zeros(*batch_shape, num_inducing_points))
 
+    def natural_sites(self):
+        """(lam1, lam2) [B,N] fp64: the sites of ``VariationalELBO.natural_gradient_step`` (the optimal q has precision
+        K_M^-1 + diag(lam2) and mean mu + P^-1 lam1).  Non-persistent buffers made at the first call, zeros
+        (q = prior), on the parameters' device: a ``state_dict`` never holds them."""
+        m = self.variational_mean
+        n = m.shape[-1]
+        for name in ("_natural_lam1", "_natural_lam2"):
+            t = getattr(self, name, None)
+            if t is None or t.device != m.device or t.numel() != m.numel() or t.dtype != torch.float64:
+                self.register_buffer(name, torch.zeros(m.numel() // n, n, dtype=torch.float64, device=m.device), persistent=False)
+        return self._natural_lam1, self._natural_lam2
+
 
 class MarkovVariationalLatent(MultivariateNormal):
     """What ``SingleTaskVariationalGP(prior_solver="markov")(train_x)`` returns: q(u) of ``MarkovVariationalDistribution``,
@@ -783,6 +795,48 @@ class VariationalELBO(Module):
         res = _GPCVMarkovElbo.apply(f32(m), f32(latent._rho), f32(latent._gamma), f32(prior.mean.expand(m.shape)), lazy.scale,
                                     lazy.x, f32(target), *self._likelihood_raws(B, m), self, *self._weights(n))
         return res.reshape(m.shape[:-1]) if m.ndim > 1 else res.reshape(())
+
+    def natural_gradient_step(self, target, step=1.0):
+        """One natural-gradient (conjugate-computation VI) update of q for ``SingleTaskVariationalGP(prior_solver="markov")``:
+        ONE launch, O(N), no host read (ops.gpcv_markov_natgrad).  The weights, the likelihood's transformed
+        a, b, c, the prior mean and the vol are what ``forward`` hands the ELBO step.  The sites live on the
+        ``MarkovVariationalDistribution`` (``natural_sites``: fp64, zeros at first use, not in the ``state_dict``); the three
+        variational parameters are overwritten IN PLACE, under ``no_grad``.  ``step`` in (0, 1]: 1 jumps to the q the current
+        sites' targets define (the "exp" likelihood converges in about ten such updates); the "cv" likelihood is not
+        log-concave -- its negative lam2 targets are clamped at 0 and F need not rise monotonically: use a step of 0.5.
+        Returns ``out`` [B,4] fp64: the number of clamped sites and max |change| of the mean, log_diag_precision_root and
+        coupling -- a convergence measure; ``info`` stays on the workspace (1: a non-finite series, now NaN)."""
+        model = self.model
+        strategy = getattr(model, "variational_strategy", None)
+        dist = getattr(strategy, "_variational_distribution", None)
+        if not isinstance(dist, MarkovVariationalDistribution):
+            raise ValueError('VariationalELBO.natural_gradient_step needs SingleTaskVariationalGP(prior_solver="markov"): only '
+                             f"the Markov variational family contains the optimal q (got {type(model).__name__}"
+                             f"(prior_solver={getattr(model, 'prior_solver', None)!r}))")
+        m = dist.variational_mean
+        self._need_cuda(m)
+        with torch.no_grad():
+            prior = model.forward(strategy.inducing_points)
+            lazy = prior.lazy_covariance_matrix
+            if not isinstance(lazy, _BrownianLevelPrior):
+                raise TypeError("VariationalELBO: the Markov variational family needs the prior of prior_solver='markov'")
+            n = m.shape[-1]
+            B = m.numel() // n
+            q = [p.data.view(B, n) for p in (m, dist.log_diag_precision_root, dist.coupling)]
+            if any(t.dtype != torch.float32 or not t.is_contiguous() for t in q):
+                raise ValueError("VariationalELBO.natural_gradient_step: the variational parameters must be contiguous fp32")
+            num_gh, w_ell, w_kl = self._weights(n)
+            gh_x, gh_w = _gauss_hermite(num_gh, m.device)
+            raws = self._likelihood_raws(B, m)
+            abc = _cv_transform(*raws, B)[0] if raws[0] is not None else None
+            lam1, lam2 = dist.natural_sites()
+            # (the update's workspace is no ELBO step's: it lives beside the five of `_WS_ATTR`, kept the same way)
+            ws = ops.cached_workspace(self, "_markov_ng_ws", ops.GpcvMarkovNgWorkspace, B, n, m.device,
+                                      abc.shape[-1] if abc is not None else 0)
+            ops.gpcv_markov_natgrad(lazy.x, lazy.scale, prior.mean.expand(m.shape).reshape(B, n), *q,
+                                    target.reshape(B, n).to(torch.float32), gh_x, gh_w, lam1, lam2, ws, abc=abc, into=tuple(q),
+                                    jitter=PRIOR_JITTER, min_var=MIN_VARIANCE, w_ell=w_ell, w_kl=w_kl, step=step)
+        return ws.out
 
     def forward(self, approximate_dist_f, target):
         if isinstance(approximate_dist_f, MultitaskMarkovVariationalLatent):
