@@ -78,6 +78,13 @@ int volt_sched_describe(int B, int n, int has_y, int k, int G, int S, float frac
  * phases: stamps [B,32] int64 (load, factor32 x4 with panel / trailing updates, L out, inverse, W out, publish). */
 int volt_tune_diag_f32(float* A, float* Winv, int* info, int B, int Np, int k, long long* stamps, void* stream);
 
+/* Test hook (tests/test_gpu_syrk_core.py): ONE symmetric update of diagonal tile (kb,kb) of one matrix A [Np,Np],
+ * A[kb,kb] -= sum_{m < nblk} A[kb,m] A[kb,m]^T (1 <= nblk <= kb), through the two-operand core (sym = 0: the whole tile)
+ * or the symmetric one (sym = 1: the lower 32x32 blocks; the blocks above the diagonal are left as they are).  image
+ * NULL: the tile is stored to A.  Else A is left alone and the tile is put into the pivot image (lower triangle, zeros
+ * above) and copied out of it to image [128][128]. */
+int volt_tune_syrk_f32(float* A, int Np, int kb, int nblk, int sym, float* image, void* stream);
+
 /* The fp64 diagonal-block kernel alone on block column k, with s_memtime stamps of its phases: stamps [B,32] int64
  * (0 start, 1 loaded, per 32-wide sub-block kb: 2+4kb factored, 3+4kb L out + inverted, 4+4kb panel, 5+4kb trailing;
  * 18 L out, 19 W computed, 20 W out). */

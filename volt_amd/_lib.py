@@ -127,6 +127,7 @@ _TUNE_SIGS = {
     "volt_sched_describe": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _ptr, _i32, _ptr]),
     "volt_tune_diag_f32": (C.c_int, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _ptr, _ptr]),
     "volt_tune_diag_f64": (C.c_int, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _ptr, _ptr]),
+    "volt_tune_syrk_f32": (C.c_int, [_ptr, _i32, _i32, _i32, _i32, _ptr, _ptr]),
     "volt_tune_small_stamps": (C.c_int, [_ptr]),
     "volt_long_describe": (C.c_int, [_i32, _i32, _i32, _ptr, _i32, _ptr, _ptr]),
     "volt_batch_describe": (C.c_int, [_i32, _i32, _i32, _i32, _ptr, _i32]),

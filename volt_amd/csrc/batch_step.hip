@@ -192,8 +192,8 @@ __device__ __forceinline__ void batch_piece(const BatchArgs a, const int w, cons
         // L[k,k-1] (and with it all of row k) is there; k >= 2: the look-ahead part of A[k,k] is parked
         batch_wait<LOCAL>(rowp + k, k, k >= 2 ? la + k : nullptr, 1, info_b);
         if (stamps && threadIdx.x == 0) stamps[(int64_t)w * 8 + 3] = __builtin_amdgcn_s_memrealtime();
-        if (k >= 2) update_body<FROMK>(A, Np, k, k, k - 1, k, false, b, src, smem, true);
-        else update_body<FROMK>(A, Np, 1, 1, 0, 1, true, b, src, smem, true);
+        if (k >= 2) update_body<FROMK, 0, false, false, true>(A, Np, k, k, k - 1, k, false, b, src, smem, true);
+        else update_body<FROMK, 0, false, false, true>(A, Np, 1, 1, 0, 1, true, b, src, smem, true);
         if (stamps && threadIdx.x == 0) stamps[(int64_t)w * 8 + 4] = __builtin_amdgcn_s_memrealtime();
         diag_body<false, false, LOCAL>(A, Winv, info, Np, k, b, smem, nullptr, true);
         return;
@@ -203,7 +203,7 @@ __device__ __forceinline__ void batch_piece(const BatchArgs a, const int w, cons
         Chase ch;
         ch.p0 = ch.p1 = rowp + k + 1;
         bool ok = true;
-        update_body<FROMK, 0, true, LOCAL>(A, Np, k + 1, k + 1, 0, k, true, b, src, smem, false, &ch, &ok);
+        update_body<FROMK, 0, true, LOCAL, true>(A, Np, k + 1, k + 1, 0, k, true, b, src, smem, false, &ch, &ok);
         if (!ok && (threadIdx.x & 63) == 0) report_timeout(info_b);
         publish_release<LOCAL>(la + k + 1, 1);
         return;

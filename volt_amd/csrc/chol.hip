@@ -88,15 +88,15 @@ __global__ __launch_bounds__(256, 2) void factor_step_kernel(float* __restrict__
     if (k_upd >= 0) {
         const int k = k_upd;
         if (w < B) {                                                      // diagonal tile of matrix w
-            if (k >= 2) update_body<FROMK>(A, Np, k, k, k - 1, k, false, w, src, smem, true);
-            else if (k == 1) update_body<FROMK>(A, Np, 1, 1, 0, 1, true, w, src, smem, true);
+            if (k >= 2) update_body<FROMK, 0, false, false, true>(A, Np, k, k, k - 1, k, false, w, src, smem, true);
+            else if (k == 1) update_body<FROMK, 0, false, false, true>(A, Np, 1, 1, 0, 1, true, w, src, smem, true);
             diag_body(A, Winv, info, Np, k, w, smem, nullptr, k > 0);
             return;
         }
         w -= B;
         const int npre = (k >= 1 && k + 1 < n) ? B : 0;
         if (w < npre) {
-            update_body<FROMK>(A, Np, k + 1, k + 1, 0, k, true, w, src, smem);
+            update_body<FROMK, 0, false, false, true>(A, Np, k + 1, k + 1, 0, k, true, w, src, smem);
             return;
         }
         w -= npre;
@@ -274,8 +274,8 @@ __global__ __launch_bounds__(256, 2) void factor_step_split_kernel(float* __rest
     const int k = k_upd;                                     // k >= 0 always here (the trailing trtri row passes k = n)
     // ---- diagonal tiles: as in factor_step_kernel
     if (k < n && w < B) {
-        if (k >= 2) update_body<FROMK>(A, Np, k, k, k - 1, k, false, w, src, smem, true);
-        else if (k == 1) update_body<FROMK>(A, Np, 1, 1, 0, 1, true, w, src, smem, true);
+        if (k >= 2) update_body<FROMK, 0, false, false, true>(A, Np, k, k, k - 1, k, false, w, src, smem, true);
+        else if (k == 1) update_body<FROMK, 0, false, false, true>(A, Np, 1, 1, 0, 1, true, w, src, smem, true);
         diag_body(A, Winv, info, Np, k, w, smem, nullptr, k > 0);
         return;
     }
@@ -356,8 +356,8 @@ __global__ __launch_bounds__(256, 1) void factor_step_sched_kernel(float* __rest
     const int b0 = d.w & 0xffff, b1 = d.w >> 16;
     float* slabs = sk.slab + (int64_t)tile * S * TS * TS;
     if (kind == 0) {
-        if (k >= 2) update_body<FROMK>(A, Np, k, k, k - 1, k, false, b, src, smem, true);
-        else if (k == 1) update_body<FROMK>(A, Np, 1, 1, 0, 1, true, b, src, smem, true);
+        if (k >= 2) update_body<FROMK, 0, false, false, true>(A, Np, k, k, k - 1, k, false, b, src, smem, true);
+        else if (k == 1) update_body<FROMK, 0, false, false, true>(A, Np, 1, 1, 0, 1, true, b, src, smem, true);
         diag_body(A, Winv, info, Np, k, b, smem, nullptr, k > 0);
     } else if (kind == 4) {
         trtri_diag_body(Winv, Y, Np, i_tri, b, red, smem);
@@ -415,6 +415,18 @@ __global__ __launch_bounds__(256, 2) void tune_update_sq_kernel(float* __restric
     update_body<false, ABL>(A, Np, k + 1 + t, k, 0, k, true, b, src, smem);
 }
 __global__ void tune_empty_kernel(float* A) { if (A == nullptr) A[0] = 0.f; }
+// One symmetric update of diagonal tile (kb,kb) of ONE matrix over K blocks [0, nblk), through the two-operand core or the
+// symmetric one (test hook): stored to A, or -- `image` set -- left in the pivot image and copied out of it, [128][128]
+template <bool SYM>
+__global__ __launch_bounds__(256, 2) void tune_syrk_kernel(float* __restrict__ A, int Np, int kb, int nblk,
+                                                          float* __restrict__ image, KSource src) {
+    __shared__ __attribute__((aligned(16))) float smem[2 * STAGE_FLOATS];
+    update_body<false, 0, false, false, SYM>(A, Np, kb, kb, 0, nblk, true, 0, src, smem, image != nullptr);
+    if (image) {
+        __syncthreads();
+        for (int e = threadIdx.x; e < TS * TS; e += NT) image[e] = smem[(e >> 7) * DT + (e & (TS - 1))];
+    }
+}
 
 }  // namespace volt
 
@@ -936,6 +948,19 @@ int volt_tune_diag_f32(float* A, float* Winv, int* info, int B, int Np, int k, l
     if (k < 0 || k >= Np / TS) return -6;
     if (!stamps) return -7;
     hipLaunchKernelGGL(tune_diag_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, A, Winv, info, Np, k, stamps);
+    VOLT_LAUNCH_CHECK();
+    return 0;
+}
+
+int volt_tune_syrk_f32(float* A, int Np, int kb, int nblk, int sym, float* image, void* stream) {
+    if (!A) return -1;
+    if (Np < TS || Np % TS) return -2;
+    if (kb < 1 || kb >= Np / TS) return -3;
+    if (nblk < 1 || nblk > kb) return -4;
+    if (sym < 0 || sym > 1) return -5;
+    const KSource none{nullptr, 0, 0, nullptr, 0.f, 0};
+    if (sym) hipLaunchKernelGGL(tune_syrk_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, A, Np, kb, nblk, image, none);
+    else hipLaunchKernelGGL(tune_syrk_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, A, Np, kb, nblk, image, none);
     VOLT_LAUNCH_CHECK();
     return 0;
 }

@@ -335,6 +335,208 @@ __device__ __forceinline__ void gemm_nt_128(const float* __restrict__ A, int64_t
     __syncthreads();                           // smem is free for reuse on return
 }
 
+// ---- the symmetric core:  acc += Rows Rows^T, lower 32x32 blocks only ------------------------------------------------
+// A diagonal tile's update has ONE operand (A[kb,kb] -= L[kb,m] L[kb,m]^T) and only its 10 lower blocks are ever read.
+// gemm_nt_128<0> stages that operand twice and has every wave issue 16 MFMAs per K step of 8, 6 of the 16 blocks for
+// nothing.  Here the rows go to LDS once (4 loads + 4 LDS writes per thread and chunk) and the ten blocks are dealt out
+// WHOLE, three to waves 0 and 1 and two to waves 2 and 3:
+//     wave 0:  (1,0) (1,1) (0,0)      fragments of row blocks 0, 1
+//     wave 1:  (3,2) (3,3) (2,2)      fragments of row blocks 2, 3
+//     wave 2:  (2,0) (2,1)            fragments of row blocks 2, 0, 1
+//     wave 3:  (3,0) (3,1)            fragments of row blocks 3, 0, 1
+// (block (r,c) = rows 32 r.., columns 32 c..; the fragment of row block r is the A operand of (r,.) and the B operand of
+// (.,r).)  Waves 0 and 1 run one instruction stream (NB = 3: acc[0] = (hi,lo), acc[1] = (hi,hi), acc[2] = (lo,lo)), waves
+// 2 and 3 another (NB = 2: acc[0] = (p,0), acc[1] = (p,1)): two copies of the K loop behind ONE wave-uniform branch, both
+// with gemm_nt_128's skeleton -- the same barriers in the same places, which is all the waves of a workgroup share.
+// Every element keeps the chain of FMAs it has in gemm_nt_128<0>: same MFMA, same k per lane half, chunks ascending, P
+// from zero per segment of 4 chunks, one add of P per segment -- which wave runs a block, and where in the shadow of the
+// MFMAs its flush is issued, changes no bit.
+struct SyrkStage { f32x4 a[4]; };
+struct SyrkAddr {
+    __amdgpu_buffer_rsrc_t ra;
+    int va[4];
+};
+__device__ __forceinline__ SyrkAddr syrk_addr(const float* A, int64_t lda) {
+    SyrkAddr sa;
+    sa.ra = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, 0x7fffffff, 0x00020000);
+    const int t = threadIdx.x;
+    const int row = t >> 3, cq = (t & 7) * 4;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) sa.va[p] = (int)(((int64_t)(row + 32 * p) * lda + cq) * 4);
+    return sa;
+}
+__device__ __forceinline__ void syrk_load_piece(SyrkStage& s, const SyrkAddr& sa, int so, int p) {
+    s.a[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sa.ra, sa.va[p], so, 0));
+}
+__device__ __forceinline__ void syrk_store_piece(const SyrkStage& s, float* __restrict__ buf, int p) {
+    const int t = threadIdx.x;
+    const int row = t >> 3, cq = (t & 7) * 4;
+    *reinterpret_cast<f32x4*>(buf + (row + 32 * p) * SLD + cq) = s.a[p];
+}
+// the blocks of a wave: t < syrk_nblocks(wave)
+__device__ __forceinline__ int syrk_nblocks(int wave) { return wave < 2 ? 3 : 2; }
+__device__ __forceinline__ void syrk_block(int wave, int t, int& r, int& c) {
+    if (wave < 2) {
+        r = 2 * wave + (t < 2 ? 1 : 0);
+        c = 2 * wave + (t == 1 ? 1 : 0);
+    } else {
+        r = wave;
+        c = t;
+    }
+}
+template <int NB> struct SyrkFrag;
+template <> struct SyrkFrag<3> { f32x4 lo, hi; };
+template <> struct SyrkFrag<2> { f32x4 p, q0, q1; };
+template <int NB>
+__device__ __forceinline__ void syrk_frag_load(SyrkFrag<NB>& f, const float* __restrict__ buf, int kk) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l31 = lane & 31, lh = lane >> 5;
+    const int ko = kk * 8 + 4 * lh;
+    if constexpr (NB == 3) {
+        f.lo = *reinterpret_cast<const f32x4*>(buf + (wave * 64 + l31) * SLD + ko);
+        f.hi = *reinterpret_cast<const f32x4*>(buf + (wave * 64 + 32 + l31) * SLD + ko);
+    } else {
+        f.q0 = *reinterpret_cast<const f32x4*>(buf + l31 * SLD + ko);
+        f.q1 = *reinterpret_cast<const f32x4*>(buf + (32 + l31) * SLD + ko);
+        f.p = *reinterpret_cast<const f32x4*>(buf + (wave * 32 + l31) * SLD + ko);
+    }
+}
+// MFMA (m, t) of a fragment set: K sub-step m, accumulator t
+template <int NB>
+__device__ __forceinline__ f32x16 syrk_mma_one(const SyrkFrag<NB>& f, int m, int t, const f32x16& c) {
+    if constexpr (NB == 3) {
+        const float a = (t < 2) ? f.hi[m] : f.lo[m], b = (t == 1) ? f.hi[m] : f.lo[m];
+        return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+    } else {
+        return __builtin_amdgcn_mfma_f32_32x32x2f32(f.p[m], t ? f.q1[m] : f.q0[m], c, 0, 0, 0);
+    }
+}
+template <int NB>
+__device__ __forceinline__ void syrk_mma_m(const SyrkFrag<NB>& f, int m, f32x16 (&acc)[3]) {
+#pragma unroll
+    for (int t = 0; t < NB; ++t) acc[t] = syrk_mma_one<NB>(f, m, t, acc[t]);
+}
+template <int NB>
+__device__ __forceinline__ void syrk_mma(const SyrkFrag<NB>& f, f32x16 (&acc)[3]) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) syrk_mma_m<NB>(f, m, acc);
+}
+// seg_first_group / seg_last_group for NB accumulators: block t is flushed behind MFMA t + 1 of the segment's last K
+// sub-step, the last block behind the first MFMA of the next segment
+template <int NB>
+__device__ __forceinline__ void syrk_first_group(const SyrkFrag<NB>& f, f32x16 (&P)[3], f32x16 (&T)[3]) {
+    const f32x16 z = zero16c();
+    P[0] = syrk_mma_one<NB>(f, 0, 0, z);
+    VOLT_SB();
+    T[NB - 1] += P[NB - 1];                         // the previous segment's last block (zero before the first segment)
+    VOLT_SB();
+#pragma unroll
+    for (int t = 1; t < NB; ++t) P[t] = syrk_mma_one<NB>(f, 0, t, z);
+#pragma unroll
+    for (int m = 1; m < 4; ++m) syrk_mma_m<NB>(f, m, P);
+}
+template <int NB>
+__device__ __forceinline__ void syrk_last_group(const SyrkFrag<NB>& f, f32x16 (&P)[3], f32x16 (&T)[3]) {
+#pragma unroll
+    for (int m = 0; m < 3; ++m) syrk_mma_m<NB>(f, m, P);
+    P[0] = syrk_mma_one<NB>(f, 3, 0, P[0]);
+    P[1] = syrk_mma_one<NB>(f, 3, 1, P[1]);
+    VOLT_SB();
+    T[0] += P[0];
+    VOLT_SB();
+    if constexpr (NB == 3) {
+        P[2] = syrk_mma_one<NB>(f, 3, 2, P[2]);
+        VOLT_SB();
+        T[1] += P[1];
+        VOLT_SB();
+    }
+}
+// chunk_run for the symmetric core: the same order, pinned the same way; one staging instruction per group of NB MFMAs
+template <int NB, bool MORE, bool ST, bool LD, int ROLE = SEG_MID>
+__device__ __forceinline__ void syrk_chunk_run(const float* cur, float* nxt, SyrkFrag<NB>& F0, SyrkFrag<NB>& F1,
+                                               f32x16 (&acc)[3], f32x16 (&run)[3], SyrkStage& s, const SyrkAddr& sa,
+                                               int k_ld) {
+    syrk_frag_load<NB>(F1, cur, 1);
+    VOLT_SB();
+    if constexpr (ROLE == SEG_FIRST) syrk_first_group<NB>(F0, acc, run);
+    else syrk_mma<NB>(F0, acc);
+    VOLT_SB();
+    syrk_frag_load<NB>(F0, cur, 2);
+    VOLT_SB();
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        syrk_mma_m<NB>(F1, m, acc);
+        if constexpr (ST) syrk_store_piece(s, nxt, m);
+        VOLT_SB();
+    }
+    syrk_frag_load<NB>(F1, cur, 3);
+    VOLT_SB();
+    const int so = __builtin_amdgcn_readfirstlane(k_ld * 4);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        syrk_mma_m<NB>(F0, m, acc);
+        if constexpr (LD) syrk_load_piece(s, sa, so, m);
+        VOLT_SB();
+    }
+    __syncthreads();
+    if constexpr (MORE) syrk_frag_load<NB>(F0, nxt, 0);
+    VOLT_SB();
+    if constexpr (ROLE == SEG_LAST) syrk_last_group<NB>(F1, acc, run);
+    else syrk_mma<NB>(F1, acc);
+    VOLT_SB();
+}
+// the K loop of one instruction stream; the prologue (chunk 0 in LDS, chunks 1 and 2 requested, one barrier) is the caller's
+template <int NB, bool CHASE, bool LOCALP>
+__device__ __forceinline__ void syrk_loop(const SyrkAddr& sa, SyrkStage& s0, SyrkStage& s1, int nchunks, f32x16 (&acc)[3],
+                                          float* smem, int ready, const Chase* ch, bool* ch_ok) {
+    SyrkFrag<NB> F0, F1;
+    syrk_frag_load<NB>(F0, smem, 0);
+    float* b0 = smem;
+    float* b1 = smem + STAGE_FLOATS;
+    f32x16 P[3];
+    P[NB - 1] = zero16c();
+    int c = 0;
+    for (; c + SEG_CHUNKS < nchunks; c += SEG_CHUNKS) {
+        if constexpr (CHASE) {
+            const int need = (c >> 2) + 2;
+            if (ready < need) ready = chase_wait<LOCALP>(*ch, need, *ch_ok);
+        }
+        syrk_chunk_run<NB, true, true, true, SEG_FIRST>(b0, b1, F0, F1, P, acc, s0, sa, (c + 3) * BK);
+        syrk_chunk_run<NB, true, true, true>(b1, b0, F0, F1, P, acc, s1, sa, (c + 4) * BK);
+        syrk_chunk_run<NB, true, true, true>(b0, b1, F0, F1, P, acc, s0, sa, (c + 5) * BK);
+        syrk_chunk_run<NB, true, true, true, SEG_LAST>(b1, b0, F0, F1, P, acc, s1, sa, (c + 6) * BK);
+    }
+    syrk_chunk_run<NB, true, true, true, SEG_FIRST>(b0, b1, F0, F1, P, acc, s0, sa, (c + 3) * BK);
+    syrk_chunk_run<NB, true, true, false>(b1, b0, F0, F1, P, acc, s1, sa, 0);
+    syrk_chunk_run<NB, true, true, false>(b0, b1, F0, F1, P, acc, s0, sa, 0);
+    syrk_chunk_run<NB, false, false, false, SEG_LAST>(b1, b0, F0, F1, P, acc, s1, sa, 0);
+    acc[NB - 1] += P[NB - 1];                  // the last segment's last block
+}
+// acc[t], t < syrk_nblocks(wave): block syrk_block(wave, t) of the tile.  nchunks: a multiple of 4, like gemm_nt_128's.
+template <bool CHASE = false, bool LOCALP = false>
+__device__ __forceinline__ void gemm_syrk_128(const float* __restrict__ A, int64_t lda, int nchunks, f32x16 (&acc)[3],
+                                              float* smem, const Chase* ch = nullptr, bool* ch_ok = nullptr) {
+    if (nchunks <= 0) return;
+    int ready = 0;
+    if constexpr (CHASE) ready = chase_wait<LOCALP>(*ch, 1, *ch_ok);
+    SyrkStage s0, s1;
+    const SyrkAddr sa = syrk_addr(A, lda);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) syrk_load_piece(s0, sa, 0, p);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) syrk_store_piece(s0, smem, p);
+    const int so1 = __builtin_amdgcn_readfirstlane(BK * 4), so2 = __builtin_amdgcn_readfirstlane(2 * BK * 4);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) syrk_load_piece(s0, sa, so1, p);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) syrk_load_piece(s1, sa, so2, p);
+    __syncthreads();
+    // (said to be uniform: a scalar branch, so that each wave meets the barriers of ONE of the two loops)
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < 2) syrk_loop<3, CHASE, LOCALP>(sa, s0, s1, nchunks, acc, smem, ready, ch, ch_ok);
+    else syrk_loop<2, CHASE, LOCALP>(sa, s0, s1, nchunks, acc, smem, ready, ch, ch_ok);
+    __syncthreads();                           // smem is free for reuse on return
+}
+
 // ---- two-phase tile:  T += X Z^T  (K = 32 n1), then  O[c][r] = sum_p T[p][c] W[r][p]  --------------------------------
 // The shape shared by a row tile of the triangular inverse (X = L[i,:], Z = Y[j,:], W = W_i) and by the fused
 // panel-update + panel-solve tile of the factorisation (X = L[k,:], Z = L[i,:], T0 = -A[i,k]^T, W = W_k).  Waves side

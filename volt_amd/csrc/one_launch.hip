@@ -589,7 +589,7 @@ __global__ __launch_bounds__(256, 2) void small_step_kernel(float* __restrict__ 
         // ---- U(k): what block columns m < k-1 owe the diagonal tile (k,k), parked in A for the spine
         small_wait(lf + k * n + (k - 2), nullptr, want, info_b);
         SMALL_STAMP(1);
-        update_body<true>(A, Np, k, k, 0, k - 1, true, b, src, smem);
+        update_body<true, 0, false, false, true, true>(A, Np, k, k, 0, k - 1, true, b, src, smem);   // (ZUP: spine_load_c reads the whole tile)
         SMALL_STAMP(3);
         publish_release<false>(uf + k, want);
         SMALL_STAMP(4);
@@ -781,7 +781,7 @@ __device__ __forceinline__ void long_piece(float* __restrict__ A, float* __restr
     if (pk == LG_D0) {
         if (tid == 0) *info_b = 0;
         for (int c = tid; c < Np; c += NT) tl.rpad[c] = c < tl.N ? tl.resid[c] : 0.f;
-        update_body<true>(A, Np, 0, 0, 0, 0, true, 0, src, smem, true);
+        update_body<true, 0, false, false, true>(A, Np, 0, 0, 0, 0, true, 0, src, smem, true);
         diag_body<false, true>(A, Winv, info, Np, 0, 0, smem, nullptr, true, wf, want, sf);
     } else if (pk == LG_U || pk == LG_E_U) {
         // ---- the look-ahead part of diagonal tile (k,k): U(k) adds its early slices (if any) to its own block(s) and parks

@@ -27,10 +27,94 @@ __device__ __forceinline__ float input_elem(const KSource& src, const float* Kb,
 // launch (diagonal look-ahead, see factor_step_kernel).  The C tile is loaded NEGATED straight into the accumulators
 // before the K loop (acc = -C + sum, C <- -acc): nothing is held back for an epilogue read-modify-write, and no
 // prefetch registers are carried through the loop.
-template <bool FROMK, int ABL = 0, bool CHASE = false, bool LOCALP = false>
+// SYM (compile time, rowblk == colblk at the call site): the tile is symmetric and only its lower triangle is ever read --
+// the one-operand core gemm_syrk_128 and its block map: the 10 lower 32x32 blocks are loaded, updated and stored (or put
+// into the image, zeros above the diagonal as before); the 6 blocks above the diagonal are neither read nor written.
+// Nothing reads them: the diagonal block loads c <= r (diag_body, or this function again when a later launch continues the
+// sum) and writes zeros there when it puts L out.  ZUP: they are stored as zeros all the same, for a reader that loads the
+// whole tile and masks afterwards (one_launch.hip, spine_load_c).
+template <bool FROMK, bool CHASE, bool LOCALP, bool ZUP>
+__device__ __forceinline__ void update_body_sym(float* __restrict__ A, int Np, int kb, int kb0, int kb1, bool fromk, int b,
+                                                const KSource& src, float* smem, bool to_image, const Chase* ch,
+                                                bool* ch_ok) {
+    float* Ab = A + (int64_t)b * Np * Np;
+    const float* rows = Ab + (int64_t)kb * TS * Np + (int64_t)kb0 * TS;        // L[kb, kb0:kb1]
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nb = syrk_nblocks(wave);
+    float* C = Ab + (int64_t)kb * TS * Np + (int64_t)kb * TS;
+    f32x16 acc[3];
+    const bool usek = FROMK && fromk;                      // workgroup-uniform
+    const float add = usek ? ((src.sigma2 ? src.sigma2[b] : 0.f) + src.jitter) : 0.f;
+    const float* Kb = usek ? src.K + (int64_t)b * src.bsk : nullptr;
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+        if (t < nb) {
+            int rb, cb;
+            syrk_block(wave, t, rb, cb);
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int r = rb * 32 + accrow(q, lane);
+                const int c = cb * 32 + (lane & 31);
+                acc[t][q] = -input_elem(src, Kb, add, Ab, Np, usek, kb * TS + r, kb * TS + c);
+            }
+        }
+    gemm_syrk_128<CHASE, LOCALP>(rows, Np, (kb1 - kb0) * (TS / BK), acc, smem, ch, ch_ok);
+    if (to_image) {
+        __syncthreads();                                           // the staging buffers the image overlays are drained
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+            if (t < nb) {
+                int rb, cb;
+                syrk_block(wave, t, rb, cb);
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const int r = rb * 32 + accrow(q, lane);
+                    const int c = cb * 32 + (lane & 31);
+                    smem[r * (TS + 1) + c] = (c <= r) ? -acc[t][q] : 0.f;
+                }
+            }
+        // the zeros above the diagonal: three blocks each from the two waves that own two blocks of the triangle
+        if (wave >= 2) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                const int rb = wave == 2 ? 0 : (t < 2 ? 1 : 2), cb = wave == 2 ? 1 + t : (t < 1 ? 2 : 3);
+#pragma unroll
+                for (int q = 0; q < 16; ++q) smem[(rb * 32 + accrow(q, lane)) * (TS + 1) + cb * 32 + (lane & 31)] = 0.f;
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+        if (t < nb) {
+            int rb, cb;
+            syrk_block(wave, t, rb, cb);
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int r = rb * 32 + accrow(q, lane);
+                const int c = cb * 32 + (lane & 31);
+                C[(int64_t)r * Np + c] = -acc[t][q];
+            }
+        }
+    if (ZUP && wave >= 2) {
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const int rb = wave == 2 ? 0 : (t < 2 ? 1 : 2), cb = wave == 2 ? 1 + t : (t < 1 ? 2 : 3);
+#pragma unroll
+            for (int q = 0; q < 16; ++q) C[(int64_t)(rb * 32 + accrow(q, lane)) * Np + cb * 32 + (lane & 31)] = 0.f;
+        }
+    }
+}
+
+template <bool FROMK, int ABL = 0, bool CHASE = false, bool LOCALP = false, bool SYM = false, bool ZUP = false>
 __device__ __forceinline__ void update_body(float* __restrict__ A, int Np, int rowblk, int colblk, int kb0, int kb1,
                                             bool fromk, int b, const KSource& src, float* smem,
                                             bool to_image = false, const Chase* ch = nullptr, bool* ch_ok = nullptr) {
+    if constexpr (SYM) {
+        static_assert(ABL == 0, "the ablations are the two-operand core's");
+        update_body_sym<FROMK, CHASE, LOCALP, ZUP>(A, Np, rowblk, kb0, kb1, fromk, b, src, smem, to_image, ch, ch_ok);
+        return;
+    }
     float* Ab = A + (int64_t)b * Np * Np;
     const float* Arows = Ab + (int64_t)rowblk * TS * Np + (int64_t)kb0 * TS;   // L[rowblk, kb0:kb1]
     const float* Brows = Ab + (int64_t)colblk * TS * Np + (int64_t)kb0 * TS;   // L[colblk, kb0:kb1]
